@@ -15,6 +15,12 @@ own B clips (weak scaling, no data-path collective).  Rank 0 prints ONE JSON lin
 SD-v1-4 architecture from the counter RNG, inputs are synthetic normals (no checkpoints / datasets offline).
 
 ``--dtype bf16`` is BASELINE configs[2] (bf16 UNet3D / VAE with fp32 GroupNorm statistics; default batch 32).
+
+A plain run does only what its headline figure needs: setup, W warm-up steps, K timed steps, the line.  ``--full`` adds
+everything else the line can carry: the CPU-oracle baseline and its parity clip, the HIP-event roofline of one pass, the
+configs[2] leg (bf16, B = 32) and the separate timing of the exchange and the D2H copy.  ``--dump-outputs DIR`` writes the
+frames the last timed step delivered to the host as float32 .npy files (``dump_outputs``); the inputs and weights come from
+fixed seeds, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -47,7 +53,7 @@ def log(*a):
 def parse_args(argv):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--steps", type=int, default=2, help="timed steps (>= 1); ms_per_step is their mean")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=0, help="clips per GPU (default: 8 = BASELINE configs[1]; 32 with --dtype bf16 = configs[2])")
     ap.add_argument("--ddim-steps", type=int, default=50)
@@ -69,7 +75,7 @@ def parse_args(argv):
                     help="the all-gather through torch.distributed (default) or below the C ABI (e2v_allgather_frames on the library's own "
                          "RCCL communicator; torch.distributed then only ships the 128-byte id)")
     ap.add_argument("--no-configs2", action="store_true",
-                    help="skip the BASELINE configs[2] leg (bf16, B = 32) that a default fp32 run at N = 1 attaches to its JSON line")
+                    help="skip the BASELINE configs[2] leg (bf16, B = 32) that a --full fp32 run at N = 1 attaches to its JSON line")
     ap.add_argument("--configs2-steps", type=int, default=4, help="timed passes of the configs[2] leg")
     ap.add_argument("--configs2-budget-s", type=float, default=455.0,
                     help="run the configs[2] leg only if the process is younger than this when the fp32 part is done (the driver's limit "
@@ -77,7 +83,38 @@ def parse_args(argv):
     ap.add_argument("--dist-single", action="store_true",
                     help="N = 1 rehearsal of the collective: initialise the process group (world size 1) and run the frame "
                          "all-gather through it, so that the RCCL code path executes on a one-GPU box")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baseline + parity clip, the roofline pass, the configs[2] "
+                         "leg and the separate exchange / D2H timing (--no-cpu-baseline, --no-roofline, --no-configs2 act within it)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frames of the last timed step as DIR/<name>.npy (float32; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_SAMPLE = 1 << 22        # elements of the seeded sample over all clips: 16 MiB of float32
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, frames) -> dict:
+    """``--dump-outputs``: the frames the caller of the timed path received in the LAST timed step (rank 0's host buffer, all
+    N*B clips, fp32 or uint8 as gathered), written as float32: ``frames_clip0.npy`` is the whole first clip, ``frames_sample.npy``
+    the elements at DUMP_SAMPLE flat indices drawn with seed DUMP_SEED over the whole buffer, in index order (all of it when the
+    buffer is smaller).  The whole buffer would be 85 MB at B = 8; the two files hold 27 MB."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = np.asarray(frames.numpy() if hasattr(frames, "numpy") else frames)
+    flat = a.reshape(-1)
+    if flat.size <= DUMP_SAMPLE:
+        sample = flat
+    else:
+        sample = flat[np.sort(np.random.default_rng(DUMP_SEED).integers(0, flat.size, DUMP_SAMPLE))]
+    out = {"frames_clip0": a[0].astype(np.float32), "frames_sample": sample.astype(np.float32)}
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {k: list(v.shape) for k, v in out.items()}
 
 
 def free_port() -> int:
@@ -133,7 +170,7 @@ def host_cores() -> dict:
 def cpu_oracle_run(usd, vsd, ucfg, vcfg, guidance):
     """BASELINE configs[0] for real, CPU part: the oracle (CPU restatement of the reference's op sequence, fp32) generates ONE clip
     -- random [1,4,6,36,64] latent, [1,77,768] cond, 4-step DDIM with classifier-free guidance, UNet3D + VAE decode -- on this box's
-    host cores.  Touches no GPU state: the default run executes it on a thread beside the untimed warm-up steps (whose host thread
+    host cores.  Touches no GPU state: a --full run executes it on a thread beside the untimed warm-up steps (whose host thread
     sleeps in the HIP runtime) and joins it before the timed region starts."""
     import numpy as np
     import torch
@@ -259,7 +296,7 @@ def roofline_of(table, ddim_steps, B, dtype, value_per_gpu, kernel_table_path=""
 
 
 def configs2_leg(eng, args, host_frames_u8=None):
-    """BASELINE configs[2] inside the default run: "1xMI355X: bf16 UNet3D with fp32 GroupNorm, batch=32" -- the same engine switched
+    """BASELINE configs[2] inside a --full run: "1xMI355X: bf16 UNet3D with fp32 GroupNorm, batch=32" -- the same engine switched
     to the bf16-activation mode, B = 32 fresh synthetic clips resident in HBM, one event-instrumented full pass that doubles as the
     warm-up (builds the bf16 weight forms), then --configs2-steps (4) timed passes (e2v_generate + D2H of the fp32 frames, as the
     headline)."""
@@ -354,19 +391,20 @@ def rank_body(args, rank, world, eng, *, use_dist, B, frame_shape=(3, 6, 288, 51
 
     # The CPU baseline (the oracle on the host cores, ~1 min) runs on a thread BESIDE THE WARM-UP STEPS and is joined before the timed
     # region starts: the warm-up is untimed GPU work whose host thread sleeps in the HIP runtime, so the two share nothing, the timed
-    # region never sees the oracle's threads, and the default run is a minute shorter than with the leg at its end.  Without a warm-up
+    # region never sees the oracle's threads, and a --full run is a minute shorter than with the leg at its end.  Without a warm-up
     # to hide it under, the leg runs ALONE at the very end (after the configs[2] leg: its threads never sit beside a timed region).
-    cpu_wanted = cpu_leg is not None and rank == 0 and world == 1 and not args.no_cpu_baseline
+    cpu_wanted = args.full and cpu_leg is not None and rank == 0 and world == 1 and not args.no_cpu_baseline
     cpu_overlap = None
     if cpu_wanted and args.warmup > 0:
         cpu_leg.start()
         cpu_overlap = f"the {args.warmup} untimed warm-up step(s); joined before the timed region started"
 
     # The LAST warm-up step of rank 0 carries the HIP-event instrumentation (the roofline's table): it is a full pass of the timed
-    # workload either way, and it saves the default run a separate 14 s pass.  (No warm-up, or a different --profile-ddim-steps:
+    # workload either way, and it saves a --full run a separate 14 s pass.  (No warm-up, or a different --profile-ddim-steps:
     # a separate instrumented pass after the timed region, as before.)
     warm_table = None
-    instr_in_warmup = (rank == 0 and not args.no_roofline and args.warmup > 0 and args.profile_ddim_steps in (0, args.ddim_steps))
+    instr_in_warmup = (args.full and rank == 0 and not args.no_roofline and args.warmup > 0
+                       and args.profile_ddim_steps in (0, args.ddim_steps))
     for i in range(args.warmup):
         if instr_in_warmup and i == args.warmup - 1:
             eng.profile_begin()
@@ -403,33 +441,36 @@ def rank_body(args, rank, world, eng, *, use_dist, B, frame_shape=(3, 6, 288, 51
     clips = world * B * args.steps
     value = clips / elapsed
     host_snapshot = host_frames.clone() if host_frames is not None and not pin else host_frames     # (tests read the timed steps' buffer)
+    if args.dump_outputs and host_frames is not None:       # before anything below reuses the host buffer
+        log(f"outputs of the last timed step written to {args.dump_outputs}: {dump_outputs(args.dump_outputs, host_frames)}")
 
     # the exchange and the D2H on their own (both are inside the timed step above)
     gather_ms = d2h_ms = None
-    frames1 = eng.generate(lat, cond, unc, 1, args.guidance, 0.0, decode=True)
-    sync()
-    if use_dist:
-        dist.barrier()
-        t1 = time.perf_counter()
-        for _ in range(3):
-            g = all_gather_frames(frames1, as_uint8=as_u8, force_collective=True, engine=gather_engine, uniform=True)
+    if args.full:
+        frames1 = eng.generate(lat, cond, unc, 1, args.guidance, 0.0, decode=True)
         sync()
-        gather_ms = 1e3 * (time.perf_counter() - t1) / 3
-    else:
-        g = eng.frames_to_uint8(frames1) if as_u8 else frames1
-    if host_frames is not None:
-        t1 = time.perf_counter()
-        for _ in range(3):
-            host_frames.copy_(g, non_blocking=True)
-        sync()
-        d2h_ms = 1e3 * (time.perf_counter() - t1) / 3
+        if use_dist:
+            dist.barrier()
+            t1 = time.perf_counter()
+            for _ in range(3):
+                g = all_gather_frames(frames1, as_uint8=as_u8, force_collective=True, engine=gather_engine, uniform=True)
+            sync()
+            gather_ms = 1e3 * (time.perf_counter() - t1) / 3
+        else:
+            g = eng.frames_to_uint8(frames1) if as_u8 else frames1
+        if host_frames is not None:
+            t1 = time.perf_counter()
+            for _ in range(3):
+                host_frames.copy_(g, non_blocking=True)
+            sync()
+            d2h_ms = 1e3 * (time.perf_counter() - t1) / 3
+        del g, frames1
     rccl_ranks = dist.get_world_size() if use_dist else 0
-    del g, frames1
 
     result = None
     if rank == 0:
         roof = None
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             if args.profile_ddim_steps <= 0:
                 args.profile_ddim_steps = args.ddim_steps
             if warm_table is not None:
@@ -439,9 +480,10 @@ def rank_body(args, rank, world, eng, *, use_dist, B, frame_shape=(3, 6, 288, 51
                 roof, _ = instrumented_pass(eng, lat, cond, unc, args.profile_ddim_steps, args.guidance, B, args.dtype, value / world,
                                             args.kernel_table)
 
-        # ---- BASELINE configs[2] (bf16, B = 32) as a second leg of the default run, inside the driver's wall-clock budget ----
+        # ---- BASELINE configs[2] (bf16, B = 32) as a second leg of a --full run, inside the driver's wall-clock budget ----
         c2 = None
-        if configs2 is not None and world == 1 and args.dtype == "fp32" and not args.no_configs2 and not args.no_roofline and not use_dist:
+        if (args.full and configs2 is not None and world == 1 and args.dtype == "fp32" and not args.no_configs2 and not args.no_roofline
+                and not use_dist):
             age = process_age_s()
             if age < args.configs2_budget_s:
                 log(f"configs[2] leg: process age {age:.0f} s < {args.configs2_budget_s:.0f} s, running")

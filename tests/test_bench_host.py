@@ -105,3 +105,89 @@ def test_committed_bench_lines_keep_the_contract_and_quote_the_committed_pmc_tra
             assert quoted in open(os.path.join(ROOT, doc)).read(), (doc, quoted)
     wp = b["roofline"]["whole_path"]
     assert abs(wp["achieved_tflops"] - b["value"] * wp["algorithmic_tflop_per_clip"]) < 1e-6 and abs(wp["frac"] - wp["achieved_tflops"] / wp["peak"]) < 1e-9
+
+
+class _StubEngine:
+    """Stands where the HIP engine stands in rank_body (one rank, CPU): clip k's frames are a function of its latent."""
+    device = "cpu"
+
+    def __init__(self):
+        self.calls, self.profiled = [], 0
+
+    def generate(self, lat, cond, unc, steps, guidance, eta, decode=True, return_latents=False):
+        import torch
+        self.calls.append(steps)
+        return torch.stack([torch.full((3, 2, 4, 6), float(lat[k].flatten()[0])) + torch.arange(144.).reshape(3, 2, 4, 6) / 144
+                            for k in range(lat.shape[0])])
+
+    def frames_to_uint8(self, f):
+        import torch
+        return (f * 255).to(torch.uint8)
+
+    def profile_begin(self):
+        self.profiled += 1
+
+    def profile_end(self):
+        return {"igemm_f32": {"ms": 1.0, "launches": 10, "flops": 1e9, "bytes": 1e6}}
+
+    def device_bytes(self):
+        return 0
+
+
+def _one_rank(bench, argv):
+    args = bench.parse_args(["--ddim-steps", "3"] + argv)
+    eng = _StubEngine()
+    r = bench.rank_body(args, 0, 1, eng, use_dist=False, B=2, frame_shape=(3, 2, 4, 6), latent_shape=(4, 2, 4, 6), cond_shape=(5, 8),
+                        sync=lambda: None, pin=False, configs2=lambda *a: {"value": 1.0})
+    return eng, r
+
+
+def test_plain_run_does_only_the_headline(bench):
+    """Without --full: the warm-up and timed steps run and nothing else (no instrumented pass, no exchange / D2H timing pass, no
+    configs[2] leg, no CPU baseline); --steps sets the number of timed steps and ms_per_step is their mean."""
+    eng, r = _one_rank(bench, ["--steps", "5", "--warmup", "2"])
+    d = r["result"]
+    assert eng.calls == [3] * 7 and eng.profiled == 0
+    assert d["steps"] == 5 and d["warmup"] == 2 and d["ms_per_step"] > 0
+    assert abs(d["value"] - 2 * 5 / (d["ms_per_step"] * 5 / 1e3)) < 1e-6 * d["value"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["roofline"] is None and d["configs2"] is None and d["cpu_baseline"] is None and d["d2h_ms"] is None
+    # --full brings them back: the instrumented last warm-up, the one-step exchange / D2H pass, the configs[2] leg
+    eng, r = _one_rank(bench, ["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"])
+    d = r["result"]
+    assert eng.calls == [3, 3, 3, 1] and eng.profiled == 1
+    assert d["roofline"]["kernel"] == "igemm_f32" and d["configs2"] == {"value": 1.0} and d["d2h_ms"] is not None
+
+
+def test_steps_must_be_positive(bench):
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])
+
+
+def test_dump_outputs_writes_the_last_timed_step(bench, tmp_path):
+    """--dump-outputs DIR: float32 .npy of the frames the last timed step delivered to the host, the same from run to run."""
+    import numpy as np
+    out1, out2 = tmp_path / "a", tmp_path / "b"
+    _, r = _one_rank(bench, ["--steps", "2", "--warmup", "1", "--dump-outputs", str(out1)])
+    _one_rank(bench, ["--steps", "2", "--warmup", "1", "--dump-outputs", str(out2)])
+    host = r["host_frames"].numpy()
+    names = sorted(os.listdir(out1))
+    assert names == ["frames_clip0.npy", "frames_sample.npy"] and sorted(os.listdir(out2)) == names
+    c0, s = np.load(out1 / "frames_clip0.npy"), np.load(out1 / "frames_sample.npy")
+    assert c0.dtype == np.float32 and s.dtype == np.float32
+    assert np.array_equal(c0, host[0]) and np.array_equal(s, host.reshape(-1))       # small buffer: the sample is all of it
+    for n in names:
+        assert np.array_equal(np.load(out1 / n), np.load(out2 / n))
+
+
+def test_dump_sample_of_a_large_buffer_is_fixed_and_bounded(bench, tmp_path):
+    import numpy as np
+    frames = np.arange(3 * (bench.DUMP_SAMPLE + 7), dtype=np.float32).reshape(3, -1)
+    shapes = bench.dump_outputs(str(tmp_path / "a"), frames)
+    bench.dump_outputs(str(tmp_path / "b"), frames)
+    assert shapes == {"frames_clip0": [bench.DUMP_SAMPLE + 7], "frames_sample": [bench.DUMP_SAMPLE]}
+    s = np.load(tmp_path / "a" / "frames_sample.npy")
+    assert np.array_equal(s, np.load(tmp_path / "b" / "frames_sample.npy"))
+    assert np.all(np.diff(s) >= 0) and s[-1] - s[0] > 2 * bench.DUMP_SAMPLE     # index order, spread over the whole buffer
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in os.listdir(tmp_path / "a")) < 64 * 2**20

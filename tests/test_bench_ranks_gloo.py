@@ -70,7 +70,7 @@ def _worker(rank, world, port, gather, q):
     try:
         bench = _bench()
         args = bench.parse_args(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--backend", "gloo", "--gather", gather,
-                                 "--ddim-steps", "3", "--no-cpu-baseline"])
+                                 "--ddim-steps", "3", "--no-cpu-baseline", "--full"])
         eng = StubEngine()
         r = bench.rank_body(args, rank, world, eng, use_dist=True, B=B, frame_shape=FRAME, latent_shape=LAT, cond_shape=COND,
                             sync=lambda: None, pin=False)
