@@ -922,7 +922,7 @@ e2v_status e2v_op_temporal_attention(e2v_ctx* c, const float* qkv, float* out, i
                                      float scale, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(qkv && out && F <= 8 && D % 4 == 0, E2V_EINVAL, "bad temporal attention arguments");
+        E2V_REQUIRE(qkv && out && D % 4 == 0, E2V_EINVAL, "bad temporal attention arguments");
         const int C = heads * D;
         hipStream_t s = S(c, stream);
         if (c->bf16_compute) {

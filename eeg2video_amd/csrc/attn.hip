@@ -1525,6 +1525,194 @@ static bool temporal_wave_launch(const T* qkv, int ld, T* out, int ldo, int n, i
     return true;
 }
 
+// Long clips (F > 8): F x F per (pixel, head) on the matrix pipe, any F.  Frames go in tiles of 16; one wave owns a unit = (pixel,
+// head, tile of 16 query frames) and walks the key tiles with an online softmax (running max / sum per query, accumulator rescaled).
+//   scores  S^T = K Q^T   v_mfma_f32_16x16x32_{bf16,f16} over 32-channel steps (fp32 rows: v_mfma_f32_16x16x4_f32, exact f32): the
+//           operands are plain row reads -- lane l feeds key / query frame l & 15 and channels 8 (l >> 4) ... of the step -- and the
+//           result puts query l & 15 on the lane and keys 4 (l >> 4) + r in its 4 registers: the softmax is in-register plus two
+//           exchanges over the lane quarters;
+//   output  O^T = V^T P^T v_mfma_f32_16x16x4_f32, 4 per 16-channel tile: P^T's register r is already the B operand of k-slot l >> 4
+//           (key 4 (l >> 4) + r), so P stays fp32 and never moves; the V operand is one element per lane (channel l & 15 of that key).
+//           Lane l ends with 4 consecutive channels 4 (l >> 4) ... of query l & 15.
+// Frames past F and channels past D are fed as clamped / zero rows and their scores masked; the arithmetic of a (pixel, head) is the
+// same whatever the launch geometry, so a result does not depend on n or on the neighbours.
+// STAGED: a block copies q, k, v of PB pixels x F frames x a slab of hs whole heads into LDS with 16-byte coalesced row reads (all in
+// flight before the first write), works out of LDS, writes each unit's output over its own q rows and copies the slab out with 16-byte
+// row writes.  Not STAGED (one pixel-head of all F frames does not fit 64 KB of LDS): the same walk reads q, k, v from global memory.
+template <typename T, int D, bool STAGED>
+__global__ __launch_bounds__(256) void temporal_attn_long_kernel(const T* __restrict__ qkv, int ld, T* __restrict__ out, int ldo,
+                                                                 int F, int HW, int C, float scale_log2, int PB, int hs, int npg) {
+    constexpr bool B16 = !std::is_same<T, float>::value;
+    constexpr int NCT = (D + 15) / 16;                      // 16-channel output tiles
+    constexpr int VE = 16 / (int)sizeof(T);                 // elements per 16-byte piece
+    typedef unsigned u4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) unsigned char tl_smem[];
+    T* sm = reinterpret_cast<T*>(tl_smem);                  // [F][PB][q | k | v][CS] + one 16-byte pad per frame (bank spread)
+    const int smp = blockIdx.x / npg, p0 = (blockIdx.x - smp * npg) * PB;
+    const int CS = hs * D, h0 = blockIdx.y * hs;
+    const int FS = PB * 3 * CS + VE;
+    const int CO = CS / VE;
+    // staging walk: piece idx = row * CO + co, row = (f * PB + pp) * 3 + part (PB a power of two, 1 << lpb); a thread's pieces are
+    // 256 apart, so (row, co) advances by a fixed step -- no run-time division per piece (it cost more than the arithmetic)
+    const int lpb = 31 - __builtin_clz(PB);
+    const int rstep = 256 / CO, cstep = 256 - rstep * CO;
+    if constexpr (STAGED) {
+        constexpr int NB = 8;
+        const int rows = F * PB * 3;
+        int row = (int)threadIdx.x / CO, co = (int)threadIdx.x - row * CO;
+        while (row < rows) {
+            u4 v[NB];
+            int so[NB];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                const int part = row % 3, fp = row / 3, pp = fp & (PB - 1), f = fp >> lpb;
+                v[b] = u4{0u, 0u, 0u, 0u};
+                so[b] = row < rows ? f * FS + (pp * 3 + part) * CS + co * VE : -1;
+                if (row < rows && p0 + pp < HW)
+                    v[b] = *reinterpret_cast<const u4*>(qkv + ((size_t)(smp * F + f) * HW + p0 + pp) * ld + part * C + h0 * D + co * VE);
+                row += rstep;
+                co += cstep;
+                if (co >= CO) { co -= CO; ++row; }
+            }
+#pragma unroll
+            for (int b = 0; b < NB; ++b)
+                if (so[b] >= 0) *reinterpret_cast<u4*>(sm + so[b]) = v[b];
+        }
+        __syncthreads();
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int li = lane & 15, g = lane >> 4;
+    const int nt = (F + 15) >> 4;
+    const int units = PB * hs * nt;
+    for (int u = wave; u < units; u += 4) {
+        const int qt = u % nt, hh = (u / nt) % hs, pp = u / (nt * hs);
+        const int pix = p0 + pp;
+        if (pix >= HW) continue;                            // wave-uniform
+        typedef typename std::conditional<STAGED, int, size_t>::type I;     // LDS offsets fit 32 bits
+        const T* src;
+        I fs;
+        int ps;
+        if constexpr (STAGED) { src = sm + pp * 3 * CS + hh * D; fs = FS; ps = CS; }
+        else { src = qkv + ((size_t)smp * F * HW + pix) * ld + (h0 + hh) * D; fs = (size_t)HW * ld; ps = C; }
+        const T* qrow = src + (I)min(qt * 16 + li, F - 1) * fs;
+        f32x4 acc[NCT];
+#pragma unroll
+        for (int t = 0; t < NCT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+        float m = -INFINITY, l = 0.f;
+        for (int kt = 0; kt < nt; ++kt) {
+            const T* krow = src + (I)min(kt * 16 + li, F - 1) * fs + ps;
+            f32x4 st = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (B16) {
+#pragma unroll
+                for (int c0 = 0; c0 < D; c0 += 32) {
+                    const int c = c0 + 8 * g;
+                    hx8<T> a = {}, b = {};
+                    if (c < D) { a = *reinterpret_cast<const hx8<T>*>(krow + c); b = *reinterpret_cast<const hx8<T>*>(qrow + c); }
+                    st = mfma_16x16x32(a, b, st);
+                }
+            } else {
+#pragma unroll
+                for (int c0 = 0; c0 < D; c0 += 16) {            // k-slot l >> 4 of step e <-> channel c0 + 4 (l >> 4) + e
+                    const int c = c0 + 4 * g;
+                    f32x4 a = {0.f, 0.f, 0.f, 0.f}, b = a;
+                    if (c < D) { a = *reinterpret_cast<const f32x4*>(krow + c); b = *reinterpret_cast<const f32x4*>(qrow + c); }
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) st = __builtin_amdgcn_mfma_f32_16x16x4f32(a[e], b[e], st, 0, 0, 0);
+                }
+            }
+            // online softmax in log2 units; query li's 16 scores sit on lanes li, li + 16, li + 32, li + 48
+            float p[4], tm = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                p[r] = kt * 16 + 4 * g + r < F ? st[r] * scale_log2 : -INFINITY;
+                tm = fmaxf(tm, p[r]);
+            }
+            tm = fmaxf(tm, __shfl_xor(tm, 16));
+            tm = fmaxf(tm, __shfl_xor(tm, 32));
+            const float mn = fmaxf(m, tm);                   // finite: every key tile holds at least one frame
+            const float alpha = exp2f(m - mn);
+            float ts = 0.f;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { p[r] = exp2f(p[r] - mn); ts += p[r]; }
+            ts += __shfl_xor(ts, 16);
+            ts += __shfl_xor(ts, 32);
+            l = l * alpha + ts;
+            m = mn;
+            const T* vrow = src + 2 * ps;
+            I vo[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) vo[r] = (I)min(kt * 16 + 4 * g + r, F - 1) * fs;
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) acc[t] *= alpha;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)                      // the NCT accumulators are independent: back-to-back MFMAs
+#pragma unroll
+                for (int t = 0; t < NCT; ++t) {
+                    const float a = (float)vrow[vo[r] + min(t * 16 + li, D - 1)];
+                    acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, p[r], acc[t], 0, 0, 0);
+                }
+        }
+        const float inv = 1.0f / l;
+        const int q = qt * 16 + li;
+        T* orow;
+        if constexpr (STAGED) orow = const_cast<T*>(qrow);      // this unit's own q rows: read by no one else
+        else orow = out + ((size_t)(smp * F + q) * HW + pix) * ldo + (h0 + hh) * D;
+        if (q < F) {
+#pragma unroll
+            for (int t = 0; t < NCT; ++t) {
+                const int c = t * 16 + 4 * g;
+                if (c < D) {
+                    if constexpr (B16) {
+                        hx4<T> o;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) o[e] = (T)(acc[t][e] * inv);
+                        *reinterpret_cast<hx4<T>*>(orow + c) = o;
+                    } else {
+                        *reinterpret_cast<f32x4*>(orow + c) = acc[t] * inv;
+                    }
+                }
+            }
+        }
+    }
+    if constexpr (STAGED) {
+        __syncthreads();
+        const int rows = F * PB;                            // the output (q) rows: row = f * PB + pp
+        int row = (int)threadIdx.x / CO, co = (int)threadIdx.x - row * CO;
+        for (; row < rows; row += rstep) {
+            const int pp = row & (PB - 1), f = row >> lpb;
+            if (p0 + pp < HW)
+                *reinterpret_cast<u4*>(out + ((size_t)(smp * F + f) * HW + p0 + pp) * ldo + h0 * D + co * VE) =
+                    *reinterpret_cast<const u4*>(sm + f * FS + pp * 3 * CS + co * VE);
+            co += cstep;
+            if (co >= CO) { co -= CO; ++row; }
+        }
+    }
+}
+
+template <typename T, int D>
+static void temporal_long_launch(const T* qkv, int ld, T* out, int ldo, int n, int F, int HW, int heads, float scale, hipStream_t s) {
+    constexpr size_t sz = sizeof(T);
+    // a slab of whole heads and a pixel count whose q / k / v image fits 32 KB (several blocks per CU keep loads in flight); one
+    // pixel-head alone may take up to 64 KB, past that the kernel reads global memory in place
+    const size_t budget = 32 * 1024;
+    int hs = heads;
+    while (hs > 1 && (size_t)F * 3 * hs * D * sz > budget) hs = (hs + 1) / 2;
+    while (heads % hs) --hs;
+    const int CS = hs * D;
+    int PB = (int)(budget / ((size_t)F * 3 * CS * sz));
+    PB = PB >= 8 ? 8 : PB >= 4 ? 4 : PB >= 2 ? 2 : 1;       // a power of two (the kernel's staging walk); CS / 16 B < 256 pieces
+    const size_t smem = (size_t)F * ((size_t)PB * 3 * CS * sz + 16);
+    const float sl2 = scale * 1.4426950408889634f;
+    if (smem <= 64 * 1024) {
+        const int npg = (HW + PB - 1) / PB;
+        E2V_KLAUNCH((temporal_attn_long_kernel<T, D, true>), dim3((unsigned)(n * npg), heads / hs), dim3(256), smem, s, qkv, ld, out, ldo, F,
+                    HW, heads * D, sl2, PB, hs, npg);
+    } else {
+        E2V_KLAUNCH((temporal_attn_long_kernel<T, D, false>), dim3((unsigned)(n * HW), heads), dim3(256), 0, s, qkv, ld, out, ldo, F, HW,
+                    heads * D, sl2, 1, 1, HW);
+    }
+}
+
 template <typename T>
 static void temporal_attention_launch(const T* qkv, int ld, T* out, int ldo, int n, int F, int HW, int heads, int D, float scale,
                                       hipStream_t s);
@@ -1550,6 +1738,20 @@ static void temporal_attention_launch(const T* qkv, int ld, T* out, int ldo, int
                                       hipStream_t s) {
     const size_t total = (size_t)n * HW * heads * F;
     const int C = heads * D;
+    if (F > 8) {
+        E2V_REQUIRE(ld % 8 == 0 && ldo % 8 == 0, E2V_EINVAL, "temporal attention over more than 8 frames needs row strides % 8 == 0");
+        dry_tag(" -> temporal_attn_long_kernel");
+        switch (D) {
+            case 8: temporal_long_launch<T, 8>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 16: temporal_long_launch<T, 16>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 32: temporal_long_launch<T, 32>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 40: temporal_long_launch<T, 40>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 64: temporal_long_launch<T, 64>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 80: temporal_long_launch<T, 80>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            case 160: temporal_long_launch<T, 160>(qkv, ld, out, ldo, n, F, HW, heads, scale, s); return;
+            default: E2V_REQUIRE(false, E2V_EINVAL, "temporal attention over more than 8 frames: head dim not in {8,16,32,40,64,80,160}");
+        }
+    }
     static const int* const wave_on = knob("E2V_TATTN_WAVE", 1);      // 0: the LDS-staged kernel (same-process A/B, the op test)
     if (*wave_on) {
         bool done = false;

@@ -857,7 +857,6 @@ struct Runner {
             t = linear(w.ff2, hgate.p, 4 * C, rows, t.p, C);
         }
         {   // temporal attention over the F frames of each pixel                                         :261-267
-            E2V_REQUIRE(F <= 8, E2V_EINVAL, "temporal attention supports at most 8 frames");
             Act nrm = ln(w.lnt, t);
             Act qkv = linear(w.at_qkv, nrm.p, C, rows);
             nrm.reset();
