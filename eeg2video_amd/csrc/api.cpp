@@ -350,21 +350,28 @@ e2v_status e2v_set_conv_algo(e2v_ctx* c, int algo) {
 int64_t e2v_device_bytes(const e2v_ctx* c) { return c ? (int64_t)(c->weight_bytes + c->pool.bytes()) : 0; }
 
 // ---------------------------------------------------------------------------------------------------
+// The body of the three UNet entry points: NCFHW in, unet_forward_cl, NCFHW out.  host_tf != null: fractional timesteps;
+// sink != null: the taps of e2v_op_unet_forward_taps are collected on the way.
+static void unet_forward_ncfhw(e2v_ctx* c, const float* sample, const int64_t* host_t, const float* host_tf, int n_t, const float* cond,
+                               int N, int F, int H, int W, int T, float* out, e2v_ctx::TapSink* sink, e2v_stream stream) {
+    E2V_REQUIRE(sample && (host_t || host_tf) && cond && out && (!sink || sink->buf), E2V_EINVAL, "null argument");
+    E2V_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && T > 0 && (!sink || sink->cap > 0), E2V_ESHAPE, "non-positive dimension");
+    hipStream_t s = S(c, stream);
+    const int Cin = c->cfg.in_channels, Cout = c->cfg.out_channels;
+    const int FHW = F * H * W;
+    struct Guard { e2v_ctx* c; ~Guard() { c->tap_sink = nullptr; } } guard{c};
+    c->tap_sink = sink;
+    Act x(c->pool, (int64_t)N * FHW, Cin);
+    ncfhw_to_cl(sample, x.p, N, Cin, Cin, FHW, 1.0f, s);
+    Act y = c->unet_forward_cl(x.p, host_t, n_t, cond, N, F, H, W, T, s, false, host_tf);
+    cl_to_ncfhw(y.p, Cout, out, N, Cout, FHW, 1.0f, 0.0f, 0, 0.f, 0.f, s);
+    E2V_HIP(hipGetLastError());
+}
+
 e2v_status e2v_unet_forward(e2v_ctx* c, const float* sample, const int64_t* host_t, int n_t, const float* cond, int N,
                             int F, int H, int W, int T, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
-    return guarded(c, [&] {
-        E2V_REQUIRE(sample && host_t && cond && out, E2V_EINVAL, "null argument");
-        E2V_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && T > 0, E2V_ESHAPE, "non-positive dimension");
-        hipStream_t s = S(c, stream);
-        const int Cin = c->cfg.in_channels, Cout = c->cfg.out_channels;
-        const int FHW = F * H * W;
-        Act x(c->pool, (int64_t)N * FHW, Cin);
-        ncfhw_to_cl(sample, x.p, N, Cin, Cin, FHW, 1.0f, s);
-        Act y = c->unet_forward_cl(x.p, host_t, n_t, cond, N, F, H, W, T, s);
-        cl_to_ncfhw(y.p, Cout, out, N, Cout, FHW, 1.0f, 0.0f, 0, 0.f, 0.f, s);
-        E2V_HIP(hipGetLastError());
-    });
+    return guarded(c, [&] { unet_forward_ncfhw(c, sample, host_t, nullptr, n_t, cond, N, F, H, W, T, out, nullptr, stream); });
 }
 
 // Test aid (eeg2video_hip_ops.h): the forward above with the block outputs the oracle exposes copied out on the way.
@@ -373,20 +380,10 @@ e2v_status e2v_op_unet_forward_taps(e2v_ctx* c, const float* sample, const int64
                                     int* n_taps, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(sample && host_t && cond && out && taps && shapes && n_taps, E2V_EINVAL, "null argument");
-        E2V_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && T > 0 && taps_cap > 0, E2V_ESHAPE, "non-positive dimension");
-        hipStream_t s = S(c, stream);
-        const int Cin = c->cfg.in_channels, Cout = c->cfg.out_channels;
-        const int FHW = F * H * W;
+        E2V_REQUIRE(host_t && shapes && n_taps, E2V_EINVAL, "null argument");
         e2v_ctx::TapSink sink;
         sink.buf = taps; sink.cap = taps_cap;
-        struct Guard { e2v_ctx* c; ~Guard() { c->tap_sink = nullptr; } } guard{c};
-        c->tap_sink = &sink;
-        Act x(c->pool, (int64_t)N * FHW, Cin);
-        ncfhw_to_cl(sample, x.p, N, Cin, Cin, FHW, 1.0f, s);
-        Act y = c->unet_forward_cl(x.p, host_t, n_t, cond, N, F, H, W, T, s);
-        cl_to_ncfhw(y.p, Cout, out, N, Cout, FHW, 1.0f, 0.0f, 0, 0.f, 0.f, s);
-        E2V_HIP(hipGetLastError());
+        unet_forward_ncfhw(c, sample, host_t, nullptr, n_t, cond, N, F, H, W, T, out, &sink, stream);
         *n_taps = sink.count;
         for (int i = 0; i < sink.count; ++i)
             for (int k = 0; k < 5; ++k) shapes[5 * i + k] = sink.shapes[i][k];
@@ -396,18 +393,7 @@ e2v_status e2v_op_unet_forward_taps(e2v_ctx* c, const float* sample, const int64
 e2v_status e2v_unet_forward_ft(e2v_ctx* c, const float* sample, const float* host_t, int n_t, const float* cond, int N,
                                int F, int H, int W, int T, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
-    return guarded(c, [&] {
-        E2V_REQUIRE(sample && host_t && cond && out, E2V_EINVAL, "null argument");
-        E2V_REQUIRE(N > 0 && F > 0 && H > 0 && W > 0 && T > 0, E2V_ESHAPE, "non-positive dimension");
-        hipStream_t s = S(c, stream);
-        const int Cin = c->cfg.in_channels, Cout = c->cfg.out_channels;
-        const int FHW = F * H * W;
-        Act x(c->pool, (int64_t)N * FHW, Cin);
-        ncfhw_to_cl(sample, x.p, N, Cin, Cin, FHW, 1.0f, s);
-        Act y = c->unet_forward_cl(x.p, nullptr, n_t, cond, N, F, H, W, T, s, false, host_t);
-        cl_to_ncfhw(y.p, Cout, out, N, Cout, FHW, 1.0f, 0.0f, 0, 0.f, 0.f, s);
-        E2V_HIP(hipGetLastError());
-    });
+    return guarded(c, [&] { unet_forward_ncfhw(c, sample, nullptr, host_t, n_t, cond, N, F, H, W, T, out, nullptr, stream); });
 }
 
 static void ddim_coeffs(const e2v_ctx* c, int64_t t, int64_t t_prev, float co[4]) {
@@ -444,7 +430,7 @@ static void decode_to_video(e2v_ctx* c, const float* z_cl, int B, int F, int h, 
     for (int b = 0; b < B; b += group) {
         const int nb = B - b < group ? B - b : group;
         c->vae_decode_frames(z_cl + (size_t)b * F * h * w * c->cfg.vae_latent_channels, nb * F, h, w,
-                             frames.p + (size_t)b * F * HW8 * C3, s, B <= *knob("E2V_SMALL_FAMILY_CLIPS", 4));      // the dispatch family is the CALL's (model.h), not the pass's
+                             frames.p + (size_t)b * F * HW8 * C3, s, B <= small_family_clips());      // the dispatch family is the CALL's (model.h), not the pass's; clips, not samples (ADVICE.md finding 3)
     }
     nchw_frames_to_ncfhw(frames.p, C3, videos, B, F, C3, HW8, post ? 0.5f : 1.0f, post ? 0.5f : 0.0f, post ? 1 : 0, s);
 }
@@ -520,7 +506,10 @@ e2v_status e2v_generate(e2v_ctx* c, const float* latents, const float* cond, con
             e2v_ctx* c;
             ~CacheGuard() { c->step_cache_on = false; c->temb_cache.clear(); c->kv_cache.clear(); }
         } guard{c};
-        c->build_step_caches(ts.data(), steps, embp, N, T, s);
+        // (the family of the UNet passes this call makes, so that the caches do not depend on what an earlier call ran.  No launch in
+        // there is eligible for split-K at the shipped thresholds -- cross-attention K = cross_attention_dim < 2 x 2048, the
+        // time-embedding linears are fp32 rows -- so the caches are the same bits in both families)
+        c->build_step_caches(ts.data(), steps, embp, N, T, unet_small_family(N), s);
         c->step_cache_on = true;
         // latent_model_input = cat([latents] * 2) (:313) is not materialised: the UNet is told that its input stands for the
         // pair, and computes what the two copies share (up to the first cross-attention) once
@@ -682,6 +671,11 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
         hipStream_t s = S(c, stream);
         const int cin = c0 + c1;
         E2V_REQUIRE(c1 == 0 || c0 % 32 == 0, E2V_ESHAPE, "conv: the concat seam must be a multiple of 32 channels");
+        Conv3 d;                     // the launch as the graph runner describes it (model.h); the weight forms are pool temporaries here
+        d.x0 = x0; d.c0 = c0; d.x1 = x1; d.c1 = c1; d.nimg = n_img; d.Hs = Hs; d.Ws = Ws;
+        d.Hi = Hi; d.Wi = Wi; d.Ho = Ho; d.Wo = Wo; d.stride = stride; d.pad = pad_lo;
+        d.cout = cout; d.out = out; d.bias = bias;
+        d.rowbias = rowbias; d.rb_ld = cout; d.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; d.resid = resid;
         if (c->bf16_compute) {       // bf16-activation mode: operands rounded to bf16 once (channels zero-padded to 8), fp32 result
             E2V_REQUIRE(c1 == 0 || c0 % 64 == 0, E2V_ESHAPE, "bf16 conv: the concat seam must be a multiple of 64 channels");
             const int c0p = c1 > 0 ? c0 : (c0 + 7) / 8 * 8, c1p = (c1 + 7) / 8 * 8;
@@ -693,81 +687,42 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
             Act w64(c->pool, cout, ld64), w16(c->pool, cout, (ld64 + 1) / 2);
             pack_conv3x3(w_oihw, w64.p, cout, cin, 64, s);
             to_h16(w64.p, w16.p, (size_t)cout * ld64, c->h16_mode, s);
-            IgemmArgs g;
-            g.a0 = a0.p; g.c0 = c0p; g.lda0 = c0p; g.a1 = c1 > 0 ? a1.p : nullptr; g.c1 = c1 > 0 ? c1p : 0; g.lda1 = c1p;
-            g.w16 = w16.p; g.ldw16 = ld64; g.ldw = ld64; g.out = out; g.ldc = cout; g.bias = bias;
-            g.rowbias = rowbias; g.rb_ld = cout; g.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
-            g.resid = resid; g.ldr = cout; g.M = n_img * Ho * Wo; g.N = cout; g.taps = 9;
-            g.Ho = Ho; g.Wo = Wo; g.Hi = Hi; g.Wi = Wi; g.Hs = Hs; g.Ws = Ws; g.stride = stride; g.pad = pad_lo;
-            if (Hi != Hs || Wi != Ws) { g.upsample = 1; g.ups_h = (float)Hs / (float)Hi; g.ups_w = (float)Ws / (float)Wi; }
+            d.x0 = a0.p; d.c0 = c0p; d.x1 = a1.p; d.c1 = c1p;
+            IgemmArgs g = conv3_igemm(d);
+            g.w16 = w16.p; g.ldw16 = ld64; g.ldw = ld64;
             g.a_bf16 = c->h16_mode; g.out_f32 = 1;
             // test aid: E2V_SPLITK_FORCE = S runs the launch as split-K with S runs where it is eligible (the graph asks for it by itself
             // in the small-batch family, model.cpp Runner::sk_setup)
             static const int* const sk_force = knob("E2V_SPLITK_FORCE", 0);
             Act skws;
-            if (*sk_force >= 2 && !g.upsample) {
-                const int runs = splitk_plan(g, *sk_force);
-                if (runs >= 2) { skws = Act(c->pool, (int64_t)runs * g.M, g.N); g.sk = *sk_force; g.sk_ws = skws.p; }
-            }
+            if (*sk_force >= 2 && !g.upsample) skws = splitk_attach(c->pool, g, *sk_force);
             if (c1 == 0 && c0p == c0 && bgemm_up2x_applies(g)) {   // exact 2x resize: the sub-pixel form the graph runner takes
                 const size_t n = 4 * (size_t)cout * conv_up2x_packed_ld(cin);
                 Act u32(c->pool, (int64_t)((n + 1023) / 1024), 1024), u16(c->pool, (int64_t)((n + 2047) / 2048), 1024);
                 pack_conv_up2x(w_oihw, u32.p, cout, cin, s);
                 to_h16(u32.p, u16.p, n, c->h16_mode, s);
                 bgemm_up2x_launch(g, u16.p, s);
-                E2V_HIP(hipGetLastError());
-                return;
+            } else {
+                igemm(g, s);
             }
-            igemm(g, s);
-            E2V_HIP(hipGetLastError());
-            return;
-        }
-        const bool wino_shape = stride == 1 && pad_lo == 1 && Hi == Ho && Wi == Wo && cout % 4 == 0;
-        int wm = 0;                                            // same policy as the graph runner (model.cpp: Runner::winograd)
-        if (wino_shape && c->conv_algo == E2V_CONV_WINOGRAD) wm = 2;
-        if (wino_shape && c->conv_algo == E2V_CONV_WINOGRAD4) wm = 4;
-        if (wino_shape && c->conv_algo == E2V_CONV_AUTO) {
-            const int cmin = std::min(cin, cout);
-            const double padded = (double)((Ho + 3) / 4 * 4) * ((Wo + 3) / 4 * 4);
-            if (c->wino_f4 && cmin >= c->wino4_min_c && padded <= c->wino_f4_pad * Ho * Wo) wm = 4;
-            else if (cmin >= c->wino_min_c) wm = 2;
-        }
-        if (wm) {
+        } else if (const int wm = c->conv_wino_tile(cin, cout, stride, pad_lo, Hi, Wi, Ho, Wo)) {      // the graph runner's policy
             Act u(c->pool, (int64_t)(wm + 2) * (wm + 2) * cout, cin);
             wino_pack_weights(w_oihw, u.p, cout, cin, wm, s);
-            WinoArgs a;
-            a.m = wm;
-            a.x0 = x0; a.c0 = c0; a.ld0 = c0; a.x1 = x1; a.c1 = c1; a.ld1 = c1;
-            a.nimg = n_img; a.Hs = Hs; a.Ws = Ws; a.Ho = Ho; a.Wo = Wo;
-            if (Hi != Hs || Wi != Ws) { a.upsample = 1; a.ups_h = (float)Hs / (float)Hi; a.ups_w = (float)Ws / (float)Wi; }
-            a.U = u.p; a.N = cout; a.out = out; a.ldc = cout; a.bias = bias;
             Act u3;
             if (c->x3_compute) {
                 const size_t n = (size_t)(wm + 2) * (wm + 2) * cout * cin;
                 u3 = Act(c->pool, (int64_t)((3 * n + 1) / 2 + 1023) / 1024, 1024);
                 split_bf16x3(u.p, u3.p, n, n, s);
-                a.U3 = u3.p;
             }
-            a.rowbias = rowbias; a.rb_ld = cout; a.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
-            a.resid = resid; a.ldr = cout;
-            const int chunk = wino_chunk_images(a, c->wino_ws_floats);
-            const size_t need = wino_workspace_floats(a, chunk);
-            Act ws(c->pool, (int64_t)((need + 1023) / 1024), 1024);
-            wino_conv3x3(a, ws.p, chunk, s);
-            E2V_HIP(hipGetLastError());
-            return;
+            conv3_wino(c, d, wm, u.p, u3.p, nullptr, 0, s);
+        } else {
+            const int ld32 = conv3x3_packed_ld(cin, 32);
+            Act wp(c->pool, cout, ld32);
+            pack_conv3x3(w_oihw, wp.p, cout, cin, 32, s);
+            IgemmArgs g = conv3_igemm(d);
+            g.w = wp.p; g.ldw = ld32;
+            igemm(g, s);
         }
-        const int ld32 = conv3x3_packed_ld(cin, 32);
-        Act wp(c->pool, cout, ld32);
-        pack_conv3x3(w_oihw, wp.p, cout, cin, 32, s);
-        IgemmArgs g;
-        g.a0 = x0; g.c0 = c0; g.lda0 = c0; g.a1 = x1; g.c1 = c1; g.lda1 = c1;
-        g.w = wp.p; g.ldw = ld32; g.out = out; g.ldc = cout; g.bias = bias;
-        g.rowbias = rowbias; g.rb_ld = cout; g.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
-        g.resid = resid; g.ldr = cout; g.M = n_img * Ho * Wo; g.N = cout; g.taps = 9;
-        g.Ho = Ho; g.Wo = Wo; g.Hi = Hi; g.Wi = Wi; g.Hs = Hs; g.Ws = Ws; g.stride = stride; g.pad = pad_lo;
-        if (Hi != Hs || Wi != Ws) { g.upsample = 1; g.ups_h = (float)Hs / (float)Hi; g.ups_w = (float)Ws / (float)Wi; }
-        igemm(g, s);
         E2V_HIP(hipGetLastError());
     });
 }
@@ -786,12 +741,7 @@ e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, 
             E2V_REQUIRE(N % 32 == 0 && bias, E2V_EINVAL, "GEGLU width must be a multiple of 32 and have a bias");
             wp = Act(c->pool, 2 * N, K);
             bp = Act(c->pool, 1, 2 * N);
-            for (int q = 0; q < N / 32; ++q) {
-                copy_rows(w + (size_t)(q * 32) * K, K, wp.p + (size_t)(q * 64) * K, K, 32, K, s);
-                copy_rows(w + (size_t)(N + q * 32) * K, K, wp.p + (size_t)(q * 64 + 32) * K, K, 32, K, s);
-                copy_rows(bias + q * 32, 32, bp.p + q * 64, 32, 1, 32, s);
-                copy_rows(bias + N + q * 32, 32, bp.p + q * 64 + 32, 32, 1, 32, s);
-            }
+            geglu_interleave(w, bias, N, K, wp.p, bp.p, s);
             g.w = wp.p; g.bias = bp.p; g.N = 2 * N; g.ldc = N; g.geglu = 1;
         } else {
             g.w = w; g.bias = bias; g.N = N; g.ldc = N; g.ldr = N;
@@ -808,10 +758,7 @@ e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, 
         }
         static const int* const sk_force = knob("E2V_SPLITK_FORCE", 0);      // test aid, as in e2v_op_conv3x3
         Act skws;
-        if (c->bf16_compute && *sk_force >= 2) {
-            const int runs = splitk_plan(g, *sk_force);
-            if (runs >= 2) { skws = Act(c->pool, (int64_t)runs * g.M, g.N); g.sk = *sk_force; g.sk_ws = skws.p; }
-        }
+        if (c->bf16_compute && *sk_force >= 2) skws = splitk_attach(c->pool, g, *sk_force);
         Act w3;
         if (c->x3_compute) {
             const size_t n = (size_t)g.N * K;

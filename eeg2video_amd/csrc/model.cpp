@@ -159,23 +159,87 @@ void e2v_ctx::free_part(int part) {
     owned_part[part].clear();
 }
 
-bool e2v_ctx::conv_has_wino(const ConvW& w, int m) const {
-    if (!w.stride1 || conv_algo == 1) return false;
-    const int cmin = std::min(w.cin, w.cout);
-    if (m == 2) return conv_algo == 2 || (conv_algo == 0 && cmin >= wino_min_c);
-    return conv_algo == 3 || (conv_algo == 0 && wino_f4 && cmin >= wino4_min_c);
+// fp32 arithmetic only (in a 16-bit mode the transforms would dominate and rounding the transformed inputs costs accuracy), for a
+// stride-1, pad-1 conv whose channel counts are multiples of 4.  conv_algo 1 / 2 / 3: direct / F(2x2) / F(4x4) wherever it applies.
+int e2v_ctx::conv_wino_tile(int cin, int cout, int stride, int pad, int Hi, int Wi, int Ho, int Wo) const {
+    if (bf16_compute || stride != 1 || pad != 1 || Hi != Ho || Wi != Wo || cin % 4 != 0 || cout % 4 != 0) return 0;
+    if (conv_algo == 2 || conv_algo == 3) return conv_algo == 3 ? 4 : 2;
+    if (conv_algo != 0) return 0;
+    const int cmin = std::min(cin, cout);
+    const double padded = (double)((Ho + 3) / 4 * 4) * ((Wo + 3) / 4 * 4);
+    if (wino_f4 && cmin >= wino4_min_c && padded <= wino_f4_pad * Ho * Wo) return 4;
+    return cmin >= wino_min_c ? 2 : 0;
+}
+
+int e2v::small_family_clips() {
+    static const int* const clips = knob("E2V_SMALL_FAMILY_CLIPS", 4);
+    return *clips;
+}
+
+IgemmArgs e2v::conv3_igemm(const Conv3& d) {
+    IgemmArgs g;
+    g.a0 = d.x0; g.c0 = d.c0; g.lda0 = d.c0; g.a1 = d.x1; g.c1 = d.c1; g.lda1 = d.c1;
+    g.out = d.out; g.ldc = d.cout; g.bias = d.bias;
+    g.rowbias = d.rowbias; g.rb_ld = d.rb_ld; g.rows_per_sample = d.rows_per_sample;
+    g.resid = d.resid; g.ldr = d.cout;
+    g.M = d.nimg * d.Ho * d.Wo; g.N = d.cout; g.taps = 9;
+    g.Ho = d.Ho; g.Wo = d.Wo; g.Hi = d.Hi; g.Wi = d.Wi; g.Hs = d.Hs; g.Ws = d.Ws; g.stride = d.stride; g.pad = d.pad;
+    g.upsample = d.resized(); g.ups_h = d.ups_h(); g.ups_w = d.ups_w();
+    return g;
+}
+
+void e2v::conv3_wino(e2v_ctx* c, const Conv3& d, int m, const float* U, const void* U3, const float* gn_scsh, int gn_P, hipStream_t s) {
+    WinoArgs a;
+    a.m = m;
+    a.x0 = d.x0; a.c0 = d.c0; a.ld0 = d.c0; a.x1 = d.x1; a.c1 = d.c1; a.ld1 = d.c1;
+    a.nimg = d.nimg; a.Hs = d.Hs; a.Ws = d.Ws; a.Ho = d.Ho; a.Wo = d.Wo;
+    a.upsample = d.resized(); a.ups_h = d.ups_h(); a.ups_w = d.ups_w();
+    if (gn_P > 0) { a.gn_scsh = gn_scsh; a.gn_P = gn_P; a.gn_silu = 1; }
+    a.U = U; a.U3 = U3; a.N = d.cout; a.out = d.out; a.ldc = d.cout; a.bias = d.bias;
+    a.rowbias = d.rowbias; a.rb_ld = d.rb_ld; a.rows_per_sample = d.rows_per_sample; a.resid = d.resid; a.ldr = d.cout;
+    const int chunk = wino_chunk_images(a, c->wino_ws_floats);
+    const size_t need = wino_workspace_floats(a, chunk);
+    Act ws(c->pool, (int64_t)((need + 1023) / 1024), 1024);
+    wino_conv3x3(a, ws.p, chunk, s);
+}
+
+void e2v::geglu_interleave(const float* w, const float* b, int half, int in, float* dw, float* db, hipStream_t s) {
+    for (int q = 0; q < half / 32; ++q) {
+        copy_rows(w + (size_t)(q * 32) * in, in, dw + (size_t)(q * 64) * in, in, 32, in, s);
+        copy_rows(w + (size_t)(half + q * 32) * in, in, dw + (size_t)(q * 64 + 32) * in, in, 32, in, s);
+        copy_rows(b + q * 32, 32, db + q * 64, 32, 1, 32, s);
+        copy_rows(b + half + q * 32, 32, db + q * 64 + 32, 32, 1, 32, s);
+    }
+}
+
+Act e2v::splitk_attach(Pool& pool, IgemmArgs& g, int want) {
+    Act ws;
+    const int runs = splitk_plan(g, want);
+    if (runs < 2) return ws;
+    ws = Act(pool, (int64_t)runs * g.M, g.N);
+    g.sk = want; g.sk_ws = ws.p;
+    return ws;
 }
 
 // First use of a layout: allocate it under the owning finalize() group (freed when that part is finalized again) and derive
 // it from the torch-layout weight on the calling stream -- ordered before the launch that asked for it.
 void e2v_ctx::conv_form(const ConvW& w, ConvForm f, hipStream_t s) {
-    const int saved = alloc_part;
-    struct Restore { e2v_ctx* c; int v; ~Restore() { c->alloc_part = v; } } restore{this, saved};
-    alloc_part = w.part;
+    AllocPart guard(this, w.part);
     auto split3 = [&](const float* u, size_t n) -> const void* {
         float* d = dev_alloc((3 * n + 1) / 2);
         split_bf16x3(u, d, n, n, s);
         return d;
+    };
+    // a 16-bit layout of n elements: packed in fp32 staging (the up2x tap sums are formed in fp32), rounded once
+    auto form16 = [&](const void*& dst, bool up2, int mode) {
+        if (dst) return;
+        const size_t n = up2 ? 4 * (size_t)w.cout * conv_up2x_packed_ld(w.cin) : (size_t)w.cout * w.ldw16;
+        Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);
+        if (up2) pack_conv_up2x(w.raw, tmp.p, w.cout, w.cin, s);
+        else pack_conv3x3(w.raw, tmp.p, w.cout, w.cin, 64, s);                // the 64-channel-chunk layout
+        float* d16 = dev_alloc((n + 1) / 2);
+        to_h16(tmp.p, d16, n, mode, s);
+        dst = d16;
     };
     switch (f) {
         case FORM_DIRECT32:
@@ -185,32 +249,10 @@ void e2v_ctx::conv_form(const ConvW& w, ConvForm f, hipStream_t s) {
                 w.w = d;
             }
             break;
-        case FORM_BF16:
-        case FORM_F16: {
-            const void*& dst = f == FORM_F16 ? w.w16h : w.w16;
-            if (!dst) {
-                const size_t n = (size_t)w.cout * w.ldw16;
-                Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);            // fp32 staging of the 64-channel-chunk layout
-                pack_conv3x3(w.raw, tmp.p, w.cout, w.cin, 64, s);
-                float* d16 = dev_alloc((n + 1) / 2);
-                to_h16(tmp.p, d16, n, f == FORM_F16 ? H16_FP16 : H16_BF16, s);
-                dst = d16;
-            }
-            break;
-        }
-        case FORM_BF16_UP2:
-        case FORM_F16_UP2: {
-            const void*& dst = f == FORM_F16_UP2 ? w.w16h_up2 : w.w16_up2;
-            if (!dst) {
-                const size_t n = 4 * (size_t)w.cout * conv_up2x_packed_ld(w.cin);
-                Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);            // fp32 staging: the tap sums are formed in fp32, rounded once
-                pack_conv_up2x(w.raw, tmp.p, w.cout, w.cin, s);
-                float* d16 = dev_alloc((n + 1) / 2);
-                to_h16(tmp.p, d16, n, f == FORM_F16_UP2 ? H16_FP16 : H16_BF16, s);
-                dst = d16;
-            }
-            break;
-        }
+        case FORM_BF16: form16(w.w16, false, H16_BF16); break;
+        case FORM_F16: form16(w.w16h, false, H16_FP16); break;
+        case FORM_BF16_UP2: form16(w.w16_up2, true, H16_BF16); break;
+        case FORM_F16_UP2: form16(w.w16h_up2, true, H16_FP16); break;
         case FORM_WINO2:
         case FORM_WINO4: {
             const int m = f == FORM_WINO4 ? 4 : 2;
@@ -232,9 +274,7 @@ void e2v_ctx::conv_form(const ConvW& w, ConvForm f, hipStream_t s) {
 // bf16 copy: rows zero-padded to in16), filed under the finalize() group that owns the layer.
 const void* e2v_ctx::lin_f16(const LinW& w, hipStream_t s) {
     if (w.w16h) return w.w16h;
-    const int saved = alloc_part;
-    struct Restore { e2v_ctx* c; int v; ~Restore() { c->alloc_part = v; } } restore{this, saved};
-    alloc_part = w.part;
+    AllocPart guard(this, w.part);
     const size_t n = (size_t)w.out * w.in16;
     float* d16 = dev_alloc((n + 1) / 2);
     if (w.in16 == w.in) {
@@ -246,6 +286,14 @@ const void* e2v_ctx::lin_f16(const LinW& w, hipStream_t s) {
     }
     w.w16h = d16;
     return d16;
+}
+
+void e2v_ctx::grow_timesteps(int n, hipStream_t s) {
+    if (d_timesteps_cap >= n) return;
+    E2V_HIP(hipStreamSynchronize(s));
+    if (d_timesteps) (void)hipFree(d_timesteps);
+    E2V_HIP(hipMalloc((void**)&d_timesteps, sizeof(long long) * n));
+    d_timesteps_cap = n;
 }
 
 void e2v_ctx::enter_stream(hipStream_t s) {
@@ -312,14 +360,13 @@ struct Packer {
         return mk_lin(w.d, bias ? t(n + ".bias").d : nullptr, (int)w.shape[1], (int)w.shape[0]);
     }
     // 3x3 conv: the torch-layout weight stays; kernel layouts are built on first use (e2v_ctx::conv_form)
-    ConvW conv3(const std::string& n, bool stride1 = true) {
+    ConvW conv3(const std::string& n) {
         const WTensor& w = t(n + ".weight");
         ConvW cw;
         cw.raw = w.d; cw.b = t(n + ".bias").d;
         cw.cout = (int)w.shape[0]; cw.cin = (int)w.shape[1];
         cw.cin_pad = (cw.cin + 3) / 4 * 4; cw.cin_pad16 = (cw.cin + 7) / 8 * 8;
         cw.ldw = conv3x3_packed_ld(cw.cin, 32); cw.ldw16 = conv3x3_packed_ld(cw.cin, 64);
-        cw.stride1 = stride1 && cw.cin % 4 == 0 && cw.cout % 4 == 0;
         cw.part = c->alloc_part >= 0 ? c->alloc_part : 0;
         return cw;
     }
@@ -344,12 +391,7 @@ struct Packer {
         E2V_REQUIRE(half % 32 == 0, E2V_EINVAL, "GEGLU inner width must be a multiple of 32");
         float* d = c->dev_alloc((size_t)out * in);
         float* b = c->dev_alloc(out);
-        for (int q = 0; q < half / 32; ++q) {
-            copy_rows(w.d + (size_t)(q * 32) * in, in, d + (size_t)(q * 64) * in, in, 32, in, s);
-            copy_rows(w.d + (size_t)(half + q * 32) * in, in, d + (size_t)(q * 64 + 32) * in, in, 32, in, s);
-            copy_rows(bsrc.d + q * 32, 32, b + q * 64, 32, 1, 32, s);
-            copy_rows(bsrc.d + half + q * 32, 32, b + q * 64 + 32, 32, 1, 32, s);
-        }
+        geglu_interleave(w.d, bsrc.d, half, in, d, b, s);
         return mk_lin(d, b, in, out);
     }
     ResW resnet(const std::string& p, bool temb) {
@@ -392,7 +434,7 @@ struct Packer {
 void e2v_ctx::finalize(int which) {
     Packer P{this};
     const int L = cfg.layers_per_block;
-    struct PartGuard { e2v_ctx* c; ~PartGuard() { c->alloc_part = -1; } } part_guard{this};
+    AllocPart part_guard(this, -1);                  // (an error below leaves no part selected)
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
     if (which & 1) {
         free_part(0);
@@ -406,7 +448,7 @@ void e2v_ctx::finalize(int which) {
                 b.res.push_back(P.resnet(idx("down_blocks", i, "resnets", j), true));
                 if (i < 3) b.attn.push_back(P.transformer(idx("down_blocks", i, "attentions", j)));
             }
-            if (i != 3) { b.resample = true; b.rs = P.conv3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv", false); }
+            if (i != 3) { b.resample = true; b.rs = P.conv3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
             u.down.push_back(std::move(b));
         }
         u.mid_r0 = P.resnet("mid_block.resnets.0", true);
@@ -448,7 +490,7 @@ void e2v_ctx::finalize(int which) {
         for (int i = 0; i < 4; ++i) {
             VAEW::Block b;
             for (int j = 0; j < VL; ++j) b.res.push_back(P.resnet(idx("vae.encoder.down_blocks", i, "resnets", j), false));
-            if (i != 3) { b.resample = true; b.rs = P.conv3("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv", false); }
+            if (i != 3) { b.resample = true; b.rs = P.conv3("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
             v.enc_down.push_back(std::move(b));
         }
         v.enc_mid0 = P.resnet("vae.encoder.mid_block.resnets.0", false);
@@ -502,15 +544,12 @@ void e2v_ctx::finalize(int which) {
         const bool is_vae = k.rfind("vae.", 0) == 0;
         if (k.rfind("semantic.", 0) == 0) continue;
         if ((is_vae && !(which & 2)) || (!is_vae && !(which & 1))) continue;
-        const WTensor& w = raw[k];
-        const bool conv3 = w.shape.size() == 4 && w.shape[2] == 3;
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
                            k.find(".value.") != std::string::npos;
         const bool keep_q = k.find(".attn2.to_q.") != std::string::npos;
-        (void)conv3;                            // 3x3 conv weights stay: their kernel layouts are derived from them on first use
-        if (fused && !keep_q) drop(k);
+        if (fused && !keep_q) drop(k);          // (3x3 conv weights stay: their kernel layouts are derived from them on first use)
     }
     if (which & 1) unet_ready = true;
     if (which & 2) vae_ready = true;
@@ -524,9 +563,31 @@ namespace {
 
 struct Geo { int nimg, H, W; };     // images (= n*F frames) and their map size
 
+// What a launch sets beyond its required arguments, by name (plain aggregates: a call site assigns the fields it means)
+struct LinOpt {
+    const float* resid = nullptr; int ldr = 0;               // out += resid
+    const float* a1 = nullptr; int c1 = 0, lda1 = 0;         // second source: the last c1 of the K columns come from a1
+    bool geglu = false;                                      // out[M][N/2]
+    bool f32_io = false, out_f32 = false;                    // bf16-activation mode: see Runner::linear
+};
+struct ConvOpt {
+    const float* rowbias = nullptr; int rows_per_sample = 1;
+    int rb_ld = -1;              // stride between the samples' rowbias rows (0: one row for all; < 0: cout)
+    const float* resid = nullptr;
+    int gn_P = 0;                // > 0: the input is the RAW tensor and GroupNorm's affine + SiLU (statistics already in c->gn_scale,
+                                 // slabs of gn_P rows) is applied on the way in -- only valid where the policy picks a Winograd form
+    bool out_f32 = false;
+    bool want_rb = false;        // a GroupNorm follows -- leave the row-block sums with the output (Act::rb) where the tensor can carry them
+};
+struct ResOpt {
+    const float* temb_silu = nullptr; int temb_dim = 0;      // SiLU(emb) rows, one per sample (null: the block has no time embedding)
+    const float* rb0 = nullptr; const float* rb1 = nullptr;  // row-block sums of x0 / x1 (Act::rb of the tensors; null: none)
+};
+
 struct Runner {
     e2v_ctx* c;
     hipStream_t s;
+    const bool small_family;          // the dispatch family of the API call this runner serves (model.h), fixed for its lifetime
     int res_idx = 0, tr_idx = 0;      // position in the per-generate caches (resnets with a time embedding / transformers)
     Pool& pool() { return c->pool; }
     // bf16-activation mode (e2v_set_compute_dtype(E2V_BF16)): every activation the graph stores in HBM is bf16; accumulation,
@@ -547,67 +608,32 @@ struct Runner {
     // partials (each run at least E2V_SPLITK_MIN_DEPTH deep: the partial planes cost 8 bytes per output and run, a run of depth d
     // 2 d flops per output).  Returns the workspace the launch needs (kept alive by the caller until the launch is queued).
     Act sk_setup(IgemmArgs& g) {
-        Act ws;
         static const int* const on = knob("E2V_SPLITK", 1);
         static const int* const min_depth = E2V_AB_KNOB("E2V_SPLITK_MIN_DEPTH", 2048);     // (1024 / 640 and 400 tiles measured +-0: `make ab` only)
         static const int* const max_tiles = E2V_AB_KNOB("E2V_SPLITK_MAX_TILES", 256);
-        if (!c->small_family || !g.a_bf16 || !*on || *min_depth < 64) return ws;
+        if (!small_family || !g.a_bf16 || !*on || *min_depth < 64) return Act();
         const long K = (long)g.taps * (g.c0 + g.c1);
         const long tiles = (long)((g.M + 127) / 128) * ((g.N + 127) / 128);
-        if (tiles >= *max_tiles || K < 2L * *min_depth) return ws;
+        if (tiles >= *max_tiles || K < 2L * *min_depth) return Act();
         const int want = (int)std::min<long>(std::min<long>((512 + tiles - 1) / tiles, K / *min_depth), 16);
-        const int runs = splitk_plan(g, want);
-        if (runs < 2) return ws;
-        ws = Act(pool(), (int64_t)runs * g.M, g.N);
-        g.sk = want; g.sk_ws = ws.p;
-        return ws;
+        return splitk_attach(pool(), g, want);
     }
 
     void gn_ws(int samples, int P, int C) {
-        const size_t need_p = (size_t)samples * groupnorm_chunks(P) * C * 2;
-        const size_t need_s = (size_t)samples * C * 2;
-        if (need_p > c->gn_part_floats) {
+        auto grow = [&](float*& p, size_t& have, size_t need) {
+            if (need <= have) return;
             E2V_HIP(hipStreamSynchronize(s));
-            if (c->gn_part && !dry_run()) (void)hipFree(c->gn_part);
-            E2V_HIP(hipMalloc((void**)&c->gn_part, need_p * sizeof(float)));
-            if (dry_run()) c->gn_part = dry_fake_ptr(need_p * sizeof(float));       // (pointers steer the graph: a null workspace reads as "no GroupNorm in front")
-            c->gn_part_floats = need_p;
-        }
-        if (need_s > c->gn_scale_floats) {
-            E2V_HIP(hipStreamSynchronize(s));
-            if (c->gn_scale && !dry_run()) (void)hipFree(c->gn_scale);
-            E2V_HIP(hipMalloc((void**)&c->gn_scale, need_s * sizeof(float)));
-            if (dry_run()) c->gn_scale = dry_fake_ptr(need_s * sizeof(float));
-            c->gn_scale_floats = need_s;
-        }
+            if (p && !dry_run()) (void)hipFree(p);
+            E2V_HIP(hipMalloc((void**)&p, need * sizeof(float)));
+            if (dry_run()) p = dry_fake_ptr(need * sizeof(float));       // (pointers steer the graph: a null workspace reads as "no GroupNorm in front")
+            have = need;
+        };
+        grow(c->gn_part, c->gn_part_floats, (size_t)samples * groupnorm_chunks(P) * C * 2);
+        grow(c->gn_scale, c->gn_scale_floats, (size_t)samples * C * 2);
     }
 
-    // rb0 / rb1: row-block sums that came with the source tensors (Act::rb; null: none) -- the statistics pass over such a source is
-    // skipped (bf16 mode, P a multiple of 64)
-    Act gn(const NormW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, int groups, float eps,
-           bool act, const float* rb0 = nullptr, const float* rb1 = nullptr) {
-        const int C = c0 + c1;
-        E2V_REQUIRE(C == w.c && C % groups == 0 && c0 % 4 == 0 && c1 % 4 == 0, E2V_ESHAPE, "GroupNorm channel mismatch");
-        gn_ws(samples, P, C);
-        Act out = new_act((int64_t)samples * P, C);
-        GroupNormArgs a;
-        a.bf16 = h16();
-        a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.ld0 = c0; a.ld1 = c1;
-        a.gamma = w.g; a.beta = w.b; a.out = out.p; a.ldo = C;
-        a.samples = samples; a.P = P; a.groups = groups; a.eps = eps; a.silu = act ? 1 : 0;
-        a.ws_part = c->gn_part; a.ws_scale = c->gn_scale;
-        if (bf() && P % 64 == 0) { a.rb0 = rb0; a.rb1 = c1 > 0 ? rb1 : nullptr; }
-        // (16-bit modes only: the fp32 mode keeps one summation order at every batch.  E2V_GN_FUSED_SMALL = 3: the one-kernel form in
-        // BOTH families -- the A/B that priced it at B = 32, profiles/r05_shape_ab_b32_gn_fused.log)
-        static const int* const gn_fused = knob("E2V_GN_FUSED_SMALL", 1);
-        a.small_chunks = (c->small_family && bf()) ? 1 : 0;
-        a.fused_small = (bf() && (c->small_family || *gn_fused == 3)) ? 1 : 0;
-        groupnorm(a, s);
-        return out;
-    }
-
-    // statistics only: (scale, shift) per (slab, channel) left in c->gn_scale for the conv's input transform
-    void gn_stats(const NormW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, int groups, float eps) {
+    // what gn and gn_stats share: the two sources, the affine, the slabs and the workspaces (grown here)
+    GroupNormArgs gn_args(const NormW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, int groups, float eps) {
         const int C = c0 + c1;
         E2V_REQUIRE(C == w.c && C % groups == 0 && c0 % 4 == 0 && c1 % 4 == 0, E2V_ESHAPE, "GroupNorm channel mismatch");
         gn_ws(samples, P, C);
@@ -616,20 +642,29 @@ struct Runner {
         a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.ld0 = c0; a.ld1 = c1;
         a.gamma = w.g; a.beta = w.b; a.samples = samples; a.P = P; a.groups = groups; a.eps = eps;
         a.ws_part = c->gn_part; a.ws_scale = c->gn_scale;
-        groupnorm_stats(a, s);
+        return a;
     }
 
-    // does this conv run in Winograd form?  (fp32 arithmetic only: in bf16 the transforms would dominate and the
-    // rounding of transformed inputs costs accuracy)
-    // returns the output tile size: 0 = direct, 2 = F(2x2,3x3), 4 = F(4x4,3x3).  fp32 arithmetic only: in bf16 the
-    // transforms would dominate and rounding the transformed inputs costs accuracy.
-    int winograd(const ConvW& w, int stride, int pad, int Hi, int Wi, int Ho, int Wo) const {
-        if (c->conv_algo == 1 || c->bf16_compute || stride != 1 || pad != 1 || Hi != Ho || Wi != Wo) return 0;
-        if (c->conv_algo == 2) return c->conv_has_wino(w, 2) ? 2 : 0;
-        if (c->conv_algo == 3) return c->conv_has_wino(w, 4) ? 4 : 0;
-        const double padded = (double)((Ho + 3) / 4 * 4) * ((Wo + 3) / 4 * 4);
-        if (c->conv_has_wino(w, 4) && padded <= c->wino_f4_pad * Ho * Wo) return 4;
-        return c->conv_has_wino(w, 2) ? 2 : 0;
+    // rb0 / rb1: row-block sums that came with the source tensors (Act::rb; null: none) -- the statistics pass over such a source is
+    // skipped (bf16 mode, P a multiple of 64)
+    Act gn(const NormW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, int groups, float eps,
+           bool act, const float* rb0 = nullptr, const float* rb1 = nullptr) {
+        GroupNormArgs a = gn_args(w, x0, c0, x1, c1, samples, P, groups, eps);
+        Act out = new_act((int64_t)samples * P, c0 + c1);
+        a.out = out.p; a.ldo = c0 + c1; a.silu = act ? 1 : 0;
+        if (bf() && P % 64 == 0) { a.rb0 = rb0; a.rb1 = c1 > 0 ? rb1 : nullptr; }
+        // (16-bit modes only: the fp32 mode keeps one summation order at every batch.  E2V_GN_FUSED_SMALL = 3: the one-kernel form in
+        // BOTH families -- the A/B that priced it at B = 32, profiles/r05_shape_ab_b32_gn_fused.log)
+        static const int* const gn_fused = knob("E2V_GN_FUSED_SMALL", 1);
+        a.small_chunks = (small_family && bf()) ? 1 : 0;
+        a.fused_small = (bf() && (small_family || *gn_fused == 3)) ? 1 : 0;
+        groupnorm(a, s);
+        return out;
+    }
+
+    // statistics only: (scale, shift) per (slab, channel) left in c->gn_scale for the conv's input transform
+    void gn_stats(const NormW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, int groups, float eps) {
+        groupnorm_stats(gn_args(w, x0, c0, x1, c1, samples, P, groups, eps), s);
     }
 
     Act ln(const NormW& w, const Act& x) {
@@ -642,74 +677,50 @@ struct Runner {
     // out[M][N] = A[M][K] W^T + b (+ resid); geglu: out[M][N/2].
     // bf16-activation mode: A, resid and out are bf16 unless `f32_io` (the time-embedding MLP: fp32 rows in, fp32 rows out,
     // fp32 arithmetic) or `out_f32` (a boundary tensor: VAE moments, attention scores)
-    Act linear(const LinW& w, const float* a, int lda, int64_t M, const float* resid = nullptr, int ldr = 0,
-               bool geglu = false, const float* a1 = nullptr, int c1 = 0, int lda1 = 0, bool f32_io = false, bool out_f32 = false) {
-        const bool b16 = bf() && !f32_io;
+    Act linear(const LinW& w, const float* a, int lda, int64_t M, const LinOpt& o = {}) {
+        const bool b16 = bf() && !o.f32_io;
         const int K = b16 ? w.in16 : w.in;
-        const int K0 = K - c1;
+        const int K0 = K - o.c1;
         const int gran = b16 ? 8 : 4;
-        E2V_REQUIRE(K0 > 0 && K0 % gran == 0 && c1 % gran == 0 && lda % gran == 0, E2V_ESHAPE, "linear: K must be a multiple of 4 (bf16: 8)");
-        Act out(pool(), M, geglu ? w.out / 2 : w.out, b16 && !out_f32);
+        E2V_REQUIRE(K0 > 0 && K0 % gran == 0 && o.c1 % gran == 0 && lda % gran == 0, E2V_ESHAPE, "linear: K must be a multiple of 4 (bf16: 8)");
+        Act out(pool(), M, o.geglu ? w.out / 2 : w.out, b16 && !o.out_f32);
         IgemmArgs g;
-        g.a0 = a; g.c0 = K0; g.lda0 = lda; g.a1 = a1; g.c1 = c1; g.lda1 = lda1;
+        g.a0 = a; g.c0 = K0; g.lda0 = lda; g.a1 = o.a1; g.c1 = o.c1; g.lda1 = o.lda1;
         g.w = w.w; g.ldw = w.in; g.ldw16 = w.in16; g.out = out.p; g.ldc = out.C; g.bias = w.b;
-        g.resid = resid; g.ldr = ldr; g.M = (int)M; g.N = w.out; g.taps = 1; g.geglu = geglu ? 1 : 0;
-        if (b16) { g.w16 = w16_of(w); g.a_bf16 = h16(); g.out_f32 = out_f32 ? 1 : 0; g.resid_bf16 = resid ? 1 : 0; }
+        g.resid = o.resid; g.ldr = o.ldr; g.M = (int)M; g.N = w.out; g.taps = 1; g.geglu = o.geglu ? 1 : 0;
+        if (b16) { g.w16 = w16_of(w); g.a_bf16 = h16(); g.out_f32 = o.out_f32 ? 1 : 0; g.resid_bf16 = o.resid ? 1 : 0; }
         if (c->x3_compute && w.w3) { g.x3 = 1; g.w3 = w.w3; g.w3_plane = (long long)w.out * w.in; }
         Act skws = sk_setup(g);
         igemm(g, s);
         return out;
     }
+    static LinOpt residual(const float* resid, int ldr) { LinOpt o; o.resid = resid; o.ldr = ldr; return o; }
+    static LinOpt f32_rows() { LinOpt o; o.f32_io = true; return o; }
 
     // 3x3 conv over `geo.nimg` images; (Hi, Wi) = logical input size (after nearest resize), (Ho, Wo) output size
-    // gn_P > 0: the input is the RAW tensor and GroupNorm's affine + SiLU (statistics already in c->gn_scale, slabs of
-    // gn_P rows) is applied on the way in -- only valid when winograd() says so
     Act conv3(const ConvW& w, const float* x0, int c0, const float* x1, int c1, Geo geo, int Hi, int Wi, int Ho, int Wo,
-              int stride, int pad, const float* rowbias = nullptr, int rows_per_sample = 1, const float* resid = nullptr,
-              int gn_P = 0, int rb_ld = -1, bool out_f32 = false, bool want_rb = false) {   // rb_ld: stride between the samples' rowbias rows (0: one row for all)
-        // want_rb: a GroupNorm follows -- leave the row-block sums with the output (Act::rb) where the tensor can carry them
-        if (rb_ld < 0) rb_ld = w.cout;
+              int stride, int pad, const ConvOpt& o = {}) {
         E2V_REQUIRE(c0 + c1 == (bf() ? w.cin_pad16 : w.cin_pad), E2V_ESHAPE, "conv: input channels do not match the weight");
-        Act out(pool(), (int64_t)geo.nimg * Ho * Wo, w.cout, bf() && !out_f32);
-        if (const int wm = winograd(w, stride, pad, Hi, Wi, Ho, Wo)) {
-            WinoArgs a;
-            a.m = wm;
-            a.x0 = x0; a.c0 = c0; a.ld0 = c0; a.x1 = x1; a.c1 = c1; a.ld1 = c1;
-            a.nimg = geo.nimg; a.Hs = geo.H; a.Ws = geo.W; a.Ho = Ho; a.Wo = Wo;
-            if (Hi != geo.H || Wi != geo.W) {
-                a.upsample = 1;
-                a.ups_h = (float)geo.H / (float)Hi;        // torch: scale = (float)input_size / output_size
-                a.ups_w = (float)geo.W / (float)Wi;
-            }
-            if (gn_P > 0) { a.gn_scsh = c->gn_scale; a.gn_P = gn_P; a.gn_silu = 1; }
+        Act out(pool(), (int64_t)geo.nimg * Ho * Wo, w.cout, bf() && !o.out_f32);
+        Conv3 d;
+        d.x0 = x0; d.c0 = c0; d.x1 = x1; d.c1 = c1; d.nimg = geo.nimg; d.Hs = geo.H; d.Ws = geo.W;
+        d.Hi = Hi; d.Wi = Wi; d.Ho = Ho; d.Wo = Wo; d.stride = stride; d.pad = pad;
+        d.cout = w.cout; d.out = out.p; d.bias = w.b;
+        d.rowbias = o.rowbias; d.rb_ld = o.rb_ld < 0 ? w.cout : o.rb_ld; d.rows_per_sample = o.rows_per_sample; d.resid = o.resid;
+        if (const int wm = c->conv_wino_tile(w.cin, w.cout, stride, pad, Hi, Wi, Ho, Wo)) {
             c->conv_form(w, wm == 4 ? e2v_ctx::FORM_WINO4 : e2v_ctx::FORM_WINO2, s);
-            a.U = wm == 4 ? w.wino4 : w.wino; a.N = w.cout; a.out = out.p; a.ldc = w.cout; a.bias = w.b;
-            if (c->x3_compute) a.U3 = wm == 4 ? w.wino4_x3 : w.wino_x3;
-            a.rowbias = rowbias; a.rb_ld = rb_ld; a.rows_per_sample = rows_per_sample; a.resid = resid; a.ldr = w.cout;
-            const int chunk = wino_chunk_images(a, c->wino_ws_floats);
-            const size_t need = wino_workspace_floats(a, chunk);
-            Act ws(pool(), (int64_t)((need + 1023) / 1024), 1024);
-            wino_conv3x3(a, ws.p, chunk, s);
+            const void* U3 = !c->x3_compute ? nullptr : wm == 4 ? w.wino4_x3 : w.wino_x3;
+            conv3_wino(c, d, wm, wm == 4 ? w.wino4 : w.wino, U3, c->gn_scale, o.gn_P, s);
             return out;
         }
-        E2V_REQUIRE(gn_P == 0, E2V_EINVAL, "conv: fused GroupNorm needs the Winograd path");
-        IgemmArgs g;
-        g.a0 = x0; g.c0 = c0; g.lda0 = c0; g.a1 = x1; g.c1 = c1; g.lda1 = c1;
+        E2V_REQUIRE(o.gn_P == 0, E2V_EINVAL, "conv: fused GroupNorm needs the Winograd path");
         E2V_REQUIRE(c1 == 0 || c0 % 32 == 0, E2V_ESHAPE, "conv: the concat seam must be a multiple of 32 channels");
-        g.ldw = w.ldw; g.ldw16 = w.ldw16; g.out = out.p; g.ldc = w.cout; g.bias = w.b;
-        g.rowbias = rowbias; g.rb_ld = rb_ld; g.rows_per_sample = rows_per_sample;
-        g.resid = resid; g.ldr = w.cout;
-        g.M = (int)out.rows; g.N = w.cout; g.taps = 9;
-        if (bf()) { g.a_bf16 = h16(); g.out_f32 = out_f32 ? 1 : 0; g.resid_bf16 = resid ? 1 : 0; }
-        g.Ho = Ho; g.Wo = Wo; g.Hi = Hi; g.Wi = Wi; g.Hs = geo.H; g.Ws = geo.W; g.stride = stride; g.pad = pad;
-        if (Hi != geo.H || Wi != geo.W) {
-            g.upsample = 1;
-            g.ups_h = (float)geo.H / (float)Hi;        // torch: scale = (float)input_size / output_size
-            g.ups_w = (float)geo.W / (float)Wi;
-        }
+        IgemmArgs g = conv3_igemm(d);
+        g.ldw = w.ldw; g.ldw16 = w.ldw16;
+        if (bf()) { g.a_bf16 = h16(); g.out_f32 = o.out_f32 ? 1 : 0; g.resid_bf16 = o.resid ? 1 : 0; }
         // (small-batch family: the four parity launches of a small layer are a handful of 256-row tiles each -- 131 us per launch
         // measured at B = 1 on the 9x16 -> 18x32 conv -- while the gather form takes split-K: the sub-pixel form needs >= 128 tiles)
-        const bool up2x_small = c->small_family && (long)((out.rows / 4 + 255) / 256) * ((w.cout + 319) / 320) < 128;
+        const bool up2x_small = small_family && (long)((out.rows / 4 + 255) / 256) * ((w.cout + 319) / 320) < 128;
         if (bf() && c0 == w.cin && !up2x_small && bgemm_up2x_applies(g)) {       // exact 2x resize (Upsample3D): four 2x2 convs on the source map
             c->conv_form(w, fp16() ? e2v_ctx::FORM_F16_UP2 : e2v_ctx::FORM_BF16_UP2, s);
             bgemm_up2x_launch(g, fp16() ? w.w16h_up2 : w.w16_up2, s);
@@ -726,7 +737,7 @@ struct Runner {
         static const int* const rb_on = E2V_AB_KNOB("E2V_GN_RB", 0);
         static const int* const rb_epi = E2V_AB_KNOB("E2V_GN_RB_EPILOGUE", 1);
         bool epilogue_sums = false;
-        if (*rb_on && want_rb && h16() == H16_BF16 && !out_f32 && rbsum_capable(out.rows, w.cout)) {
+        if (*rb_on && o.want_rb && h16() == H16_BF16 && !o.out_f32 && rbsum_capable(out.rows, w.cout)) {
             out.rb = pool().get((size_t)(out.rows / 64) * w.cout * 2);
             if (*rb_epi) { g.rbsum = out.rb; epilogue_sums = igemm_writes_rbsum(g); if (!epilogue_sums) g.rbsum = nullptr; }
         }
@@ -739,48 +750,54 @@ struct Runner {
 
     // ResnetBlock3D.forward (resnet.py:174-204); x1 = skip tensor concatenated on channels (may be null).
     // samples x P rows share GroupNorm statistics and one time-embedding row; geo describes the frames.
-    // rb0 / rb1: row-block sums of x0 / x1 (Act::rb of the tensors; null: none).  The output carries its own when P allows.
+    // The output carries its own row-block sums when P allows.
     Act resnet(const ResW& w, const float* x0, int c0, const float* x1, int c1, int samples, int P, Geo geo, int groups,
-               float eps, const float* temb_silu, int temb_dim, const float* rb0 = nullptr, const float* rb1 = nullptr) {
+               float eps, const ResOpt& o = {}) {
         const bool rbw = bf() && P % 64 == 0;            // the GroupNorms that read conv1's / this block's output can use the sums
         E2V_REQUIRE(c0 + c1 == w.cin, E2V_ESHAPE, "resnet: channel mismatch");
+        auto wino = [&](const ConvW& cw) { return c->conv_wino_tile(cw.cin, cw.cout, 1, 1, geo.H, geo.W, geo.H, geo.W) != 0; };
         Act tp;
-        const float* tpp = nullptr;
-        int tp_ld = w.cout;
+        ConvOpt o1, o2;                                  // conv1 adds the time-embedding row of its sample, conv2 the shortcut
+        o1.rows_per_sample = P;
         if (w.temb.w) {
             if (c->step_cache_on) {      // e2v_generate: time_emb_proj(SiLU(emb(t))) of every step was computed up front; one row
-                tpp = c->temb_cache[res_idx++].p + (size_t)c->step_cache_step * w.cout;    // serves all samples (stride 0)
-                tp_ld = 0;
+                o1.rowbias = c->temb_cache[res_idx++].p + (size_t)c->step_cache_step * w.cout;    // serves all samples (stride 0)
+                o1.rb_ld = 0;
             } else {
-                E2V_REQUIRE(temb_silu != nullptr, E2V_EINVAL, "resnet needs a time embedding");
-                tp = linear(w.temb, temb_silu, temb_dim, samples, nullptr, 0, false, nullptr, 0, 0, true);   // :183 (fp32 rows)
-                tpp = tp.p;
+                E2V_REQUIRE(o.temb_silu != nullptr, E2V_EINVAL, "resnet needs a time embedding");
+                tp = linear(w.temb, o.temb_silu, o.temb_dim, samples, f32_rows());                          // :183 (fp32 rows)
+                o1.rowbias = tp.p;
             }
         }
         Act h1;
-        if (winograd(w.c1, 1, 1, geo.H, geo.W, geo.H, geo.W)) {        // GroupNorm + SiLU applied inside the conv's input transform
+        if (wino(w.c1)) {                        // GroupNorm + SiLU applied inside the conv's input transform
             gn_stats(w.n1, x0, c0, x1, c1, samples, P, groups, eps);                                  // :177-178
-            h1 = conv3(w.c1, x0, c0, x1, c1, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, tpp, P, nullptr, P, tp_ld);   // :180,186
+            o1.gn_P = P;
+            h1 = conv3(w.c1, x0, c0, x1, c1, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, o1);              // :180,186
         } else {
-            Act hn = gn(w.n1, x0, c0, x1, c1, samples, P, groups, eps, true, rb0, rb1);              // :177-178
-            h1 = conv3(w.c1, hn.p, w.cin, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1,          // :180,186
-                       tpp, P, nullptr, 0, tp_ld, false, rbw);
+            Act hn = gn(w.n1, x0, c0, x1, c1, samples, P, groups, eps, true, o.rb0, o.rb1);          // :177-178
+            o1.want_rb = rbw;
+            h1 = conv3(w.c1, hn.p, w.cin, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, o1);     // :180,186
         }
         Act sc;
-        const float* resid = x0;
+        o2.resid = x0;
         if (w.sc.w) {                                                                                 // :199-200
-            sc = linear(w.sc, x0, c0, (int64_t)samples * P, nullptr, 0, false, x1, c1, c1);
-            resid = sc.p;
+            LinOpt cat;
+            cat.a1 = x1; cat.c1 = c1; cat.lda1 = c1;
+            sc = linear(w.sc, x0, c0, (int64_t)samples * P, cat);
+            o2.resid = sc.p;
         } else {
             E2V_REQUIRE(c1 == 0, E2V_ESHAPE, "identity shortcut with a concatenated input");
         }
-        if (winograd(w.c2, 1, 1, geo.H, geo.W, geo.H, geo.W)) {
+        if (wino(w.c2)) {
             gn_stats(w.n2, h1.p, w.cout, nullptr, 0, samples, P, groups, eps);                        // :188,194
-            return conv3(w.c2, h1.p, w.cout, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, nullptr, 1, resid, P);   // :197,202
+            o2.gn_P = P;
+            return conv3(w.c2, h1.p, w.cout, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, o2);  // :197,202
         }
         Act h2 = gn(w.n2, h1.p, w.cout, nullptr, 0, samples, P, groups, eps, true, h1.rb);           // :188,194
         h1.reset();
-        return conv3(w.c2, h2.p, w.cout, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, nullptr, 1, resid, 0, -1, false, rbw);   // :197,202
+        o2.want_rb = rbw;
+        return conv3(w.c2, h2.p, w.cout, nullptr, 0, geo, geo.H, geo.W, geo.H, geo.W, 1, 1, o2);      // :197,202
     }
 
     // Transformer3DModel.forward + BasicTransformerBlock.forward (attention.py:89-136, 232-269)
@@ -824,7 +841,7 @@ struct Runner {
             a.x3 = c->x3_compute ? 1 : 0;
             flash_attention(a, s);
             qkv.reset();
-            t = linear(w.a1_out, ao.p, C, rows1, t.p, C);
+            t = linear(w.a1_out, ao.p, C, rows1, residual(t.p, C));
         }
         Act x2;
         if (n_shared > 0) {                          // from here on the two halves see different conditioning
@@ -848,13 +865,15 @@ struct Runner {
             a.io_bf16 = io16;
             a.x3 = c->x3_compute ? 1 : 0;
             flash_attention(a, s);
-            t = linear(w.a2_out, ao.p, C, rows, t.p, C);
+            t = linear(w.a2_out, ao.p, C, rows, residual(t.p, C));
         }
         {   // GEGLU feed-forward                                                                          :258
             Act nrm = ln(w.ln3, t);
-            Act hgate = linear(w.ff1, nrm.p, C, rows, nullptr, 0, true);
+            LinOpt gated;
+            gated.geglu = true;
+            Act hgate = linear(w.ff1, nrm.p, C, rows, gated);
             nrm.reset();
-            t = linear(w.ff2, hgate.p, 4 * C, rows, t.p, C);
+            t = linear(w.ff2, hgate.p, 4 * C, rows, residual(t.p, C));
         }
         {   // temporal attention over the F frames of each pixel                                         :261-267
             Act nrm = ln(w.lnt, t);
@@ -863,9 +882,9 @@ struct Runner {
             Act ao = new_act(rows, C);
             temporal_attention(qkv.p, 3 * C, ao.p, C, n, F, HW, heads, D, scale, s, io16);
             qkv.reset();
-            t = linear(w.at_out, ao.p, C, rows, t.p, C);
+            t = linear(w.at_out, ao.p, C, rows, residual(t.p, C));
         }
-        return linear(w.proj_out, t.p, C, rows, xp->p, C);                                            // :123,130
+        return linear(w.proj_out, t.p, C, rows, residual(xp->p, C));                                           // :123,130
     }
 
     // AttentionBlock of the VAE mid block (diffusers 0.11.1): one head over H*W tokens, per image.  The scores and the softmax
@@ -903,7 +922,22 @@ struct Runner {
             if (bf()) { g.a_bf16 = h16(); g.w16 = vt.p; g.ldw16 = HW; }
             igemm(g, s);
         }
-        return linear(w.proj, o.p, C, rows, x.p, C);
+        return linear(w.proj, o.p, C, rows, residual(x.p, C));
+    }
+
+    // time embedding (unet.py:324-345) of the n_t timesteps in c->d_timesteps, `rows` rows: sinusoid -> linear_1 -> SiLU -> linear_2
+    // -> SiLU (resnets consume SiLU(emb)); fp32 rows in both modes.  tap(emb) sees linear_2's output (unet.py:345).
+    template <class Tap>
+    Act time_embedding(int n_t, int rows, int t_is_f32, Tap&& tap) {
+        const int boc0 = c->cfg.block_out_channels[0], temb_dim = boc0 * 4;
+        Act sin(pool(), rows, boc0);
+        timestep_sinusoid(c->d_timesteps, n_t, sin.p, rows, boc0, c->cfg.flip_sin_to_cos, c->cfg.freq_shift, s, t_is_f32);
+        Act e1 = linear(c->unet.te1, sin.p, boc0, rows, f32_rows());
+        silu(e1.p, e1.p, (long long)rows * temb_dim, s);
+        Act emb = linear(c->unet.te2, e1.p, temb_dim, rows, f32_rows());
+        tap(emb);
+        silu(emb.p, emb.p, (long long)rows * temb_dim, s);
+        return emb;
     }
 };
 
@@ -922,9 +956,7 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
     // conditioning -- conv_in, the first resnet, the first transformer block up to its cross-attention -- is computed once
     E2V_REQUIRE(!cfg_pair || (N % 2 == 0 && n_t == 1 && !unet.down[0].attn.empty()), E2V_EINVAL, "cfg_pair needs an even batch, one timestep and a first block with attention");
     const int N1 = cfg_pair ? N / 2 : N;
-    static const int* const fam_clips = knob("E2V_SMALL_FAMILY_CLIPS", 4);      // (where the boundary lies was an A/B; 0: the large family at every batch -- the parity tests hold BOTH families to the oracle with one clip)
-    small_family = N <= 2 * *fam_clips;                       // B <= 4 clips with their guidance pairs (model.h)
-    Runner R{this, s};
+    Runner R{this, s, unet_small_family(N)};                  // B <= 4 clips with their guidance pairs (model.h)
     const int groups = cfg.norm_num_groups;
     // heads of the blocks of resolution level l (unet.py:110-111,131,151,165,194: down block l, the mid block = level 3, up block 3 - l)
     auto heads_at = [&](int l) { return cfg.attention_heads_per_block[l] > 0 ? cfg.attention_heads_per_block[l] : cfg.attention_heads; };
@@ -948,27 +980,13 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
         for (int i = 0; i < 5; ++i) t.shapes[t.count][i] = shp[i];
         t.used += count; ++t.count;
     };
-    // time embedding (unet.py:324-345): sinusoid -> linear_1 -> SiLU -> linear_2; resnets consume SiLU(emb)
-    if (d_timesteps_cap < N) {
-        E2V_HIP(hipStreamSynchronize(s));
-        if (d_timesteps) (void)hipFree(d_timesteps);
-        E2V_HIP(hipMalloc((void**)&d_timesteps, sizeof(long long) * N));
-        d_timesteps_cap = N;
-    }
+    grow_timesteps(N, s);
     static_assert(sizeof(long long) == sizeof(int64_t), "int64");
     if (host_tf) E2V_HIP(hipMemcpyAsync(d_timesteps, host_tf, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
     else E2V_HIP(hipMemcpyAsync(d_timesteps, host_t, sizeof(int64_t) * n_t, hipMemcpyHostToDevice, s));
     Act temb_silu;
-    if (!step_cache_on) {
-        Act sin(pool, N, boc0);
-        timestep_sinusoid(d_timesteps, n_t, sin.p, N, boc0, cfg.flip_sin_to_cos, cfg.freq_shift, s, host_tf ? 1 : 0);
-        Act e1 = R.linear(unet.te1, sin.p, boc0, N, nullptr, 0, false, nullptr, 0, 0, true);        // fp32 rows in both modes
-        silu(e1.p, e1.p, (long long)N * temb_dim, s);
-        Act emb = R.linear(unet.te2, e1.p, temb_dim, N, nullptr, 0, false, nullptr, 0, 0, true);
-        if (tap_sink) tap(emb, N, temb_dim, 1, 1, 1);                                              // taps["emb"] (unet.py:345)
-        silu(emb.p, emb.p, (long long)N * temb_dim, s);
-        temb_silu = std::move(emb);
-    }
+    if (!step_cache_on)
+        temb_silu = R.time_embedding(n_t, N, host_tf ? 1 : 0, [&](const Act& emb) { if (tap_sink) tap(emb, N, temb_dim, 1, 1, 1); });   // taps["emb"]
     // bf16-activation mode: the two fp32 boundary tensors are converted once -- the latents (zero-padded to 8 channels, the
     // 16-byte granule of the bf16 kernels) and, when no per-run cache holds to_k / to_v already, the conditioning
     Act sample16, cond16;
@@ -991,6 +1009,9 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
     skips.reserve(16);
     auto P_of = [&](int l) { return F * hs[l] * ws[l]; };
     auto geo_of = [&](int l) { return Geo{N * F, hs[l], ws[l]}; };
+    ResOpt ro;                                                                      // every resnet: SiLU(emb) ...
+    ro.temb_silu = temb_silu.p; ro.temb_dim = temb_dim;
+    auto res_opt = [&](const float* rb0, const float* rb1 = nullptr) { ResOpt o = ro; o.rb0 = rb0; o.rb1 = rb1; return o; };   // ... + the sources' row-block sums
 
     Act x = R.conv3(unet.conv_in, sample_cl, cin_act, nullptr, 0, Geo{N1 * F, hs[0], ws[0]}, H, W, H, W, 1, 1);   // :358
     Act x_shared;                                     // cfg_pair: the N / 2-sample conv_in output feeding the first resnet
@@ -1007,27 +1028,27 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
         for (size_t j = 0; j < b.res.size(); ++j) {
             Act h;
             if (cfg_pair && i == 0 && j == 0) {      // shared prefix: N / 2 samples through the resnet and up to attn2
-                h = R.resnet(b.res[j], x_shared.p, x_shared.C, nullptr, 0, N1, P_of(i), Geo{N1 * F, hs[0], ws[0]}, groups, eps,
-                             temb_silu.p, temb_dim);
+                h = R.resnet(b.res[j], x_shared.p, x_shared.C, nullptr, 0, N1, P_of(i), Geo{N1 * F, hs[0], ws[0]}, groups, eps, ro);
                 x_shared.reset();
                 h = R.transformer(b.attn[j], h, N, F, hs[i] * ws[i], cond, T, heads_at(i), groups, N1);
             } else {
-                h = R.resnet(b.res[j], cur->p, cur->C, nullptr, 0, N, P_of(i), geo_of(i), groups, eps, temb_silu.p, temb_dim, cur->rb);
+                h = R.resnet(b.res[j], cur->p, cur->C, nullptr, 0, N, P_of(i), geo_of(i), groups, eps, res_opt(cur->rb));
                 if (!b.attn.empty()) h = R.transformer(b.attn[j], h, N, F, hs[i] * ws[i], cond, T, heads_at(i), groups);
             }
             cur = &keep(std::move(h), i);
         }
         if (b.resample) {                                                                            // resnet.py:99-107
-            Act d = R.conv3(b.rs, cur->p, cur->C, nullptr, 0, geo_of(i), hs[i], ws[i], hs[i + 1], ws[i + 1], 2, 1, nullptr, 1, nullptr, 0, -1, false,
-                            R.bf() && P_of(i + 1) % 64 == 0);          // (the next level's first GroupNorm and, as a skip, a later one read it)
+            ConvOpt o;
+            o.want_rb = R.bf() && P_of(i + 1) % 64 == 0;               // (the next level's first GroupNorm and, as a skip, a later one read it)
+            Act d = R.conv3(b.rs, cur->p, cur->C, nullptr, 0, geo_of(i), hs[i], ws[i], hs[i + 1], ws[i + 1], 2, 1, o);
             cur = &keep(std::move(d), i + 1);
         }
         if (tap_sink) { const int l = b.resample ? i + 1 : i; tap(*cur, N, cfg.block_out_channels[i], F, hs[l], ws[l]); }       // taps["down{i}"]
     }
     // mid (unet_blocks.py:199-205)
-    Act h = R.resnet(unet.mid_r0, cur->p, cur->C, nullptr, 0, N, P_of(3), geo_of(3), groups, eps, temb_silu.p, temb_dim, cur->rb);
+    Act h = R.resnet(unet.mid_r0, cur->p, cur->C, nullptr, 0, N, P_of(3), geo_of(3), groups, eps, res_opt(cur->rb));
     h = R.transformer(unet.mid_attn, h, N, F, hs[3] * ws[3], cond, T, heads_at(3), groups);
-    h = R.resnet(unet.mid_r1, h.p, h.C, nullptr, 0, N, P_of(3), geo_of(3), groups, eps, temb_silu.p, temb_dim, h.rb);
+    h = R.resnet(unet.mid_r1, h.p, h.C, nullptr, 0, N, P_of(3), geo_of(3), groups, eps, res_opt(h.rb));
     if (tap_sink) tap(h, N, cfg.block_out_channels[3], F, hs[3], ws[3]);                               // taps["mid"]
     // up (unet.py:381-404)
     for (int i = 0; i < 4; ++i) {
@@ -1037,7 +1058,7 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
             E2V_REQUIRE(!skips.empty() && skips.back().lvl == lvl, E2V_ESTATE, "skip bookkeeping out of step");
             Skip sk = std::move(skips.back());                                                       // unet_blocks.py:485-487
             skips.pop_back();
-            Act o = R.resnet(b.res[j], h.p, h.C, sk.a.p, sk.a.C, N, P_of(lvl), geo_of(lvl), groups, eps, temb_silu.p, temb_dim, h.rb, sk.a.rb);
+            Act o = R.resnet(b.res[j], h.p, h.C, sk.a.p, sk.a.C, N, P_of(lvl), geo_of(lvl), groups, eps, res_opt(h.rb, sk.a.rb));
             if (!b.attn.empty()) o = R.transformer(b.attn[j], o, N, F, hs[lvl] * ws[lvl], cond, T, heads_at(lvl), groups);
             h = std::move(o);
         }
@@ -1048,7 +1069,9 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
     }
     Act hn = R.gn(unet.norm_out, h.p, h.C, nullptr, 0, N, P_of(0), groups, eps, true, h.rb);           // :406-407
     h.reset();
-    Act out = R.conv3(unet.conv_out, hn.p, hn.C, nullptr, 0, geo_of(0), H, W, H, W, 1, 1, nullptr, 1, nullptr, 0, -1, true);   // :408 (eps: fp32)
+    ConvOpt f32_out;
+    f32_out.out_f32 = true;                                                                            // eps: fp32
+    Act out = R.conv3(unet.conv_out, hn.p, hn.C, nullptr, 0, geo_of(0), H, W, H, W, 1, 1, f32_out);   // :408
     E2V_HIP(hipGetLastError());
     return out;
 }
@@ -1057,31 +1080,21 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
 // run"): the time-embedding MLP and every resnet's time_emb_proj for all timesteps (one GEMM of `steps` rows per resnet
 // instead of `steps` GEMMs of N identical rows), and to_k / to_v of the conditioning of every cross-attention.  Row-wise
 // the arithmetic is the uncached one, so results are bit-identical.
-void e2v_ctx::build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, hipStream_t s) {
-    Runner R{this, s};
+void e2v_ctx::build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s) {
+    Runner R{this, s, small_family};
     temb_cache.clear();
     kv_cache.clear();
-    const int boc0 = cfg.block_out_channels[0], temb_dim = boc0 * 4;
-    if (d_timesteps_cap < steps) {
-        E2V_HIP(hipStreamSynchronize(s));
-        if (d_timesteps) (void)hipFree(d_timesteps);
-        E2V_HIP(hipMalloc((void**)&d_timesteps, sizeof(long long) * steps));
-        d_timesteps_cap = steps;
-    }
+    const int temb_dim = cfg.block_out_channels[0] * 4;
+    grow_timesteps(steps, s);
     E2V_HIP(hipMemcpyAsync(d_timesteps, ts, sizeof(int64_t) * steps, hipMemcpyHostToDevice, s));
-    Act sin(pool, steps, boc0);
-    timestep_sinusoid(d_timesteps, steps, sin.p, steps, boc0, cfg.flip_sin_to_cos, cfg.freq_shift, s);
-    Act e1 = R.linear(unet.te1, sin.p, boc0, steps, nullptr, 0, false, nullptr, 0, 0, true);
-    silu(e1.p, e1.p, (long long)steps * temb_dim, s);
-    Act emb = R.linear(unet.te2, e1.p, temb_dim, steps, nullptr, 0, false, nullptr, 0, 0, true);
-    silu(emb.p, emb.p, (long long)steps * temb_dim, s);
+    Act emb = R.time_embedding(steps, steps, 0, [](const Act&) {});
     Act cond16;
     if (R.bf()) {
         cond16 = R.to_act16(cond, cfg.cross_attention_dim, cfg.cross_attention_dim, (int64_t)N * T);
         cond = cond16.p;
     }
     auto add_res = [&](const ResW& r) {
-        if (r.temb.w) temb_cache.push_back(R.linear(r.temb, emb.p, temb_dim, steps, nullptr, 0, false, nullptr, 0, 0, true));
+        if (r.temb.w) temb_cache.push_back(R.linear(r.temb, emb.p, temb_dim, steps, R.f32_rows()));
     };
     auto add_tr = [&](const TransW& w) { kv_cache.push_back(R.linear(w.a2_kv, cond, w.a2_kv.in, (int64_t)N * T)); };
     for (const auto& b : unet.down) { for (const auto& r : b.res) add_res(r); for (const auto& a : b.attn) add_tr(a); }
@@ -1094,8 +1107,7 @@ void e2v_ctx::build_step_caches(const int64_t* ts, int steps, const float* cond,
 // -----------------------------------------------------------------------------------------------------
 void e2v_ctx::vae_decode_frames(const float* z_cl, int nf, int h, int w, float* out_cl, hipStream_t s, bool small) {
     E2V_REQUIRE(vae_ready, E2V_ESTATE, "VAE weights are not finalized");
-    small_family = small;                                     // the CALL decodes at most four clips (the caller knows: a pass may be a call's ragged last group)
-    Runner R{this, s};
+    Runner R{this, s, small};                                 // the CALL decodes at most four clips (the caller knows: a pass may be a call's ragged last group)
     const int g = cfg.vae_norm_num_groups;
     const float eps = cfg.vae_norm_eps;
     const int lat = cfg.vae_latent_channels;
@@ -1115,12 +1127,12 @@ void e2v_ctx::vae_decode_frames(const float* z_cl, int nf, int h, int w, float* 
         x = std::move(xp);
     }
     x = R.conv3(vae.dec_in, x.p, x.C, nullptr, 0, Geo{nf, H, W}, H, W, H, W, 1, 1);
-    x = R.resnet(vae.dec_mid0, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps, nullptr, 0);
+    x = R.resnet(vae.dec_mid0, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps);
     x = R.vae_attention(vae.dec_attn, x, nf, H * W, g, eps);
-    x = R.resnet(vae.dec_mid1, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps, nullptr, 0);
+    x = R.resnet(vae.dec_mid1, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps);
     for (size_t i = 0; i < vae.dec_up.size(); ++i) {
         const VAEW::Block& b = vae.dec_up[i];
-        for (const ResW& r : b.res) x = R.resnet(r, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps, nullptr, 0);
+        for (const ResW& r : b.res) x = R.resnet(r, x.p, x.C, nullptr, 0, nf, H * W, Geo{nf, H, W}, g, eps);
         if (b.resample) {        // F.interpolate(scale_factor=2, nearest) + 3x3 conv
             x = R.conv3(b.rs, x.p, x.C, nullptr, 0, Geo{nf, H, W}, 2 * H, 2 * W, 2 * H, 2 * W, 1, 1);
             H *= 2; W *= 2;
@@ -1128,15 +1140,16 @@ void e2v_ctx::vae_decode_frames(const float* z_cl, int nf, int h, int w, float* 
     }
     Act hn = R.gn(vae.dec_norm_out, x.p, x.C, nullptr, 0, nf, H * W, g, eps, true);
     x.reset();
-    Act y = R.conv3(vae.dec_out, hn.p, hn.C, nullptr, 0, Geo{nf, H, W}, H, W, H, W, 1, 1, nullptr, 1, nullptr, 0, -1, true);   // frames: fp32
+    ConvOpt f32_out;
+    f32_out.out_f32 = true;                                                                            // frames: fp32
+    Act y = R.conv3(vae.dec_out, hn.p, hn.C, nullptr, 0, Geo{nf, H, W}, H, W, H, W, 1, 1, f32_out);
     E2V_HIP(hipMemcpyAsync(out_cl, y.p, (size_t)y.rows * y.C * sizeof(float), hipMemcpyDeviceToDevice, s));
     E2V_HIP(hipGetLastError());
 }
 
 void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, float* moments_cl, hipStream_t s) {
     E2V_REQUIRE(vae_ready, E2V_ESTATE, "VAE weights are not finalized");
-    small_family = n <= 12;
-    Runner R{this, s};
+    Runner R{this, s, n <= 12};                               // frames, whatever E2V_SMALL_FAMILY_CLIPS says (ADVICE.md finding 2 would derive it from the knob)
     const int g = cfg.vae_norm_num_groups;
     const float eps = cfg.vae_norm_eps;
     int H = H0, W = W0;
@@ -1150,20 +1163,22 @@ void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, flo
     Act x = R.conv3(vae.enc_in, img_cl4, ic, nullptr, 0, Geo{n, H, W}, H, W, H, W, 1, 1);
     for (size_t i = 0; i < vae.enc_down.size(); ++i) {
         const VAEW::Block& b = vae.enc_down[i];
-        for (const ResW& r : b.res) x = R.resnet(r, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps, nullptr, 0);
+        for (const ResW& r : b.res) x = R.resnet(r, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps);
         if (b.resample) {        // F.pad(x, (0,1,0,1)) then 3x3 stride-2 conv without padding
             const int Ho = (H + 1 - 3) / 2 + 1, Wo = (W + 1 - 3) / 2 + 1;
             x = R.conv3(b.rs, x.p, x.C, nullptr, 0, Geo{n, H, W}, H, W, Ho, Wo, 2, 0);
             H = Ho; W = Wo;
         }
     }
-    x = R.resnet(vae.enc_mid0, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps, nullptr, 0);
+    x = R.resnet(vae.enc_mid0, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps);
     x = R.vae_attention(vae.enc_attn, x, n, H * W, g, eps);
-    x = R.resnet(vae.enc_mid1, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps, nullptr, 0);
+    x = R.resnet(vae.enc_mid1, x.p, x.C, nullptr, 0, n, H * W, Geo{n, H, W}, g, eps);
     Act hn = R.gn(vae.enc_norm_out, x.p, x.C, nullptr, 0, n, H * W, g, eps, true);
     x.reset();
     Act y = R.conv3(vae.enc_out, hn.p, hn.C, nullptr, 0, Geo{n, H, W}, H, W, H, W, 1, 1);
-    Act m = R.linear(vae.quant, y.p, y.C, y.rows, nullptr, 0, false, nullptr, 0, 0, false, true);          // moments: fp32
+    LinOpt f32_out;
+    f32_out.out_f32 = true;                                                                            // moments: fp32
+    Act m = R.linear(vae.quant, y.p, y.C, y.rows, f32_out);
     E2V_HIP(hipMemcpyAsync(moments_cl, m.p, (size_t)m.rows * m.C * sizeof(float), hipMemcpyDeviceToDevice, s));
     E2V_HIP(hipGetLastError());
 }

@@ -27,7 +27,6 @@ struct ConvW {
     int cin = 0, cin_pad = 0, cout = 0;
     int ldw = 0, ldw16 = 0;                      // row lengths of the fp32 (32-channel chunks) / bf16 (64-channel chunks) packed forms
     int cin_pad16 = 0;                           // channels of the bf16 input: cin rounded up to 8
-    bool stride1 = true;                         // a Winograd form exists (stride-1 conv, channel counts multiples of 4)
     int part = 0;                                // 0 UNet, 1 VAE: which finalize() group owns the lazily built forms
     mutable const float* w = nullptr;            // [O][chunk32][tap][32]
     mutable const void* w16 = nullptr;           // [O][chunk64][tap][64] bf16
@@ -91,6 +90,39 @@ struct VAEW {
     NormW enc_norm_out;
 };
 
+// The SMALL-BATCH dispatch family (16-bit modes), decided ONCE per API call and handed to the graph runner by value: the call runs at
+// most 8 UNet samples (B <= 4 clips with their guidance pairs: the reference's clip-by-clip loop, inference_eeg2video.py:90-100, and
+// a caller that batches a few clips; the boundary was measured -- B = 3 / 4 gain 7 / 4 %, B = 5 / 6 / 8 2.4 / 1.7 / 0.5 %:
+// profiles/r05_family_boundary.json).  Launches that would leave most of the chip idle then take split-K (kernels.h: IgemmArgs::sk)
+// -- another summation order, so bit-identity across batch sizes holds WITHIN a family (B >= 5: every kernel choice is a
+// bit-identical alternative; B <= 4: held to the oracle bounds).
+int small_family_clips();      // the boundary E2V_SMALL_FAMILY_CLIPS, read live (an A/B; 0: the large family at every batch -- the parity tests hold BOTH families to the oracle with one clip)
+inline bool unet_small_family(int N) { return N <= 2 * small_family_clips(); }   // in SAMPLES (ADVICE.md finding 3 would count clips)
+
+// One 3x3 conv launch as the graph runner (Runner::conv3) and e2v_op_conv3x3 both describe it; the packed weight and the
+// arithmetic-mode flags stay with the caller
+struct Conv3 {
+    const float* x0 = nullptr; int c0 = 0;       // channel-last sources (row stride = channels); x1: the concatenated skip
+    const float* x1 = nullptr; int c1 = 0;
+    int nimg = 0, Hs = 1, Ws = 1;                // images and their physical source map
+    int Hi = 1, Wi = 1, Ho = 1, Wo = 1;          // logical input (after nearest resize) and output maps
+    int stride = 1, pad = 0;
+    int cout = 0; float* out = nullptr; const float* bias = nullptr;
+    const float* rowbias = nullptr; int rb_ld = 0, rows_per_sample = 1;
+    const float* resid = nullptr;
+    int resized() const { return (Hi != Hs || Wi != Ws) ? 1 : 0; }      // nearest resize in front of the conv (Upsample3D)
+    float ups_h() const { return (float)Hs / (float)Hi; }               // torch: scale = (float)input_size / output_size
+    float ups_w() const { return (float)Ws / (float)Wi; }
+};
+IgemmArgs conv3_igemm(const Conv3& d);          // the geometry part of the direct form's arguments
+// the Winograd form F(m x m, 3x3), workspace sizing and chunking included (U3: the f32x3 planes of U or null; gn_P > 0:
+// GroupNorm's affine + SiLU from gn_scsh, slabs of gn_P rows, applied on the way in)
+void conv3_wino(e2v_ctx* c, const Conv3& d, int m, const float* U, const void* U3, const float* gn_scsh, int gn_P, hipStream_t s);
+// rows [value 0..half) | gate 0..half)] of w [2 half][in] and b [2 half] -> per 64: [32 value | 32 gate] (the GEGLU epilogue's layout)
+void geglu_interleave(const float* w, const float* b, int half, int in, float* dw, float* db, hipStream_t s);
+// ask for `want` split-K runs of launch g: where it is eligible the workspace is attached and returned (alive until the launch is queued)
+Act splitk_attach(Pool& pool, IgemmArgs& g, int want);
+
 }  // namespace e2v
 
 struct e2v_ctx {
@@ -115,12 +147,6 @@ struct e2v_ctx {
     bool bf16_compute = false;                                   // e2v_set_compute_dtype: a 16-bit activation mode (16-bit MFMA, 16-bit rows in HBM) ...
     int h16_mode = 0;                                            // ... and which: 0 none, 1 bf16 (E2V_BF16), 2 fp16 (E2V_F16) -- the flag every 16-bit launch carries (h16.h)
     void set_h16_mode(int m) { h16_mode = m; bf16_compute = m != 0; }
-    // The SMALL-BATCH dispatch family (16-bit modes): set per call when the graph runs at most 8 UNet samples (B <= 4 clips with their
-    // guidance pairs: the reference's clip-by-clip loop, inference_eeg2video.py:90-100, and a caller that batches a few clips; the boundary
-    // was measured -- B = 3 / 4 gain 7 / 4 %, B = 5 / 6 / 8 2.4 / 1.7 / 0.5 %: profiles/r05_family_boundary.json).  Launches that would leave most of the chip idle
-    // then take split-K (kernels.h: IgemmArgs::sk) -- another summation order, so bit-identity across batch sizes holds WITHIN a family
-    // (B >= 5: every kernel choice is a bit-identical alternative; B <= 4: held to the oracle bounds).
-    bool small_family = false;
     std::vector<e2v::LinW> sem;                                  // semantic predictor layers (first one K-padded to 4)
     int sem_in_pad = 0;
     std::vector<float> alphas;                                   // host alpha-bar table
@@ -131,7 +157,8 @@ struct e2v_ctx {
     // ([steps][cout] each, call order) and to_k / to_v of the conditioning of every transformer ([N*T][2C] each)
     bool step_cache_on = false; int step_cache_step = 0;
     std::vector<e2v::Act> temb_cache, kv_cache;
-    void build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, hipStream_t s);
+    void grow_timesteps(int n, hipStream_t s);                   // d_timesteps holds at least n entries
+    void build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s);
 
     // stream of the previous call (workspace reuse is stream-ordered): see enter_stream
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
@@ -145,13 +172,19 @@ struct e2v_ctx {
     struct TapSink { float* buf = nullptr; int64_t cap = 0, used = 0; int count = 0; int64_t shapes[16][5]; };
     TapSink* tap_sink = nullptr;
     int alloc_part = -1;                                         // >= 0: dev_alloc files the block under owned_part[alloc_part]
+    struct AllocPart {                                           // dev_alloc files under `part` for the guard's lifetime
+        e2v_ctx* c; int saved;
+        AllocPart(e2v_ctx* ctx, int part) : c(ctx), saved(ctx->alloc_part) { c->alloc_part = part; }
+        ~AllocPart() { c->alloc_part = saved; }
+    };
     void free_part(int part);
 
     float* dev_alloc(size_t floats);
     enum ConvForm { FORM_DIRECT32, FORM_BF16, FORM_WINO2, FORM_WINO4, FORM_BF16_UP2, FORM_F16, FORM_F16_UP2 };
     const void* lin_f16(const e2v::LinW& w, hipStream_t s);              // the fp16 copy of a linear's weight (built on first use)
     void conv_form(const e2v::ConvW& w, ConvForm f, hipStream_t s);     // build the layout if this is its first use
-    bool conv_has_wino(const e2v::ConvW& w, int m) const;               // would the policy allow the F(m x m) form for this layer?
+    // THE Winograd policy: the output tile a 3x3 conv of this shape runs with -- 0 direct, 2 F(2x2,3x3), 4 F(4x4,3x3)
+    int conv_wino_tile(int cin, int cout, int stride, int pad, int Hi, int Wi, int Ho, int Wo) const;
     void expected_keys();
     void finalize(int which);
     // graphs (channel-last in/out); see model.cpp
@@ -159,6 +192,6 @@ struct e2v_ctx {
     // host_tf != null: fractional timesteps (fp32) instead of host_t
     e2v::Act unet_forward_cl(const float* sample_cl, const int64_t* host_t, int n_t, const float* cond, int N, int F,
                              int H, int W, int T, hipStream_t s, bool cfg_pair = false, const float* host_tf = nullptr);
-    void vae_decode_frames(const float* z_cl, int nframes, int h, int w, float* out_cl3, hipStream_t s, bool small_family_call = false);
+    void vae_decode_frames(const float* z_cl, int nframes, int h, int w, float* out_cl3, hipStream_t s, bool small_family);
     void vae_encode_frames(const float* img_cl4, int n, int H, int W, float* moments_cl8, hipStream_t s);
 };

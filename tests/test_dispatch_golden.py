@@ -1,5 +1,5 @@
 """CPU: the dispatch of the SD-v1-4 UNet3D + VAE is pinned.  Which kernel a layer takes depends on M, N, K, taps, the tile count and the
-residual (bgemm256.hip t256_tile_cols, bgemm.hip's launch rules, model.cpp Runner::winograd, attn_q64.hip's rule, norm.hip's chunk rows):
+residual (bgemm256.hip t256_tile_cols, bgemm.hip's launch rules, model.cpp e2v_ctx::conv_wino_tile, attn_q64.hip's rule, norm.hip's chunk rows):
 `e2v_op_describe_dispatch` walks e2v_generate as a dry run on a host-only context and records every launch's kernel and tile; the table
 for B in {1, 8, 32} and both arithmetic modes is committed (tests/golden/dispatch_sd_v1_4.json, written by make_dispatch_golden.py), so a
 rule change shows up HERE as a diff, not as a slower bench."""
