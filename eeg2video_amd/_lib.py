@@ -81,6 +81,7 @@ SIGNATURES = {
     "e2v_profile_end": (_i64, [_ctx, C.c_char_p, _i64]),
     # eeg2video_hip_ops.h
     "e2v_op_conv3x3": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _stream]),
+    "e2v_op_conv3x3_gn": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _i, _p, _i, _p, _p, _stream]),
     "e2v_op_linear": (_i, [_ctx, _p, _i, _i64, _i, _p, _p, _i, _p, _i, _p, _stream]),
     "e2v_op_groupnorm": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _stream]),
     "e2v_op_layernorm": (_i, [_ctx, _p, _i64, _i, _p, _p, _f, _p, _stream]),

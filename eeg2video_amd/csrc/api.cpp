@@ -727,6 +727,52 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
     });
 }
 
+e2v_status e2v_op_conv3x3_gn(e2v_ctx* c, const float* x0, int c0, const float* x1, int c1, int n_img, int Hs, int Ws, int Hi, int Wi,
+                             int Ho, int Wo, int stride, int pad_lo, int gn_P, int groups, float eps, const float* gamma,
+                             const float* beta, const float* w_oihw, const float* bias, int cout, const float* rowbias,
+                             int rows_per_sample, const float* resid, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    // the argument and shape checks make no HIP call, so they come before guarded(): a host-only context answers them too
+    const int cin = c0 + c1;
+    const int64_t rows = (int64_t)n_img * Hs * Ws;
+    if (!(x0 && gamma && beta && w_oihw && out && c0 > 0 && c0 % 4 == 0 && c1 >= 0 && c1 % 4 == 0 && (c1 == 0 || x1) && cout > 0 && n_img > 0 &&
+          Hs > 0 && Ws > 0 && groups > 0 && cin % groups == 0 && gn_P > 0 && rows % gn_P == 0)) {
+        c->err = "bad conv3x3_gn arguments";
+        return E2V_EINVAL;
+    }
+    const int wm = c->conv_wino_tile(cin, cout, stride, pad_lo, Hi, Wi, Ho, Wo);      // the graph runner's policy
+    if (wm == 0) {
+        c->err = "conv: fused GroupNorm needs the Winograd path";
+        return E2V_ESHAPE;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        const int samples = (int)(rows / gn_P);
+        Act part(c->pool, (int64_t)samples * groupnorm_chunks(gn_P), cin * 2);
+        Act sc(c->pool, samples, cin * 2);
+        GroupNormArgs a;                     // statistics only: (scale, shift) per (slab, channel) for the conv's input transform
+        a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.ld0 = c0; a.ld1 = c1; a.gamma = gamma; a.beta = beta;
+        a.samples = samples; a.P = gn_P; a.groups = groups; a.eps = eps;
+        a.ws_part = part.p; a.ws_scale = sc.p;
+        groupnorm_stats(a, s);
+        Conv3 d;
+        d.x0 = x0; d.c0 = c0; d.x1 = x1; d.c1 = c1; d.nimg = n_img; d.Hs = Hs; d.Ws = Ws;
+        d.Hi = Hi; d.Wi = Wi; d.Ho = Ho; d.Wo = Wo; d.stride = stride; d.pad = pad_lo;
+        d.cout = cout; d.out = out; d.bias = bias;
+        d.rowbias = rowbias; d.rb_ld = cout; d.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1; d.resid = resid;
+        Act u(c->pool, (int64_t)(wm + 2) * (wm + 2) * cout, cin);
+        wino_pack_weights(w_oihw, u.p, cout, cin, wm, s);
+        Act u3;
+        if (c->x3_compute) {
+            const size_t n = (size_t)(wm + 2) * (wm + 2) * cout * cin;
+            u3 = Act(c->pool, (int64_t)((3 * n + 1) / 2 + 1023) / 1024, 1024);
+            split_bf16x3(u.p, u3.p, n, n, s);
+        }
+        conv3_wino(c, d, wm, u.p, u3.p, sc.p, gn_P, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
 e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, const float* w, const float* bias, int N,
                          const float* resid, int geglu, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;

@@ -417,6 +417,22 @@ class Engine:
                                             p(rowbias), rows_per_sample, p(resid), out.data_ptr(), _stream()))
         return out
 
+    def op_conv3x3_gn(self, x0, gamma, beta, w, bias=None, x1=None, *, n_img, Hs, Ws, gn_P, groups, eps, Hi=None, Wi=None, stride=1,
+                      pad_lo=1, pad_hi=1, rowbias=None, rows_per_sample=1, resid=None):
+        """GroupNorm + SiLU + 3x3 conv as the fp32 resnets run them (``e2v_op_conv3x3_gn``): statistics over slabs of ``gn_P`` source
+        rows, affine + SiLU inside the Winograd input transform.  Raises ``ValueError`` where the conv takes no Winograd form."""
+        Hi, Wi = Hi or Hs, Wi or Ws
+        Ho = (Hi + pad_lo + pad_hi - 3) // stride + 1
+        Wo = (Wi + pad_lo + pad_hi - 3) // stride + 1
+        cout = w.shape[0]
+        out = torch.empty((n_img * Ho * Wo, cout), device=self.device, dtype=torch.float32)
+        p = lambda t: t.data_ptr() if t is not None else None
+        self._check(self.lib.e2v_op_conv3x3_gn(self.ctx, x0.data_ptr(), x0.shape[1], p(x1), x1.shape[1] if x1 is not None else 0,
+                                               n_img, Hs, Ws, Hi, Wi, Ho, Wo, stride, pad_lo, gn_P, groups, float(eps),
+                                               gamma.data_ptr(), beta.data_ptr(), w.data_ptr(), p(bias), cout, p(rowbias),
+                                               rows_per_sample, p(resid), out.data_ptr(), _stream()))
+        return out
+
     def op_linear(self, x, w, bias=None, resid=None, geglu=False):
         m, k = x.shape
         n = w.shape[0] // 2 if geglu else w.shape[0]

@@ -25,6 +25,18 @@ e2v_status e2v_op_conv3x3(e2v_ctx* ctx, const float* x0, int c0, const float* x1
                           int cout, const float* rowbias, int rows_per_sample, const float* resid, float* out,
                           e2v_stream stream);
 
+/* GroupNorm + SiLU + InflatedConv3d 3x3 as ResnetBlock3D runs them (resnet.py:177-180, 188-197) in the fp32 mode: the statistics pass of
+ * e2v_op_groupnorm over slabs of gn_P source rows (n_img * Hs * Ws must be a multiple of gn_P), then the Winograd form of e2v_op_conv3x3
+ * whose input transform applies the affine and the SiLU while it reads the tensor -- the normalised activation is never stored.  gamma /
+ * beta: [c0 + c1].  Exists only where the library picks a Winograd form for the conv (stride 1, pad_lo 1, Ho = Hi, Wo = Wi, fp32
+ * arithmetic, channel counts multiples of 4, e2v_set_conv_algo): any other shape is refused with E2V_ESHAPE, as the graph refuses it.
+ * The concat seam c0 only has to be a multiple of 4 here (the direct kernels behind e2v_op_conv3x3 need 32; the transforms read quads).
+ * That check needs no GPU: a host-only context answers it too (and then E2V_ESTATE for a shape that would run). */
+e2v_status e2v_op_conv3x3_gn(e2v_ctx* ctx, const float* x0, int c0, const float* x1, int c1, int n_img, int Hs, int Ws, int Hi, int Wi,
+                             int Ho, int Wo, int stride, int pad_lo, int gn_P, int groups, float eps, const float* gamma,
+                             const float* beta, const float* w_oihw, const float* bias, int cout, const float* rowbias,
+                             int rows_per_sample, const float* resid, float* out, e2v_stream stream);
+
 /* nn.Linear / 1x1 conv: out[M][N] = x[M][K] w[N][K]^T + bias (+ resid).  geglu != 0: w is the GEGLU
  * projection [2*N2][K] in torch row order (value rows then gate rows, attention.py:189 via diffusers GEGLU);
  * out[M][N2] = (x w_v^T + b_v) * gelu_erf(x w_g^T + b_g). */
