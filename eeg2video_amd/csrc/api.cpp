@@ -189,10 +189,55 @@ e2v_status e2v_load_tensor(e2v_ctx* c, const char* key, const void* host, e2v_dt
             const uint16_t* h = static_cast<const uint16_t*>(host);
             for (size_t i = 0; i < t.numel; ++i) tmp[i] = half_to_float(h[i]);
             E2V_HIP(hipMemcpy(t.d, tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
+        } else if (dtype == E2V_BF16) {                           // bf16 is the high half of the fp32 pattern
+            std::vector<uint32_t> tmp(t.numel);
+            const uint16_t* h = static_cast<const uint16_t*>(host);
+            for (size_t i = 0; i < t.numel; ++i) tmp[i] = (uint32_t)h[i] << 16;
+            E2V_HIP(hipMemcpy(t.d, tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
         } else {
             throw Error(E2V_EINVAL, "unsupported dtype");
         }
         t.loaded = true;
+    });
+}
+
+}  // extern "C"
+
+namespace {
+// the tensor behind `key`, once the part that owns it is finalized
+const WTensor& updatable(e2v_ctx* c, const char* key) {
+    auto it = c->raw.find(key);
+    E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
+    const std::string k(key);
+    const bool ready = k.rfind("semantic.", 0) == 0 ? c->sem_ready : k.rfind("vae.", 0) == 0 ? c->vae_ready : c->unet_ready;
+    E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
+    return it->second;
+}
+}  // namespace
+
+extern "C" {
+
+e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_dtype dtype, int on_device, const int64_t* shape,
+                             int ndim, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    if (!key || !data || !shape) { c->err = "null argument"; return E2V_EINVAL; }
+    if (dtype != E2V_F32 && dtype != E2V_F16 && dtype != E2V_BF16) { c->err = "e2v_update_tensor: the source is fp32, fp16 or bf16"; return E2V_EINVAL; }
+    return guarded(c, [&] {
+        E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no weights in a dry run");
+        const WTensor& t = updatable(c, key);
+        bool same = (int)t.shape.size() == ndim;
+        for (int d = 0; same && d < ndim; ++d) same = t.shape[d] == shape[d];
+        E2V_REQUIRE(same, E2V_ENOWEIGHT, std::string("shape mismatch for ") + key);
+        c->update_tensor(key, data, dtype, on_device != 0, S(c, stream));
+    });
+}
+
+e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
+    if (!c) return E2V_EINVAL;
+    if (!key || !mask) { c->err = "null argument"; return E2V_EINVAL; }
+    return guarded(c, [&] {
+        updatable(c, key);
+        *mask = c->weight_forms(key);
     });
 }
 

@@ -237,6 +237,22 @@ void dana_noise(const float* x0, const float* eps_div, const float* eps_same, co
 void frames_to_u8(const float* in, unsigned char* out, long long count, hipStream_t s);
 void pad_cols(const float* in, int cols, float* out, int cols_pad, long long rows, hipStream_t s, int out_bf16 = 0);   // fp32 in; out fp32 or bf16
 
+// In-place weight update (e2v_update_tensor): one pass over a [rows][in] source (fp32, bf16 or fp16; src_mode as the h16.h flags:
+// 0 / 1 / 2) that writes every form a finalized linear keeps of it -- the fp32 matrix, the bf16 and fp16 copies (rows zero-padded
+// to ld16, a multiple of 8) and the three f32x3 planes -- with the roundings of to_h16 / split_bf16x3, so the bits equal a fresh
+// finalize.  A null destination is skipped.  Source row j lands in row  row_off + j  of each destination (half == 0), or, for the
+// GEGLU interleave (half > 0: rows [value 0..half) | gate 0..half)] -> blocks of [blk value | blk gate]), in row
+// row_off + 2 blk (jj / blk) + jj % blk + (j >= half ? blk : 0)  with jj = j % half.  Columns in .. ld - 1 of a destination row are zeros.
+struct WeightScatterArgs {
+    const void* src = nullptr; int src_mode = 0;
+    int rows = 0, in = 0;
+    int row_off = 0, half = 0, blk = 1;
+    float* d32 = nullptr; int ld32 = 0;
+    void* d16b = nullptr; void* d16h = nullptr; int ld16 = 0;
+    void* d3 = nullptr; int ld3 = 0; long long plane = 0;        // planes `plane` elements apart
+};
+void weight_scatter(const WeightScatterArgs& a, hipStream_t s);
+
 // weight-streaming GEMV (gemv.hip): out[b][n] = act(x[b] . W[n] + bias[n]) for B <= 16 rows, x / out fp32 rows, W [N][ldw] fp32 or
 // bf16 (rows zero-padded to ldw); the Semantic Predictor at the reference's batch sizes
 bool gemv_rows_supported(int B, int K, int w_bf16);

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "prof.h"
 #include "act_io.h"
+#include "runtime.h"
 
 namespace e2v {
 
@@ -264,6 +265,121 @@ void pad_cols(const float* in, int cols, float* out, int cols_pad, long long row
         });
     else
         E2V_KLAUNCH(pad_cols_kernel<float>, dim3(grid_for((size_t)rows * cols_pad)), dim3(256), 0, s, in, cols, out, cols_pad, (size_t)rows);
+}
+
+// ---- in-place weight update (e2v_update_tensor; kernels.h: WeightScatterArgs) --------------------------------------------------
+// One lane per 8-column piece of a source row: the piece is read ONCE (16-byte loads) and written to every live form of the linear --
+// fp32 (two 16-byte stores), bf16 / fp16 (one each) and the three truncation planes of the f32x3 mode (one each).  The conversions are
+// the ones finalize() uses: the compiler's round-to-nearest-even casts of to_h16_kernel and the subtraction chain of
+// split_bf16x3_kernel, so an updated matrix has the bits a fresh finalize would give it.  VEC = false serves what 16-byte accesses
+// cannot: a row length that is no multiple of 8 (22, 310: the Semantic Predictor's first layer, 4: the VAE's latent convs) or a source
+// that is not 16-byte aligned -- element loads guarded by the row length (nothing is read past the source), element stores for the
+// fp32 and plane rows; the 16-bit rows are padded to a multiple of 8 and always take whole pieces.
+template <typename Src, bool VEC>
+__global__ __launch_bounds__(256) void weight_scatter_kernel(const WeightScatterArgs a, int pieces) {
+    const Src* __restrict__ src = static_cast<const Src*>(a.src);
+    const size_t total = (size_t)a.rows * pieces;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i % pieces);
+        const int r = (int)(i / pieces);
+        const int c0 = p * 8;
+        float v[8];
+        if constexpr (VEC) {
+            const Src* sp = src + (size_t)r * a.in + c0;
+            if constexpr (sizeof(Src) == 4) {
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(sp), hi = *reinterpret_cast<const f32x4*>(sp + 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { v[k] = lo[k]; v[4 + k] = hi[k]; }
+            } else {
+                const hx8<Src> q = *reinterpret_cast<const hx8<Src>*>(sp);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = (float)q[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = c0 + k < a.in ? (float)src[(size_t)r * a.in + c0 + k] : 0.f;
+        }
+        int dr = r;
+        if (a.half > 0) {
+            const int jj = r % a.half;
+            dr = 2 * a.blk * (jj / a.blk) + jj % a.blk + (r >= a.half ? a.blk : 0);
+        }
+        dr += a.row_off;
+        if (a.d32) {
+            float* d = a.d32 + (size_t)dr * a.ld32 + c0;
+            if constexpr (VEC) {
+                *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k) if (c0 + k < a.ld32) d[k] = v[k];
+            }
+        }
+        if (c0 < a.ld16) {              // (ld16 is a multiple of 8: a piece is inside the row or past it)
+            if (a.d16b) {
+                hx8<__bf16> o;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) o[k] = (__bf16)v[k];
+                *reinterpret_cast<hx8<__bf16>*>(static_cast<__bf16*>(a.d16b) + (size_t)dr * a.ld16 + c0) = o;
+            }
+            if (a.d16h) {
+                hx8<_Float16> o;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) o[k] = (_Float16)v[k];
+                *reinterpret_cast<hx8<_Float16>*>(static_cast<_Float16*>(a.d16h) + (size_t)dr * a.ld16 + c0) = o;
+            }
+        }
+        if (a.d3) {                     // x = p0 + p1 + p2 exactly (split_bf16x3_kernel)
+            hx8<unsigned short> p0, p1, p2;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const float x = v[k];
+                const unsigned b1 = __builtin_bit_cast(unsigned, x) & 0xFFFF0000u;
+                const float r1 = x - __builtin_bit_cast(float, b1);
+                const unsigned b2 = __builtin_bit_cast(unsigned, r1) & 0xFFFF0000u;
+                const float r2 = r1 - __builtin_bit_cast(float, b2);
+                p0[k] = (unsigned short)(b1 >> 16);
+                p1[k] = (unsigned short)(b2 >> 16);
+                p2[k] = (unsigned short)(__builtin_bit_cast(unsigned, r2) >> 16);
+            }
+            unsigned short* d = static_cast<unsigned short*>(a.d3) + (size_t)dr * a.ld3 + c0;
+            if constexpr (VEC) {
+                *reinterpret_cast<hx8<unsigned short>*>(d) = p0;
+                *reinterpret_cast<hx8<unsigned short>*>(d + a.plane) = p1;
+                *reinterpret_cast<hx8<unsigned short>*>(d + 2 * a.plane) = p2;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (c0 + k < a.ld3) { d[k] = p0[k]; d[a.plane + k] = p1[k]; d[2 * a.plane + k] = p2[k]; }
+            }
+        }
+    }
+}
+void weight_scatter(const WeightScatterArgs& a, hipStream_t s) {
+    if (a.rows <= 0 || a.in <= 0) return;
+    const bool any16 = a.d16b || a.d16h;
+    E2V_REQUIRE(a.src && (!a.d32 || a.ld32 >= a.in) && (!any16 || (a.ld16 >= a.in && a.ld16 % 8 == 0)) && (!a.d3 || a.ld3 >= a.in) &&
+                    a.blk > 0 && (a.half == 0 || (a.rows == 2 * a.half && a.half % a.blk == 0)),
+                E2V_EINVAL, "weight_scatter: bad destination geometry");
+    int cols = a.in;
+    if (a.d32) cols = cols > a.ld32 ? cols : a.ld32;
+    if (any16) cols = cols > a.ld16 ? cols : a.ld16;
+    if (a.d3) cols = cols > a.ld3 ? cols : a.ld3;
+    const int pieces = (cols + 7) / 8;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // 16-byte accesses everywhere: whole pieces in the source and in every destination row, every row start aligned
+    const bool vec = a.in % 8 == 0 && al16(a.src) &&
+                     (!a.d32 || (a.ld32 == a.in && al16(a.d32 + (size_t)a.row_off * a.ld32))) &&
+                     (!a.d3 || (a.ld3 == a.in && a.plane % 8 == 0 && al16(a.d3))) && (!any16 || (al16(a.d16b) && al16(a.d16h)));
+    const size_t total = (size_t)a.rows * pieces;
+    const dim3 g(grid_for(total)), b(256);
+    auto launch = [&](auto src_tag) {
+        using Src = decltype(src_tag);
+        if (vec) E2V_KLAUNCH((weight_scatter_kernel<Src, true>), g, b, 0, s, a, pieces);
+        else E2V_KLAUNCH((weight_scatter_kernel<Src, false>), g, b, 0, s, a, pieces);
+    };
+    if (a.src_mode == H16_NONE) launch(float{});
+    else h16_dispatch(a.src_mode, launch);
 }
 
 // strided row copy with a storage-type change: out[r][c] = in[r][c] for c < cols, 0 for cols <= c < cols_out

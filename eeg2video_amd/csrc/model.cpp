@@ -1,6 +1,7 @@
 // Model graphs of the EEG2Video generation hot path on one HIP stream (see model.h).
 #include "model.h"
 #include "h16.h"
+#include "../../include/eeg2video_hip_ops.h"
 
 #include <algorithm>
 #include <cmath>
@@ -225,46 +226,56 @@ Act e2v::splitk_attach(Pool& pool, IgemmArgs& g, int want) {
 // it from the torch-layout weight on the calling stream -- ordered before the launch that asked for it.
 void e2v_ctx::conv_form(const ConvW& w, ConvForm f, hipStream_t s) {
     AllocPart guard(this, w.part);
-    auto split3 = [&](const float* u, size_t n) -> const void* {
-        float* d = dev_alloc((3 * n + 1) / 2);
-        split_bf16x3(u, d, n, n, s);
-        return d;
-    };
-    // a 16-bit layout of n elements: packed in fp32 staging (the up2x tap sums are formed in fp32), rounded once
-    auto form16 = [&](const void*& dst, bool up2, int mode) {
+    bool fresh = false;
+    auto need = [&](auto& dst, size_t floats) {
         if (dst) return;
-        const size_t n = up2 ? 4 * (size_t)w.cout * conv_up2x_packed_ld(w.cin) : (size_t)w.cout * w.ldw16;
-        Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);
-        if (up2) pack_conv_up2x(w.raw, tmp.p, w.cout, w.cin, s);
-        else pack_conv3x3(w.raw, tmp.p, w.cout, w.cin, 64, s);                // the 64-channel-chunk layout
-        float* d16 = dev_alloc((n + 1) / 2);
-        to_h16(tmp.p, d16, n, mode, s);
-        dst = d16;
+        dst = dev_alloc(floats);
+        fresh = true;
     };
+    const size_t n16 = (size_t)w.cout * w.ldw16, n16_up2 = 4 * (size_t)w.cout * conv_up2x_packed_ld(w.cin);
     switch (f) {
-        case FORM_DIRECT32:
-            if (!w.w) {
-                float* d = dev_alloc((size_t)w.cout * w.ldw);
-                pack_conv3x3(w.raw, d, w.cout, w.cin, 32, s);
-                w.w = d;
-            }
-            break;
-        case FORM_BF16: form16(w.w16, false, H16_BF16); break;
-        case FORM_F16: form16(w.w16h, false, H16_FP16); break;
-        case FORM_BF16_UP2: form16(w.w16_up2, true, H16_BF16); break;
-        case FORM_F16_UP2: form16(w.w16h_up2, true, H16_FP16); break;
+        case FORM_DIRECT32: need(w.w, (size_t)w.cout * w.ldw); break;
+        case FORM_BF16: need(w.w16, (n16 + 1) / 2); break;
+        case FORM_F16: need(w.w16h, (n16 + 1) / 2); break;
+        case FORM_BF16_UP2: need(w.w16_up2, (n16_up2 + 1) / 2); break;
+        case FORM_F16_UP2: need(w.w16h_up2, (n16_up2 + 1) / 2); break;
         case FORM_WINO2:
         case FORM_WINO4: {
             const int m = f == FORM_WINO4 ? 4 : 2;
             const size_t n = (size_t)(m + 2) * (m + 2) * w.cout * w.cin;
-            const float*& u = m == 4 ? w.wino4 : w.wino;
-            const void*& u3 = m == 4 ? w.wino4_x3 : w.wino_x3;
-            if (!u) {
-                float* d = dev_alloc(n);
-                wino_pack_weights(w.raw, d, w.cout, w.cin, m, s);
-                u = d;
-            }
-            if (x3_compute && !u3) u3 = split3(u, n);
+            need(m == 4 ? w.wino4 : w.wino, n);
+            if (x3_compute) need(m == 4 ? w.wino4_x3 : w.wino_x3, (3 * n + 1) / 2);
+            break;
+        }
+    }
+    if (fresh) conv_fill(w, f, s);
+}
+
+// The one place a layout's contents come from: pack from the torch-layout weight, round once.  Runs when conv_form allocates the
+// layout and when e2v_update_tensor has overwritten w.raw -- the same launches in the same order, so the bits are the same.
+void e2v_ctx::conv_fill(const ConvW& w, ConvForm f, hipStream_t s) {
+    // a 16-bit layout of n elements: packed in fp32 staging (the up2x tap sums are formed in fp32), rounded once
+    auto fill16 = [&](const void* dst, bool up2, int mode) {
+        const size_t n = up2 ? 4 * (size_t)w.cout * conv_up2x_packed_ld(w.cin) : (size_t)w.cout * w.ldw16;
+        Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);
+        if (up2) pack_conv_up2x(w.raw, tmp.p, w.cout, w.cin, s);
+        else pack_conv3x3(w.raw, tmp.p, w.cout, w.cin, 64, s);                // the 64-channel-chunk layout
+        to_h16(tmp.p, const_cast<void*>(dst), n, mode, s);
+    };
+    switch (f) {
+        case FORM_DIRECT32: pack_conv3x3(w.raw, const_cast<float*>(w.w), w.cout, w.cin, 32, s); break;
+        case FORM_BF16: fill16(w.w16, false, H16_BF16); break;
+        case FORM_F16: fill16(w.w16h, false, H16_FP16); break;
+        case FORM_BF16_UP2: fill16(w.w16_up2, true, H16_BF16); break;
+        case FORM_F16_UP2: fill16(w.w16h_up2, true, H16_FP16); break;
+        case FORM_WINO2:
+        case FORM_WINO4: {
+            const int m = f == FORM_WINO4 ? 4 : 2;
+            const size_t n = (size_t)(m + 2) * (m + 2) * w.cout * w.cin;
+            const float* u = m == 4 ? w.wino4 : w.wino;
+            const void* u3 = m == 4 ? w.wino4_x3 : w.wino_x3;
+            wino_pack_weights(w.raw, const_cast<float*>(u), w.cout, w.cin, m, s);
+            if (u3) split_bf16x3(u, const_cast<void*>(u3), n, n, s);
             break;
         }
     }
@@ -324,6 +335,19 @@ struct Packer {
         E2V_REQUIRE(it->second.loaded, E2V_ENOWEIGHT, "state-dict key not loaded: " + k);
         return it->second;
     }
+    // ---- where each raw key lands (model.h: WBind), for e2v_update_tensor ----
+    void bind_raw(const std::string& k, const float* dst, int rows, int in, int half = 0) {
+        WBind b;
+        b.kind = WBind::RAW; b.dst = const_cast<float*>(dst); b.rows = rows; b.in = in; b.half = half;
+        c->bind[k] = b;
+    }
+    void bind_lin(const std::string& k, const float* anchor, int row_off, int half = 0) {
+        const WTensor& w = t(k);
+        WBind b;
+        b.kind = WBind::LIN; b.anchor = anchor; b.rows = (int)w.shape[0]; b.in = (int)w.shape[1]; b.row_off = row_off;
+        b.half = half; b.blk = 32;
+        c->bind[k] = b;
+    }
     const void* half(const float* w, size_t n) {             // bf16 copy of a (packed) weight for the bf16-MFMA mode
         float* d = c->dev_alloc((n + 1) / 2);
         to_bf16(w, d, n, s);
@@ -354,9 +378,15 @@ struct Packer {
         split_bf16x3(w, d, n, n, s);
         return d;
     }
-    NormW norm(const std::string& n) { return NormW{t(n + ".weight").d, t(n + ".bias").d, (int)t(n + ".weight").shape[0]}; }
+    NormW norm(const std::string& n) {
+        const NormW w{t(n + ".weight").d, t(n + ".bias").d, (int)t(n + ".weight").shape[0]};
+        bind_raw(n + ".weight", w.g, 1, w.c); bind_raw(n + ".bias", w.b, 1, w.c);
+        return w;
+    }
     LinW lin(const std::string& n, bool bias = true) {       // Linear or 1x1 conv: [out][in] as it is
         const WTensor& w = t(n + ".weight");
+        bind_lin(n + ".weight", w.d, 0);
+        if (bias) bind_raw(n + ".bias", t(n + ".bias").d, 1, (int)w.shape[0]);
         return mk_lin(w.d, bias ? t(n + ".bias").d : nullptr, (int)w.shape[1], (int)w.shape[0]);
     }
     // 3x3 conv: the torch-layout weight stays; kernel layouts are built on first use (e2v_ctx::conv_form)
@@ -368,6 +398,10 @@ struct Packer {
         cw.cin_pad = (cw.cin + 3) / 4 * 4; cw.cin_pad16 = (cw.cin + 7) / 8 * 8;
         cw.ldw = conv3x3_packed_ld(cw.cin, 32); cw.ldw16 = conv3x3_packed_ld(cw.cin, 64);
         cw.part = c->alloc_part >= 0 ? c->alloc_part : 0;
+        WBind b;
+        b.kind = WBind::CONV; b.anchor = cw.raw; b.rows = 1; b.in = (int)w.numel;
+        c->bind[n + ".weight"] = b;
+        bind_raw(n + ".bias", cw.b, 1, cw.cout);
         return cw;
     }
     LinW fuse_rows(const std::vector<std::string>& names, bool bias) {   // stack Linear weights along `out`
@@ -380,6 +414,8 @@ struct Packer {
             const WTensor& w = t(n + ".weight");
             copy_rows(w.d, in, d + (size_t)r * in, in, (int)w.shape[0], in, s);
             if (bias) copy_rows(t(n + ".bias").d, (int)w.shape[0], b + r, (int)w.shape[0], 1, (int)w.shape[0], s);
+            bind_lin(n + ".weight", d, r);
+            if (bias) bind_raw(n + ".bias", b + r, 1, (int)w.shape[0]);
             r += (int)w.shape[0];
         }
         return mk_lin(d, b, in, out);
@@ -392,6 +428,8 @@ struct Packer {
         float* d = c->dev_alloc((size_t)out * in);
         float* b = c->dev_alloc(out);
         geglu_interleave(w.d, bsrc.d, half, in, d, b, s);
+        bind_lin(n + ".weight", d, 0, half);
+        bind_raw(n + ".bias", b, out / 32, 32, half / 32);       // 32-element groups, interleaved one by one
         return mk_lin(d, b, in, out);
     }
     ResW resnet(const std::string& p, bool temb) {
@@ -435,6 +473,12 @@ void e2v_ctx::finalize(int which) {
     Packer P{this};
     const int L = cfg.layers_per_block;
     AllocPart part_guard(this, -1);                  // (an error below leaves no part selected)
+    // everything that can refuse the call is checked BEFORE a part is freed: a failed finalize leaves the context as it was
+    E2V_REQUIRE(!(which & 4) || (cfg.sem_in_features > 0 && cfg.sem_hidden > 0), E2V_ESTATE, "the config has no semantic predictor");
+    for (const auto& k : keys) {
+        const int part = k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : 1;
+        if (which & part) P.t(k);
+    }
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
     if (which & 1) {
         free_part(0);
@@ -501,7 +545,6 @@ void e2v_ctx::finalize(int which) {
         vae = std::move(v);
     }
     if (which & 4) {
-        E2V_REQUIRE(cfg.sem_in_features > 0 && cfg.sem_hidden > 0, E2V_ESTATE, "the config has no semantic predictor");
         free_part(2);
         alloc_part = 2;
         sem.clear();
@@ -516,6 +559,8 @@ void e2v_ctx::finalize(int which) {
                 const int out = (int)w.shape[0];
                 float* wp = dev_alloc((size_t)out * sem_in_pad);
                 pad_cols(w.d, cfg.sem_in_features, wp, sem_in_pad, out, nullptr);
+                P.bind_lin(n + ".weight", wp, 0);
+                P.bind_raw(n + ".bias", P.t(n + ".bias").d, 1, out);
                 sem.push_back(P.mk_lin(wp, P.t(n + ".bias").d, sem_in_pad, out));
             } else {
                 sem.push_back(P.lin(n));
@@ -523,6 +568,7 @@ void e2v_ctx::finalize(int which) {
         }
     }
     alloc_part = -1;
+    resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
     E2V_HIP(hipGetLastError());
     if (dry_run()) {                                         // nothing was allocated: nothing to drop
@@ -554,6 +600,128 @@ void e2v_ctx::finalize(int which) {
     if (which & 1) unet_ready = true;
     if (which & 2) vae_ready = true;
     if (which & 4) sem_ready = true;
+}
+
+// =====================================================================================================
+// in-place weight update (e2v_update_tensor)
+// =====================================================================================================
+namespace {
+
+template <class FL, class FC> void visit(ResW& r, FL& fl, FC& fc) { fc(r.c1); fc(r.c2); fl(r.temb); fl(r.sc); }
+template <class FL> void visit(TransW& w, FL& fl) {
+    for (LinW* l : {&w.proj_in, &w.proj_out, &w.a1_qkv, &w.a1_out, &w.a2_q, &w.a2_kv, &w.a2_out, &w.ff1, &w.ff2, &w.at_qkv, &w.at_out}) fl(*l);
+}
+template <class FL, class FC> void visit(UNetW& u, FL& fl, FC& fc) {
+    fc(u.conv_in); fc(u.conv_out); fl(u.te1); fl(u.te2);
+    for (auto* blocks : {&u.down, &u.up})
+        for (auto& b : *blocks) {
+            for (auto& r : b.res) visit(r, fl, fc);
+            for (auto& a : b.attn) visit(a, fl);
+            if (b.resample) fc(b.rs);
+        }
+    visit(u.mid_r0, fl, fc); visit(u.mid_r1, fl, fc); visit(u.mid_attn, fl);
+}
+template <class FL, class FC> void visit(VAEW& v, FL& fl, FC& fc) {
+    fl(v.post_quant); fl(v.quant);
+    for (ConvW* c : {&v.dec_in, &v.dec_out, &v.enc_in, &v.enc_out}) fc(*c);
+    for (ResW* r : {&v.dec_mid0, &v.dec_mid1, &v.enc_mid0, &v.enc_mid1}) visit(*r, fl, fc);
+    for (VAEAttnW* a : {&v.dec_attn, &v.enc_attn}) { fl(a->qkv); fl(a->proj); }
+    for (auto* blocks : {&v.dec_up, &v.enc_down})
+        for (auto& b : *blocks) {
+            for (auto& r : b.res) visit(r, fl, fc);
+            if (b.resample) fc(b.rs);
+        }
+}
+
+}  // namespace
+
+// finalize() records a binding while the owner is still a temporary of the Packer; once the parts sit in the context, the owner is
+// found again by the fp32 block it was built around (LinW::w / ConvW::raw: one per object)
+void e2v_ctx::resolve_bindings() {
+    std::unordered_map<const void*, LinW*> lins;
+    std::unordered_map<const void*, ConvW*> convs;
+    auto fl = [&](LinW& l) { if (l.w) lins[l.w] = &l; };
+    auto fc = [&](ConvW& c) { if (c.raw) convs[c.raw] = &c; };
+    visit(unet, fl, fc);
+    visit(vae, fl, fc);
+    for (auto& l : sem) fl(l);
+    for (auto& kv : bind) {
+        WBind& b = kv.second;
+        if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
+        if (b.kind == WBind::CONV) { auto it = convs.find(b.anchor); b.conv = it != convs.end() ? it->second : nullptr; }
+    }
+}
+
+void e2v_ctx::update_tensor(const std::string& key, const void* data, e2v_dtype dtype, bool on_device, hipStream_t s) {
+    WTensor& t = raw.at(key);
+    auto bi = bind.find(key);
+    E2V_REQUIRE(bi != bind.end(), E2V_ESTATE, "no binding for " + key);
+    const WBind& b = bi->second;
+    const size_t esz = dtype == E2V_F32 ? 4 : 2;
+    Act stage;
+    if (!on_device) {                       // host source: staged in its own type, widened by the kernel
+        stage = Act(pool, (int64_t)((t.numel * esz + 4095) / 4096), 1024);
+        E2V_HIP(hipMemcpyAsync(stage.p, data, t.numel * esz, hipMemcpyHostToDevice, s));
+        data = stage.p;
+    }
+    WeightScatterArgs a;
+    a.src = data; a.src_mode = dtype == E2V_F32 ? H16_NONE : dtype == E2V_BF16 ? H16_BF16 : H16_FP16;
+    a.rows = b.rows; a.in = b.in; a.row_off = b.row_off; a.half = b.half; a.blk = b.blk;
+    const float* main32 = nullptr;          // the fp32 destination of the main launch
+    switch (b.kind) {
+        case WBind::RAW:
+            a.d32 = b.dst; a.ld32 = b.in;
+            break;
+        case WBind::LIN: {
+            E2V_REQUIRE(b.lin && b.row_off + b.rows <= b.lin->out && b.in <= b.lin->in, E2V_ESTATE, "stale binding for " + key);
+            const LinW& l = *b.lin;
+            a.d32 = const_cast<float*>(l.w); a.ld32 = l.in;
+            a.d16b = const_cast<void*>(l.w16); a.d16h = const_cast<void*>(l.w16h); a.ld16 = l.in16;
+            a.d3 = const_cast<void*>(l.w3); a.ld3 = l.in; a.plane = (long long)l.out * l.in;
+            break;
+        }
+        case WBind::CONV:
+            E2V_REQUIRE(b.conv && (size_t)b.conv->cout * b.conv->cin * 9 == t.numel, E2V_ESTATE, "stale binding for " + key);
+            a.d32 = const_cast<float*>(b.conv->raw); a.ld32 = b.in;
+            break;
+    }
+    main32 = a.d32;
+    weight_scatter(a, s);
+    if (t.d && t.loaded && t.d != main32) {         // the uploaded block is kept next to a re-laid-out copy (K-padded layer): a later
+        WeightScatterArgs r;                        // finalize of this part must find the new values there
+        r.src = data; r.src_mode = a.src_mode; r.rows = 1; r.in = (int)t.numel; r.d32 = t.d; r.ld32 = r.in;
+        weight_scatter(r, s);
+    }
+    if (b.kind == WBind::CONV) {            // every layout that exists is derived again, as conv_form derived it
+        const ConvW& w = *b.conv;
+        if (w.w) conv_fill(w, FORM_DIRECT32, s);
+        if (w.w16) conv_fill(w, FORM_BF16, s);
+        if (w.w16h) conv_fill(w, FORM_F16, s);
+        if (w.w16_up2) conv_fill(w, FORM_BF16_UP2, s);
+        if (w.w16h_up2) conv_fill(w, FORM_F16_UP2, s);
+        if (w.wino) conv_fill(w, FORM_WINO2, s);
+        if (w.wino4) conv_fill(w, FORM_WINO4, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
+
+int e2v_ctx::weight_forms(const std::string& key) {
+    auto bi = bind.find(key);
+    E2V_REQUIRE(bi != bind.end(), E2V_ESTATE, "no binding for " + key);
+    const WBind& b = bi->second;
+    int m = 0;
+    if (b.kind == WBind::RAW) m = b.dst ? E2V_FORM_F32 : 0;
+    if (b.kind == WBind::LIN && b.lin) {
+        const LinW& l = *b.lin;
+        m = (l.w ? E2V_FORM_F32 : 0) | (l.w16 ? E2V_FORM_BF16 : 0) | (l.w16h ? E2V_FORM_F16 : 0) | (l.w3 ? E2V_FORM_X3 : 0);
+    }
+    if (b.kind == WBind::CONV && b.conv) {
+        const ConvW& w = *b.conv;
+        m = (w.raw ? E2V_FORM_F32 : 0) | (w.w16 ? E2V_FORM_BF16 : 0) | (w.w16h ? E2V_FORM_F16 : 0) | (w.w ? E2V_FORM_CONV_DIRECT32 : 0) |
+            (w.wino ? E2V_FORM_WINO2 : 0) | (w.wino4 ? E2V_FORM_WINO4 : 0) | (w.w16_up2 ? E2V_FORM_BF16_UP2 : 0) |
+            (w.w16h_up2 ? E2V_FORM_F16_UP2 : 0) | (w.wino_x3 ? E2V_FORM_WINO2_X3 : 0) | (w.wino4_x3 ? E2V_FORM_WINO4_X3 : 0);
+    }
+    return m;
 }
 
 // =====================================================================================================

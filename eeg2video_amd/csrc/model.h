@@ -90,6 +90,22 @@ struct VAEW {
     NormW enc_norm_out;
 };
 
+// Where one raw state-dict tensor lives in the packed world of a finalized part (recorded by finalize(), used by e2v_update_tensor):
+//   RAW   the fp32 block the kernels read -- norm affines, plain biases (the uploaded block itself), a slice of a fused bias, the
+//         GEGLU bias (32-element groups interleaved);
+//   LIN   rows of a LinW: the whole matrix (plain linear / 1x1 conv, K-padded first layer of the Semantic Predictor), a row range
+//         of a fused one (a1_qkv, a2_kv, at_qkv, the VAE's qkv) or the GEGLU interleave of ff1 -- every form the LinW holds;
+//   CONV  a 3x3 conv: ConvW::raw, from which each layout that has been built is derived again.
+struct WBind {
+    enum Kind { RAW, LIN, CONV } kind = RAW;
+    const void* anchor = nullptr;    // LinW::w / ConvW::raw of the owner as finalize() made it; resolved to `lin` / `conv` once the part is in place
+    LinW* lin = nullptr;
+    ConvW* conv = nullptr;
+    float* dst = nullptr;            // RAW: destination
+    int rows = 1, in = 0;            // the source viewed as a matrix
+    int row_off = 0, half = 0, blk = 1;      // destination row map (kernels.h: WeightScatterArgs)
+};
+
 // The SMALL-BATCH dispatch family (16-bit modes), decided ONCE per API call and handed to the graph runner by value: the call runs at
 // most 8 UNet samples (B <= 4 clips with their guidance pairs: the reference's clip-by-clip loop, inference_eeg2video.py:90-100, and
 // a caller that batches a few clips; the boundary was measured -- B = 3 / 4 gain 7 / 4 %, B = 5 / 6 / 8 2.4 / 1.7 / 0.5 %:
@@ -178,11 +194,17 @@ struct e2v_ctx {
         ~AllocPart() { c->alloc_part = saved; }
     };
     void free_part(int part);
+    std::unordered_map<std::string, e2v::WBind> bind;            // raw key -> its place in the packed weights (keys of finalized parts)
+    void resolve_bindings();
+    // e2v_update_tensor: overwrite every existing form of `key` on stream s (data: [numel] of dtype, device or host)
+    void update_tensor(const std::string& key, const void* data, e2v_dtype dtype, bool on_device, hipStream_t s);
+    int weight_forms(const std::string& key);                    // e2v_op_weight_forms
 
     float* dev_alloc(size_t floats);
     enum ConvForm { FORM_DIRECT32, FORM_BF16, FORM_WINO2, FORM_WINO4, FORM_BF16_UP2, FORM_F16, FORM_F16_UP2 };
     const void* lin_f16(const e2v::LinW& w, hipStream_t s);              // the fp16 copy of a linear's weight (built on first use)
     void conv_form(const e2v::ConvW& w, ConvForm f, hipStream_t s);     // build the layout if this is its first use
+    void conv_fill(const e2v::ConvW& w, ConvForm f, hipStream_t s);     // derive the (allocated) layout from w.raw: first use and weight updates
     // THE Winograd policy: the output tile a 3x3 conv of this shape runs with -- 0 direct, 2 F(2x2,3x3), 4 F(4x4,3x3)
     int conv_wino_tile(int cin, int cout, int stride, int pad, int Hi, int Wi, int Ho, int Wo) const;
     void expected_keys();

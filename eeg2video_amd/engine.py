@@ -120,6 +120,53 @@ class Engine:
         self._check(self.lib.e2v_finalize_weights(self.ctx, which))
         self.ready |= which
 
+    _UPDATE_DTYPES = {torch.float32: _lib.E2V_F32, torch.float16: _lib.E2V_F16, torch.bfloat16: _lib.E2V_BF16}
+
+    def update_state_dict(self, sd, prefix: str = "") -> None:
+        """Overwrite tensors of a FINALIZED part in place (``e2v_update_tensor``): every form the engine holds of each tensor
+        (fused / interleaved fp32 matrices, 16-bit copies, f32x3 planes, conv layouts already built) is rewritten on the current
+        stream, with no device synchronisation and no reload -- what ``optimizer.step()`` looks like to the validation pipeline of
+        ``train_finetune_videodiffusion.py:196-200,320-335``.  ``sd``: a mapping or an iterable of ``(name, tensor)``.  Tensors
+        already on the engine's device in fp32 / fp16 / bf16 are read where they are (device pointer); anything else goes by host
+        pointer in its own 16-bit type or as fp32 (fp64 is narrowed as ``load_state_dict`` does)."""
+        stream = torch.cuda.current_stream(self.device)
+        self._pending = [(ev, src) for ev, src in getattr(self, "_pending", []) if not ev.query()]
+        host_sources = []
+        for k, v in (sd.items() if isinstance(sd, Mapping) else sd):
+            on_device = 0
+            if isinstance(v, torch.Tensor):
+                v = v.detach()
+                if v.device == self.device and v.dtype in self._UPDATE_DTYPES:
+                    v = v.contiguous()
+                    v.record_stream(stream)              # the allocator must not hand the block out before the queued read
+                    on_device = 1
+                else:
+                    v = v.cpu()
+                    v = (v if v.dtype in self._UPDATE_DTYPES else v.float()).contiguous()
+                    host_sources.append(v)
+                dt, ptr, shape = self._UPDATE_DTYPES[v.dtype], v.data_ptr(), tuple(v.shape)
+            else:
+                a = np.ascontiguousarray(v)
+                if a.dtype != np.float16:
+                    a = np.ascontiguousarray(a, dtype=np.float32)
+                host_sources.append(a)
+                dt, ptr, shape = (_lib.E2V_F16 if a.dtype == np.float16 else _lib.E2V_F32), a.ctypes.data, a.shape
+            if not shape or 0 in shape:
+                raise ValueError(f"{prefix + k}: an empty or 0-dim tensor is no weight")
+            cshape = (C.c_int64 * len(shape))(*shape)
+            self._check(self.lib.e2v_update_tensor(self.ctx, (prefix + k).encode(), C.c_void_p(ptr), dt, on_device, cshape, len(shape),
+                                                   stream.cuda_stream))
+        if host_sources:                                 # host memory stays referenced until the stream has passed its copies
+            ev = torch.cuda.Event()
+            ev.record(stream)
+            self._pending.append((ev, host_sources))
+
+    def weight_forms(self, key: str) -> int:
+        """Test aid (``e2v_op_weight_forms``): bit mask of the forms of ``key`` that exist on the device (``_lib.FORM_BITS``)."""
+        mask = C.c_int(0)
+        self._check(self.lib.e2v_op_weight_forms(self.ctx, key.encode(), C.byref(mask)))
+        return mask.value
+
     def set_compute_dtype(self, dtype) -> None:
         """'fp32' (default, parity configuration), 'bf16' (BASELINE configs[2]: bf16 MFMA, bf16 activations in HBM, fp32 accumulate /
         statistics / softmax) or 'fp16' (the same kernels on IEEE half: the reference's own inference dtype,
@@ -477,6 +524,16 @@ class Engine:
         self._check(self.lib.e2v_op_temporal_attention(self.ctx, qkv.data_ptr(), out.data_ptr(), n, F, HW, heads, D,
                                                        float(scale), _stream()))
         return out
+
+
+def named_tensors(source, only_trainable: bool = False):
+    """``(name, tensor)`` pairs of what ``sync_from`` accepts: an ``nn.Module`` (its ``named_parameters()``, those with
+    ``requires_grad`` when ``only_trainable``), a mapping, or an iterable of pairs."""
+    if hasattr(source, "named_parameters"):
+        return [(n, p) for n, p in source.named_parameters() if not only_trainable or p.requires_grad]
+    if only_trainable:
+        raise ValueError("only_trainable needs a module: a state dict does not say which of its tensors train")
+    return list(source.items()) if isinstance(source, Mapping) else list(source)
 
 
 def compute_dtype_code(dtype) -> int:

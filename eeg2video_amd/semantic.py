@@ -10,7 +10,7 @@ from typing import Optional
 
 import torch
 
-from .engine import Engine
+from .engine import Engine, named_tensors
 from .weights import SemanticConfig, synth_state_dict, semantic_param_spec
 
 
@@ -30,8 +30,19 @@ class CLIP:
         missing = [k for k in spec if k not in sd]
         if strict and missing:
             raise RuntimeError(f"Error(s) in loading state_dict for CLIP: missing {missing[:4]}...")
-        self.engine.load_state_dict({k: v for k, v in sd.items() if k in spec}, prefix="semantic.")
+        given = {k: v for k, v in sd.items() if k in spec}
+        if missing and self.engine.ready & Engine.SEMANTIC:  # strict=False, some keys of a built model: those tensors move, in place
+            self.engine.update_state_dict(given, prefix="semantic.")
+            return self
+        self.engine.load_state_dict(given, prefix="semantic.")
         self.engine.finalize(Engine.SEMANTIC)
+        return self
+
+    def sync_from(self, source, only_trainable: bool = False):
+        """Follow the predictor while ``train_semantic_predictor.py`` trains it: the built model takes the tensors of ``source`` (the
+        ``nn.Module``, a mapping, or ``(name, tensor)`` pairs) in place, on the current stream (``Engine.update_state_dict``)."""
+        spec = self.state_dict_spec()
+        self.engine.update_state_dict({k: v for k, v in named_tensors(source, only_trainable) if k in spec}, prefix="semantic.")
         return self
 
     def init_synthetic(self, seed: int = 44, mode: str = "reference_init"):

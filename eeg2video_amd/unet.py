@@ -15,7 +15,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
-from .engine import Engine
+from .engine import Engine, named_tensors
 from .weights import UNetConfig, VAEConfig, synth_state_dict, unet_param_spec
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"      # diffusers.utils.WEIGHTS_NAME (unet.py:439-441)
@@ -214,24 +214,44 @@ class UNet3DConditionModel:
         return unet_param_spec(self.ucfg)
 
     # -- weights -----------------------------------------------------------------------------
+    def _engine_layout(self, state_dict, strict: bool):
+        """nn.Linear proj_in / proj_out (use_linear_projection) -> the 1x1-conv layout the engine's key scheme holds"""
+        if not self.use_linear_projection:
+            return state_dict
+        state_dict = dict(state_dict)
+        for k, v in list(state_dict.items()):
+            if k.endswith(".proj_in.weight") or k.endswith(".proj_out.weight"):
+                if strict and getattr(v, "ndim", 0) != 2:       # the reference's strict load refuses a conv-shaped weight for an nn.Linear
+                    raise RuntimeError(f"Error(s) in loading state_dict for UNet3DConditionModel: size mismatch for {k}: copying a param "
+                                       f"with shape {tuple(v.shape)} from checkpoint, the shape in current model is {tuple(v.shape[:2])}.")
+                if getattr(v, "ndim", 0) == 2:
+                    state_dict[k] = v.reshape(v.shape[0], v.shape[1], 1, 1)
+        return state_dict
+
     def load_state_dict(self, state_dict, strict: bool = True):
         spec = self.state_dict_spec()
-        if self.use_linear_projection:           # nn.Linear proj_in / proj_out -> the 1x1-conv layout the engine's key scheme holds
-            state_dict = dict(state_dict)
-            for k, v in list(state_dict.items()):
-                if k.endswith(".proj_in.weight") or k.endswith(".proj_out.weight"):
-                    if strict and getattr(v, "ndim", 0) != 2:       # the reference's strict load refuses a conv-shaped weight for an nn.Linear
-                        raise RuntimeError(f"Error(s) in loading state_dict for UNet3DConditionModel: size mismatch for {k}: copying a param "
-                                           f"with shape {tuple(v.shape)} from checkpoint, the shape in current model is {tuple(v.shape[:2])}.")
-                    if getattr(v, "ndim", 0) == 2:
-                        state_dict[k] = v.reshape(v.shape[0], v.shape[1], 1, 1)
+        state_dict = self._engine_layout(state_dict, strict)
         missing = [k for k in spec if k not in state_dict]
         unexpected = [k for k in state_dict if k not in spec]
         if strict and (missing or unexpected):
             raise RuntimeError(f"Error(s) in loading state_dict for UNet3DConditionModel: missing {missing[:4]}... "
                                f"unexpected {unexpected[:4]}...")
-        self.engine.load_state_dict({k: v for k, v in state_dict.items() if k in spec})
+        given = {k: v for k, v in state_dict.items() if k in spec}
+        if missing and self.engine.ready & Engine.UNET:      # strict=False, some keys of a built model: those tensors move, in place
+            self.engine.update_state_dict(given)
+            return self
+        self.engine.load_state_dict(given)
         self.engine.finalize(Engine.UNET)
+        return self
+
+    def sync_from(self, source, only_trainable: bool = False):
+        """Follow weights that move: ``hip_unet.sync_from(unet, only_trainable=True)`` in front of the validation block of
+        ``train_finetune_videodiffusion.py:320-335`` brings the built model to the live module's parameters (:47-51,117-121: attn1.to_q,
+        attn2.to_q, attn_temp.*) on the current stream -- ``Engine.update_state_dict``; names this model does not have are ignored.
+        ``source``: an ``nn.Module``, a mapping, or an iterable of ``(name, tensor)``."""
+        spec = self.state_dict_spec()
+        sd = self._engine_layout(dict(named_tensors(source, only_trainable)), strict=False)
+        self.engine.update_state_dict({k: v for k, v in sd.items() if k in spec})
         return self
 
     def init_synthetic(self, seed: int = 42, mode: str = "reference_init"):

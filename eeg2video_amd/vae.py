@@ -13,7 +13,7 @@ from typing import Optional
 
 import torch
 
-from .engine import Engine
+from .engine import Engine, named_tensors
 from .unet import FrozenDict
 from .weights import UNetConfig, VAEConfig, synth_state_dict, vae_param_spec
 
@@ -93,8 +93,19 @@ class AutoencoderKL:
         missing = [k for k in spec if k not in state_dict]
         if strict and missing:
             raise RuntimeError(f"Error(s) in loading state_dict for AutoencoderKL: missing {missing[:4]}...")
-        self.engine.load_state_dict({k: v for k, v in state_dict.items() if k in spec}, prefix="vae.")
+        given = {k: v for k, v in state_dict.items() if k in spec}
+        if missing and self.engine.ready & Engine.VAE:       # strict=False, some keys of a built model: those tensors move, in place
+            self.engine.update_state_dict(given, prefix="vae.")
+            return self
+        self.engine.load_state_dict(given, prefix="vae.")
         self.engine.finalize(Engine.VAE)
+        return self
+
+    def sync_from(self, source, only_trainable: bool = False):
+        """Bring the built VAE to the tensors of ``source`` (an ``nn.Module``, a mapping, or ``(name, tensor)`` pairs) in place, on the
+        current stream (``Engine.update_state_dict``); names this model does not have are ignored."""
+        spec = self.state_dict_spec()
+        self.engine.update_state_dict({k: v for k, v in named_tensors(source, only_trainable) if k in spec}, prefix="vae.")
         return self
 
     def init_synthetic(self, seed: int = 43, mode: str = "reference_init"):

@@ -95,7 +95,8 @@ const char* e2v_last_error(const e2v_ctx* ctx);      /* ctx may be NULL: last er
 /* replaces: ModelMixin.from_pretrained / load_state_dict (unet.py:415-449, inference_eeg2video.py:69).
  * `key` is the reference state-dict key; UNet keys as they are ("conv_in.weight", "down_blocks.0....",
  * SURVEY App. D), VAE keys prefixed "vae." ("vae.decoder.conv_in.weight").  `data` is a HOST pointer in
- * the torch layout (Conv2d [Cout,Cin,kh,kw], Linear [out,in]); the shape is checked against the config. */
+ * the torch layout (Conv2d [Cout,Cin,kh,kw], Linear [out,in]); the shape is checked against the config.
+ * dtype: E2V_F32, E2V_F16 or E2V_BF16 (16-bit checkpoints are widened to fp32, exactly). */
 e2v_status e2v_load_tensor(e2v_ctx* ctx, const char* key, const void* host_data, e2v_dtype dtype,
                            const int64_t* shape, int ndim);
 /* number of keys the config expects / a key by index (for loaders that iterate) */
@@ -105,6 +106,21 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * which: bit 0 = UNet, bit 1 = VAE, bit 2 = semantic predictor (keys "semantic.mlp.{0,2,4,6,8}.{weight,bias}");
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
+/* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
+ * pipeline is built around the LIVE unet, and only attn1.to_q, attn2.to_q and attn_temp.* move between two validations, :47-51)
+ * and load_state_dict(partial, strict=False) on a built model.
+ * Overwrites one tensor of a FINALIZED part in place: every form of it that exists on the device (the fp32 matrix or its slice of a
+ * fused / interleaved one, the bf16 and fp16 copies, the f32x3 planes, every 3x3-conv layout already built) receives the new values,
+ * with the roundings finalize uses -- the device state is bit-identical to a fresh context that loaded the state dict with this
+ * tensor replaced and was finalized in the same mode.  Forms not built yet stay unbuilt and derive from the new values on first use.
+ * `key`: any expected key (UNet, "vae.", "semantic.").  dtype: E2V_F32, E2V_F16 or E2V_BF16 (E2V_F32X3: E2V_EINVAL).
+ * on_device = 1: `data` is a device pointer on the ctx's device, read on `stream` (no host round trip); on_device = 0: a host
+ * pointer, copied into the workspace pool in its own type (hipMemcpyAsync: pinned memory must stay valid until the stream has
+ * passed the call) and widened on the device.  Stream-ordered: calls queued earlier on `stream` see the old weights, later ones
+ * the new; no device synchronisation, and no allocation once the workspace of such a call is cached (e2v_device_bytes does not move).
+ * Part not finalized: E2V_ESTATE (use e2v_load_tensor); unknown key / shape mismatch: E2V_ENOWEIGHT as e2v_load_tensor. */
+e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
+                             const int64_t* shape, int ndim, e2v_stream stream);
 
 /* ---- schedule (host, integer-exact) ---------------------------------------------------------------- */
 /* replaces: DDIMScheduler.set_timesteps (call site pipeline_tuneeeg2video.py:287-288).
