@@ -97,6 +97,9 @@ SIGNATURES = {
     "e2v_op_rowblock_sums": (_i, [_ctx, _p, _i64, _i, _p, _stream]),
     "e2v_op_describe_dispatch": (_i, [_ctx, _i, _i, _i, _i, _i, _i, C.c_char_p, _i64, c_int64_p]),
     "e2v_op_weight_forms": (_i, [_ctx, C.c_char_p, C.POINTER(_i)]),
+    "e2v_op_pool_guard_report": (_i, [_ctx, c_int64_p, c_int64_p, C.c_char_p, _i64]),
+    "e2v_op_pool_gets": (_i64, [_ctx]),
+    "e2v_op_pool_guard_selftest": (_i, [_ctx, _i64, _i64, _stream]),
     "e2v_op_unet_forward_taps": (_i, [_ctx, _p, c_int64_p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, c_int64_p, C.POINTER(_i), _stream]),
 }
 

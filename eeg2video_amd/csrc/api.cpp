@@ -1,4 +1,5 @@
 // extern "C" surface of libeeg2video_hip.so (include/eeg2video_hip.h, include/eeg2video_hip_ops.h).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -142,6 +143,7 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
 void e2v_destroy(e2v_ctx* c) {
     if (!c) return;
     if (c->device < 0) { delete c; return; }
+    c->pool.closing();                                       // (E2V_POOL_GUARD: the step caches released below are not compared any more)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     (void)e2v_comm_destroy(c);
@@ -149,8 +151,8 @@ void e2v_destroy(e2v_ctx* c) {
     for (float* p : c->owned) (void)hipFree(p);
     for (auto& part : c->owned_part) for (float* p : part) (void)hipFree(p);
     if (c->stream_ev) (void)hipEventDestroy(c->stream_ev);
-    if (c->gn_part) (void)hipFree(c->gn_part);
-    if (c->gn_scale) (void)hipFree(c->gn_scale);
+    if (c->gn_part_base) (void)hipFree(c->gn_part_base);
+    if (c->gn_scale_base) (void)hipFree(c->gn_scale_base);
     if (c->d_timesteps) (void)hipFree(c->d_timesteps);
     delete c;
 }
@@ -984,6 +986,49 @@ e2v_status e2v_op_to_channels_last(e2v_ctx* c, const float* in, float* out, int 
 e2v_status e2v_op_from_channels_last(e2v_ctx* c, const float* in, int ld, float* out, int n, int C, int FHW, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] { cl_to_ncfhw(in, ld, out, n, C, FHW, 1.f, 0.f, 0, 0.f, 0.f, S(c, stream)); E2V_HIP(hipGetLastError()); });
+}
+
+// Test aid (E2V_POOL_GUARD, runtime.h): drain the stream, compare the guard zones of the blocks that are still live -- pool blocks,
+// dev_alloc blocks, the GroupNorm workspaces -- and hand out the totals since the previous report.
+e2v_status e2v_op_pool_guard_report(e2v_ctx* c, int64_t* blocks_checked, int64_t* violations, char* buf, int64_t cap) {
+    if (!c) return E2V_EINVAL;
+    if (!blocks_checked || !violations || cap < 0 || (cap > 0 && !buf)) { c->err = "null argument"; return E2V_EINVAL; }
+    return guarded(c, [&] {
+        E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no guarded blocks in a dry run");
+        const hipStream_t s = c->last_stream;
+        c->pool.check_live(s);
+        for (const auto& kv : c->guard_dev)
+            c->guard_tally.check(kv.second, kv.first == c->gn_part_base || kv.first == c->gn_scale_base ? "GroupNorm workspace" : "dev_alloc", s);
+        E2V_HIP(hipStreamSynchronize(s));
+        E2V_HIP(hipGetLastError());
+        c->guard_tally.collect();
+        std::string text;
+        c->guard_tally.take(*blocks_checked, *violations, text);
+        if (cap > 0) {
+            const size_t n = std::min(text.size(), (size_t)cap - 1);
+            std::memcpy(buf, text.data(), n);
+            buf[n] = 0;
+        }
+    });
+}
+
+int64_t e2v_op_pool_gets(const e2v_ctx* c) { return c ? c->pool.gets() : 0; }
+
+// Test aid: the detector's own test.  Takes one block of payload_bytes through the pool, sets the word `offset` bytes into its trailing
+// guard zone to zero from the host side (hipMemsetAsync: an address inside the block the pool allocated) and releases the block.
+e2v_status e2v_op_pool_guard_selftest(e2v_ctx* c, int64_t payload_bytes, int64_t offset, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        const int kib = pool_guard_kib();
+        E2V_REQUIRE(kib > 0, E2V_ESTATE, "E2V_POOL_GUARD is off");
+        E2V_REQUIRE(payload_bytes > 0 && payload_bytes % 4 == 0 && offset >= 0 && offset % 4 == 0 && offset + 4 <= (int64_t)kib * 1024, E2V_EINVAL,
+                    "the payload is whole words and the offset a word inside the guard zone");
+        hipStream_t s = S(c, stream);
+        float* p = c->pool.get_bytes((size_t)payload_bytes);
+        hipError_t e = hipMemsetAsync(reinterpret_cast<char*>(p) + payload_bytes + offset, 0, 4, s);
+        c->pool.put(p);
+        E2V_HIP(e);
+    });
 }
 
 e2v_status e2v_op_set_knob(const char* name, int value) {

@@ -411,4 +411,32 @@ void cvt_rows(const void* in, int ld_in, int in_bf16, void* out, int ld_out, int
         E2V_KLAUNCH((cvt_rows_kernel<float, float>), g, b, 0, s, static_cast<const float*>(in), ld_in, static_cast<float*>(out), ld_out, (size_t)rows, cols, cols_out);
 }
 
+// E2V_POOL_GUARD (runtime.h): compare the two guard zones of one block with the pattern, in 16-bit units (a 16-bit tensor may end on
+// a 2-byte boundary).  One workgroup; each thread keeps the first altered unit of its stride, thread 0 folds the 256 candidates and
+// writes the slot -- plain loads and stores, nothing shared between launches.
+__global__ __launch_bounds__(256) void pool_guard_check_kernel(const unsigned short* __restrict__ lead, const unsigned short* __restrict__ trail,
+                                                               unsigned units, unsigned* __restrict__ slot) {
+    __shared__ unsigned first[2][256];
+    for (int z = 0; z < 2; ++z) {
+        const unsigned short* p = z ? trail : lead;
+        unsigned f = 0xFFFFFFFFu;
+        for (unsigned i = threadIdx.x; i < units; i += 256)
+            if (p[i] != (unsigned short)(kGuardPattern & 0xFFFFu) && f == 0xFFFFFFFFu) f = i;
+        first[z][threadIdx.x] = f;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int z = 0; z < 2; ++z) {
+            unsigned f = 0xFFFFFFFFu;
+            for (int t = 0; t < 256; ++t) f = first[z][t] < f ? first[z][t] : f;
+            slot[z] = f;
+        }
+}
+void pool_guard_check(const void* lead, const void* trail, size_t guard_bytes, uint32_t* slot, hipStream_t s) {
+    E2V_KLAUNCH(pool_guard_check_kernel, dim3(1), dim3(256), 0, s, static_cast<const unsigned short*>(lead),
+                static_cast<const unsigned short*>(trail), (unsigned)(guard_bytes / 2), slot);
+    const hipError_t e = hipGetLastError();                  // (e.g. a stream the caller has destroyed since)
+    if (e != hipSuccess) throw Error(E2V_EHIP, std::string("pool_guard_check: ") + hipGetErrorString(e));
+}
+
 }  // namespace e2v

@@ -144,6 +144,14 @@ float* e2v_ctx::dev_alloc(size_t floats) {
     void* p = nullptr;
     const size_t bytes = std::max<size_t>(floats, 1) * sizeof(float);
     if (dry_run()) return dry_fake_ptr(bytes);               // e2v_op_describe_dispatch: an address nobody dereferences, not owned
+    if (const int kib = pool_guard_kib()) {                  // E2V_POOL_GUARD: guards on both sides, payload poisoned before its first write
+        const GuardBlock b = guard_alloc(bytes, (size_t)kib * 1024, nullptr, true);
+        (alloc_part >= 0 ? owned_part[alloc_part] : owned).push_back(static_cast<float*>(b.base));
+        owned_bytes[b.base] = b.total;
+        weight_bytes += b.total;
+        guard_dev[b.base] = b;
+        return reinterpret_cast<float*>(b.data());
+    }
     E2V_HIP(hipMalloc(&p, bytes));
     (alloc_part >= 0 ? owned_part[alloc_part] : owned).push_back(static_cast<float*>(p));
     owned_bytes[p] = bytes;
@@ -155,6 +163,7 @@ void e2v_ctx::free_part(int part) {
     for (float* p : owned_part[part]) {
         auto it = owned_bytes.find(p);
         if (it != owned_bytes.end()) { weight_bytes -= it->second; owned_bytes.erase(it); }
+        guard_dev.erase(p);
         (void)hipFree(p);
     }
     owned_part[part].clear();
@@ -788,16 +797,26 @@ struct Runner {
     }
 
     void gn_ws(int samples, int P, int C) {
-        auto grow = [&](float*& p, size_t& have, size_t need) {
+        auto grow = [&](float*& p, void*& base, size_t& have, size_t need) {
             if (need <= have) return;
             E2V_HIP(hipStreamSynchronize(s));
-            if (p && !dry_run()) (void)hipFree(p);
-            E2V_HIP(hipMalloc((void**)&p, need * sizeof(float)));
+            if (base && !dry_run()) { c->guard_dev.erase(base); (void)hipFree(base); }
+            p = nullptr; base = nullptr; have = 0;
+            const int kib = dry_run() ? 0 : pool_guard_kib();
+            if (kib > 0) {                                               // E2V_POOL_GUARD: guarded like a dev_alloc block
+                const GuardBlock b = guard_alloc(need * sizeof(float), (size_t)kib * 1024, s, true);
+                c->guard_dev[b.base] = b;
+                base = b.base;
+                p = reinterpret_cast<float*>(b.data());
+            } else {
+                E2V_HIP(hipMalloc(&base, need * sizeof(float)));
+                p = static_cast<float*>(base);
+            }
             if (dry_run()) p = dry_fake_ptr(need * sizeof(float));       // (pointers steer the graph: a null workspace reads as "no GroupNorm in front")
             have = need;
         };
-        grow(c->gn_part, c->gn_part_floats, (size_t)samples * groupnorm_chunks(P) * C * 2);
-        grow(c->gn_scale, c->gn_scale_floats, (size_t)samples * C * 2);
+        grow(c->gn_part, c->gn_part_base, c->gn_part_floats, (size_t)samples * groupnorm_chunks(P) * C * 2);
+        grow(c->gn_scale, c->gn_scale_base, c->gn_scale_floats, (size_t)samples * C * 2);
     }
 
     // what gn and gn_stats share: the two sources, the affine, the slabs and the workspaces (grown here)

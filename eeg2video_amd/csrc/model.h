@@ -150,6 +150,14 @@ struct e2v_ctx {
     std::vector<float*> owned;                                   // packed weights + misc device blocks
     size_t weight_bytes = 0;
     e2v::Pool pool;
+    // E2V_POOL_GUARD (runtime.h): the tally of this context, and the guarded blocks outside the pool -- dev_alloc blocks and the
+    // GroupNorm workspaces -- by base address (checked by e2v_op_pool_guard_report, freed by their base)
+    e2v::GuardTally guard_tally;
+    std::unordered_map<void*, e2v::GuardBlock> guard_dev;
+    void* gn_part_base = nullptr; void* gn_scale_base = nullptr;      // what hipFree takes (== gn_part / gn_scale while unguarded)
+    e2v_ctx() { pool.bind(&last_stream, &guard_tally); }
+    e2v_ctx(const e2v_ctx&) = delete;
+    e2v_ctx& operator=(const e2v_ctx&) = delete;
     e2v::UNetW unet;
     e2v::VAEW vae;
     bool unet_ready = false, vae_ready = false, sem_ready = false;

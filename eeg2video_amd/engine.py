@@ -451,13 +451,29 @@ class Engine:
         return out
 
     # ------------------------------------------------------------------ kernel-level ops (channel-last tensors)
+    def _op_out(self, out, shape, strided=False):
+        """The result tensor of an op wrapper: a fresh one, or the caller's ``out=`` used where it is (never copied).  ``strided``: the
+        C ABI takes an output row stride, so a 2-D view with unit column stride will do; everywhere else ``out`` must be contiguous."""
+        if out is None:
+            return torch.empty(shape, device=self.device, dtype=torch.float32)
+        if not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32:
+            raise ValueError("`out` has to be a float32 tensor on the engine's device")
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"`out` has shape {tuple(out.shape)}, the op writes {tuple(shape)}")
+        if strided:
+            if out.dim() != 2 or (out.shape[1] > 1 and out.stride(1) != 1) or out.stride(0) < out.shape[1]:
+                raise ValueError("`out` has to be a 2-D view with unit column stride")
+        elif not out.is_contiguous():
+            raise ValueError("`out` has to be contiguous: this op takes no output row stride")
+        return out
+
     def op_conv3x3(self, x0, w, bias=None, x1=None, *, n_img, Hs, Ws, Hi=None, Wi=None, stride=1, pad_lo=1, pad_hi=1,
-                   rowbias=None, rows_per_sample=1, resid=None):
+                   rowbias=None, rows_per_sample=1, resid=None, out=None):
         Hi, Wi = Hi or Hs, Wi or Ws
         Ho = (Hi + pad_lo + pad_hi - 3) // stride + 1
         Wo = (Wi + pad_lo + pad_hi - 3) // stride + 1
         cout = w.shape[0]
-        out = torch.empty((n_img * Ho * Wo, cout), device=self.device, dtype=torch.float32)
+        out = self._op_out(out, (n_img * Ho * Wo, cout))
         p = lambda t: t.data_ptr() if t is not None else None
         self._check(self.lib.e2v_op_conv3x3(self.ctx, x0.data_ptr(), x0.shape[1], p(x1), x1.shape[1] if x1 is not None else 0,
                                             n_img, Hs, Ws, Hi, Wi, Ho, Wo, stride, pad_lo, w.data_ptr(), p(bias), cout,
@@ -465,14 +481,14 @@ class Engine:
         return out
 
     def op_conv3x3_gn(self, x0, gamma, beta, w, bias=None, x1=None, *, n_img, Hs, Ws, gn_P, groups, eps, Hi=None, Wi=None, stride=1,
-                      pad_lo=1, pad_hi=1, rowbias=None, rows_per_sample=1, resid=None):
+                      pad_lo=1, pad_hi=1, rowbias=None, rows_per_sample=1, resid=None, out=None):
         """GroupNorm + SiLU + 3x3 conv as the fp32 resnets run them (``e2v_op_conv3x3_gn``): statistics over slabs of ``gn_P`` source
         rows, affine + SiLU inside the Winograd input transform.  Raises ``ValueError`` where the conv takes no Winograd form."""
         Hi, Wi = Hi or Hs, Wi or Ws
         Ho = (Hi + pad_lo + pad_hi - 3) // stride + 1
         Wo = (Wi + pad_lo + pad_hi - 3) // stride + 1
         cout = w.shape[0]
-        out = torch.empty((n_img * Ho * Wo, cout), device=self.device, dtype=torch.float32)
+        out = self._op_out(out, (n_img * Ho * Wo, cout))
         p = lambda t: t.data_ptr() if t is not None else None
         self._check(self.lib.e2v_op_conv3x3_gn(self.ctx, x0.data_ptr(), x0.shape[1], p(x1), x1.shape[1] if x1 is not None else 0,
                                                n_img, Hs, Ws, Hi, Wi, Ho, Wo, stride, pad_lo, gn_P, groups, float(eps),
@@ -480,50 +496,84 @@ class Engine:
                                                rows_per_sample, p(resid), out.data_ptr(), _stream()))
         return out
 
-    def op_linear(self, x, w, bias=None, resid=None, geglu=False):
+    def op_linear(self, x, w, bias=None, resid=None, geglu=False, out=None):
         m, k = x.shape
         n = w.shape[0] // 2 if geglu else w.shape[0]
-        out = torch.empty((m, n), device=self.device, dtype=torch.float32)
+        out = self._op_out(out, (m, n))
         p = lambda t: t.data_ptr() if t is not None else None
         self._check(self.lib.e2v_op_linear(self.ctx, x.data_ptr(), x.stride(0), m, k, w.data_ptr(), p(bias), n, p(resid),
                                            int(geglu), out.data_ptr(), _stream()))
         return out
 
-    def op_rowblock_sums(self, x):
+    def op_rowblock_sums(self, x, out=None):
         """Canonical (sum, sum of squares) per 64-row block and column of ``x`` rounded to bf16: ``[rows / 64, C, 2]``."""
         rows, c = x.shape
-        out = torch.empty((rows // 64, c, 2), device=self.device, dtype=torch.float32)
+        out = self._op_out(out, (rows // 64, c, 2))
         self._check(self.lib.e2v_op_rowblock_sums(self.ctx, x.data_ptr(), rows, c, out.data_ptr(), _stream()))
         return out
 
-    def op_groupnorm(self, x0, gamma, beta, *, samples, P, groups, eps, silu=False, x1=None):
+    def op_groupnorm(self, x0, gamma, beta, *, samples, P, groups, eps, silu=False, x1=None, out=None):
         c = x0.shape[1] + (x1.shape[1] if x1 is not None else 0)
-        out = torch.empty((samples * P, c), device=self.device, dtype=torch.float32)
+        out = self._op_out(out, (samples * P, c))
         self._check(self.lib.e2v_op_groupnorm(self.ctx, x0.data_ptr(), x0.shape[1], x1.data_ptr() if x1 is not None else None,
                                               x1.shape[1] if x1 is not None else 0, samples, P, groups, float(eps),
                                               gamma.data_ptr(), beta.data_ptr(), int(silu), out.data_ptr(), _stream()))
         return out
 
-    def op_layernorm(self, x, gamma, beta, eps=1e-5):
-        out = torch.empty_like(x)
+    def op_layernorm(self, x, gamma, beta, eps=1e-5, out=None):
+        out = self._op_out(out, tuple(x.shape))
         self._check(self.lib.e2v_op_layernorm(self.ctx, x.data_ptr(), x.shape[0], x.shape[1], gamma.data_ptr(),
                                               beta.data_ptr(), float(eps), out.data_ptr(), _stream()))
         return out
 
-    def op_attention(self, q, k, v, *, n, F, heads, D, Nq, Nk, mode, scale):
-        """q/k/v: 2-D views (row stride = ``.stride(0)``) of channel-last buffers; returns [n*F*Nq, heads*D]."""
-        out = torch.empty((n * F * Nq, heads * D), device=self.device, dtype=torch.float32)
+    def op_attention(self, q, k, v, *, n, F, heads, D, Nq, Nk, mode, scale, out=None):
+        """q/k/v: 2-D views (row stride = ``.stride(0)``) of channel-last buffers; returns [n*F*Nq, heads*D].  ``out``: a 2-D view
+        whose ``.stride(0)`` is the output row stride ``ldo``."""
+        out = self._op_out(out, (n * F * Nq, heads * D), strided=True)
         assert k.stride(0) == v.stride(0)
         self._check(self.lib.e2v_op_attention(self.ctx, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0),
                                               out.data_ptr(), out.stride(0), n, F, heads, D, Nq, Nk, mode, float(scale),
                                               _stream()))
         return out
 
-    def op_temporal_attention(self, qkv, *, n, F, HW, heads, D, scale):
-        out = torch.empty((n * F * HW, heads * D), device=self.device, dtype=torch.float32)
+    def op_temporal_attention(self, qkv, *, n, F, HW, heads, D, scale, out=None):
+        out = self._op_out(out, (n * F * HW, heads * D))
         self._check(self.lib.e2v_op_temporal_attention(self.ctx, qkv.data_ptr(), out.data_ptr(), n, F, HW, heads, D,
                                                        float(scale), _stream()))
         return out
+
+    def op_to_channels_last(self, x, *, Cpad=None, out=None):
+        """``[n, C, FHW]`` -> channel-last rows ``[n * FHW, Cpad]`` (``e2v_op_to_channels_last``; columns C.. are written as zeros)."""
+        n, c, fhw = x.shape
+        cpad = Cpad or c
+        out = self._op_out(out, (n * fhw, cpad))
+        self._check(self.lib.e2v_op_to_channels_last(self.ctx, x.data_ptr(), out.data_ptr(), n, c, cpad, fhw, _stream()))
+        return out
+
+    def op_from_channels_last(self, x, *, n, C, out=None):
+        """Channel-last rows ``[n * FHW, >= C]`` (a 2-D view, row stride = ``.stride(0)``) -> ``[n, C, FHW]``
+        (``e2v_op_from_channels_last``)."""
+        fhw = x.shape[0] // n
+        out = self._op_out(out, (n, C, fhw))
+        self._check(self.lib.e2v_op_from_channels_last(self.ctx, x.data_ptr(), x.stride(0), out.data_ptr(), n, C, fhw, _stream()))
+        return out
+
+    def pool_guard_report(self):
+        """Test aid (``e2v_op_pool_guard_report``, switch ``E2V_POOL_GUARD``): ``(blocks_checked, violations, text)`` since the previous
+        report, one line of ``text`` per violated guard zone."""
+        checked, bad = C.c_int64(0), C.c_int64(0)
+        buf = C.create_string_buffer(1 << 16)
+        self._check(self.lib.e2v_op_pool_guard_report(self.ctx, C.byref(checked), C.byref(bad), buf, len(buf)))
+        return checked.value, bad.value, buf.value.decode()
+
+    def pool_gets(self) -> int:
+        """Test aid (``e2v_op_pool_gets``): blocks the workspace pool has handed out so far."""
+        return int(self.lib.e2v_op_pool_gets(self.ctx))
+
+    def pool_guard_selftest(self, payload_bytes: int, offset: int) -> None:
+        """Test aid (``e2v_op_pool_guard_selftest``): take one guarded block, alter the word ``offset`` bytes into its trailing guard
+        zone from the host, release it -- the next report must name it."""
+        self._check(self.lib.e2v_op_pool_guard_selftest(self.ctx, int(payload_bytes), int(offset), _stream()))
 
 
 def named_tensors(source, only_trainable: bool = False):

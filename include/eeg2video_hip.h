@@ -12,6 +12,9 @@
  *     parameter says "host", pointers are DEVICE pointers of the ctx's device, owned by the caller.
  *   - the library owns weights and workspace inside the ctx; after e2v_finalize_weights() and one
  *     warm-up call of a given shape no further device allocation happens (workspace is cached).
+ *     (The debug switch E2V_POOL_GUARD -- eeg2video_hip_ops.h: e2v_op_pool_guard_report, off by default --
+ *     puts guard zones around these blocks; while it is on, allocations are larger, some calls synchronise and
+ *     the tally of released blocks grows until e2v_op_pool_guard_report is called.)
  *   - one ctx per device; calls on one ctx must be externally serialised (the reference is a single
  *     Python thread on the default stream, @torch.no_grad()).  `stream` is a hipStream_t (NULL = the
  *     default stream); all work of a call is enqueued on it and the call does not synchronise unless

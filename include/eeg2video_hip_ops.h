@@ -120,6 +120,31 @@ enum {
 };
 e2v_status e2v_op_weight_forms(e2v_ctx* ctx, const char* key, int* mask);
 
+/* Test aid for the bounds tests: the guarded workspace pool.  While the run-time switch "E2V_POOL_GUARD" (e2v_op_set_knob, or the
+ * environment variable; default 0) is N > 0, every block the library allocates for its own kernels -- workspace-pool blocks (activations,
+ * converted operands of the 16-bit op entry points, split-K and Winograd workspaces), the weight layouts of e2v_finalize_weights and those
+ * built on first use, the GroupNorm workspaces -- lies between two guard zones of N KiB inside a larger allocation; the second zone starts
+ * at the payload's exact last byte.  Guards and payload are filled with 0x7FC07FC0 (a NaN as fp32, and per half as bf16 and IEEE half)
+ * before the block is handed out, so a result that depends on memory nobody wrote carries NaNs.  A pool block's zones are compared with
+ * the pattern on the context's stream when it is released.  This call drains the stream, compares the zones of the blocks still live
+ * (weight layouts and GroupNorm workspaces always are) and returns the totals since the previous report: blocks compared, zones found
+ * altered, and one text line per altered zone in buf (NUL-terminated, cut at cap): kind of block, payload bytes, side, byte offset of
+ * the first altered word.  Every released block keeps a result slot (8 bytes of device memory and a host record) until the next
+ * report, so a guarded run that never calls this grows by 128 KiB per 16384 released blocks.  The switch takes effect for blocks allocated from then on (the pool drops its free blocks when it flips):
+ * set it before e2v_create to have the weights guarded.  Off, the library makes no extra launch, byte or synchronisation.
+ * E2V_ESTATE on a host-only context.  No reference counterpart. */
+e2v_status e2v_op_pool_guard_report(e2v_ctx* ctx, int64_t* blocks_checked, int64_t* violations, char* buf, int64_t cap);
+
+/* Test aid: how many blocks the context's workspace pool has handed out so far (guarded or not) -- the number of pool tensors a call
+ * takes is the difference across it; a guarded run of the same call must report at least that many blocks checked. */
+int64_t e2v_op_pool_gets(const e2v_ctx* ctx);
+
+/* Test aid: the test of the detector above.  With the switch on, takes one pool block of payload_bytes (a multiple of 4), sets the 32-bit
+ * word `offset` bytes (a multiple of 4, inside the zone) into its TRAILING guard zone to zero with hipMemsetAsync on `stream` -- an
+ * address inside the block the pool allocated -- and releases the block: the next report shows exactly that violation, the one after it
+ * none.  E2V_ESTATE while the switch is off.  No reference counterpart. */
+e2v_status e2v_op_pool_guard_selftest(e2v_ctx* ctx, int64_t payload_bytes, int64_t offset, e2v_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
