@@ -7,6 +7,7 @@ Layout (only what the path needs):
 * ``unet`` / ``vae`` / ``scheduler`` / ``pipeline``   mirrors of the reference's interfaces
   (``UNet3DConditionModel.forward`` / ``.from_pretrained``, ``AutoencoderKL``, the six scheduler types the pipeline's
   constructor accepts, ``TuneAVideoPipeline.__call__`` / ``.from_pretrained``)
+* ``text_encoder`` / ``pipeline_tuneavideo``   ``transformers``' ``CLIPTextModel`` on the library and the text-prompt twin of the pipeline
 * ``semantic`` / ``util``   the steps either side of the path: Semantic Predictor, DDIM inversion, ``save_videos_grid``
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
@@ -14,9 +15,9 @@ Layout (only what the path needs):
 
 The compute path has no CPU fallback: without the built library or without a GPU it raises.
 """
-from .weights import TINY_SEMANTIC, TINY_UNET, TINY_VAE, SemanticConfig, UNetConfig, VAEConfig  # noqa: F401
+from .weights import TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, SemanticConfig, TextConfig, UNetConfig, VAEConfig  # noqa: F401
 
-__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL",
+__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig",
            "DDIMScheduler", "PNDMScheduler", "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler",
            "DPMSolverMultistepScheduler", "TuneAVideoPipeline", "build_pipeline", "save_videos_grid"]
 
@@ -28,6 +29,9 @@ def __getattr__(name):          # lazy: importing the package must not need torc
     if name == "UNet3DConditionModel":
         from .unet import UNet3DConditionModel
         return UNet3DConditionModel
+    if name == "CLIPTextModel":
+        from .text_encoder import CLIPTextModel
+        return CLIPTextModel
     if name == "AutoencoderKL":
         from .vae import AutoencoderKL
         return AutoencoderKL

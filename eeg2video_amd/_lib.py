@@ -30,6 +30,8 @@ class E2VConfig(C.Structure):
         ("steps_offset", C.c_int),
         ("sem_in_features", C.c_int), ("sem_hidden", C.c_int), ("sem_tokens", C.c_int),
         ("attention_heads_per_block", C.c_int * 4),
+        ("text_vocab_size", C.c_int), ("text_hidden", C.c_int), ("text_heads", C.c_int), ("text_layers", C.c_int),
+        ("text_intermediate", C.c_int), ("text_max_positions", C.c_int), ("text_act", C.c_int), ("text_norm_eps", C.c_float),
     ]
 
 
@@ -67,6 +69,7 @@ SIGNATURES = {
     "e2v_vae_encode": (_i, [_ctx, _p, _i, _i, _i, _p, _p, _stream]),
     "e2v_generate": (_i, [_ctx, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _stream]),
     "e2v_semantic_predict": (_i, [_ctx, _p, _i, _p, _stream]),
+    "e2v_text_encode": (_i, [_ctx, c_int64_p, _i, _i, _p, _stream]),
     "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
     "e2v_cfg_combine": (_i, [_ctx, _p, _p, _f, _p, _i64, _stream]),
@@ -91,6 +94,7 @@ SIGNATURES = {
     "e2v_op_layernorm": (_i, [_ctx, _p, _i64, _i, _p, _p, _f, _p, _stream]),
     "e2v_op_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _stream]),
     "e2v_op_temporal_attention": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _i, _f, _stream]),
+    "e2v_op_causal_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
     "e2v_op_set_knob": (_i, [C.c_char_p, _i]),

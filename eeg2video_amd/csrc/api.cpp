@@ -122,6 +122,16 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
         }
         E2V_REQUIRE(cfg->cross_attention_dim % 4 == 0 && cfg->in_channels % 4 == 0, E2V_EINVAL,
                     "cross_attention_dim and in_channels must be multiples of 4");
+        if (cfg->text_layers != 0) {                     // (all zero: no text encoder)
+            E2V_REQUIRE(cfg->text_layers > 0 && cfg->text_vocab_size > 0 && cfg->text_heads > 0 && cfg->text_intermediate > 0 &&
+                            cfg->text_intermediate % 4 == 0 && (cfg->text_act == 0 || cfg->text_act == 1) && cfg->text_norm_eps > 0.f,
+                        E2V_EINVAL, "bad text encoder config (sizes must be positive, text_intermediate a multiple of 4, text_act 0 = quick_gelu or 1 = gelu)");
+            E2V_REQUIRE(cfg->text_hidden == 64 * cfg->text_heads, E2V_EINVAL,
+                        "text_hidden must be 64 * text_heads: 64 is the head dim of the text attention kernel's only instance");
+            E2V_REQUIRE(cfg->text_hidden % 4 == 0 && cfg->text_hidden <= 1280, E2V_EINVAL, "text_hidden must be a multiple of 4, at most 1280 (the LayerNorm kernel's limit)");
+            E2V_REQUIRE(cfg->text_max_positions >= 1 && cfg->text_max_positions <= kTextAttnMaxT, E2V_EINVAL,
+                        "text_max_positions must be in 1 .. " + std::to_string(kTextAttnMaxT) + ": the text attention kernel keeps K and V of a prompt in LDS");
+        }
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
@@ -211,7 +221,8 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     auto it = c->raw.find(key);
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
-    const bool ready = k.rfind("semantic.", 0) == 0 ? c->sem_ready : k.rfind("vae.", 0) == 0 ? c->vae_ready : c->unet_ready;
+    const int part = e2v_ctx::key_part(k);
+    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : c->unet_ready;
     E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
@@ -224,6 +235,10 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
     if (!c) return E2V_EINVAL;
     if (!key || !data || !shape) { c->err = "null argument"; return E2V_EINVAL; }
     if (dtype != E2V_F32 && dtype != E2V_F16 && dtype != E2V_BF16) { c->err = "e2v_update_tensor: the source is fp32, fp16 or bf16"; return E2V_EINVAL; }
+    if (e2v_ctx::key_part(key) == 8) {
+        c->err = "e2v_update_tensor: the text encoder is frozen on this path (train_finetune_videodiffusion.py:115); load a new one with e2v_load_tensor + e2v_finalize_weights";
+        return E2V_EINVAL;
+    }
     return guarded(c, [&] {
         E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no weights in a dry run");
         const WTensor& t = updatable(c, key);
@@ -246,7 +261,7 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(which >= 1 && which <= 7, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor");
+        E2V_REQUIRE(which >= 1 && which <= 15, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder");
         c->finalize(which);
     });
 }
@@ -319,6 +334,29 @@ e2v_status e2v_semantic_predict(e2v_ctx* c, const float* eeg, int B, float* out,
             if (!last) x = std::move(y);
         }
         E2V_HIP(hipGetLastError());
+    });
+}
+
+// CLIPTextModel.forward(input_ids)[0]: the ids are checked and narrowed on the host, everything else is enqueued on the stream
+e2v_status e2v_text_encode(e2v_ctx* c, const int64_t* host_ids, int B, int T, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(c->cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
+        E2V_REQUIRE(c->text_ready, E2V_ESTATE, "text encoder weights are not finalized");
+        E2V_REQUIRE(host_ids && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0, E2V_EINVAL, "null or misaligned argument (out: 16 bytes)");
+        E2V_REQUIRE(B > 0 && T >= 1 && T <= c->cfg.text_max_positions, E2V_ESHAPE,
+                    "input_ids must be [B >= 1][1 <= T <= text_max_positions = " + std::to_string(c->cfg.text_max_positions) + "]");
+        const size_t n = (size_t)B * T;
+        std::vector<int> ids(n);
+        for (size_t i = 0; i < n; ++i) {
+            E2V_REQUIRE(host_ids[i] >= 0 && host_ids[i] < c->cfg.text_vocab_size, E2V_EINVAL,
+                        "input id " + std::to_string((long long)host_ids[i]) + " is outside [0, text_vocab_size = " + std::to_string(c->cfg.text_vocab_size) + ")");
+            ids[i] = (int)host_ids[i];
+        }
+        hipStream_t s = S(c, stream);
+        Act d(c->pool, (int64_t)n, 1);
+        E2V_HIP(hipMemcpyAsync(d.p, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+        c->text_encode(reinterpret_cast<const int*>(d.p), B, T, out, s);
     });
 }
 
@@ -974,6 +1012,18 @@ e2v_status e2v_op_temporal_attention(e2v_ctx* c, const float* qkv, float* out, i
         } else {
             temporal_attention(qkv, 3 * C, out, C, n, F, HW, heads, D, scale, s);
         }
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// fp32 in every compute mode, as e2v_text_encode runs it
+e2v_status e2v_op_causal_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(qkv && out && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0, E2V_EINVAL, "null or misaligned argument (qkv: 16 bytes)");
+        E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && T <= kTextAttnMaxT, E2V_ESHAPE, "causal attention: B, heads >= 1 and 1 <= T <= " + std::to_string(kTextAttnMaxT));
+        E2V_REQUIRE(ldqkv % 4 == 0 && ldqkv >= 3 * 64 * heads && ldo >= 64 * heads, E2V_EINVAL, "bad strides: ldqkv >= 3 * 64 * heads (a multiple of 4), ldo >= 64 * heads");
+        text_causal_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
         E2V_HIP(hipGetLastError());
     });
 }

@@ -206,6 +206,18 @@ void temporal_attention(const float* qkv, int ld, float* out, int ldo, int n, in
 void softmax_rows(float* x, int ld, int rows, int cols, hipStream_t s, void* out_bf16 = nullptr, int out_mode = 1);   // out_mode: 1 bf16 / 2 fp16
 
 // ---------------------------------------------------------------------------------------
+// CLIP text encoder (text.hip): fp32 in every compute mode
+// ---------------------------------------------------------------------------------------
+// out[row][:] = tok[ids[row]][:] + pos[row % T][:]  (ids: device int32, already range-checked on the host; C a multiple of 4)
+void text_embed(const int* ids, const float* tok, const float* pos, float* out, int rows, int T, int C, hipStream_t s);
+// causal self-attention over each of B prompts of T tokens, head dim 64, scale 64^-0.5: qkv [B*T][ldqkv] holds q | k | v of
+// heads * 64 columns each, out [B*T][ldo].  K and V of a head live in LDS, which bounds T:
+constexpr int kTextAttnMaxT = 128;      // 2 x 128 rows x 272 bytes = 68 KiB of the CU's 160; two keys per lane
+void text_causal_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
+// in place: act 0 = quick-GELU x sigmoid(1.702 x), 1 = erf GELU; count a multiple of 4
+void text_activation(float* x, long long count, int act, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)
 // ---------------------------------------------------------------------------------------
 void ncfhw_to_cl(const float* in, float* out, int n, int C, int Cpad, int FHW, float scale, hipStream_t s, int out_bf16 = 0);

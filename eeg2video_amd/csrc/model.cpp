@@ -138,6 +138,21 @@ void e2v_ctx::expected_keys() {
                              cfg.sem_tokens * cfg.cross_attention_dim};
         for (int i = 0; i < 5; ++i) s.lin("semantic.mlp." + std::to_string(2 * i), dims[i + 1], dims[i]);
     }
+
+    // ---- CLIP text encoder ("text." prefix; the keys of the SD-v1-4 text_encoder checkpoint, transformers CLIPTextModel) ----
+    if (cfg.text_layers > 0) {
+        const int C = cfg.text_hidden, I = cfg.text_intermediate;
+        const std::string m = "text.text_model.";
+        s.add(m + "embeddings.token_embedding.weight", {cfg.text_vocab_size, C});
+        s.add(m + "embeddings.position_embedding.weight", {cfg.text_max_positions, C});
+        for (int i = 0; i < cfg.text_layers; ++i) {
+            const std::string l = m + "encoder.layers." + std::to_string(i);
+            for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) s.lin(l + ".self_attn." + n, C, C);
+            s.norm(l + ".layer_norm1", C); s.norm(l + ".layer_norm2", C);
+            s.lin(l + ".mlp.fc1", I, C); s.lin(l + ".mlp.fc2", C, I);
+        }
+        s.norm(m + "final_layer_norm", C);
+    }
 }
 
 float* e2v_ctx::dev_alloc(size_t floats) {
@@ -334,6 +349,7 @@ namespace {
 struct Packer {
     e2v_ctx* c;
     hipStream_t s = nullptr;
+    bool f32_only = false;           // the text encoder: a linear keeps its fp32 matrix and nothing else, in every compute mode
     const WTensor& t(const std::string& k) {
         auto it = c->raw.find(k);
         E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, "unknown key " + k);
@@ -365,6 +381,12 @@ struct Packer {
     // every form of one [out][in] matrix: fp32 as it is, bf16 with rows padded to a multiple of 8 (16-byte pieces), f32x3 planes
     LinW mk_lin(const float* w, const float* b, int in, int out) {
         const int in16 = (in + 7) / 8 * 8;
+        if (f32_only) {
+            LinW l{w, b, in, out};
+            l.in16 = in16;
+            l.part = c->alloc_part >= 0 ? c->alloc_part : 0;
+            return l;
+        }
         const void* w16;
         if (in16 == in) {
             w16 = half(w, (size_t)out * in);
@@ -484,10 +506,9 @@ void e2v_ctx::finalize(int which) {
     AllocPart part_guard(this, -1);                  // (an error below leaves no part selected)
     // everything that can refuse the call is checked BEFORE a part is freed: a failed finalize leaves the context as it was
     E2V_REQUIRE(!(which & 4) || (cfg.sem_in_features > 0 && cfg.sem_hidden > 0), E2V_ESTATE, "the config has no semantic predictor");
-    for (const auto& k : keys) {
-        const int part = k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : 1;
-        if (which & part) P.t(k);
-    }
+    E2V_REQUIRE(!(which & 8) || cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
+    for (const auto& k : keys)
+        if (which & key_part(k)) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
     if (which & 1) {
         free_part(0);
@@ -576,6 +597,30 @@ void e2v_ctx::finalize(int which) {
             }
         }
     }
+    if (which & 8) {
+        free_part(3);
+        alloc_part = 3;
+        P.f32_only = true;
+        TextW t;
+        const std::string m = "text.text_model.";
+        const WTensor& tok = P.t(m + "embeddings.token_embedding.weight");
+        const WTensor& pos = P.t(m + "embeddings.position_embedding.weight");
+        t.tok = tok.d; t.pos = pos.d;
+        P.bind_raw(m + "embeddings.token_embedding.weight", tok.d, (int)tok.shape[0], (int)tok.shape[1]);
+        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d, (int)pos.shape[0], (int)pos.shape[1]);
+        for (int i = 0; i < cfg.text_layers; ++i) {
+            const std::string l = m + "encoder.layers." + std::to_string(i);
+            TextLayerW w;
+            w.ln1 = P.norm(l + ".layer_norm1"); w.ln2 = P.norm(l + ".layer_norm2");
+            w.qkv = P.fuse_rows({l + ".self_attn.q_proj", l + ".self_attn.k_proj", l + ".self_attn.v_proj"}, true);
+            w.out = P.lin(l + ".self_attn.out_proj");
+            w.fc1 = P.lin(l + ".mlp.fc1"); w.fc2 = P.lin(l + ".mlp.fc2");
+            t.layers.push_back(w);
+        }
+        t.ln_f = P.norm(m + "final_layer_norm");
+        P.f32_only = false;
+        text = std::move(t);
+    }
     alloc_part = -1;
     resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
@@ -596,9 +641,12 @@ void e2v_ctx::finalize(int which) {
         }
     };
     for (const auto& k : keys) {
-        const bool is_vae = k.rfind("vae.", 0) == 0;
-        if (k.rfind("semantic.", 0) == 0) continue;
-        if ((is_vae && !(which & 2)) || (!is_vae && !(which & 1))) continue;
+        const int part = key_part(k);
+        if (part == 4 || !(which & part)) continue;
+        if (part == 8) {                         // q / k / v projections live on in the fused matrix and bias
+            if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
+            continue;
+        }
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
@@ -609,6 +657,7 @@ void e2v_ctx::finalize(int which) {
     if (which & 1) unet_ready = true;
     if (which & 2) vae_ready = true;
     if (which & 4) sem_ready = true;
+    if (which & 8) text_ready = true;
 }
 
 // =====================================================================================================
@@ -654,6 +703,7 @@ void e2v_ctx::resolve_bindings() {
     visit(unet, fl, fc);
     visit(vae, fl, fc);
     for (auto& l : sem) fl(l);
+    for (auto& l : text.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
     for (auto& kv : bind) {
         WBind& b = kv.second;
         if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
@@ -1367,5 +1417,36 @@ void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, flo
     f32_out.out_f32 = true;                                                                            // moments: fp32
     Act m = R.linear(vae.quant, y.p, y.C, y.rows, f32_out);
     E2V_HIP(hipMemcpyAsync(moments_cl, m.p, (size_t)m.rows * m.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// CLIPTextModel.forward(input_ids)[0] (transformers: CLIPTextTransformer -- embeddings, pre-LN encoder layers under the causal
+// mask, final_layer_norm).  fp32 rows and fp32 arithmetic whatever the context's compute mode (the linears go the way of the
+// time-embedding MLP), so the same ids give the same bits in every mode.
+// -----------------------------------------------------------------------------------------------------
+void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t s) {
+    E2V_REQUIRE(text_ready, E2V_ESTATE, "text encoder weights are not finalized");
+    Runner R{this, s, false};
+    const int C = cfg.text_hidden, I = cfg.text_intermediate;
+    const int64_t M = (int64_t)B * T;
+    const float eps = cfg.text_norm_eps;
+    auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
+    auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
+    Act x(pool, M, C);
+    text_embed(ids, text.tok, text.pos, x.p, (int)M, T, C, s);
+    for (const TextLayerW& l : text.layers) {
+        Act h(pool, M, C);
+        ln(l.ln1, x.p, h.p);
+        Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
+        Act a(pool, M, C);
+        text_causal_attention(qkv.p, 3 * C, a.p, C, B, T, cfg.text_heads, s);
+        x = R.linear(l.out, a.p, C, M, plus(x));
+        ln(l.ln2, x.p, h.p);
+        Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
+        text_activation(f.p, M * I, cfg.text_act, s);
+        x = R.linear(l.fc2, f.p, I, M, plus(x));
+    }
+    ln(text.ln_f, x.p, out);
     E2V_HIP(hipGetLastError());
 }

@@ -90,6 +90,14 @@ struct VAEW {
     NormW enc_norm_out;
 };
 
+// CLIPTextModel (transformers: the text tower of SD-v1-4, keys "text.text_model...."): fp32 matrices only, in every compute mode
+struct TextLayerW { NormW ln1, ln2; LinW qkv, out, fc1, fc2; };      // qkv: q_proj | k_proj | v_proj fused [3C][C] with its [3C] bias
+struct TextW {
+    const float* tok = nullptr; const float* pos = nullptr;          // [vocab][C], [max_positions][C]
+    std::vector<TextLayerW> layers;
+    NormW ln_f;
+};
+
 // Where one raw state-dict tensor lives in the packed world of a finalized part (recorded by finalize(), used by e2v_update_tensor):
 //   RAW   the fp32 block the kernels read -- norm affines, plain biases (the uploaded block itself), a slice of a fused bias, the
 //         GEGLU bias (32-element groups interleaved);
@@ -160,7 +168,8 @@ struct e2v_ctx {
     e2v_ctx& operator=(const e2v_ctx&) = delete;
     e2v::UNetW unet;
     e2v::VAEW vae;
-    bool unet_ready = false, vae_ready = false, sem_ready = false;
+    e2v::TextW text;
+    bool unet_ready = false, vae_ready = false, sem_ready = false, text_ready = false;
     int conv_algo = 0;                                           // e2v_set_conv_algo: 0 auto, 1 direct, 2 / 3 Winograd F(2x2) / F(4x4) wherever it applies
     bool wino_f4 = true;                                         // auto: F(4x4,3x3) where min(Cin, Cout) >= wino4_min_c and the map, padded to
     int wino4_min_c = 128;                                       //   multiples of 4, grows by <= wino_f4_pad (E2V_WINO_F4 / _F4_MIN_C / _F4_PAD)
@@ -188,7 +197,7 @@ struct e2v_ctx {
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
     void enter_stream(hipStream_t s);
     // device blocks made by finalize(), per part (bit index of `which`), so that finalizing a part again frees what it replaces
-    std::vector<float*> owned_part[3];
+    std::vector<float*> owned_part[4];
     std::unordered_map<void*, size_t> owned_bytes;
     void* comm = nullptr; int comm_rank = 0, comm_world = 0;     // RCCL communicator of e2v_comm_init (comm.cpp)
     // e2v_op_unet_forward_taps (test aid): while set, unet_forward_cl copies the tensors the oracle exposes (emb, down0..3, mid,
@@ -224,4 +233,10 @@ struct e2v_ctx {
                              int H, int W, int T, hipStream_t s, bool cfg_pair = false, const float* host_tf = nullptr);
     void vae_decode_frames(const float* z_cl, int nframes, int h, int w, float* out_cl3, hipStream_t s, bool small_family);
     void vae_encode_frames(const float* img_cl4, int n, int H, int W, float* moments_cl8, hipStream_t s);
+    // CLIPTextModel.forward(input_ids)[0]: ids [B*T] int32 on the device (range-checked by the caller), out [B*T][text_hidden] fp32
+    void text_encode(const int* ids, int B, int T, float* out, hipStream_t s);
+    // which finalize() part owns a state-dict key: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder
+    static int key_part(const std::string& k) {
+        return k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : k.rfind("text.", 0) == 0 ? 8 : 1;
+    }
 };

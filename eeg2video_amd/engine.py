@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import SemanticConfig, UNetConfig, VAEConfig
+from .weights import TEXT_ACTS, SemanticConfig, TextConfig, UNetConfig, VAEConfig
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -28,17 +28,18 @@ def _stream() -> int:
 
 
 class Engine:
-    """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs."""
+    """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
+    the ``CLIPTextModel`` one."""
 
-    UNET, VAE, SEMANTIC = 1, 2, 4
+    UNET, VAE, SEMANTIC, TEXT = 1, 2, 4, 8
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
-                 sem_cfg: SemanticConfig = SemanticConfig()):
+                 sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
         self.lib = _lib.load()
-        self.unet_cfg, self.vae_cfg, self.sem_cfg = unet_cfg, vae_cfg, sem_cfg
+        self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -64,6 +65,8 @@ class Engine:
         cfg.vae_norm_num_groups, cfg.vae_norm_eps = vae_cfg.norm_num_groups, vae_cfg.norm_eps
         cfg.vae_scaling_factor = vae_cfg.scaling_factor
         cfg.sem_in_features, cfg.sem_hidden, cfg.sem_tokens = sem_cfg.in_features, sem_cfg.hidden, sem_cfg.tokens
+        if text_cfg is not None:
+            fill_text_config(cfg, text_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
         st = self.lib.e2v_create(C.byref(cfg), device, C.byref(ctx))
@@ -390,6 +393,24 @@ class Engine:
         self._check(self.lib.e2v_semantic_predict(self.ctx, x.data_ptr(), x.shape[0], out.data_ptr(), _stream()))
         return out
 
+    def text_encode(self, input_ids, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``CLIPTextModel.forward(input_ids)[0]`` (``e2v_text_encode``): ``[B,T]`` token ids (a tensor on any device, an array or
+        nested lists -- they travel as a HOST int64 array) -> the last hidden state ``[B,T,hidden]`` fp32 on the engine's device.
+        fp32 arithmetic whatever the engine's compute dtype.  ``out``: a contiguous fp32 ``[B,T,hidden]`` tensor to write instead."""
+        if self.text_cfg is None:
+            raise RuntimeError("this engine was built without a text encoder (Engine(..., text_cfg=TextConfig()))")
+        if isinstance(input_ids, torch.Tensor):
+            input_ids = input_ids.detach().cpu().numpy()
+        ids = np.ascontiguousarray(np.asarray(input_ids), dtype=np.int64)
+        if ids.ndim == 1:
+            ids = ids[None]
+        if ids.ndim != 2 or ids.size == 0:
+            raise ValueError(f"expected input_ids [B,T], got shape {ids.shape}")
+        b, t = ids.shape
+        out = self._op_out(out, (b, t, self.text_cfg.hidden))
+        self._check(self.lib.e2v_text_encode(self.ctx, ids.ctypes.data_as(_lib.c_int64_p), b, t, out.data_ptr(), _stream()))
+        return out
+
     def dana_noise(self, x0: torch.Tensor, eps_div: torch.Tensor, eps_same: torch.Tensor, t: Sequence[int],
                    dynamic_beta: float, time_steps: int = 500) -> torch.Tensor:
         """``[B,F,C,H,W]`` Seq2Seq latents + the two noise draws -> noised latents in the pipeline layout ``[B,C,F,H,W]``."""
@@ -542,6 +563,16 @@ class Engine:
                                                        float(scale), _stream()))
         return out
 
+    def op_causal_attention(self, qkv, *, B, T, heads, out=None):
+        """``qkv``: a 2-D view ``[B*T, 3 * heads * 64]`` (row stride = ``.stride(0)``) holding q | k | v; returns ``[B*T, heads * 64]``
+        (``e2v_op_causal_attention``: query i of a prompt attends to its keys 0 .. i).  ``out``: a 2-D view with its own row stride."""
+        out = self._op_out(out, (B * T, heads * 64), strided=True)
+        if tuple(qkv.shape) != (B * T, 3 * heads * 64) or qkv.stride(1) != 1:
+            raise ValueError(f"`qkv` has shape {tuple(qkv.shape)}, expected {(B * T, 3 * heads * 64)} with unit column stride")
+        self._check(self.lib.e2v_op_causal_attention(self.ctx, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B, T,
+                                                     heads, _stream()))
+        return out
+
     def op_to_channels_last(self, x, *, Cpad=None, out=None):
         """``[n, C, FHW]`` -> channel-last rows ``[n * FHW, Cpad]`` (``e2v_op_to_channels_last``; columns C.. are written as zeros)."""
         n, c, fhw = x.shape
@@ -574,6 +605,15 @@ class Engine:
         """Test aid (``e2v_op_pool_guard_selftest``): take one guarded block, alter the word ``offset`` bytes into its trailing guard
         zone from the host, release it -- the next report must name it."""
         self._check(self.lib.e2v_op_pool_guard_selftest(self.ctx, int(payload_bytes), int(offset), _stream()))
+
+
+def fill_text_config(cfg: "_lib.E2VConfig", text_cfg: TextConfig) -> None:
+    """The ``text_*`` fields of an ``e2v_config`` from a ``TextConfig``."""
+    if text_cfg.hidden_act not in TEXT_ACTS:
+        raise NotImplementedError(f"hidden_act={text_cfg.hidden_act!r}: the text encoder implements {sorted(TEXT_ACTS)}")
+    cfg.text_vocab_size, cfg.text_hidden, cfg.text_heads = text_cfg.vocab_size, text_cfg.hidden, text_cfg.heads
+    cfg.text_layers, cfg.text_intermediate, cfg.text_max_positions = text_cfg.layers, text_cfg.intermediate, text_cfg.max_positions
+    cfg.text_act, cfg.text_norm_eps = TEXT_ACTS[text_cfg.hidden_act], text_cfg.layer_norm_eps
 
 
 def named_tensors(source, only_trainable: bool = False):

@@ -52,17 +52,21 @@ class TuneAVideoPipeline:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, unet: Optional[UNet3DConditionModel] = None, vae: Optional[AutoencoderKL] = None,
-                        scheduler=None, tokenizer=None, torch_dtype=None, device: int = 0, **kwargs):
+                        scheduler=None, tokenizer=None, torch_dtype=None, device: int = 0, text_config=None, **kwargs):
         """``TuneAVideoPipeline.from_pretrained(pretrained_model_path, unet=unet, torch_dtype=torch.float16)``
         (``inference_eeg2video.py:70``) for a LOCAL Stable-Diffusion directory: ``model_index.json`` names the components,
         ``vae/`` (config.json + weights) and ``scheduler/scheduler_config.json`` (DDIM in the tuned checkpoints, PNDM in the
         stock SD-v1-4 one; any of the six types the constructor accepts) are loaded here, components passed in are used as
-        they are.  The VAE is created on the UNet's engine so that the fused device loop applies.  Checkpoints of any float type are
+        they are.  The VAE is created on the UNet's engine so that the fused device loop applies (``text_config``: a ``TextConfig`` for
+        that engine, so that the text-prompt twin can put its ``CLIPTextModel`` there too).  Checkpoints of any float type are
         widened to fp32 at load; ``torch_dtype`` selects the ARITHMETIC of the shared engine as it does for the reference pipeline:
         ``torch.float16`` (the reference script) -> the fp16 mode, ``torch.bfloat16`` -> the bf16 mode, ``torch.float32`` -> fp32,
         ``None`` -> whatever the UNet passed in was set to (``pipe.unet.engine.set_compute_dtype`` changes it afterwards)."""
         import json
         import os
+        if text_config is not None and unet is not None:
+            raise ValueError("`text_config` sizes the engine of the UNet this call builds; with `unet=` given, create that UNet with "
+                             "text_config= instead")
         index_file = os.path.join(pretrained_model_path, "model_index.json")
         index = {}
         if os.path.isfile(index_file):
@@ -73,7 +77,7 @@ class TuneAVideoPipeline:
         if unet is None:
             vcfg = vae.vcfg if vae is not None else AutoencoderKL.config_from_dir(os.path.join(pretrained_model_path, "vae"))
             unet = UNet3DConditionModel.from_pretrained(pretrained_model_path, subfolder="unet", torch_dtype=torch_dtype, device=device,
-                                                        vae_config=vcfg)
+                                                        vae_config=vcfg, text_config=text_config)
         if vae is None:
             vae = AutoencoderKL.from_pretrained(pretrained_model_path, subfolder="vae", torch_dtype=torch_dtype, engine=unet.engine)
         if scheduler is None:

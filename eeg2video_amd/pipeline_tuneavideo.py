@@ -1,14 +1,16 @@
 """Text-prompt twin of the pipeline: ``EEG2Video/pipelines/pipeline_tuneavideo.py:315-412`` (caller
 ``train_finetune_videodiffusion.py:331-335``: ``validation_pipeline(prompt, generator=..., latents=..., **validation_data)``).
 
-Same class name, ``__call__`` kwargs (``prompt``, ``negative_prompt``, ``num_videos_per_prompt``), checks and error types.  The CLIP
-text encoder is outside the accelerated path, so the conditioning enters in one of two ways:
+Same class name, ``__call__`` kwargs (``prompt``, ``negative_prompt``, ``num_videos_per_prompt``), checks and error types.  The
+conditioning enters in one of two ways:
 
 * ``prompt`` is a ``[B,77,768]`` tensor of precomputed prompt embeddings (``negative_prompt`` then a ``[1 or B,77,768]`` tensor, or
-  ``pipe.negative_embeddings``) -- nothing but this library runs;
-* ``prompt`` is a ``str`` / ``list`` as in the reference, and the pipeline was given a ``tokenizer`` and a ``text_encoder`` (host-side
-  torch modules with the ``transformers`` CLIP interface): ``_encode_prompt`` (:149-243) tokenises and encodes exactly as the
-  reference does, the empty prompt giving the unconditional embedding.
+  ``pipe.negative_embeddings``);
+* ``prompt`` is a ``str`` / ``list`` as in the reference: ``_encode_prompt`` (:149-243) tokenises and encodes exactly as the reference
+  does, the empty prompt giving the unconditional embedding.  The ``text_encoder`` is the library's own ``CLIPTextModel``
+  (``text_encoder.py``, ``e2v_text_encode``: ``from_pretrained`` builds it on the pipeline's engine when the directory has a
+  ``text_encoder/``, and the tokenizer's ids go to it as a host array), or a host-side torch module with the ``transformers`` CLIP
+  interface that the caller hands in.  Only the tokenizer (BPE) stays outside the library.
 
 From there on it is the EEG pipeline's loop (``pipeline.py``): the fused device loop for deterministic DDIM, else stepped.
 """
@@ -19,6 +21,7 @@ from typing import Callable, List, Optional, Union
 import torch
 
 from .pipeline import TuneAVideoPipeline as _EEGPipeline, TuneAVideoPipelineOutput  # noqa: F401
+from .text_encoder import CLIPTextModel
 
 
 class TuneAVideoPipeline(_EEGPipeline):
@@ -28,16 +31,34 @@ class TuneAVideoPipeline(_EEGPipeline):
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, text_encoder=None, **kwargs):
+        """``text_encoder=None``: when the directory has ``text_encoder/config.json`` the library's own ``CLIPTextModel`` is built on the
+        pipeline's engine (``train_finetune_videodiffusion.py:109,196-199``) -- the engine this call creates, or that of a ``unet=``
+        passed in if it was created for that text encoder (``UNet3DConditionModel(..., text_config=CLIPTextModel.config_from_dir(...))``);
+        a ``unet=`` whose engine has no (or another) text config gives the embeddings-only pipeline it always gave.  ``False``: none
+        (embeddings are passed as tensors); a module: used as it is."""
+        import os
+        te_dir = os.path.join(pretrained_model_path, "text_encoder")
+        text_cfg = None
+        if text_encoder is None and os.path.isfile(os.path.join(te_dir, "config.json")):
+            text_cfg = CLIPTextModel.config_from_dir(te_dir)
+            if kwargs.get("unet") is None:
+                kwargs["text_config"] = text_cfg
         base = _EEGPipeline.from_pretrained(pretrained_model_path, **kwargs)
+        if text_cfg is not None and base.unet.engine.text_cfg == text_cfg:
+            text_encoder = CLIPTextModel.from_pretrained(pretrained_model_path, subfolder="text_encoder", engine=base.unet.engine)
+        elif text_encoder is False:
+            text_encoder = None
         return cls(vae=base.vae, text_encoder=text_encoder, tokenizer=base.tokenizer, unet=base.unet, scheduler=base.scheduler)
 
     def _encode_text(self, prompts: List[str], device, max_length=None):
-        """tokenizer + text encoder on the host side, as :152-179 / :211-229."""
+        """tokenizer + text encoder, as :152-179 / :211-229."""
         if self.tokenizer is None or self.text_encoder is None:
             raise ValueError("a `str` / `list` prompt needs the pipeline's `tokenizer` and `text_encoder` (host-side CLIP modules, outside "
                              "the accelerated path); pass precomputed embeddings as a [B,77,768] tensor instead")
         tok = self.tokenizer(prompts, padding="max_length", max_length=max_length or self.tokenizer.model_max_length, truncation=True,
                              return_tensors="pt")
+        if getattr(self.text_encoder, "native", False):      # the library's own: the ids stay on the host (e2v_text_encode takes them there)
+            return self.text_encoder(tok.input_ids)[0]
         cfg = getattr(self.text_encoder, "config", None)
         mask = tok.attention_mask.to(device) if getattr(cfg, "use_attention_mask", False) else None
         return self.text_encoder(tok.input_ids.to(device), attention_mask=mask)[0].float()

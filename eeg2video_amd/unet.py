@@ -16,20 +16,21 @@ import numpy as np
 import torch
 
 from .engine import Engine, named_tensors
-from .weights import UNetConfig, VAEConfig, synth_state_dict, unet_param_spec
+from .weights import TextConfig, UNetConfig, VAEConfig, synth_state_dict, unet_param_spec
 
 WEIGHTS_NAME = "diffusion_pytorch_model.bin"      # diffusers.utils.WEIGHTS_NAME (unet.py:439-441)
 SAFETENSORS_NAME = "diffusion_pytorch_model.safetensors"
 
 
-def _load_checkpoint(path: str) -> dict:
+def _load_checkpoint(path: str, safetensors_name: str = SAFETENSORS_NAME, weights_name: str = WEIGHTS_NAME) -> dict:
     """State dict of a diffusers-layout model directory: the ``.safetensors`` file when there is one, else the ``.bin`` unpickled
-    with ``weights_only=True`` (a state dict of tensors needs nothing more; a checkpoint directory is user-supplied input)."""
-    st = os.path.join(path, SAFETENSORS_NAME)
+    with ``weights_only=True`` (a state dict of tensors needs nothing more; a checkpoint directory is user-supplied input).  The file
+    names are diffusers' by default; a ``transformers`` model directory (the text encoder) names its own."""
+    st = os.path.join(path, safetensors_name)
     if os.path.isfile(st):
         from safetensors.torch import load_file
         return dict(load_file(st, device="cpu"))
-    return torch.load(os.path.join(path, WEIGHTS_NAME), map_location="cpu", weights_only=True)
+    return torch.load(os.path.join(path, weights_name), map_location="cpu", weights_only=True)
 
 
 class FrozenDict(dict):
@@ -84,10 +85,11 @@ class UNet3DConditionModel:
         *,
         engine: Optional[Engine] = None,
         vae_config: Optional[VAEConfig] = None,
+        text_config: Optional[TextConfig] = None,
         device: int = 0,
     ):
         cfg = dict(locals())
-        for k in ("self", "engine", "vae_config", "device"):
+        for k in ("self", "engine", "vae_config", "text_config", "device"):
             cfg.pop(k)
         self._internal_dict = FrozenDict(cfg)
         unsupported = {
@@ -128,7 +130,8 @@ class UNet3DConditionModel:
                                cross_attention_dim=cross_attention_dim, attention_head_dim=attention_head_dim,
                                norm_num_groups=norm_num_groups, norm_eps=norm_eps,
                                flip_sin_to_cos=flip_sin_to_cos, freq_shift=freq_shift)
-        self.engine = engine if engine is not None else Engine(self.ucfg, vae_config or VAEConfig(), device)
+        # (text_config: the engine this model creates also holds a CLIP text encoder -- text_encoder.CLIPTextModel(engine=unet.engine))
+        self.engine = engine if engine is not None else Engine(self.ucfg, vae_config or VAEConfig(), device, text_cfg=text_config)
         self.training = False
 
     # -- attributes the callers rely on -------------------------------------------------------

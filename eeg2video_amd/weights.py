@@ -133,6 +133,46 @@ def semantic_param_spec(cfg: SemanticConfig, cross_attention_dim: int) -> "Order
     return spec
 
 
+@dataclass(frozen=True)
+class TextConfig:
+    """``CLIPTextModel`` of the SD checkpoint's ``text_encoder/config.json`` (``transformers`` ``CLIPTextConfig``: ``vocab_size``,
+    ``hidden_size``, ``num_attention_heads``, ``num_hidden_layers``, ``intermediate_size``, ``max_position_embeddings``, ``hidden_act``,
+    ``layer_norm_eps``); defaults are the SD-v1-4 values.  The head dim is 64 (``hidden == 64 * heads``)."""
+    vocab_size: int = 49408
+    hidden: int = 768
+    heads: int = 12
+    layers: int = 12
+    intermediate: int = 3072
+    max_positions: int = 77
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+
+
+TINY_TEXT = TextConfig(vocab_size=128, hidden=128, heads=2, layers=2, intermediate=256, max_positions=77)
+
+#: ``e2v_config.text_act`` of a ``hidden_act``
+TEXT_ACTS = {"quick_gelu": 0, "gelu": 1}
+
+
+def text_param_spec(cfg: TextConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of the ``CLIPTextModel`` state dict as the SD-v1-4 ``text_encoder`` checkpoint keys it (``text_model.`` prefix,
+    no ``position_ids`` buffer); the engine holds them under ``text.``."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c = cfg.hidden
+    spec["text_model.embeddings.token_embedding.weight"] = (cfg.vocab_size, c)
+    spec["text_model.embeddings.position_embedding.weight"] = (cfg.max_positions, c)
+    for i in range(cfg.layers):
+        p = f"text_model.encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            _lin(spec, f"{p}.self_attn.{n}", c, c)
+        _norm(spec, f"{p}.layer_norm1", c)
+        _norm(spec, f"{p}.layer_norm2", c)
+        _lin(spec, f"{p}.mlp.fc1", cfg.intermediate, c)
+        _lin(spec, f"{p}.mlp.fc2", c, cfg.intermediate)
+    _norm(spec, "text_model.final_layer_norm", c)
+    return spec
+
+
 #: tiny configs used by the parity tests (oracle finishes in well under a second).
 TINY_UNET = UNetConfig(sample_size=8, block_out_channels=(64, 128, 256, 256), cross_attention_dim=64)
 TINY_VAE = VAEConfig(block_out_channels=(32, 64, 64, 64), norm_num_groups=8)
@@ -283,7 +323,7 @@ def vae_param_spec(cfg: VAEConfig) -> "OrderedDict[str, Tuple[int, ...]]":
 # --------------------------------------------------------------------------------------
 def _is_norm(name: str) -> bool:
     leaf = name.rsplit(".", 2)[-2]
-    return leaf.startswith("norm") or leaf in ("group_norm", "conv_norm_out")
+    return leaf.startswith("norm") or leaf.startswith("layer_norm") or leaf in ("group_norm", "conv_norm_out", "final_layer_norm")
 
 
 def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 42, mode: str = "perturbed",

@@ -76,6 +76,15 @@ typedef struct {
      * [3] (:151), up block i the reversed list's [i] (:165,194); the SD-2.x UNet's 5 / 10 / 20 / 20).  All zero (the default): every
      * block has `attention_heads` heads.  Appended in round 5: e2v_config_size() tells a binding which layout a library has. */
     int attention_heads_per_block[4];
+    /* CLIP text encoder (transformers CLIPTextModel, text_encoder/config.json of the SD checkpoint: vocab_size, hidden_size,
+     * num_attention_heads, num_hidden_layers, intermediate_size, max_position_embeddings, hidden_act, layer_norm_eps; SD-v1-4:
+     * 49408, 768, 12, 12, 3072, 77, quick_gelu, 1e-5).  All zero (the default): the context has no text encoder and expects none of
+     * its keys.  text_layers > 0: text_hidden must be 64 * text_heads (64 is the head dim of both SD text towers and of the
+     * attention kernel's only instance), a multiple of 4 and at most 1280 (the LayerNorm kernel), text_intermediate a multiple of 4,
+     * text_max_positions at most 128 (the attention kernel keeps K and V of a prompt in LDS, two keys per lane). */
+    int text_vocab_size, text_hidden, text_heads, text_layers, text_intermediate, text_max_positions;
+    int text_act;                           /* 0 = quick_gelu (x sigmoid(1.702 x)), 1 = gelu (erf) */
+    float text_norm_eps;
 } e2v_config;
 
 void e2v_default_config(e2v_config* cfg);
@@ -106,7 +115,12 @@ e2v_status e2v_load_tensor(e2v_ctx* ctx, const char* key, const void* host_data,
 int64_t e2v_num_expected_keys(const e2v_ctx* ctx);
 const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int* ndim);
 /* re-layout to the kernels' formats (tap-major convs, fused QKV / KV, GEGLU row interleave).
- * which: bit 0 = UNet, bit 1 = VAE, bit 2 = semantic predictor (keys "semantic.mlp.{0,2,4,6,8}.{weight,bias}");
+ * which: bit 0 = UNet, bit 1 = VAE, bit 2 = semantic predictor (keys "semantic.mlp.{0,2,4,6,8}.{weight,bias}"), bit 3 = CLIP text
+ * encoder (config with text_layers > 0; the keys of the checkpoint's text_encoder under the prefix "text.":
+ * "text.text_model.embeddings.{token,position}_embedding.weight", per layer "text.text_model.encoder.layers.{i}."
+ * "self_attn.{q,k,v,out}_proj.{weight,bias}", "layer_norm{1,2}.{weight,bias}", "mlp.fc{1,2}.{weight,bias}", and
+ * "text.text_model.final_layer_norm.{weight,bias}"; q / k / v become one [3C][C] matrix with its [3C] bias).  The text part keeps
+ * fp32 matrices only, in every compute mode (E2V_F32X3 included).
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -121,7 +135,9 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * pointer, copied into the workspace pool in its own type (hipMemcpyAsync: pinned memory must stay valid until the stream has
  * passed the call) and widened on the device.  Stream-ordered: calls queued earlier on `stream` see the old weights, later ones
  * the new; no device synchronisation, and no allocation once the workspace of such a call is cached (e2v_device_bytes does not move).
- * Part not finalized: E2V_ESTATE (use e2v_load_tensor); unknown key / shape mismatch: E2V_ENOWEIGHT as e2v_load_tensor. */
+ * Part not finalized: E2V_ESTATE (use e2v_load_tensor); unknown key / shape mismatch: E2V_ENOWEIGHT as e2v_load_tensor.
+ * A "text." key: E2V_EINVAL -- the text encoder is frozen on this path (train_finetune_videodiffusion.py:115
+ * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8). */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
@@ -212,6 +228,19 @@ e2v_status e2v_generate(e2v_ctx* ctx, const float* latents, const float* cond, c
  * at pipeline_tuneeeg2video.py:149): eeg [B, sem_in_features] -> embeddings [B, sem_tokens * cross_attention_dim]
  * (the caller reshapes to [B,77,768], :150), all on device. */
 e2v_status e2v_semantic_predict(e2v_ctx* ctx, const float* eeg, int B, float* out, e2v_stream stream);
+
+/* replaces: CLIPTextModel.forward(input_ids)[0] (pipelines/pipeline_tuneavideo.py:174-177,220-223; train_finetune_videodiffusion.py:281)
+ * -- the prompt embeddings, the unconditional embedding (negative.npy) and the targets the Semantic Predictor regresses to.
+ * host_ids: HOST [B][T] token ids (as host_timesteps / host_t: the tokenizer's output never has to visit the device); every id is
+ * checked against [0, text_vocab_size) before anything is enqueued (E2V_EINVAL); 1 <= T <= text_max_positions (else E2V_ESHAPE).
+ * out: device [B][T][text_hidden] fp32, 16-byte aligned (E2V_EINVAL otherwise), the last hidden state after final_layer_norm -- directly usable as cond / uncond of
+ * e2v_generate.  Causal mask, no padding mask (use_attention_mask is absent from the SD text_encoder config); no pooled output.
+ * ARITHMETIC IS FP32 IN EVERY COMPUTE MODE (fp32 rows, fp32 matrices, the linears of the time-embedding MLP's kind): the same
+ * ids give the same bits under E2V_F32, E2V_BF16, E2V_F16 and E2V_F32X3 contexts.  (The reference runs this model in fp16; at
+ * 13 GFLOP per prompt against the 600 TFLOP of a clip the tighter choice costs nothing.)
+ * No text config / text part not finalized / host-only context: E2V_ESTATE.  Stream-ordered, does not synchronise, allocates nothing
+ * once the workspace of a (B, T) is cached. */
+e2v_status e2v_text_encode(e2v_ctx* ctx, const int64_t* host_ids, int B, int T, float* out, e2v_stream stream);
 
 /* rank 2 -- replaces Diffusion.forward of DANA (EEG2Video/models/DANA_module.py:52-72) given its random draws, fused with
  * the latent layout fix 'a b c d e -> a c b d e' of inference_eeg2video.py:77,82:

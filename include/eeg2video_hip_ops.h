@@ -65,6 +65,13 @@ e2v_status e2v_op_attention(e2v_ctx* ctx, const float* q, int ldq, const float* 
 e2v_status e2v_op_temporal_attention(e2v_ctx* ctx, const float* qkv, float* out, int n, int F, int HW, int heads, int D,
                                      float scale, e2v_stream stream);
 
+/* CLIPAttention under the causal mask (transformers modeling_clip.py, as e2v_text_encode runs it): self-attention over each of B
+ * prompts of T tokens, head dim 64, scale 64^-0.5, query i attends to keys 0 .. i.  qkv [B*T][ldqkv]: q | k | v, heads * 64 columns
+ * each (16-byte aligned, ldqkv a multiple of 4); out [B*T][ldo], columns 0 .. heads * 64 - 1 written.  1 <= T <= 128 (E2V_ESHAPE).
+ * fp32 in every compute mode. */
+e2v_status e2v_op_causal_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
+                                   e2v_stream stream);
+
 /* layout conversion at the boundary: [n][C][FHW] <-> [n][FHW][Cpad] */
 e2v_status e2v_op_to_channels_last(e2v_ctx* ctx, const float* in, float* out, int n, int C, int Cpad, int FHW,
                                    e2v_stream stream);
@@ -103,7 +110,7 @@ e2v_status e2v_op_set_knob(const char* name, int value);
  * now -- one bit each in *mask.  A linear (or 1x1 conv) weight: its fp32 matrix, the bf16 copy finalize makes, the fp16 copy the fp16
  * mode builds on first use, the three bf16 planes of the f32x3 mode.  A 3x3 conv weight: F32 = the torch-layout weight, BF16 / F16 = the
  * direct 16-bit layouts, and the remaining bits the layouts built on first use by the kernel that needs them.  Norm affines and biases
- * have the F32 bit only.  The update tests use it to prove that an update ran against each form.  E2V_ENOWEIGHT for an unknown key,
+ * have the F32 bit only, and so does every tensor of the text encoder ("text." keys: fp32 in every compute mode).  The update tests use it to prove that an update ran against each form.  E2V_ENOWEIGHT for an unknown key,
  * E2V_ESTATE when the key's part is not finalized (and on a host-only context).  No reference counterpart. */
 enum {
     E2V_FORM_F32 = 1 << 0,
