@@ -152,19 +152,13 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
 
 void e2v_destroy(e2v_ctx* c) {
     if (!c) return;
-    if (c->device < 0) { delete c; return; }
-    c->pool.closing();                                       // (E2V_POOL_GUARD: the step caches released below are not compared any more)
+    if (c->device < 0) { delete c; return; }                 // (host-only, dry runs included: nothing is owned, no HIP call)
+    c->pool.closing();                                       // (E2V_POOL_GUARD: the step caches released by `delete` are not compared any more)
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
     (void)e2v_comm_destroy(c);
-    for (auto& kv : c->raw) if (kv.second.d) (void)hipFree(kv.second.d);
-    for (float* p : c->owned) (void)hipFree(p);
-    for (auto& part : c->owned_part) for (float* p : part) (void)hipFree(p);
     if (c->stream_ev) (void)hipEventDestroy(c->stream_ev);
-    if (c->gn_part_base) (void)hipFree(c->gn_part_base);
-    if (c->gn_scale_base) (void)hipFree(c->gn_scale_base);
-    if (c->d_timesteps) (void)hipFree(c->d_timesteps);
-    delete c;
+    delete c;                                                // every device block frees itself (the step caches before the pool: member order)
 }
 
 const char* e2v_last_error(const e2v_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
@@ -190,22 +184,19 @@ e2v_status e2v_load_tensor(e2v_ctx* c, const char* key, const void* host, e2v_dt
         bool same = (int)t.shape.size() == ndim;
         for (int d = 0; same && d < ndim; ++d) same = t.shape[d] == shape[d];
         E2V_REQUIRE(same, E2V_ENOWEIGHT, std::string("shape mismatch for ") + key);
-        if (!t.d) {
-            E2V_HIP(hipMalloc((void**)&t.d, t.numel * sizeof(float)));
-            c->weight_bytes += t.numel * sizeof(float);
-        }
+        if (!t.mem) t.mem = dev_block(t.numel * sizeof(float), 0, nullptr, false);
         if (dtype == E2V_F32) {
-            E2V_HIP(hipMemcpy(t.d, host, t.numel * sizeof(float), hipMemcpyHostToDevice));
+            E2V_HIP(hipMemcpy(t.d(), host, t.numel * sizeof(float), hipMemcpyHostToDevice));
         } else if (dtype == E2V_F16) {
             std::vector<float> tmp(t.numel);
             const uint16_t* h = static_cast<const uint16_t*>(host);
             for (size_t i = 0; i < t.numel; ++i) tmp[i] = half_to_float(h[i]);
-            E2V_HIP(hipMemcpy(t.d, tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
+            E2V_HIP(hipMemcpy(t.d(), tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
         } else if (dtype == E2V_BF16) {                           // bf16 is the high half of the fp32 pattern
             std::vector<uint32_t> tmp(t.numel);
             const uint16_t* h = static_cast<const uint16_t*>(host);
             for (size_t i = 0; i < t.numel; ++i) tmp[i] = (uint32_t)h[i] << 16;
-            E2V_HIP(hipMemcpy(t.d, tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
+            E2V_HIP(hipMemcpy(t.d(), tmp.data(), t.numel * sizeof(float), hipMemcpyHostToDevice));
         } else {
             throw Error(E2V_EINVAL, "unsupported dtype");
         }
@@ -432,7 +423,7 @@ e2v_status e2v_set_conv_algo(e2v_ctx* c, int algo) {
     return E2V_OK;
 }
 
-int64_t e2v_device_bytes(const e2v_ctx* c) { return c ? (int64_t)(c->weight_bytes + c->pool.bytes()) : 0; }
+int64_t e2v_device_bytes(const e2v_ctx* c) { return c ? (int64_t)(c->weight_bytes() + c->pool.bytes()) : 0; }
 
 // ---------------------------------------------------------------------------------------------------
 // The body of the three UNet entry points: NCFHW in, unet_forward_cl, NCFHW out.  host_tf != null: fractional timesteps;
@@ -1047,8 +1038,11 @@ e2v_status e2v_op_pool_guard_report(e2v_ctx* c, int64_t* blocks_checked, int64_t
         E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no guarded blocks in a dry run");
         const hipStream_t s = c->last_stream;
         c->pool.check_live(s);
-        for (const auto& kv : c->guard_dev)
-            c->guard_tally.check(kv.second, kv.first == c->gn_part_base || kv.first == c->gn_scale_base ? "GroupNorm workspace" : "dev_alloc", s);
+        for (const auto& part : c->owned_part)
+            for (const DevBlock& b : part)
+                if (b.guard) c->guard_tally.check(b, "dev_alloc", s);
+        for (const GrowBuf* ws : {&c->gn_part, &c->gn_scale})
+            if (ws->blk.guard) c->guard_tally.check(ws->blk, "GroupNorm workspace", s);
         E2V_HIP(hipStreamSynchronize(s));
         E2V_HIP(hipGetLastError());
         c->guard_tally.collect();

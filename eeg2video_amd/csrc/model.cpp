@@ -155,33 +155,22 @@ void e2v_ctx::expected_keys() {
     }
 }
 
+// a block of a weight layout, owned by the part its caller selected (AllocPart); guarded, and its payload poisoned before the first
+// write, under E2V_POOL_GUARD.  A dry run hands out an address and owns nothing.
 float* e2v_ctx::dev_alloc(size_t floats) {
-    void* p = nullptr;
-    const size_t bytes = std::max<size_t>(floats, 1) * sizeof(float);
-    if (dry_run()) return dry_fake_ptr(bytes);               // e2v_op_describe_dispatch: an address nobody dereferences, not owned
-    if (const int kib = pool_guard_kib()) {                  // E2V_POOL_GUARD: guards on both sides, payload poisoned before its first write
-        const GuardBlock b = guard_alloc(bytes, (size_t)kib * 1024, nullptr, true);
-        (alloc_part >= 0 ? owned_part[alloc_part] : owned).push_back(static_cast<float*>(b.base));
-        owned_bytes[b.base] = b.total;
-        weight_bytes += b.total;
-        guard_dev[b.base] = b;
-        return reinterpret_cast<float*>(b.data());
-    }
-    E2V_HIP(hipMalloc(&p, bytes));
-    (alloc_part >= 0 ? owned_part[alloc_part] : owned).push_back(static_cast<float*>(p));
-    owned_bytes[p] = bytes;
-    weight_bytes += bytes;
-    return static_cast<float*>(p);
+    E2V_REQUIRE(alloc_part >= 0, E2V_ESTATE, "dev_alloc outside a part");
+    DevBlock b = dev_block(std::max<size_t>(floats, 1) * sizeof(float), (size_t)pool_guard_kib() * 1024, nullptr, true);
+    float* p = b.f32();
+    if (b.total) owned_part[alloc_part].push_back(std::move(b));
+    return p;
 }
 
-void e2v_ctx::free_part(int part) {
-    for (float* p : owned_part[part]) {
-        auto it = owned_bytes.find(p);
-        if (it != owned_bytes.end()) { weight_bytes -= it->second; owned_bytes.erase(it); }
-        guard_dev.erase(p);
-        (void)hipFree(p);
-    }
-    owned_part[part].clear();
+size_t e2v_ctx::weight_bytes() const {
+    size_t n = 0;
+    for (const auto& kv : raw) n += kv.second.mem.total;
+    for (const auto& part : owned_part)
+        for (const DevBlock& b : part) n += b.total;
+    return n;
 }
 
 // fp32 arithmetic only (in a 16-bit mode the transforms would dominate and rounding the transformed inputs costs accuracy), for a
@@ -323,14 +312,6 @@ const void* e2v_ctx::lin_f16(const LinW& w, hipStream_t s) {
     return d16;
 }
 
-void e2v_ctx::grow_timesteps(int n, hipStream_t s) {
-    if (d_timesteps_cap >= n) return;
-    E2V_HIP(hipStreamSynchronize(s));
-    if (d_timesteps) (void)hipFree(d_timesteps);
-    E2V_HIP(hipMalloc((void**)&d_timesteps, sizeof(long long) * n));
-    d_timesteps_cap = n;
-}
-
 void e2v_ctx::enter_stream(hipStream_t s) {
     if (has_last_stream && s != last_stream) {
         if (!stream_ev) E2V_HIP(hipEventCreateWithFlags(&stream_ev, hipEventDisableTiming));
@@ -354,7 +335,7 @@ struct Packer {
         auto it = c->raw.find(k);
         E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, "unknown key " + k);
         if (dry_run()) {                                     // shapes only: the dispatch of a configuration does not depend on values
-            if (!it->second.d) it->second.d = dry_fake_ptr(it->second.numel * sizeof(float));
+            if (!it->second.mem) it->second.mem = dev_block(it->second.numel * sizeof(float), 0, nullptr, false);
             return it->second;
         }
         E2V_REQUIRE(it->second.loaded, E2V_ENOWEIGHT, "state-dict key not loaded: " + k);
@@ -391,12 +372,10 @@ struct Packer {
         if (in16 == in) {
             w16 = half(w, (size_t)out * in);
         } else {
-            float* tmp = nullptr;
-            E2V_HIP(hipMalloc((void**)&tmp, (size_t)out * in16 * sizeof(float)));
-            pad_cols(w, in, tmp, in16, out, s);
-            w16 = half(tmp, (size_t)out * in16);
+            const DevBlock tmp = dev_block((size_t)out * in16 * sizeof(float), 0, s, false);
+            pad_cols(w, in, tmp.f32(), in16, out, s);
+            w16 = half(tmp.f32(), (size_t)out * in16);
             E2V_HIP(hipStreamSynchronize(s));
-            if (!dry_run()) (void)hipFree(tmp);
         }
         LinW l{w, b, in, out, w16, split3(w, (size_t)out * in)};
         l.in16 = in16;
@@ -410,21 +389,21 @@ struct Packer {
         return d;
     }
     NormW norm(const std::string& n) {
-        const NormW w{t(n + ".weight").d, t(n + ".bias").d, (int)t(n + ".weight").shape[0]};
+        const NormW w{t(n + ".weight").d(), t(n + ".bias").d(), (int)t(n + ".weight").shape[0]};
         bind_raw(n + ".weight", w.g, 1, w.c); bind_raw(n + ".bias", w.b, 1, w.c);
         return w;
     }
     LinW lin(const std::string& n, bool bias = true) {       // Linear or 1x1 conv: [out][in] as it is
         const WTensor& w = t(n + ".weight");
-        bind_lin(n + ".weight", w.d, 0);
-        if (bias) bind_raw(n + ".bias", t(n + ".bias").d, 1, (int)w.shape[0]);
-        return mk_lin(w.d, bias ? t(n + ".bias").d : nullptr, (int)w.shape[1], (int)w.shape[0]);
+        bind_lin(n + ".weight", w.d(), 0);
+        if (bias) bind_raw(n + ".bias", t(n + ".bias").d(), 1, (int)w.shape[0]);
+        return mk_lin(w.d(), bias ? t(n + ".bias").d() : nullptr, (int)w.shape[1], (int)w.shape[0]);
     }
     // 3x3 conv: the torch-layout weight stays; kernel layouts are built on first use (e2v_ctx::conv_form)
     ConvW conv3(const std::string& n) {
         const WTensor& w = t(n + ".weight");
         ConvW cw;
-        cw.raw = w.d; cw.b = t(n + ".bias").d;
+        cw.raw = w.d(); cw.b = t(n + ".bias").d();
         cw.cout = (int)w.shape[0]; cw.cin = (int)w.shape[1];
         cw.cin_pad = (cw.cin + 3) / 4 * 4; cw.cin_pad16 = (cw.cin + 7) / 8 * 8;
         cw.ldw = conv3x3_packed_ld(cw.cin, 32); cw.ldw16 = conv3x3_packed_ld(cw.cin, 64);
@@ -443,8 +422,8 @@ struct Packer {
         int r = 0;
         for (auto& n : names) {
             const WTensor& w = t(n + ".weight");
-            copy_rows(w.d, in, d + (size_t)r * in, in, (int)w.shape[0], in, s);
-            if (bias) copy_rows(t(n + ".bias").d, (int)w.shape[0], b + r, (int)w.shape[0], 1, (int)w.shape[0], s);
+            copy_rows(w.d(), in, d + (size_t)r * in, in, (int)w.shape[0], in, s);
+            if (bias) copy_rows(t(n + ".bias").d(), (int)w.shape[0], b + r, (int)w.shape[0], 1, (int)w.shape[0], s);
             bind_lin(n + ".weight", d, r);
             if (bias) bind_raw(n + ".bias", b + r, 1, (int)w.shape[0]);
             r += (int)w.shape[0];
@@ -458,7 +437,7 @@ struct Packer {
         E2V_REQUIRE(half % 32 == 0, E2V_EINVAL, "GEGLU inner width must be a multiple of 32");
         float* d = c->dev_alloc((size_t)out * in);
         float* b = c->dev_alloc(out);
-        geglu_interleave(w.d, bsrc.d, half, in, d, b, s);
+        geglu_interleave(w.d(), bsrc.d(), half, in, d, b, s);
         bind_lin(n + ".weight", d, 0, half);
         bind_raw(n + ".bias", b, out / 32, 32, half / 32);       // 32-element groups, interleaved one by one
         return mk_lin(d, b, in, out);
@@ -588,10 +567,10 @@ void e2v_ctx::finalize(int which) {
                 const WTensor& w = P.t(n + ".weight");
                 const int out = (int)w.shape[0];
                 float* wp = dev_alloc((size_t)out * sem_in_pad);
-                pad_cols(w.d, cfg.sem_in_features, wp, sem_in_pad, out, nullptr);
+                pad_cols(w.d(), cfg.sem_in_features, wp, sem_in_pad, out, nullptr);
                 P.bind_lin(n + ".weight", wp, 0);
-                P.bind_raw(n + ".bias", P.t(n + ".bias").d, 1, out);
-                sem.push_back(P.mk_lin(wp, P.t(n + ".bias").d, sem_in_pad, out));
+                P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, out);
+                sem.push_back(P.mk_lin(wp, P.t(n + ".bias").d(), sem_in_pad, out));
             } else {
                 sem.push_back(P.lin(n));
             }
@@ -605,9 +584,9 @@ void e2v_ctx::finalize(int which) {
         const std::string m = "text.text_model.";
         const WTensor& tok = P.t(m + "embeddings.token_embedding.weight");
         const WTensor& pos = P.t(m + "embeddings.position_embedding.weight");
-        t.tok = tok.d; t.pos = pos.d;
-        P.bind_raw(m + "embeddings.token_embedding.weight", tok.d, (int)tok.shape[0], (int)tok.shape[1]);
-        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d, (int)pos.shape[0], (int)pos.shape[1]);
+        t.tok = tok.d(); t.pos = pos.d();
+        P.bind_raw(m + "embeddings.token_embedding.weight", tok.d(), (int)tok.shape[0], (int)tok.shape[1]);
+        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), (int)pos.shape[0], (int)pos.shape[1]);
         for (int i = 0; i < cfg.text_layers; ++i) {
             const std::string l = m + "encoder.layers." + std::to_string(i);
             TextLayerW w;
@@ -633,10 +612,8 @@ void e2v_ctx::finalize(int which) {
     // the torch-layout copies of re-laid-out tensors are no longer needed
     auto drop = [&](const std::string& k) {
         auto it = raw.find(k);
-        if (it != raw.end() && it->second.d) {
-            (void)hipFree(it->second.d);
-            weight_bytes -= it->second.numel * sizeof(float);
-            it->second.d = nullptr;
+        if (it != raw.end() && it->second.mem) {
+            it->second.mem.release();
             it->second.loaded = false;
         }
     };
@@ -746,9 +723,9 @@ void e2v_ctx::update_tensor(const std::string& key, const void* data, e2v_dtype 
     }
     main32 = a.d32;
     weight_scatter(a, s);
-    if (t.d && t.loaded && t.d != main32) {         // the uploaded block is kept next to a re-laid-out copy (K-padded layer): a later
+    if (t.d() && t.loaded && t.d() != main32) {         // the uploaded block is kept next to a re-laid-out copy (K-padded layer): a later
         WeightScatterArgs r;                        // finalize of this part must find the new values there
-        r.src = data; r.src_mode = a.src_mode; r.rows = 1; r.in = (int)t.numel; r.d32 = t.d; r.ld32 = r.in;
+        r.src = data; r.src_mode = a.src_mode; r.rows = 1; r.in = (int)t.numel; r.d32 = t.d(); r.ld32 = r.in;
         weight_scatter(r, s);
     }
     if (b.kind == WBind::CONV) {            // every layout that exists is derived again, as conv_form derived it
@@ -847,26 +824,9 @@ struct Runner {
     }
 
     void gn_ws(int samples, int P, int C) {
-        auto grow = [&](float*& p, void*& base, size_t& have, size_t need) {
-            if (need <= have) return;
-            E2V_HIP(hipStreamSynchronize(s));
-            if (base && !dry_run()) { c->guard_dev.erase(base); (void)hipFree(base); }
-            p = nullptr; base = nullptr; have = 0;
-            const int kib = dry_run() ? 0 : pool_guard_kib();
-            if (kib > 0) {                                               // E2V_POOL_GUARD: guarded like a dev_alloc block
-                const GuardBlock b = guard_alloc(need * sizeof(float), (size_t)kib * 1024, s, true);
-                c->guard_dev[b.base] = b;
-                base = b.base;
-                p = reinterpret_cast<float*>(b.data());
-            } else {
-                E2V_HIP(hipMalloc(&base, need * sizeof(float)));
-                p = static_cast<float*>(base);
-            }
-            if (dry_run()) p = dry_fake_ptr(need * sizeof(float));       // (pointers steer the graph: a null workspace reads as "no GroupNorm in front")
-            have = need;
-        };
-        grow(c->gn_part, c->gn_part_base, c->gn_part_floats, (size_t)samples * groupnorm_chunks(P) * C * 2);
-        grow(c->gn_scale, c->gn_scale_base, c->gn_scale_floats, (size_t)samples * C * 2);
+        const size_t guard = (size_t)pool_guard_kib() * 1024;          // E2V_POOL_GUARD: guarded like a dev_alloc block
+        c->gn_part.ensure((size_t)samples * groupnorm_chunks(P) * C * 2 * sizeof(float), guard, s);
+        c->gn_scale.ensure((size_t)samples * C * 2 * sizeof(float), guard, s);      // (pointers steer the graph: a null workspace reads as "no GroupNorm in front")
     }
 
     // what gn and gn_stats share: the two sources, the affine, the slabs and the workspaces (grown here)
@@ -878,7 +838,7 @@ struct Runner {
         a.bf16 = h16();
         a.x0 = x0; a.x1 = x1; a.c0 = c0; a.c1 = c1; a.ld0 = c0; a.ld1 = c1;
         a.gamma = w.g; a.beta = w.b; a.samples = samples; a.P = P; a.groups = groups; a.eps = eps;
-        a.ws_part = c->gn_part; a.ws_scale = c->gn_scale;
+        a.ws_part = c->gn_part.blk.f32(); a.ws_scale = c->gn_scale.blk.f32();
         return a;
     }
 
@@ -947,7 +907,7 @@ struct Runner {
         if (const int wm = c->conv_wino_tile(w.cin, w.cout, stride, pad, Hi, Wi, Ho, Wo)) {
             c->conv_form(w, wm == 4 ? e2v_ctx::FORM_WINO4 : e2v_ctx::FORM_WINO2, s);
             const void* U3 = !c->x3_compute ? nullptr : wm == 4 ? w.wino4_x3 : w.wino_x3;
-            conv3_wino(c, d, wm, wm == 4 ? w.wino4 : w.wino, U3, c->gn_scale, o.gn_P, s);
+            conv3_wino(c, d, wm, wm == 4 ? w.wino4 : w.wino, U3, c->gn_scale.blk.f32(), o.gn_P, s);
             return out;
         }
         E2V_REQUIRE(o.gn_P == 0, E2V_EINVAL, "conv: fused GroupNorm needs the Winograd path");
@@ -1168,7 +1128,7 @@ struct Runner {
     Act time_embedding(int n_t, int rows, int t_is_f32, Tap&& tap) {
         const int boc0 = c->cfg.block_out_channels[0], temb_dim = boc0 * 4;
         Act sin(pool(), rows, boc0);
-        timestep_sinusoid(c->d_timesteps, n_t, sin.p, rows, boc0, c->cfg.flip_sin_to_cos, c->cfg.freq_shift, s, t_is_f32);
+        timestep_sinusoid(reinterpret_cast<const long long*>(c->d_timesteps.blk.data()), n_t, sin.p, rows, boc0, c->cfg.flip_sin_to_cos, c->cfg.freq_shift, s, t_is_f32);
         Act e1 = linear(c->unet.te1, sin.p, boc0, rows, f32_rows());
         silu(e1.p, e1.p, (long long)rows * temb_dim, s);
         Act emb = linear(c->unet.te2, e1.p, temb_dim, rows, f32_rows());
@@ -1217,10 +1177,10 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
         for (int i = 0; i < 5; ++i) t.shapes[t.count][i] = shp[i];
         t.used += count; ++t.count;
     };
-    grow_timesteps(N, s);
+    long long* d_t = timesteps(N, s);
     static_assert(sizeof(long long) == sizeof(int64_t), "int64");
-    if (host_tf) E2V_HIP(hipMemcpyAsync(d_timesteps, host_tf, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
-    else E2V_HIP(hipMemcpyAsync(d_timesteps, host_t, sizeof(int64_t) * n_t, hipMemcpyHostToDevice, s));
+    if (host_tf) E2V_HIP(hipMemcpyAsync(d_t, host_tf, sizeof(float) * n_t, hipMemcpyHostToDevice, s));
+    else E2V_HIP(hipMemcpyAsync(d_t, host_t, sizeof(int64_t) * n_t, hipMemcpyHostToDevice, s));
     Act temb_silu;
     if (!step_cache_on)
         temb_silu = R.time_embedding(n_t, N, host_tf ? 1 : 0, [&](const Act& emb) { if (tap_sink) tap(emb, N, temb_dim, 1, 1, 1); });   // taps["emb"]
@@ -1322,8 +1282,7 @@ void e2v_ctx::build_step_caches(const int64_t* ts, int steps, const float* cond,
     temb_cache.clear();
     kv_cache.clear();
     const int temb_dim = cfg.block_out_channels[0] * 4;
-    grow_timesteps(steps, s);
-    E2V_HIP(hipMemcpyAsync(d_timesteps, ts, sizeof(int64_t) * steps, hipMemcpyHostToDevice, s));
+    E2V_HIP(hipMemcpyAsync(timesteps(steps, s), ts, sizeof(int64_t) * steps, hipMemcpyHostToDevice, s));
     Act emb = R.time_embedding(steps, steps, 0, [](const Act&) {});
     Act cond16;
     if (R.bf()) {

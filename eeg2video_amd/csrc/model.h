@@ -155,14 +155,8 @@ struct e2v_ctx {
     std::string err;
     std::vector<std::string> keys;                               // expected keys, in state-dict order
     std::unordered_map<std::string, e2v::WTensor> raw;           // uploaded tensors (torch layout)
-    std::vector<float*> owned;                                   // packed weights + misc device blocks
-    size_t weight_bytes = 0;
     e2v::Pool pool;
-    // E2V_POOL_GUARD (runtime.h): the tally of this context, and the guarded blocks outside the pool -- dev_alloc blocks and the
-    // GroupNorm workspaces -- by base address (checked by e2v_op_pool_guard_report, freed by their base)
-    e2v::GuardTally guard_tally;
-    std::unordered_map<void*, e2v::GuardBlock> guard_dev;
-    void* gn_part_base = nullptr; void* gn_scale_base = nullptr;      // what hipFree takes (== gn_part / gn_scale while unguarded)
+    e2v::GuardTally guard_tally;                                 // E2V_POOL_GUARD (runtime.h): the tally of this context
     e2v_ctx() { pool.bind(&last_stream, &guard_tally); }
     e2v_ctx(const e2v_ctx&) = delete;
     e2v_ctx& operator=(const e2v_ctx&) = delete;
@@ -183,34 +177,33 @@ struct e2v_ctx {
     std::vector<e2v::LinW> sem;                                  // semantic predictor layers (first one K-padded to 4)
     int sem_in_pad = 0;
     std::vector<float> alphas;                                   // host alpha-bar table
-    float* gn_part = nullptr; size_t gn_part_floats = 0;         // GroupNorm workspaces (grown on demand)
-    float* gn_scale = nullptr; size_t gn_scale_floats = 0;
-    long long* d_timesteps = nullptr; int d_timesteps_cap = 0;
+    e2v::GrowBuf gn_part, gn_scale;                              // GroupNorm workspaces (guarded under E2V_POOL_GUARD; not in weight_bytes)
+    e2v::GrowBuf d_timesteps;                                    // int64 (or fp32) timesteps of the running call (never guarded)
     // per-generate caches of what does not depend on the latents: time_emb_proj(SiLU(emb(t_i))) of every resnet and step
     // ([steps][cout] each, call order) and to_k / to_v of the conditioning of every transformer ([N*T][2C] each)
     bool step_cache_on = false; int step_cache_step = 0;
     std::vector<e2v::Act> temb_cache, kv_cache;
-    void grow_timesteps(int n, hipStream_t s);                   // d_timesteps holds at least n entries
+    long long* timesteps(int n, hipStream_t s) { return static_cast<long long*>(d_timesteps.ensure(sizeof(long long) * n, 0, s)); }
     void build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s);
 
     // stream of the previous call (workspace reuse is stream-ordered): see enter_stream
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
     void enter_stream(hipStream_t s);
-    // device blocks made by finalize(), per part (bit index of `which`), so that finalizing a part again frees what it replaces
-    std::vector<float*> owned_part[4];
-    std::unordered_map<void*, size_t> owned_bytes;
+    // device blocks made by dev_alloc, per part (bit index of `which`), so that finalizing a part again frees what it replaces
+    std::vector<e2v::DevBlock> owned_part[4];
+    size_t weight_bytes() const;                                 // what the uploaded tensors and the parts' blocks hold (e2v_device_bytes)
     void* comm = nullptr; int comm_rank = 0, comm_world = 0;     // RCCL communicator of e2v_comm_init (comm.cpp)
     // e2v_op_unet_forward_taps (test aid): while set, unet_forward_cl copies the tensors the oracle exposes (emb, down0..3, mid,
     // up0..3) out as fp32 NCFHW, back to back; shapes = {n, C, F, H, W} per tap
     struct TapSink { float* buf = nullptr; int64_t cap = 0, used = 0; int count = 0; int64_t shapes[16][5]; };
     TapSink* tap_sink = nullptr;
-    int alloc_part = -1;                                         // >= 0: dev_alloc files the block under owned_part[alloc_part]
+    int alloc_part = -1;                                         // the part dev_alloc files its blocks under (every caller selects one)
     struct AllocPart {                                           // dev_alloc files under `part` for the guard's lifetime
         e2v_ctx* c; int saved;
         AllocPart(e2v_ctx* ctx, int part) : c(ctx), saved(ctx->alloc_part) { c->alloc_part = part; }
         ~AllocPart() { c->alloc_part = saved; }
     };
-    void free_part(int part);
+    void free_part(int part) { owned_part[part].clear(); }
     std::unordered_map<std::string, e2v::WBind> bind;            // raw key -> its place in the packed weights (keys of finalized parts)
     void resolve_bindings();
     // e2v_update_tensor: overwrite every existing form of `key` on stream s (data: [numel] of dtype, device or host)

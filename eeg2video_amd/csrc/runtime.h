@@ -36,27 +36,85 @@ struct Error : std::runtime_error {
         if (!(cond)) throw ::e2v::Error((code), (msg));      \
     } while (0)
 
-// ---- E2V_POOL_GUARD: a debug facility for the bounds tests -----------------------------------------------------
-// While the switch is N > 0, every block the library hands to its own kernels -- pool blocks, dev_alloc blocks, the GroupNorm
-// workspaces -- lies inside a larger hipMalloc block: N KiB of guard zone, the payload, and a second guard zone that starts at the
-// payload's exact last byte.  Guards AND payload are filled with 0x7FC07FC0 (a NaN as fp32 and, per 16-bit half, as bf16 and as IEEE
-// half) before the block is handed out, so a kernel that stores outside its tensor changes a guard, and one whose result depends on
-// memory it never wrote produces NaNs.  The zones are compared with the pattern by a small kernel queued on the context's stream
-// (misc.hip: one workgroup per zone pair, plain loads, one thread writes the result slot); e2v_op_pool_guard_report collects.
-// Each queued comparison keeps a result slot (8 bytes on the device, a record on the host) until the next report: a guarded run that
-// never reports grows by 128 KiB of device memory per 16384 released blocks.
+// ---- device memory: one owning block type ------------------------------------------------------------------------------------------
+// Every block the library allocates for itself -- workspace-pool blocks, weight layouts (dev_alloc), the GroupNorm workspaces, the
+// timestep buffer, uploaded tensors, temporaries -- is a DevBlock: [guard | payload | pad to 256 | guard] inside one hipMalloc block,
+// owned by exactly one DevBlock object (move-only; the destructor frees).  guard == 0 is the payload alone, the normal case.
+//
+// E2V_POOL_GUARD, a debug facility for the bounds tests: while the switch is N > 0, the blocks handed to the
+// library's own kernels -- pool blocks, dev_alloc blocks, the GroupNorm workspaces -- are allocated with guard = N KiB; the second
+// guard zone starts at the payload's exact last byte.  Guards AND payload are filled with 0x7FC07FC0 (a NaN as fp32 and, per 16-bit
+// half, as bf16 and as IEEE half) before the block is handed out, so a kernel that stores outside its tensor changes a guard, and one
+// whose result depends on memory it never wrote produces NaNs.  The zones are compared with the pattern by a small kernel queued on
+// the context's stream (misc.hip: one workgroup per zone pair, plain loads, one thread writes the result slot);
+// e2v_op_pool_guard_report collects.  Each queued comparison keeps a result slot (8 bytes on the device, a record on the host) until
+// the next report: a guarded run that never reports grows by 128 KiB of device memory per 16384 released blocks.
 constexpr uint32_t kGuardPattern = 0x7FC07FC0u;
 int pool_guard_kib();                                        // the switch, read live (bgemm.hip: the knob table)
 // queue the comparison of [lead, lead + guard) and [trail, trail + guard) with the pattern, in 16-bit units: slot[0] / slot[1] receive the
 // index of the first altered unit of each zone, or 0xFFFFFFFF (misc.hip)
 void pool_guard_check(const void* lead, const void* trail, size_t guard_bytes, uint32_t* slot, hipStream_t s);
 
-struct GuardBlock {                                          // one guarded allocation: [base | guard | payload ... | guard | slack]
+struct DevBlock {
     void* base = nullptr;
-    size_t total = 0, guard = 0, payload = 0;
+    size_t total = 0, guard = 0, payload = 0;                // total == 0 with a base: the address a dry run handed out, nothing owned
+    DevBlock() = default;
+    DevBlock(const DevBlock&) = delete;
+    DevBlock& operator=(const DevBlock&) = delete;
+    DevBlock(DevBlock&& o) noexcept { *this = std::move(o); }
+    DevBlock& operator=(DevBlock&& o) noexcept {
+        if (this != &o) {
+            release();
+            base = o.base; total = o.total; guard = o.guard; payload = o.payload;
+            o.base = nullptr; o.total = o.guard = o.payload = 0;
+        }
+        return *this;
+    }
+    ~DevBlock() { release(); }
+    void release() {
+        if (total) (void)hipFree(base);
+        base = nullptr; total = guard = payload = 0;
+    }
+    explicit operator bool() const { return base != nullptr; }
     char* lead() const { return static_cast<char*>(base); }
     char* data() const { return static_cast<char*>(base) + guard; }
     char* trail() const { return data() + payload; }
+    float* f32() const { return reinterpret_cast<float*>(data()); }
+};
+
+// fill guards and payload of a guarded block with the pattern on stream s
+inline void dev_block_poison(const DevBlock& b, hipStream_t s, bool sync) {
+    hipError_t e = hipMemsetD32Async((hipDeviceptr_t)b.base, (int)kGuardPattern, b.total / 4, s);
+    if (e == hipSuccess && sync) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) throw Error(E2V_EHIP, std::string("poisoning a guarded block: ") + hipGetErrorString(e));
+}
+
+// THE allocation: `bytes` of payload, between two zones of `guard` bytes when guard > 0 and then poisoned on stream s (sync: and waited
+// for).  A dry run (e2v_op_describe_dispatch) gets a distinct address nobody dereferences and owns nothing.
+inline DevBlock dev_block(size_t bytes, size_t guard, hipStream_t s, bool sync) {
+    DevBlock b;
+    b.payload = bytes;
+    if (dry_run()) { b.base = dry_fake_ptr(bytes); return b; }
+    const size_t total = guard ? guard + (bytes + 255) / 256 * 256 + guard : bytes;
+    const hipError_t e = hipMalloc(&b.base, total);
+    if (e != hipSuccess) { b.base = nullptr; throw Error(E2V_EHIP, std::string("hipMalloc device block: ") + hipGetErrorString(e)); }
+    b.total = total; b.guard = guard;
+    if (guard) dev_block_poison(b, s, sync);
+    return b;
+}
+
+// A grow-only buffer (the GroupNorm workspaces, the timestep buffer).  Work queued on s may still read the block it replaces, so
+// growing waits for the stream first.
+struct GrowBuf {
+    DevBlock blk;
+    void* ensure(size_t bytes, size_t guard, hipStream_t s) {
+        if (!blk || blk.payload < bytes) {
+            E2V_HIP(hipStreamSynchronize(s));
+            blk.release();
+            blk = dev_block(bytes, guard, s, true);
+        }
+        return blk.data();
+    }
 };
 
 // The tally of one context: result slots on the device (one pair per queued comparison), what each pair belongs to on the host.
@@ -64,7 +122,7 @@ class GuardTally {
 public:
     ~GuardTally() { for (uint32_t* c : chunks_) (void)hipFree(c); }
     // queue the comparison of b's two zones on s
-    void check(const GuardBlock& b, const char* kind, hipStream_t s) {
+    void check(const DevBlock& b, const char* kind, hipStream_t s) {
         if (used_ == chunks_.size() * kSlots) {
             uint32_t* c = nullptr;
             if (hipMalloc((void**)&c, kSlots * 2 * sizeof(uint32_t)) != hipSuccess) throw Error(E2V_EHIP, "hipMalloc guard tally");
@@ -111,25 +169,11 @@ private:
     std::string text_;
 };
 
-// a guarded block around `bytes` of payload, all of it poisoned on stream s (null: synchronously).  The caller keeps base for hipFree.
-inline GuardBlock guard_alloc(size_t bytes, size_t guard, hipStream_t s, bool sync) {
-    GuardBlock b;
-    b.guard = guard; b.payload = bytes;
-    b.total = guard + (bytes + 255) / 256 * 256 + guard;
-    hipError_t e = hipMalloc(&b.base, b.total);
-    if (e != hipSuccess) throw Error(E2V_EHIP, std::string("hipMalloc guarded block: ") + hipGetErrorString(e));
-    e = hipMemsetD32Async((hipDeviceptr_t)b.base, (int)kGuardPattern, b.total / 4, s);
-    if (e == hipSuccess && sync) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hipFree(b.base); throw Error(E2V_EHIP, std::string("poisoning a guarded block: ") + hipGetErrorString(e)); }
-    return b;
-}
-
 // Stream-ordered workspace cache.  All work of a ctx runs on one stream at a time, so a buffer handed
 // back is immediately reusable by later launches on that stream; blocks are kept by size and reused,
 // which makes steady-state calls allocation-free (hipMalloc only while the shape mix is new).
 class Pool {
 public:
-    ~Pool() { trim(); }
     // the context's current stream and tally, for the guarded mode (E2V_POOL_GUARD)
     void bind(const hipStream_t* stream, GuardTally* tally) { stream_ = stream; tally_ = tally; }
     // e2v_destroy: blocks released from here on are not compared any more (the caller's stream may be gone, nobody reads the tally)
@@ -145,90 +189,67 @@ public:
             trim();
             guard_kib_ = guard_kib;
         }
-        if (guard_kib > 0) return get_guarded(exact, (size_t)guard_kib * 1024);
-        auto it = free_.lower_bound(bytes);
-        if (it != free_.end() && it->first <= bytes + bytes / 4) {
-            void* p = it->second;
-            size_t sz = it->first;
+        // unguarded: the payload is the 256-rounded size; guarded: the exact one (a guard zone starts at the tensor's last byte).  Blocks
+        // are filed by their total size: reuse takes the smallest one of at least this size and at most a quarter larger.
+        const size_t guard = (size_t)guard_kib * 1024;
+        const size_t payload = guard ? exact : bytes;
+        const size_t need = guard ? guard + (exact + 255) / 256 * 256 + guard : bytes;
+        const hipStream_t s = stream_ ? *stream_ : nullptr;
+        DevBlock b;
+        auto it = free_.lower_bound(need);
+        while (it != free_.end() && it->first <= need + need / 4 && it->second.guard != guard) ++it;    // (a block of the other kind, released after the flip)
+        if (it != free_.end() && it->first <= need + need / 4) {
+            b = std::move(it->second);
             free_.erase(it);
-            live_[p] = sz;
-            return static_cast<float*>(p);
+            if (guard) {
+                b.payload = exact;
+                try {
+                    dev_block_poison(b, s, false);
+                } catch (const Error&) {                     // (b is freed on the way out)
+                    total_ -= b.total;
+                    throw;
+                }
+            }
+        } else {
+            try {
+                b = dev_block(payload, guard, s, false);
+            } catch (const Error&) {                         // out of memory: give the cached blocks back and try once more
+                trim();
+                b = dev_block(payload, guard, s, false);
+            }
+            total_ += b.total;
         }
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess) {
-            trim();
-            e = hipMalloc(&p, bytes);
-        }
-        if (e != hipSuccess) throw Error(E2V_EHIP, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-        total_ += bytes;
-        live_[p] = bytes;
-        return static_cast<float*>(p);
+        float* p = b.f32();
+        live_.emplace(p, std::move(b));
+        return p;
     }
     void put(float* p) {
         if (!p) return;
         auto it = live_.find(p);
-        if (it == live_.end()) {
-            if (!guarded_.empty()) put_guarded(p);
-            return;
-        }
-        free_.emplace(it->second, p);
+        if (it == live_.end()) return;
+        const auto filed = free_.emplace(it->second.total, std::move(it->second));      // (filed first: a throw below must not leak it)
         live_.erase(it);
+        if (filed->second.guard == 0 || closing_) return;
+        try {
+            tally_->check(filed->second, "pool", stream_ ? *stream_ : nullptr);
+        } catch (const Error&) {                             // (put runs in destructors; a block that could not be checked is not counted)
+        }
     }
-    void trim() {
-        for (auto& kv : free_) {
-            (void)hipFree(kv.second);
-            total_ -= kv.first;
-        }
+    void trim() {                                            // (hipFree waits for the comparisons queued on these blocks)
+        for (auto& kv : free_) total_ -= kv.first;
         free_.clear();
-        for (auto& kv : gfree_) {                            // (hipFree waits for the comparisons queued on these blocks)
-            (void)hipFree(kv.second.base);
-            total_ -= kv.first;
-        }
-        gfree_.clear();
     }
     size_t bytes() const { return total_; }
     int64_t gets() const { return gets_; }                   // blocks handed out so far (e2v_op_pool_gets: what a guarded run must have checked)
     // e2v_op_pool_guard_report: queue the comparison of the guarded blocks that are still live
     void check_live(hipStream_t s) {
-        for (auto& kv : guarded_) tally_->check(kv.second, "pool (live)", s);
+        for (auto& kv : live_)
+            if (kv.second.guard) tally_->check(kv.second, "pool (live)", s);
     }
 
 private:
-    float* get_guarded(size_t exact, size_t guard) {
-        const hipStream_t s = stream_ ? *stream_ : nullptr;
-        const size_t need = guard + (exact + 255) / 256 * 256 + guard;
-        GuardBlock b;
-        auto it = gfree_.lower_bound(need);
-        if (it != gfree_.end() && it->first <= need + need / 4 && it->second.guard == guard) {
-            b = it->second;
-            gfree_.erase(it);
-            b.payload = exact;
-            hipError_t e = hipMemsetD32Async((hipDeviceptr_t)b.base, (int)kGuardPattern, b.total / 4, s);
-            if (e != hipSuccess) throw Error(E2V_EHIP, std::string("poisoning a guarded block: ") + hipGetErrorString(e));
-        } else {
-            b = guard_alloc(exact, guard, s, false);
-            total_ += b.total;
-        }
-        guarded_[b.data()] = b;
-        return reinterpret_cast<float*>(b.data());
-    }
-    void put_guarded(float* p) {
-        auto it = guarded_.find(p);
-        if (it == guarded_.end()) return;
-        const GuardBlock b = it->second;
-        guarded_.erase(it);
-        gfree_.emplace(b.total, b);                          // (filed first: a throw below must not leak it)
-        if (closing_) return;
-        try {
-            tally_->check(b, "pool", stream_ ? *stream_ : nullptr);
-        } catch (const Error&) {                             // (put runs in destructors; a block that could not be checked is not counted)
-        }
-    }
-    std::multimap<size_t, void*> free_;
-    std::unordered_map<void*, size_t> live_;
-    std::multimap<size_t, GuardBlock> gfree_;                // guarded blocks by total size
-    std::unordered_map<void*, GuardBlock> guarded_;          // live guarded blocks by payload address
+    std::multimap<size_t, DevBlock> free_;                   // by total size
+    std::unordered_map<void*, DevBlock> live_;               // by payload address
     const hipStream_t* stream_ = nullptr;
     GuardTally* tally_ = nullptr;
     int guard_kib_ = 0;
@@ -272,7 +293,8 @@ struct Act {
 };
 
 struct WTensor {
-    float* d = nullptr;             // device, torch layout, fp32
+    DevBlock mem;                   // device, torch layout, fp32 (unguarded: DESIGN section 5)
+    float* d() const { return mem.f32(); }
     std::vector<int64_t> shape;
     size_t numel = 0;
     bool loaded = false;

@@ -1,4 +1,5 @@
 /* Drives the host-only part of the C ABI (e2v_create(device = -1): key scheme, DDIM schedule, argument checks, error paths)
+ * and a dry-run walk of the graphs (e2v_op_describe_dispatch: finalize, the owners of device memory, the pool, with no HIP call)
  * -- built against the AddressSanitizer build of the library by tests/test_host_asan.py.  Plain C: this is also the proof
  * that include/eeg2video_hip.h is consumable from C.  Exit code 0 = every check held and ASan reported nothing. */
 #include <stdio.h>
@@ -6,6 +7,7 @@
 #include <string.h>
 
 #include "eeg2video_hip.h"
+#include "eeg2video_hip_ops.h"
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "check failed at line %d: %s\n", __LINE__, #c); return 1; } } while (0)
 
@@ -63,6 +65,21 @@ int main(void) {
     CHECK(e2v_create(&cfg, -1, &ctx) == E2V_EINVAL);
     CHECK(e2v_create(NULL, -1, &ctx) == E2V_EINVAL);
     e2v_destroy(NULL);
+    /* dry-run walk on a host-only context: finalize, dev_alloc, the conv layouts, the GroupNorm workspaces, the timestep buffer
+     * and the pool's dry-run path hand out addresses and own nothing -- e2v_destroy must find nothing to free and nothing leaked */
+    cfg.norm_num_groups = 32;
+    CHECK(e2v_create(&cfg, -1, &ctx) == E2V_OK && ctx != NULL);
+    const int modes[2] = {E2V_F32, E2V_BF16};
+    for (int m = 0; m < 2; ++m) {
+        int64_t needed = 0;
+        CHECK(e2v_op_describe_dispatch(ctx, modes[m], 1, 6, 36, 64, 77, NULL, 0, &needed) == E2V_OK && needed > 1);
+        char* text = (char*)malloc((size_t)needed);
+        CHECK(text != NULL && e2v_op_describe_dispatch(ctx, modes[m], 1, 6, 36, 64, 77, text, needed, &needed) == E2V_OK);
+        CHECK((int64_t)strlen(text) + 1 == needed && strstr(text, "x ") != NULL);
+        free(text);
+    }
+    CHECK(e2v_device_bytes(ctx) == 0);
+    e2v_destroy(ctx);
     printf("host_abi_driver: ok (%lld keys, %lld parameters)\n", (long long)n, (long long)total);
     return 0;
 }
