@@ -90,6 +90,8 @@ SIGNATURES = {
     "e2v_op_conv3x3": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _i, _p, _p, _stream]),
     "e2v_op_conv3x3_gn": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _i, _p, _i, _p, _p, _stream]),
     "e2v_op_linear": (_i, [_ctx, _p, _i, _i64, _i, _p, _p, _i, _p, _i, _p, _stream]),
+    "e2v_op_linear_cat": (_i, [_ctx, _p, _i, _i, _p, _i, _i, _i64, _p, _p, _i, _p, _i, _p, _stream]),
+    "e2v_op_last_dispatch": (_i, [C.c_char_p, _i64]),
     "e2v_op_groupnorm": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _f, _p, _p, _i, _p, _stream]),
     "e2v_op_layernorm": (_i, [_ctx, _p, _i64, _i, _p, _p, _f, _p, _stream]),
     "e2v_op_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _stream]),

@@ -74,6 +74,24 @@ hipStream_t S(e2v_ctx* c, e2v_stream s) {
     return hs;
 }
 
+// Test aid (E2V_OP_RECORD, e2v_op_last_dispatch): for the length of one kernel-level entry point the launchers' dry_tag() texts are kept
+// for the real launches too, in the calling thread's string, cleared here.  Switch off: one test of it, nothing else.
+struct OpRecord {
+    OpRecord() {
+        static const int* const on = knob("E2V_OP_RECORD", 0);
+        if (*on) { op_dispatch().clear(); op_recording() = true; }
+    }
+    ~OpRecord() { op_recording() = false; }
+};
+
+// Test aid (E2V_OP_IO16): e2v_op_linear / e2v_op_conv3x3 of a 16-bit context build the launch of Runner::linear / Runner::conv3
+// (model.cpp) -- a 16-bit pool tensor of exactly M x N for the output, the residual converted to the type, out_f32 = 0, resid_bf16 = 1
+// -- and widen the result into the caller's fp32 tensor afterwards.  Ignored in the fp32 and f32x3 modes.
+bool op_io16(const e2v_ctx* c) {
+    static const int* const on = knob("E2V_OP_IO16", 0);
+    return c->bf16_compute && *on != 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -745,6 +763,7 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
     return guarded(c, [&] {
         E2V_REQUIRE(x0 && w_oihw && out && c0 % 4 == 0 && c1 % 4 == 0 && c0 > 0, E2V_EINVAL, "bad conv arguments");
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         const int cin = c0 + c1;
         E2V_REQUIRE(c1 == 0 || c0 % 32 == 0, E2V_ESHAPE, "conv: the concat seam must be a multiple of 32 channels");
         Conv3 d;                     // the launch as the graph runner describes it (model.h); the weight forms are pool temporaries here
@@ -764,9 +783,17 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
             pack_conv3x3(w_oihw, w64.p, cout, cin, 64, s);
             to_h16(w64.p, w16.p, (size_t)cout * ld64, c->h16_mode, s);
             d.x0 = a0.p; d.c0 = c0p; d.x1 = a1.p; d.c1 = c1p;
+            const bool io16 = op_io16(c);                  // the graph's launch: 16-bit output tensor, 16-bit residual
+            const int64_t rows_out = (int64_t)n_img * Ho * Wo;
+            Act o16, r16;
+            if (io16) {
+                o16 = Act(c->pool, rows_out, cout, true);
+                d.out = o16.p;
+                if (resid) { r16 = Act(c->pool, rows_out, cout, true); cvt_rows(resid, cout, 0, r16.p, cout, c->h16_mode, rows_out, cout, cout, s); d.resid = r16.p; }
+            }
             IgemmArgs g = conv3_igemm(d);
             g.w16 = w16.p; g.ldw16 = ld64; g.ldw = ld64;
-            g.a_bf16 = c->h16_mode; g.out_f32 = 1;
+            g.a_bf16 = c->h16_mode; g.out_f32 = io16 ? 0 : 1; g.resid_bf16 = io16 && resid ? 1 : 0;
             // test aid: E2V_SPLITK_FORCE = S runs the launch as split-K with S runs where it is eligible (the graph asks for it by itself
             // in the small-batch family, model.cpp Runner::sk_setup)
             static const int* const sk_force = knob("E2V_SPLITK_FORCE", 0);
@@ -781,6 +808,7 @@ e2v_status e2v_op_conv3x3(e2v_ctx* c, const float* x0, int c0, const float* x1, 
             } else {
                 igemm(g, s);
             }
+            if (io16) cvt_rows(o16.p, cout, c->h16_mode, out, cout, 0, rows_out, cout, cout, s);      // exact
         } else if (const int wm = c->conv_wino_tile(cin, cout, stride, pad_lo, Hi, Wi, Ho, Wo)) {      // the graph runner's policy
             Act u(c->pool, (int64_t)(wm + 2) * (wm + 2) * cout, cin);
             wino_pack_weights(w_oihw, u.p, cout, cin, wm, s);
@@ -823,6 +851,7 @@ e2v_status e2v_op_conv3x3_gn(e2v_ctx* c, const float* x0, int c0, const float* x
     }
     return guarded(c, [&] {
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         const int samples = (int)(rows / gn_P);
         Act part(c->pool, (int64_t)samples * groupnorm_chunks(gn_P), cin * 2);
         Act sc(c->pool, samples, cin * 2);
@@ -851,13 +880,31 @@ e2v_status e2v_op_conv3x3_gn(e2v_ctx* c, const float* x0, int c0, const float* x
 
 e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, const float* w, const float* bias, int N,
                          const float* resid, int geglu, float* out, e2v_stream stream) {
+    return e2v_op_linear_cat(c, x, K, ldx, nullptr, 0, 0, M, w, bias, N, resid, geglu, out, stream);
+}
+
+e2v_status e2v_op_linear_cat(e2v_ctx* c, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, int64_t M, const float* w,
+                             const float* bias, int N, const float* resid, int geglu, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
+    // the argument checks make no HIP call, so they come before guarded(): a host-only context answers them too
+    // one source: fp32 arithmetic reads 16-byte row pieces of the caller's tensor; the bf16-activation mode re-lays its operands out (K padded to 8)
+    if (!(x0 && w && out && c0 > 0 && c1 >= 0 && (c1 == 0 || x1) && M >= 0 && N > 0 && (c->bf16_compute || (c0 % 4 == 0 && ld0 % 4 == 0)))) {
+        c->err = "bad linear arguments";
+        return E2V_EINVAL;
+    }
+    // two sources: the granularity Runner::linear asks for (the K loop changes source on a whole 16-byte piece)
+    const int gran = c->bf16_compute ? 8 : 4;
+    if (c1 > 0 && (c0 % gran || c1 % gran || (!c->bf16_compute && ld1 % 4) || ld0 < c0 || ld1 < c1)) {
+        c->err = "linear: K must be a multiple of 4 (bf16: 8)";
+        return E2V_ESHAPE;
+    }
     return guarded(c, [&] {
-        // fp32 arithmetic reads 16-byte row pieces of the caller's tensor; the bf16-activation mode re-lays its operands out (K padded to 8)
-        E2V_REQUIRE(x && w && out && (c->bf16_compute || (K % 4 == 0 && ldx % 4 == 0)), E2V_EINVAL, "bad linear arguments");
         hipStream_t s = S(c, stream);
+        OpRecord rec;
+        const int K = c0 + c1;
         IgemmArgs g;
-        g.a0 = x; g.c0 = K; g.lda0 = ldx; g.ldw = K; g.out = out; g.M = (int)M; g.taps = 1; g.resid = resid;
+        g.a0 = x0; g.c0 = c0; g.lda0 = ld0; g.a1 = c1 > 0 ? x1 : nullptr; g.c1 = c1; g.lda1 = c1 > 0 ? ld1 : 0;
+        g.ldw = K; g.out = out; g.M = (int)M; g.taps = 1; g.resid = resid;
         Act wp, bp;
         if (geglu) {
             E2V_REQUIRE(N % 32 == 0 && bias, E2V_EINVAL, "GEGLU width must be a multiple of 32 and have a bias");
@@ -868,15 +915,22 @@ e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, 
         } else {
             g.w = w; g.bias = bias; g.N = N; g.ldc = N; g.ldr = N;
         }
-        Act w16, wpad, a16;
+        Act w16, a16, b16, o16, r16;
+        const bool io16 = op_io16(c);      // the graph's launch: 16-bit output tensor, 16-bit residual
         if (c->bf16_compute) {       // bf16-activation mode: A and W rounded to bf16 once (K zero-padded to 8), fp32 result
-            const int K8 = (K + 7) / 8 * 8;
-            a16 = Act(c->pool, M, K8, true);
-            cvt_rows(x, ldx, 0, a16.p, K8, c->h16_mode, M, K, K8, s);
+            const int K8 = (K + 7) / 8 * 8, c0p = c1 > 0 ? c0 : K8;
+            a16 = Act(c->pool, M, c0p, true);
+            cvt_rows(x0, ld0, 0, a16.p, c0p, c->h16_mode, M, c0, c0p, s);
+            if (c1 > 0) { b16 = Act(c->pool, M, c1, true); cvt_rows(x1, ld1, 0, b16.p, c1, c->h16_mode, M, c1, c1, s); }
             w16 = Act(c->pool, g.N, K8, true);
             cvt_rows(g.w, K, 0, w16.p, K8, c->h16_mode, g.N, K, K8, s);
-            g.a0 = a16.p; g.c0 = K8; g.lda0 = K8;
+            g.a0 = a16.p; g.c0 = c0p; g.lda0 = c0p; g.a1 = b16.p; g.lda1 = c1;
             g.a_bf16 = c->h16_mode; g.out_f32 = 1; g.w16 = w16.p; g.ldw16 = K8;
+            if (io16) {
+                o16 = Act(c->pool, M, N, true);
+                g.out = o16.p; g.out_f32 = 0;
+                if (resid) { r16 = Act(c->pool, M, N, true); cvt_rows(resid, N, 0, r16.p, N, c->h16_mode, M, N, N, s); g.resid = r16.p; g.resid_bf16 = 1; }
+            }
         }
         static const int* const sk_force = knob("E2V_SPLITK_FORCE", 0);      // test aid, as in e2v_op_conv3x3
         Act skws;
@@ -889,6 +943,7 @@ e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, 
             g.x3 = 1; g.w3 = w3.p; g.w3_plane = (long long)n;
         }
         igemm(g, s);
+        if (io16) cvt_rows(o16.p, N, c->h16_mode, out, N, 0, M, N, N, s);      // exact
         E2V_HIP(hipGetLastError());
     });
 }
@@ -900,6 +955,7 @@ e2v_status e2v_op_groupnorm(e2v_ctx* c, const float* x0, int c0, const float* x1
         const int C = c0 + c1;
         E2V_REQUIRE(x0 && gamma && beta && out && c0 % 4 == 0 && c1 % 4 == 0 && C % groups == 0, E2V_EINVAL, "bad groupnorm arguments");
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         Act part(c->pool, (int64_t)samples * groupnorm_chunks(P), C * 2);
         Act sc(c->pool, samples, C * 2);
         GroupNormArgs a;
@@ -931,6 +987,7 @@ e2v_status e2v_op_layernorm(e2v_ctx* c, const float* x, int64_t rows, int C, con
     return guarded(c, [&] {
         E2V_REQUIRE(x && gamma && beta && out && C % 4 == 0 && C <= 1280, E2V_EINVAL, "bad layernorm arguments");
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         if (c->bf16_compute) {
             Act bi(c->pool, rows, C, true), bo(c->pool, rows, C, true);
             cvt_rows(x, C, 0, bi.p, C, c->h16_mode, rows, C, C, s);
@@ -950,6 +1007,7 @@ e2v_status e2v_op_rowblock_sums(e2v_ctx* c, const float* x, int64_t rows, int C,
     return guarded(c, [&] {
         E2V_REQUIRE(x && out && rows > 0 && rows % 64 == 0 && C > 0 && C % 8 == 0, E2V_EINVAL, "rowblock_sums: rows must be a multiple of 64, C of 8");
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         Act b(c->pool, rows, C, true);
         cvt_rows(x, C, 0, b.p, C, H16_BF16, rows, C, C, s);
         rowblock_sums(b.p, C, C, rows, rbsum_rows_per_pass(C), out, s);
@@ -970,6 +1028,7 @@ e2v_status e2v_op_attention(e2v_ctx* c, const float* q, int ldq, const float* k,
         a.q = q; a.ldq = ldq; a.k = k; a.v = v; a.ldkv = ldkv; a.o = o; a.ldo = ldo; a.n = n; a.F = F; a.heads = heads; a.D = D;
         a.Nq = Nq; a.Nk = Nk; a.mode = mode; a.scale = scale; a.x3 = c->x3_compute ? 1 : 0;
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         if (c->bf16_compute) {       // bf16-activation mode: Q, K, V rounded to bf16 rows once; O comes back as bf16
             const int C = heads * D;
             const int64_t qrows = (int64_t)n * F * Nq, krows = mode == 0 ? (int64_t)n * F * Nk : (int64_t)n * Nk;
@@ -994,6 +1053,7 @@ e2v_status e2v_op_temporal_attention(e2v_ctx* c, const float* qkv, float* out, i
         E2V_REQUIRE(qkv && out && D % 4 == 0, E2V_EINVAL, "bad temporal attention arguments");
         const int C = heads * D;
         hipStream_t s = S(c, stream);
+        OpRecord rec;
         if (c->bf16_compute) {
             const int64_t rows = (int64_t)n * F * HW;
             Act bi(c->pool, rows, 3 * C, true), bo(c->pool, rows, C, true);
@@ -1073,6 +1133,20 @@ e2v_status e2v_op_pool_guard_selftest(e2v_ctx* c, int64_t payload_bytes, int64_t
         c->pool.put(p);
         E2V_HIP(e);
     });
+}
+
+// Test aid: the dry_tag() texts of the launches the calling thread's latest kernel-level entry point made (E2V_OP_RECORD on), else "".
+// No HIP call: a host-only context answers it too.
+e2v_status e2v_op_last_dispatch(char* buf, int64_t cap) {
+    if (cap < 0 || (cap > 0 && !buf)) return E2V_EINVAL;
+    static const int* const on = knob("E2V_OP_RECORD", 0);
+    if (cap == 0) return E2V_OK;
+    if (!*on) { buf[0] = 0; return E2V_OK; }
+    const std::string& t = op_dispatch();
+    const size_t n = std::min(t.size(), (size_t)cap - 1);
+    std::memcpy(buf, t.data(), n);
+    buf[n] = 0;
+    return E2V_OK;
 }
 
 e2v_status e2v_op_set_knob(const char* name, int value) {

@@ -15,8 +15,16 @@ namespace e2v {
 // and every ProfScope records its (shape- and kernel-tagged) name instead of timing: the list IS the dispatch of that configuration.
 inline bool& dry_run() { static thread_local bool on = false; return on; }
 inline std::vector<std::string>& dry_log() { static thread_local std::vector<std::string> log; return log; }
+// Test aid (e2v_op_last_dispatch, switch E2V_OP_RECORD): while a kernel-level entry point runs with the switch on, the launchers' tags
+// of its REAL launches are kept too, in a string of the calling thread that the entry point cleared when it was entered.
+inline bool& op_recording() { static thread_local bool on = false; return on; }
+inline std::string& op_dispatch() { static thread_local std::string tags; return tags; }
 inline void dry_tag(const std::string& tag) {               // a launcher's decision, appended to the record its ProfScope made
-    if (dry_run() && !dry_log().empty()) dry_log().back() += tag;
+    if (dry_run()) {
+        if (!dry_log().empty()) dry_log().back() += tag;
+    } else if (op_recording()) {
+        op_dispatch() += tag;
+    }
 }
 inline float* dry_fake_ptr(size_t bytes) {                  // distinct, 256-byte aligned, never dereferenced
     static thread_local uintptr_t next = (uintptr_t)1 << 40;

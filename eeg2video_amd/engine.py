@@ -517,14 +517,28 @@ class Engine:
                                                rows_per_sample, p(resid), out.data_ptr(), _stream()))
         return out
 
-    def op_linear(self, x, w, bias=None, resid=None, geglu=False, out=None):
+    def op_linear(self, x, w, bias=None, resid=None, geglu=False, out=None, x1=None):
+        """``x`` (and ``x1``): 2-D views with unit column stride, row stride = ``.stride(0)``.  ``x1``: second source, the K columns of
+        a row are ``[x ; x1]`` (``e2v_op_linear_cat``)."""
         m, k = x.shape
         n = w.shape[0] // 2 if geglu else w.shape[0]
         out = self._op_out(out, (m, n))
         p = lambda t: t.data_ptr() if t is not None else None
-        self._check(self.lib.e2v_op_linear(self.ctx, x.data_ptr(), x.stride(0), m, k, w.data_ptr(), p(bias), n, p(resid),
-                                           int(geglu), out.data_ptr(), _stream()))
+        if x1 is None:
+            self._check(self.lib.e2v_op_linear(self.ctx, x.data_ptr(), x.stride(0), m, k, w.data_ptr(), p(bias), n, p(resid),
+                                               int(geglu), out.data_ptr(), _stream()))
+        else:
+            if x1.shape[0] != m or w.shape[1] != k + x1.shape[1]:
+                raise ValueError(f"two-source linear: x {tuple(x.shape)}, x1 {tuple(x1.shape)}, w {tuple(w.shape)}")
+            self._check(self.lib.e2v_op_linear_cat(self.ctx, x.data_ptr(), k, x.stride(0), x1.data_ptr(), x1.shape[1], x1.stride(0), m,
+                                                   w.data_ptr(), p(bias), n, p(resid), int(geglu), out.data_ptr(), _stream()))
         return out
+
+    def last_dispatch(self) -> str:
+        """Test aid (``e2v_op_last_dispatch``, switch ``E2V_OP_RECORD``): the kernels that served this thread's latest op call."""
+        buf = C.create_string_buffer(4096)
+        self._check(self.lib.e2v_op_last_dispatch(buf, len(buf)))
+        return buf.value.decode()
 
     def op_rowblock_sums(self, x, out=None):
         """Canonical (sum, sum of squares) per 64-row block and column of ``x`` rounded to bf16: ``[rows / 64, C, 2]``."""

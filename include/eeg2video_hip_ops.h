@@ -5,6 +5,12 @@
  * tensors: [n, F, H, W, C] is a row-major matrix [n*F*H*W][C].  Weights are device pointers in the
  * torch layouts the reference's modules hold (Conv2d [Cout,Cin,3,3], Linear [out,in]).
  * Reference op each one stands for is named per function (paths relative to the reference repo).
+ *
+ * In the 16-bit modes e2v_op_linear(_cat) and e2v_op_conv3x3 round their operands to the type and, by default, run the launch with an
+ * fp32 output and an fp32 residual.  While the run-time switch "E2V_OP_IO16" (e2v_op_set_knob, or the environment variable; default
+ * 0) is non-zero they run the launch the GRAPH makes instead: the output is a 16-bit workspace tensor of exactly M x N, the residual is
+ * converted to the type first, and the 16-bit result is widened (exactly) into the caller's fp32 `out`; bias and rowbias stay fp32.
+ * The fp32 and f32x3 modes ignore the switch.
  */
 #ifndef EEG2VIDEO_HIP_OPS_H
 #define EEG2VIDEO_HIP_OPS_H
@@ -42,6 +48,13 @@ e2v_status e2v_op_conv3x3_gn(e2v_ctx* ctx, const float* x0, int c0, const float*
  * out[M][N2] = (x w_v^T + b_v) * gelu_erf(x w_g^T + b_g). */
 e2v_status e2v_op_linear(e2v_ctx* ctx, const float* x, int ldx, int64_t M, int K, const float* w, const float* bias,
                          int N, const float* resid, int geglu, float* out, e2v_stream stream);
+
+/* The same with the K columns of a row coming from two tensors, [x0 (c0 columns, row stride ld0) ; x1 (c1, ld1)] -- the 1x1 shortcut of
+ * the up-block resnets over the concat [h ; skip] (resnet.py:199-202 after unet_blocks.py's torch.cat), the K loop crossing the seam.
+ * w: [N or 2 N][c0 + c1].  x1 = NULL, c1 = 0: e2v_op_linear.  With two sources c0 and c1 are multiples of 4 (16-bit modes: 8) and, in
+ * the fp32 modes, so are the row strides: E2V_ESHAPE otherwise (checked before any device work: a host-only context answers too). */
+e2v_status e2v_op_linear_cat(e2v_ctx* ctx, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, int64_t M,
+                             const float* w, const float* bias, int N, const float* resid, int geglu, float* out, e2v_stream stream);
 
 /* nn.GroupNorm (+ SiLU) with statistics over (C/groups channels) x (P rows) per slab; slabs = samples.
  * 5-D GroupNorm of ResnetBlock3D (resnet.py:177): samples = n, P = F*H*W.  Per-frame GroupNorm of
@@ -105,6 +118,13 @@ e2v_status e2v_op_describe_dispatch(e2v_ctx* ctx, int dtype, int B, int F, int h
  * same name would give it at first use), for same-process A/B comparisons of kernel variants -- e.g. "E2V_BGEMM_PERS" 0/1.
  * Process-wide; E2V_EINVAL for an unknown name.  No reference counterpart. */
 e2v_status e2v_op_set_knob(const char* name, int value);
+
+/* Test aid: which kernel served the launch I just made?  While the run-time switch "E2V_OP_RECORD" (default 0) is non-zero, every
+ * conv / linear / norm / attention entry point of this header clears a string of the calling thread when it is entered and the
+ * launchers append their decision to it (" -> kernel tile", the text e2v_op_describe_dispatch records in a dry run) for each launch
+ * they make.  This call copies that string to buf (NUL-terminated, cut at cap); switch off: "".  It makes no HIP call, so any thread
+ * may ask, with or without a GPU.  E2V_EINVAL for cap < 0 or a null buf with cap > 0.  No reference counterpart. */
+e2v_status e2v_op_last_dispatch(char* buf, int64_t cap);
 
 /* Test aid for e2v_update_tensor: which forms of the tensor behind state-dict key `key` (of a finalized part) exist on the device right
  * now -- one bit each in *mask.  A linear (or 1x1 conv) weight: its fp32 matrix, the bf16 copy finalize makes, the fp16 copy the fp16

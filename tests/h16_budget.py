@@ -1,5 +1,7 @@
 """Per-element rounding budgets for the ops of the 16-bit modes whose output is stored in 16 bits: GroupNorm, LayerNorm, sparse-causal,
-cross and temporal attention.  Pure torch on the CPU, float64; no kernel is called from here.
+cross and temporal attention and -- in a section of its own at the end, with its own references, budget, mutants and case table -- the
+GEMM-shaped ops (linear, GEGLU, 3x3 conv, split-K, sub-pixel conv, two-source linear) as the graph launches them.  Pure torch on the
+CPU, float64; no kernel is called from here.
 
 What is here, and who uses it:
 
@@ -499,3 +501,423 @@ def temporal_mutants(case):
 
 def form_id(form):
     return ",".join(f"{k[4:]}={v}" for k, v in form.items()) or "default"
+
+
+# ================================================================================================================
+# GEMM-shaped ops (linear, GEGLU, 3x3 conv, two-source linear) stored in 16 bits: the launch the graph makes (switch E2V_OP_IO16)
+# ================================================================================================================
+# Reference: float64 on operands rounded as the kernels round them -- x, w and the residual to the type (the sub-pixel form of resize +
+# conv: the tap SUMS of w, taken in fp32, rounded once), bias and the time-embedding rows ("rowbias") as the fp32 values they are.
+# Budget, per element, with S = sum_k |x_k w_k| + |bias| + |rowbias| + |resid| and e32 = DELTA S:
+#
+#     |y - ref| <= max(u (|ref| + e32), h/2) + e32
+#
+# -- ONE rounding of the stored value (of a sum that is itself e32 off) plus the suite's fp32 summation-order allowance.  GEGLU,
+# ref = v gate(g): S = S_v |gate(g)| + GATE_SLOPE |v| S_g (|gate'| <= 1.13) and e32 gets DELTA_G |v| (|g| + 1) for the gate's hardware
+# exp2 / rcp -- DELTA_G is measured (see below), everything else is derived.
+# DELTA_G: measured on an MI355X from the fp32-OUTPUT GEGLU form (switch off; tests/test_hip_h16_gemm_store.py::
+# test_geglu_gate_term_of_the_fp32_output_form repeats the measurement): what an element is off beyond DELTA S, over |v| (|g| + 1),
+# largest over the GEGLU problems of the table.  Observed 0 in both types -- that form stays within 0.003 of DELTA S, gate included
+# (the logistic / erf sequences cost a few 1e-7 |v gate(g)|, 1/100 of DELTA S_v |gate(g)|) -- so twice the observation is 0 as well
+# and the term is carried for the day a gate sequence changes: the measuring test fails when it observes more than the constant.
+DELTA_G_OBSERVED = {"bf16": 0.0, "fp16": 0.0}
+DELTA_G = {ty: 2.0 * v for ty, v in DELTA_G_OBSERVED.items()}
+GATE_SLOPE = 1.2
+EDGE_ROWS = (127, 128, 255, 256, -1)                # the first / last rows of 128- and 256-row tiles, and the last row
+SEAM_COLS = (64, 128, 192, 256, 320)                # the first columns of 64-, 128-, 256- and 320-column tiles
+GEMM_DEFAULTS = {"E2V_BGEMM_S3_SMALL": 1, "E2V_BGEMM_PERS": 1, "E2V_BGEMM_256": 1, "E2V_BGEMM_T256": 1, "E2V_BGEMM_T256P": 1,
+                 "E2V_BGEMM_T256P_BIAS_LDS": 1, "E2V_SPLITK_FORCE": 0, "E2V_BGEMM_UP2X": 1}
+
+
+def gate(g, ty):
+    """The GEGLU gate as the kernels of mode ``ty`` evaluate it (igemm_epi.h: gelu_gate16), in the precision of ``g``: bf16 mode the
+    logistic form x / (1 + exp(-(a x + b x^3))), fp16 mode (like fp32) the erf form."""
+    if ty == "fp16":
+        return 0.5 * g * (1.0 + torch.erf(g * 0.7071067811865476))
+    return g / (1.0 + torch.exp(-(1.60031415 * g + 0.06940179 * g ** 3)))
+
+
+def _edge_rows(M):
+    return sorted({r % M for r in EDGE_ROWS if r < M})
+
+
+def _seam_cols(N):
+    return sorted({c for c in SEAM_COLS if c + 8 <= N} | ({N - 8} if N >= 16 else set()))
+
+
+def _sentinel_cols(N):
+    """Eight columns spread over the width: their weights carry one sign per input channel, so that a cancellation row (whose source
+    pixels carry the same signs) has |acc| = sum |x w| there -- the rounding of the accumulator is then as large as it can be next to S."""
+    return sorted({int(c) for c in torch.linspace(1, N - 2, 8).round().long()})
+
+
+def _splitk_runs(c0, c1, want):
+    """bgemm.hip's splitk_layout: (runs in source 0, chunks per run in source 0, runs in source 1, chunks per run in source 1)."""
+    Q0, Q1 = (c0 + 63) // 64, (c1 + 63) // 64
+    want = min(want, Q0 + Q1)
+    if Q1:
+        s0 = min(max(int(want * Q0 / (Q0 + Q1) + 0.5), 1), want - 1)
+        s1 = want - s0
+    else:
+        s0, s1 = want, 0
+    q0 = (Q0 + s0 - 1) // s0
+    s0 = (Q0 + q0 - 1) // q0
+    q1 = 0
+    if Q1:
+        q1 = (Q1 + s1 - 1) // s1
+        s1 = (Q1 + q1 - 1) // q1
+    return s0, q0, s1, q1
+
+
+def _unfold(img, kh, kw, stride, pad):
+    """``img`` [n, C, H, W] float64, ``pad`` = (left, right, top, bottom) zeros -> [n * Ho * Wo, kh * kw, C] and (Ho, Wo)."""
+    import torch.nn.functional as F
+    n, C = img.shape[:2]
+    p = F.pad(img, pad)
+    Ho, Wo = (p.shape[2] - kh) // stride + 1, (p.shape[3] - kw) // stride + 1
+    cols = F.unfold(p, (kh, kw), stride=stride)                                        # [n, C * kh * kw, Ho * Wo], channel-major
+    return cols.reshape(n, C, kh * kw, Ho * Wo).permute(0, 3, 2, 1).reshape(n * Ho * Wo, kh * kw, C), (Ho, Wo)
+
+
+def _to_nchw(x_cl, n, H, W):
+    return x_cl.reshape(n, H, W, -1).permute(0, 3, 1, 2)
+
+
+_UP2_TAPS = {0: ([0], [1, 2]), 1: ([0, 1], [2])}      # output parity -> taps of the 3-wide kernel that fall on source offset 0 / 1
+
+
+def _gemm_parts(case, ty, x0, x1, w):
+    """The launch as GEMMs: a list of (output rows, A [rows, taps, C], W [N, taps, C]) in float64 on ROUNDED operands, and for every
+    output row the source rows (pixels; -1: padding) its A row was gathered from.  One part, except for the sub-pixel form (four)."""
+    if case["op"] == "linear":
+        A = rt(torch.cat([x0, x1], 1) if x1 is not None else x0, ty).double()
+        M = A.shape[0]
+        return [(torch.arange(M), A[:, None, :], rt(w, ty).double()[:, None, :])], torch.arange(M)[:, None]
+    n, Hs, Ws = case["n_img"], case["Hs"], case["Ws"]
+    xs = rt(torch.cat([x0, x1], 1) if x1 is not None else x0, ty).double()
+    img = _to_nchw(xs, n, Hs, Ws)
+    ids = torch.arange(1, n * Hs * Ws + 1, dtype=torch.float64).reshape(n, 1, Hs, Ws)     # 0 = padding
+    N, C = w.shape[:2]
+    if case.get("up2x"):
+        Ho, Wo = 2 * Hs, 2 * Ws
+        rows = torch.arange(n * Ho * Wo).reshape(n, Ho, Wo)
+        parts, src = [], torch.full((n * Ho * Wo, 4), -1, dtype=torch.long)
+        for a in (0, 1):
+            for b in (0, 1):
+                w2 = torch.stack([torch.stack([w[:, :, _UP2_TAPS[a][ty_]][:, :, :, _UP2_TAPS[b][tx]].sum((2, 3)) for tx in (0, 1)], -1)
+                                  for ty_ in (0, 1)], -2)                                  # [N, C, 2, 2], summed in fp32
+                pad = (1 - b, b, 1 - a, a)
+                A, _ = _unfold(img, 2, 2, 1, pad)
+                r = rows[:, a::2, b::2].reshape(-1)
+                parts.append((r, A, rt(w2, ty).double().reshape(N, C, 4).permute(0, 2, 1)))
+                src[r] = _unfold(ids, 2, 2, 1, pad)[0][:, :, 0].long() - 1
+        return parts, src
+    lo, st = case.get("pad_lo", 1), case.get("stride", 1)
+    A, (Ho, Wo) = _unfold(img, 3, 3, st, (lo, 1, lo, 1))
+    assert (Ho, Wo) == conv_out_map(case), (Ho, Wo)
+    src = _unfold(ids, 3, 3, st, (lo, 1, lo, 1))[0][:, :, 0].long() - 1
+    return [(torch.arange(A.shape[0]), A, rt(w, ty).double().reshape(N, C, 9).permute(0, 2, 1))], src
+
+
+def conv_out_map(case):
+    lo, st = case.get("pad_lo", 1), case.get("stride", 1)
+    Hi, Wi = (2 * case["Hs"], 2 * case["Ws"]) if case.get("up2x") else (case["Hs"], case["Ws"])
+    return (Hi + lo + 1 - 3) // st + 1, (Wi + lo + 1 - 3) // st + 1
+
+
+def _acc(parts, M, N, chan=None, absolute=False, emulate=False):
+    """sum_k x_k w_k per output element over the channels ``chan`` (a slice; None: all).  ``absolute``: of |x_k w_k|.  ``emulate``: fp32
+    accumulation in 64-channel chunks, as the kernels walk K."""
+    out = torch.zeros(M, N, dtype=torch.float32 if emulate else torch.float64)
+    for rows, A, W in parts:
+        if chan is not None:
+            A, W = A[:, :, chan], W[:, :, chan]
+        if absolute:
+            A, W = A.abs(), W.abs()
+        if emulate:
+            acc = torch.zeros(A.shape[0], N, dtype=torch.float32)
+            for q in range(0, A.shape[2], 64):
+                acc += A[:, :, q:q + 64].float().reshape(A.shape[0], -1) @ W[:, :, q:q + 64].float().reshape(N, -1).T
+            out[rows] = acc
+        else:
+            out[rows] = A.reshape(A.shape[0], -1) @ W.reshape(N, -1).T
+    return out
+
+
+def gemm_shape(case):
+    """(M, N of the launch, columns of the output)."""
+    if case["op"] == "linear":
+        M, N = case["M"], case["N"]
+    else:
+        Ho, Wo = conv_out_map(case)
+        M, N = case["n_img"] * Ho * Wo, case["N"]
+    return M, N, (N // 2 if case.get("geglu") else N)
+
+
+def gemm_problem(case, ty):
+    """Inputs of the case as the op takes them (fp32 tensors; the residual's cancellation rows depend on the type) and the float64
+    terms of its reference.  Sentinels: at every edge row (127, 128, 255, 256, M - 1) the residual is -(acc + bias + rowbias) rounded to
+    the type plus a unit normal / 16 ("cancellation rows": |ref| << |acc|), the source pixels of those rows carry one sign per channel
+    and so do the weights of eight columns (there |acc| = sum |x w|); the residual rows next to them are 8 x; the time-embedding rows of
+    neighbouring samples differ by at least 4 in every column; the bias pieces on the two sides of a tile seam are offset by +- 4."""
+    M, N, No = gemm_shape(case)
+    lin = case["op"] == "linear"
+    c0, c1 = case["c0"], case.get("c1", 0)
+    K = c0 + c1
+    seed = 500 + 7 * sum(map(ord, case["pid"]))
+    rows_in = M if lin else case["n_img"] * case["Hs"] * case["Ws"]
+    x = rnd(rows_in, K, seed=seed)
+    w = rnd(N, K, seed=seed + 1) * K ** -0.5 if lin else rnd(N, K, 3, 3, seed=seed + 1) * (9 * K) ** -0.5
+    bias = rnd(N, seed=seed + 2)
+    has_resid, geglu = bool(case.get("resid")), bool(case.get("geglu"))
+    edges = _edge_rows(M)
+    if has_resid:                                      # one sign per channel: the sentinel columns' weights, the cancellation rows' pixels
+        sign = torch.where(rnd(K, seed=seed + 3) >= 0, 1.0, -1.0)
+        cols = _sentinel_cols(N)
+        w[cols] = w[cols].abs() * (sign[None, :] if lin else sign[None, :, None, None])
+    if not geglu:
+        for c in _seam_cols(N):
+            bias[c:c + 8] += 4.0
+            bias[c - 8:c] -= 4.0
+    x0 = x[:, :c0].contiguous()
+    x1 = x[:, c0:].contiguous() if c1 else None
+    if has_resid:
+        _, src = _gemm_parts(case, ty, x0, x1, w)
+        pix = src[edges].reshape(-1)
+        pix = pix[pix >= 0].unique()
+        x[pix] = x[pix].abs() * sign[None, :]
+        x0 = x[:, :c0].contiguous()
+        x1 = x[:, c0:].contiguous() if c1 else None
+    parts, _ = _gemm_parts(case, ty, x0, x1, w)
+    acc, sabs = _acc(parts, M, N), _acc(parts, M, N, absolute=True)
+    b = bias.double()
+    rowbias, rowb = None, torch.zeros(M, N, dtype=torch.float64)
+    if case.get("rps"):
+        rps = case["rps"]
+        samples = (M + rps - 1) // rps
+        rowbias = rnd(samples, N, seed=seed + 4) * 0.2 + 6.0 * (torch.arange(samples) % 2)[:, None]
+        rowb = rowbias.double()[torch.arange(M) // rps]
+    resid, r = None, torch.zeros(M, N, dtype=torch.float64)
+    if has_resid:
+        resid = rnd(M, N, seed=seed + 5)
+        for m in edges:
+            for nb in (m - 1, m + 1):
+                if 0 <= nb < M and nb not in edges:
+                    resid[nb] *= 8.0
+        noise = rnd(len(edges), N, seed=seed + 6) / 16.0
+        resid[edges] = rt(-(acc + b + rowb)[edges], ty) + noise
+        r = rt(resid, ty).double()
+    p = dict(case=case, ty=ty, M=M, N=N, No=No, x0=x0, x1=x1, w=w, bias=bias, rowbias=rowbias, resid=resid, parts=parts, acc=acc, sabs=sabs,
+             b=b, rowb=rowb, r=r, edges=edges)
+    p["ref"], p["S"], p["extra"] = _gemm_ref(p, acc, sabs, b, rowb, r)
+    p["budget"] = gemm_budget(p["ref"], p["S"], ty, p["extra"])
+    return p
+
+
+def _gemm_ref(p, acc, sabs, b, rowb, r, swap_blocks=()):
+    """Reference, S and the gate term from the terms.  ``swap_blocks``: GEGLU mutant -- output blocks of 32 columns whose value and gate
+    are exchanged."""
+    ty = p["ty"]
+    if not p["case"].get("geglu"):
+        return acc + b + rowb + r, sabs + b.abs() + rowb.abs() + r.abs(), 0.0
+    h = p["N"] // 2
+    v, g = acc[:, :h] + b[:h], acc[:, h:] + b[h:]
+    sv, sg = sabs[:, :h] + b[:h].abs(), sabs[:, h:] + b[h:].abs()
+    for j in swap_blocks:
+        c = slice(32 * j, 32 * j + 32)
+        v, g = v.clone(), g.clone()
+        v[:, c], g[:, c] = g[:, c].clone(), v[:, c].clone()
+    return v * gate(g, ty), sv * gate(g, ty).abs() + GATE_SLOPE * v.abs() * sg, DELTA_G[ty] * v.abs() * (g.abs() + 1.0)
+
+
+def gemm_budget(ref, S, ty, extra=0.0):
+    e32 = DELTA * S + extra
+    return torch.clamp(UNIT[ty] * (ref.abs() + e32), min=SPACING[ty] / 2) + e32
+
+
+def gemm_emulation(p):
+    """The kernels' arithmetic in torch: fp32 accumulation in 64-channel chunks, bias, time-embedding row and residual added in fp32,
+    one rounding.  Returns the rounded result and the unrounded fp32 one (both as float64)."""
+    ty = p["ty"]
+    acc = _acc(p["parts"], p["M"], p["N"], emulate=True)
+    if p["case"].get("geglu"):
+        h = p["N"] // 2
+        y = (acc[:, :h] + p["bias"][:h]) * gate(acc[:, h:] + p["bias"][h:], ty)
+    else:
+        y = acc + p["bias"]
+        if p["rowbias"] is not None:
+            y = y + p["rowb"].float()
+        if p["resid"] is not None:
+            y = y + p["r"].float()
+    return rt(y, ty).double(), y.double()
+
+
+def gemm_mutants(p, form):
+    """The mutants that apply to problem ``p`` under the switches ``form``: (name, groups) with groups = [(label, rows, cols, mutated
+    reference on [rows, cols])] -- the mutant has to exceed the budget MUTANT_FACTOR times somewhere in EVERY group.  rows: an index
+    tensor, cols: a slice."""
+    case, ty, M, N, No = p["case"], p["ty"], p["M"], p["N"], p["No"]
+    acc, sabs, b, rowb, r, ref = p["acc"], p["sabs"], p["b"], p["rowb"], p["r"], p["ref"]
+    allc, allr = slice(0, No), torch.arange(M)
+    out = []
+    row = lambda m: torch.tensor([m])
+    if case.get("geglu"):
+        nblk = No // 32
+        for j in sorted({0, nblk // 2, nblk - 1}):
+            c = slice(32 * j, 32 * j + 32)
+            out.append((("geglu_swap_block", j), [(f"block {j}", allr, c, _gemm_ref(p, acc, sabs, b, rowb, r, swap_blocks=(j,))[0][:, c])]))
+        c = slice(No - 32, No)
+        out.append((("geglu_last_block_dropped",), [("last block", allr, c, torch.zeros(M, 32, dtype=torch.float64))]))
+        return out
+    if p["resid"] is not None:
+        for m in p["edges"]:
+            if m >= 1:
+                out.append((("resid_of_row_above", m), [(f"row {m}", row(m), allc, ref[m:m + 1] - r[m:m + 1] + r[m - 1:m])]))
+            if m + 1 < M:
+                out.append((("resid_of_row_below", m), [(f"row {m}", row(m), allc, ref[m:m + 1] - r[m:m + 1] + r[m + 1:m + 2])]))
+        out.append((("rounded_before_resid",), [(f"row {m}", row(m), allc, (rt(acc + b + rowb, ty).double() + r)[m:m + 1]) for m in p["edges"]]))
+    if p["rowbias"] is not None:
+        rps = case["rps"]
+        chunks = [c for c in range(0, M, 32) if c // rps != (min(c + 32, M) - 1) // rps]
+        assert chunks, "no 32-row chunk straddles two samples"
+        for which in ("first", "last"):
+            groups = []
+            for c in chunks:
+                rr = torch.arange(c, min(c + 32, M))
+                s = (c if which == "first" else int(rr[-1])) // rps
+                groups.append((f"rows {c}..{int(rr[-1])}", rr, allc, ref[rr] - rowb[rr] + p["rowbias"].double()[s]))
+            out.append((("chunk_rowbias_of_" + which + "_sample",), groups))
+    for c in _seam_cols(N):
+        cs, left = slice(c, c + 8), slice(c - 8, c)
+        out.append((("seam_piece_from_the_left", c), [(f"columns {c}..{c + 7}", allr, cs, ref[:, cs] - b[cs] - r[:, cs] + b[left] + r[:, left])]))
+    if case.get("up2x"):
+        Ho, Wo = conv_out_map(case)
+        img = ref.reshape(case["n_img"], Ho, Wo, N)
+        rows = torch.arange(M).reshape(case["n_img"], Ho, Wo)
+        a, bq = rows[:, 0::2, 1::2].reshape(-1), rows[:, 1::2, 0::2].reshape(-1)
+        out.append((("parities_exchanged", "01<->10"), [("parity (0, 1)", a, allc, img[:, 1::2, 0::2].reshape(-1, N)),
+                                                        ("parity (1, 0)", bq, allc, img[:, 0::2, 1::2].reshape(-1, N))]))
+    want = form.get("E2V_SPLITK_FORCE", 0)
+    if want >= 2:
+        c0, c1 = case["c0"], case.get("c1", 0)
+        s0, q0, s1, q1 = _splitk_runs(c0, c1, want)
+        assert s0 + s1 >= 2
+        chan = slice(c0 + (s1 - 1) * q1 * 64, c0 + c1) if s1 else slice((s0 - 1) * q0 * 64, c0)
+        last = _acc(p["parts"], M, N, chan=chan)
+        out.append((("last_run_left_out", want), [(f"row {m}", row(m), allc, (ref - last)[m:m + 1]) for m in range(M)]))
+    if case["op"] == "linear" and case.get("c1"):
+        c0, c1 = case["c0"], case["c1"]
+        A, W = p["parts"][0][1][:, 0], p["parts"][0][2][:, 0]
+        mut = []
+        if c0 != c1:                                   # source 1 read with source 0's row stride (past the end: wrapped)
+            flat = A[:, c0:].reshape(-1)
+            idx = (torch.arange(M)[:, None] * c0 + torch.arange(c1)[None, :]) % flat.numel()
+            mut.append((("source1_with_stride_of_source0",), torch.cat([A[:, :c0], flat[idx]], 1), 1))
+        if c0 >= 64:                                   # the seam one 64-channel chunk early: source 1 from there on, zeros behind its end
+            mut.append((("seam_one_chunk_early",), torch.cat([A[:, :c0 - 64], A[:, c0:], torch.zeros(M, 64, dtype=torch.float64)], 1), 0))
+        for name, Am, first in mut:
+            full = Am @ W.T + b
+            out.append((name, [(f"row {m}", row(m), allc, full[m:m + 1]) for m in range(first, M)]))
+    return out
+
+
+def where_gemm(p):
+    rps = p["case"].get("rps")
+    return lambda r, c: (f"row {r} of {p['M']} (row {r % 128} of 128-row tile {r // 128}, row {r % 256} of 256-row tile {r // 256}, "
+                         f"32-row chunk {r // 32}" + (f", sample {r // rps}" if rps else "") + f"), column {c} of {p['No']} "
+                         f"(column {c % 64} of 64-column tile {c // 64}, piece {c // 8})" + (", cancellation row" if r in p["edges"] and p["resid"] is not None else ""))
+
+
+# ---- the case table ------------------------------------------------------------------------------------------------------------
+# pid: the problem (shape + operands; forms that run the same problem share it), expect / refuse: the kernel the launch must / must
+# not be served by (e2v_op_last_dispatch).  Shapes: the smallest at which the form can still go wrong -- a ragged last row block, more
+# than one tile in both directions, every width at which the store takes another path (N % 8 != 0: element-wise).
+def _lin(pid, M, K, N, resid=False, geglu=False, c1=0):
+    return dict(pid=pid, op="linear", M=M, c0=K - c1, c1=c1, N=2 * N if geglu else N, resid=resid, geglu=geglu)
+
+
+def _conv(pid, n_img, Hs, Ws, cin, N, resid=False, rps=0, c1=0, **kw):
+    return dict(pid=pid, op="conv", n_img=n_img, Hs=Hs, Ws=Ws, c0=cin - c1, c1=c1, N=N, resid=resid, rps=rps, **kw)
+
+
+_P = {
+    "lin130x40x72": _lin("lin130x40x72", 130, 40, 72),
+    "lin300x320x192r": _lin("lin300x320x192r", 300, 320, 192, resid=True),
+    "lin77x256x70r": _lin("lin77x256x70r", 77, 256, 70, resid=True),
+    "lin77x64x70r": _lin("lin77x64x70r", 77, 64, 70, resid=True),
+    "lin257x128x64": _lin("lin257x128x64", 257, 128, 64),
+    "lin8300x64x1024r": _lin("lin8300x64x1024r", 8300, 64, 1024, resid=True),
+    "geglu300x64x96": _lin("geglu300x64x96", 300, 64, 96, geglu=True),
+    "geglu300x320x128": _lin("geglu300x320x128", 300, 320, 128, geglu=True),
+    "geglu300x640x256": _lin("geglu300x640x256", 300, 640, 256, geglu=True),
+    "lin552x320x192r": _lin("lin552x320x192r", 552, 320, 192, resid=True),
+    "lin513x640x320r": _lin("lin513x640x320r", 513, 640, 320, resid=True),
+    "lin513x640x320": _lin("lin513x640x320", 513, 640, 320),
+    "lin300x640x512r": _lin("lin300x640x512r", 300, 640, 512, resid=True),
+    "lin300x640x512": _lin("lin300x640x512", 300, 640, 512),
+    "lin130x640x72r": _lin("lin130x640x72r", 130, 640, 72, resid=True),
+    "cat300x64+64x192": _lin("cat300x64+64x192", 300, 128, 192, c1=64),
+    "cat130x128+64x72": _lin("cat130x128+64x72", 130, 192, 72, c1=64),
+    "cat513x320+320x320": _lin("cat513x320+320x320", 513, 640, 320, c1=320),
+    "conv64to136_2x7x5_rps35r": _conv("conv64to136_2x7x5_rps35r", 2, 7, 5, 64, 136, resid=True, rps=35),
+    "conv64to128_3x9x16_rps144r": _conv("conv64to128_3x9x16_rps144r", 3, 9, 16, 64, 128, resid=True, rps=144),
+    "conv64to128_2x7x5_rps35r": _conv("conv64to128_2x7x5_rps35r", 2, 7, 5, 64, 128, resid=True, rps=35),
+    "conv64to128_3x8x23_rps184r": _conv("conv64to128_3x8x23_rps184r", 3, 8, 23, 64, 128, resid=True, rps=184),
+    "conv128to320_3x9x16_rps144r": _conv("conv128to320_3x9x16_rps144r", 3, 9, 16, 128, 320, resid=True, rps=144),
+    "conv128to256_2x8x12_s2_rps24r": _conv("conv128to256_2x8x12_s2_rps24r", 2, 8, 12, 128, 256, resid=True, rps=24, stride=2, pad_lo=0),
+    "conv128+64to320_2x7x5r": _conv("conv128+64to320_2x7x5r", 2, 7, 5, 192, 320, resid=True, c1=64),
+    "conv128to64_2x5x8_rps40r": _conv("conv128to64_2x5x8_rps40r", 2, 5, 8, 128, 64, resid=True, rps=40),
+    "conv64+64to64_2x5x8r": _conv("conv64+64to64_2x5x8r", 2, 5, 8, 128, 64, resid=True, c1=64),
+    "up2x_2x128to256_7x6": _conv("up2x_2x128to256_7x6", 2, 7, 6, 128, 256, up2x=True),
+    "up2x_3x256to320_5x8": _conv("up2x_3x256to320_5x8", 3, 5, 8, 256, 320, up2x=True),
+}
+
+
+def _form(name, knobs, rows, ab=False):
+    """rows: (pid, expect[, refuse]).  The first row is the form's bounds case (run once more under E2V_POOL_GUARD)."""
+    out = []
+    for i, r in enumerate(rows):
+        case = dict(_P[r[0]], id=f"{name}-{r[0]}", form=dict(knobs), form_name=name, expect=r[1], refuse=r[2] if len(r) > 2 else None,
+                    guard=i == 0, ab=ab)
+        out.append(case)
+    return out
+
+
+_S3, _PERS, _N64, _BG = "bgemm_s3_kernel", "bgemm_pers_kernel", "bgemm_n64_kernel", "bgemm_kernel 128x128"
+_TILE = {"E2V_BGEMM_S3_SMALL": 0, "E2V_BGEMM_PERS": 0}
+_T256 = {"E2V_BGEMM_T256": 2, "E2V_BGEMM_T256P": 0}
+_T256P = {"E2V_BGEMM_T256": 2, "E2V_BGEMM_T256P": 2}
+GEMM_CASES = (
+    # the default rules at small sizes: the three-stage ring where K is at least four 64-deep stages; a linear of fewer stages
+    # without a residual and K <= 320 takes the persistent kernel (E2V_BGEMM_PERS = 1)
+    _form("default", {}, [("lin300x320x192r", _S3), ("lin130x40x72", _PERS), ("lin77x256x70r", _S3), ("conv64to136_2x7x5_rps35r", _S3)]) +
+    # the two-stage tile kernels: launches of less than one round are cut into 128 x 64 tiles (bgemm_n64_kernel) -- GEGLU excepted;
+    # 128 x 128 tiles with a 128 x 64 tail need more than a round: 8300 x 1024
+    _form("tile", _TILE, [("lin300x320x192r", _N64), ("lin130x40x72", _N64), ("lin77x64x70r", _N64), ("lin257x128x64", _N64),
+                          ("geglu300x64x96", _BG), ("lin8300x64x1024r", _BG + "+128x64")]) +
+    _form("pers", {"E2V_BGEMM_S3_SMALL": 0, "E2V_BGEMM_PERS": 2},
+          [("lin300x320x192r", _PERS), ("lin8300x64x1024r", _PERS), ("geglu300x320x128", _PERS), ("conv64to128_3x9x16_rps144r", _PERS),
+           ("conv64to128_2x7x5_rps35r", _N64, _PERS)]) +          # time-embedding rows of more than two samples under one tile: refused
+    _form("256s3", {"E2V_BGEMM_256": 2, "E2V_BGEMM_T256": 0}, [("lin552x320x192r", "bgemm256s3_kernel"), ("conv64to128_3x8x23_rps184r", "bgemm256s3_kernel")]) +
+    _form("t256", _T256, [("lin513x640x320r", "bgemm_t256_kernel 256x320"), ("lin300x640x512r", "bgemm_t256_kernel 256x256"),
+                          ("geglu300x640x256", "bgemm_t256_kernel 256x256"), ("conv128to320_3x9x16_rps144r", "bgemm_t256_kernel 256x320"),
+                          ("conv128to256_2x8x12_s2_rps24r", "bgemm_t256_kernel 256x256"), ("conv128+64to320_2x7x5r", "bgemm_t256_kernel 256x320")]) +
+    _form("t256p_blds1", dict(_T256P, E2V_BGEMM_T256P_BIAS_LDS=1),
+          [("lin513x640x320r", "bgemm_t256p_kernel 256x320", "bias-lds"), ("lin513x640x320", "bgemm_t256p_kernel 256x320 bias-lds"),
+           ("lin300x640x512r", "bgemm_t256p_kernel 256x256", "bias-lds"), ("lin300x640x512", "bgemm_t256p_kernel 256x256 bias-lds"),
+           ("geglu300x640x256", "bgemm_t256p_kernel 256x256 bias-lds")]) +
+    _form("t256p_blds0", dict(_T256P, E2V_BGEMM_T256P_BIAS_LDS=0),
+          [("lin513x640x320", "bgemm_t256p_kernel 256x320", "bias-lds"), ("lin300x640x512", "bgemm_t256p_kernel 256x256", "bias-lds"),
+           ("geglu300x640x256", "bgemm_t256p_kernel 256x256", "bias-lds")]) +
+    sum((_form(f"splitk{s}", {"E2V_SPLITK_FORCE": s},
+               [("lin130x640x72r", f"bgemm_splitk_kernel 128x128 x{s}"), ("conv128to64_2x5x8_rps40r", "bgemm_splitk_kernel 128x128 x2"),
+                ("conv64+64to64_2x5x8r", "bgemm_splitk_kernel 128x128 x2")]) for s in (2, 5)), []) +
+    _form("up2x", {"E2V_BGEMM_UP2X": 1}, [("up2x_2x128to256_7x6", "bgemm_t256_kernel 256x256"), ("up2x_3x256to320_5x8", "bgemm_t256_kernel 256x320")]) +
+    _form("cat", {}, [("cat300x64+64x192", _PERS), ("cat130x128+64x72", _PERS), ("cat513x320+320x320", _S3)]) +
+    _form("cat_pers", {"E2V_BGEMM_S3_SMALL": 0, "E2V_BGEMM_PERS": 2},
+          [("cat300x64+64x192", _PERS), ("cat130x128+64x72", _PERS), ("cat513x320+320x320", _PERS)])
+)
+GEMM_PROBLEM_BY_ID = _P
+GEMM_PROBLEMS = list(_P.values())
+GEGLU_PROBLEMS = [c for c in GEMM_PROBLEMS if c.get("geglu")]
+CAT_PROBLEMS = [c for c in GEMM_PROBLEMS if c["op"] == "linear" and c.get("c1")]

@@ -54,6 +54,23 @@ int main(void) {
     CHECK(e2v_generate(ctx, x, x, x, 1, 1, 1, 1, 1, 1, 4, 7.5f, 0.f, x, NULL, NULL) == E2V_ESTATE);
     CHECK(e2v_set_compute_dtype(ctx, E2V_BF16) == E2V_OK && e2v_set_compute_dtype(ctx, 17) == E2V_EINVAL);
     CHECK(e2v_set_conv_algo(ctx, E2V_CONV_DIRECT) == E2V_OK && e2v_set_conv_algo(ctx, 9) == E2V_EINVAL);
+    /* the two-source linear checks its arguments before any device work; e2v_op_last_dispatch makes no HIP call */
+    CHECK(e2v_set_compute_dtype(ctx, E2V_F32) == E2V_OK);
+    CHECK(e2v_op_linear_cat(NULL, x, 4, 4, x, 4, 4, 1, x, NULL, 4, NULL, 0, x, NULL) == E2V_EINVAL);
+    CHECK(e2v_op_linear_cat(ctx, x, 4, 4, NULL, 4, 4, 1, x, NULL, 4, NULL, 0, x, NULL) == E2V_EINVAL);
+    CHECK(e2v_op_linear_cat(ctx, x, 4, 4, x, 2, 4, 1, x, NULL, 4, NULL, 0, x, NULL) == E2V_ESHAPE);
+    CHECK(e2v_op_linear_cat(ctx, x, 4, 4, x, 4, 4, 1, x, NULL, 4, NULL, 0, x, NULL) == E2V_ESTATE);
+    CHECK(e2v_set_compute_dtype(ctx, E2V_BF16) == E2V_OK);
+    CHECK(e2v_op_linear_cat(ctx, x, 4, 4, x, 4, 4, 1, x, NULL, 4, NULL, 0, x, NULL) == E2V_ESHAPE);
+    CHECK(e2v_op_linear(ctx, x, 4, 1, 4, x, NULL, 4, NULL, 0, x, NULL) == E2V_ESTATE);
+    char tag[8] = "xxxxxxx";
+    CHECK(e2v_op_last_dispatch(tag, sizeof(tag)) == E2V_OK && tag[0] == 0);
+    CHECK(e2v_op_set_knob("E2V_OP_RECORD", 1) == E2V_OK);
+    tag[0] = 'x';
+    CHECK(e2v_op_linear(ctx, x, 4, 1, 4, x, NULL, 4, NULL, 0, x, NULL) == E2V_ESTATE);
+    CHECK(e2v_op_last_dispatch(tag, sizeof(tag)) == E2V_OK && tag[0] == 0);
+    CHECK(e2v_op_last_dispatch(NULL, 4) == E2V_EINVAL && e2v_op_last_dispatch(NULL, 0) == E2V_OK);
+    CHECK(e2v_op_set_knob("E2V_OP_RECORD", 0) == E2V_OK && e2v_op_set_knob("E2V_OP_IO16", 0) == E2V_OK);
     CHECK(e2v_device_bytes(ctx) == 0);
     e2v_destroy(ctx);
     /* rejected configurations leave nothing behind */

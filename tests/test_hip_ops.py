@@ -363,9 +363,8 @@ def gelu_bf16_grade(x):
     """The GEGLU gate as the kernels of the running 16-bit mode evaluate it (igemm_epi.h: gelu_gate16).  bf16 mode:
     x / (1 + exp(-(a x + b x^3))), |error| <= 2.8e-4 against the exact erf form (bounded in tests/test_oracle_anchors.py) -- 1/14 of a
     bf16 rounding; fp16 mode rounds 8x finer and keeps the erf form (A&S 7.1.26, 1.5e-7) like fp32."""
-    if H16["name"] == "fp16":
-        return F.gelu(x)
-    return x / (1.0 + torch.exp(-(1.60031415 * x + 0.06940179 * x ** 3)))
+    from h16_budget import gate          # the formula lives with the per-element budgets (tests/h16_budget.py)
+    return gate(x, H16["name"])
 
 
 def test_bf16_conv_and_linear(bf):

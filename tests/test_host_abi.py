@@ -128,6 +128,44 @@ def test_run_time_switches_by_name(lib):
     assert lib.e2v_op_set_knob(None, 1) == _lib.E2V_EINVAL
 
 
+def test_two_source_linear_argument_checks_and_last_dispatch_need_no_gpu(lib, host_ctx):
+    """e2v_op_linear_cat checks its arguments before any device work (the granularity Runner::linear asks for: 4 columns per source in
+    the fp32 modes, 8 in the 16-bit ones), and only then refuses the host-only context; e2v_op_last_dispatch makes no HIP call: E2V_OK
+    and an empty string where nothing was launched, with the switch off and on."""
+    x = (C.c_float * 64)()
+    px = C.cast(x, C.c_void_p)
+    cat = lambda c0, ld0, x1, c1, ld1: lib.e2v_op_linear_cat(host_ctx, px, c0, ld0, x1, c1, ld1, 2, px, None, 4, None, 0, px, None)
+    assert lib.e2v_op_linear_cat(None, px, 8, 8, px, 8, 8, 2, px, None, 4, None, 0, px, None) == _lib.E2V_EINVAL
+    assert cat(8, 8, None, 8, 8) == _lib.E2V_EINVAL                       # c1 > 0 without a second source
+    assert lib.e2v_op_linear_cat(host_ctx, None, 8, 8, px, 8, 8, 2, px, None, 4, None, 0, px, None) == _lib.E2V_EINVAL
+    assert cat(6, 8, None, 0, 0) == _lib.E2V_EINVAL                       # one source, fp32: K and the row stride in quads
+    assert cat(8, 8, px, 6, 8) == _lib.E2V_ESHAPE and b"multiple of 4" in lib.e2v_last_error(host_ctx)
+    assert cat(8, 8, px, 8, 6) == _lib.E2V_ESHAPE                         # fp32: the second row stride in quads / not below c1
+    assert cat(8, 8, px, 8, 8) == _lib.E2V_ESTATE and b"host-only" in lib.e2v_last_error(host_ctx)
+    assert cat(4, 4, px, 4, 4) == _lib.E2V_ESTATE
+    assert lib.e2v_set_compute_dtype(host_ctx, _lib.E2V_BF16) == 0
+    try:
+        assert cat(4, 4, px, 4, 4) == _lib.E2V_ESHAPE                     # 16-bit modes: 8 columns per source
+        assert cat(8, 8, px, 12, 12) == _lib.E2V_ESHAPE
+        assert cat(8, 8, px, 8, 8) == _lib.E2V_ESTATE
+        assert cat(6, 6, None, 0, 0) == _lib.E2V_ESTATE                   # one source: K is padded to 8, any K passes the check
+    finally:
+        assert lib.e2v_set_compute_dtype(host_ctx, _lib.E2V_F32) == 0
+    assert lib.e2v_op_linear(host_ctx, px, 8, 2, 8, px, None, 4, None, 0, px, None) == _lib.E2V_ESTATE
+    buf = C.create_string_buffer(b"x" * 15, 16)
+    assert lib.e2v_op_last_dispatch(buf, 16) == _lib.E2V_OK and buf.value == b""
+    assert lib.e2v_op_last_dispatch(None, 0) == _lib.E2V_OK
+    assert lib.e2v_op_last_dispatch(None, 4) == _lib.E2V_EINVAL and lib.e2v_op_last_dispatch(buf, -1) == _lib.E2V_EINVAL
+    assert lib.e2v_op_set_knob(b"E2V_OP_IO16", 0) == _lib.E2V_OK
+    assert lib.e2v_op_set_knob(b"E2V_OP_RECORD", 1) == _lib.E2V_OK
+    try:
+        assert cat(8, 8, px, 8, 8) == _lib.E2V_ESTATE                     # refused before a launcher ran: nothing recorded
+        buf = C.create_string_buffer(b"x" * 15, 16)
+        assert lib.e2v_op_last_dispatch(buf, 16) == _lib.E2V_OK and buf.value == b""
+    finally:
+        assert lib.e2v_op_set_knob(b"E2V_OP_RECORD", 0) == _lib.E2V_OK
+
+
 def test_device_entry_points_refuse_host_only_context(lib, host_ctx):
     assert lib.e2v_finalize_weights(host_ctx, 1) == _lib.E2V_ESTATE
     assert b"host-only" in lib.e2v_last_error(host_ctx)
