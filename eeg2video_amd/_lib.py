@@ -35,6 +35,17 @@ class E2VConfig(C.Structure):
     ]
 
 
+class E2VPlanOp(C.Structure):
+    """``e2v_plan_op`` of include/eeg2video_hip.h (field order is the ABI)."""
+    _fields_ = [
+        ("kind", C.c_int32), ("dst", C.c_int32), ("n_src", C.c_int32), ("src", C.c_int32 * 5),
+        ("coef", C.c_double * 5), ("timestep", C.c_double), ("fractional", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+E2V_PLAN_UNET, E2V_PLAN_LINCOMB = 0, 1
+E2V_PLAN_MAX_SLOTS, E2V_PLAN_MAX_TERMS = 8, 5
+
 E2V_OK, E2V_EINVAL, E2V_ESHAPE, E2V_ENOWEIGHT, E2V_EHIP, E2V_ESTATE = 0, -1, -2, -3, -4, -5
 E2V_F32, E2V_F16, E2V_BF16, E2V_F32X3 = 0, 1, 2, 3
 #: bits of e2v_op_weight_forms (include/eeg2video_hip_ops.h)
@@ -68,6 +79,8 @@ SIGNATURES = {
     "e2v_vae_decode": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_vae_encode": (_i, [_ctx, _p, _i, _i, _i, _p, _p, _stream]),
     "e2v_generate": (_i, [_ctx, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _stream]),
+    "e2v_plan_op_size": (_i64, []),
+    "e2v_generate_plan": (_i, [_ctx, _p, _p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(E2VPlanOp), _i, _i, _i, _p, _i, _f, _p, _p, _stream]),
     "e2v_semantic_predict": (_i, [_ctx, _p, _i, _p, _stream]),
     "e2v_text_encode": (_i, [_ctx, c_int64_p, _i, _i, _p, _stream]),
     "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
@@ -106,6 +119,7 @@ SIGNATURES = {
     "e2v_op_pool_guard_report": (_i, [_ctx, c_int64_p, c_int64_p, C.c_char_p, _i64]),
     "e2v_op_pool_gets": (_i64, [_ctx]),
     "e2v_op_pool_guard_selftest": (_i, [_ctx, _i64, _i64, _stream]),
+    "e2v_op_run_plan": (_i, [_ctx, C.POINTER(E2VPlanOp), _i, _i, _i, _p, _p, _p, _i, _p, _i, _f, _p, _i64, _stream]),
     "e2v_op_unet_forward_taps": (_i, [_ctx, _p, c_int64_p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _i64, c_int64_p, C.POINTER(_i), _stream]),
 }
 
@@ -134,6 +148,9 @@ def load() -> C.CDLL:
         fn.argtypes = args
     if lib.e2v_config_size() != C.sizeof(E2VConfig):
         raise ImportError(f"{LIB_PATH}: e2v_config is {lib.e2v_config_size()} bytes in the library, {C.sizeof(E2VConfig)} in this binding "
+                          "(include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
+    if lib.e2v_plan_op_size() != C.sizeof(E2VPlanOp):
+        raise ImportError(f"{LIB_PATH}: e2v_plan_op is {lib.e2v_plan_op_size()} bytes in the library, {C.sizeof(E2VPlanOp)} in this binding "
                           "(include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     _lib = lib
     return lib

@@ -562,83 +562,276 @@ e2v_status e2v_vae_encode(e2v_ctx* c, const float* images, int n, int H, int W, 
     });
 }
 
+// ---- the denoising loop (pipeline_tuneeeg2video.py:311-334), shared by e2v_generate and e2v_generate_plan -------------------------
+// Everything both loops do lives here: the [uncond ; cond] assembly, the per-run caches, the guidance-pair decision, one
+// unet_forward_cl per evaluation, latents_out and the decode.  What differs comes in as three callables:
+//   input(i)               -> the channel-last latents [B * P][Cl] evaluation i reads
+//   update(i, eps_u, eps_c) : consume the evaluation's eps (eps_c null: guidance off), B * per floats each
+//   result()               -> the channel-last latents the loop ends with
+struct LoopArgs {
+    const float *cond, *uncond;
+    int Bu, B, F, h, w, T;
+    float guidance;
+    float *videos, *latents_out;
+};
+
+static void check_loop_args(const LoopArgs& a, const float* latents) {
+    E2V_REQUIRE(latents && a.cond, E2V_EINVAL, "null argument");
+    E2V_REQUIRE(a.B > 0 && a.F > 0 && a.h > 0 && a.w > 0 && a.T > 0, E2V_ESHAPE, "non-positive dimension");
+}
+static void check_loop_uncond(const LoopArgs& a) {
+    E2V_REQUIRE(a.guidance <= 1.0f || (a.uncond && (a.Bu == 1 || a.Bu == a.B)), E2V_EINVAL, "uncond must have batch 1 or B");
+}
+
+extern "C++" {
+template <class Input, class Update, class Result>
+static void denoise_loop(e2v_ctx* c, const LoopArgs& a, const std::vector<e2v_ctx::EvalTime>& ev, hipStream_t s, Input&& input,
+                         Update&& update, Result&& result) {
+    const int B = a.B, F = a.F, h = a.h, w = a.w, T = a.T, Bu = a.Bu;
+    const bool cfg_on = a.guidance > 1.0f;                                   // pipeline_tuneeeg2video.py:281
+    const int Cl = c->cfg.in_channels, D = c->cfg.cross_attention_dim;
+    const int P = F * h * w;
+    const size_t per = (size_t)P * Cl;
+    const int N = cfg_on ? 2 * B : B;
+    const int steps = (int)ev.size();
+
+    Act emb;                                                                 // [uncond ; cond] (:162-172)
+    const float* embp = a.cond;
+    if (cfg_on) {
+        emb = Act(c->pool, (int64_t)N * T, D);
+        const size_t one = (size_t)T * D;
+        if (Bu == B) E2V_HIP(hipMemcpyAsync(emb.p, a.uncond, one * B * sizeof(float), hipMemcpyDeviceToDevice, s));
+        else for (int b = 0; b < B; ++b)
+            E2V_HIP(hipMemcpyAsync(emb.p + b * one, a.uncond, one * sizeof(float), hipMemcpyDeviceToDevice, s));
+        E2V_HIP(hipMemcpyAsync(emb.p + B * one, a.cond, one * B * sizeof(float), hipMemcpyDeviceToDevice, s));
+        embp = emb.p;
+    }
+    // everything that depends only on (t_i, conditioning) is computed once for the whole loop
+    struct CacheGuard {
+        e2v_ctx* c;
+        ~CacheGuard() { c->step_cache_on = false; c->temb_cache.clear(); c->kv_cache.clear(); }
+    } guard{c};
+    // (the family of the UNet passes this call makes, so that the caches do not depend on what an earlier call ran.  No launch in
+    // there is eligible for split-K at the shipped thresholds -- cross-attention K = cross_attention_dim < 2 x 2048, the
+    // time-embedding linears are fp32 rows -- so the caches are the same bits in both families)
+    c->build_step_caches(ev.data(), steps, embp, N, T, unet_small_family(N), s);
+    c->step_cache_on = true;
+    // latent_model_input = cat([latents] * 2) (:313) is not materialised: the UNet is told that its input stands for the
+    // pair, and computes what the two copies share (up to the first cross-attention) once
+    const bool pair = cfg_on && !c->unet.down[0].attn.empty();
+    Act xin;
+    if (cfg_on && !pair) xin = Act(c->pool, (int64_t)N * P, Cl);
+    for (int i = 0; i < steps; ++i) {                                        // :311
+        const float* x = input(i);
+        const float* in = x;
+        if (cfg_on && !pair) {
+            E2V_HIP(hipMemcpyAsync(xin.p, x, per * B * sizeof(float), hipMemcpyDeviceToDevice, s));
+            E2V_HIP(hipMemcpyAsync(xin.p + per * B, x, per * B * sizeof(float), hipMemcpyDeviceToDevice, s));
+            in = xin.p;
+        }
+        c->step_cache_step = i;
+        Act eps = c->unet_forward_cl(in, ev[i].frac ? nullptr : &ev[i].t, 1, embp, N, F, h, w, T, s, pair,
+                                     ev[i].frac ? &ev[i].tf : nullptr);      // :317
+        update(i, eps.p, cfg_on ? eps.p + per * B : nullptr);               // :320-325
+        // profiling aid: under rocprofv3 --pmc (ROCm 7.2) rocprofiler-sdk's queue-intercept callback faulted with a whole pass
+        // (~34 000 launches, ~680 per DDIM step) queued behind the GPU (profiles/r02_pmc_async_abort_README.md names the frames);
+        // E2V_SYNC_EACH_STEP=1 drains the stream after every step.  Read once per process; never set in a timed run
+        static const bool sync_each = [] { const char* e = std::getenv("E2V_SYNC_EACH_STEP"); return e && std::atoi(e) != 0; }();
+        if (sync_each) E2V_HIP(hipStreamSynchronize(s));
+    }
+    const float* x = result();
+    if (a.latents_out) cl_to_ncfhw(x, Cl, a.latents_out, B, Cl, P, 1.f, 0.f, 0, 0.f, 0.f, s);
+    if (a.videos) {                                                          // decode_latents (:175-184)
+        Act z(c->pool, (int64_t)B * P, Cl);
+        const float inv = (float)(1.0 / c->cfg.vae_scaling_factor);
+        ncfhw_to_cl(x, z.p, 1, 1, 1, (int)(per * B), inv, s);            // z = 1 / 0.18215 * latents (:177), flat scale
+        decode_to_video(c, z.p, B, F, h, w, 1, a.videos, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
+}  // extern "C++"
+
 e2v_status e2v_generate(e2v_ctx* c, const float* latents, const float* cond, const float* uncond, int Bu, int B, int F,
                         int h, int w, int T, int steps, float guidance, float eta, float* videos, float* latents_out,
                         e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(latents && cond, E2V_EINVAL, "null argument");
-        E2V_REQUIRE(B > 0 && F > 0 && h > 0 && w > 0 && T > 0, E2V_ESHAPE, "non-positive dimension");
+        const LoopArgs a{cond, uncond, Bu, B, F, h, w, T, guidance, videos, latents_out};
+        check_loop_args(a, latents);
         E2V_REQUIRE(steps > 0 && steps <= c->cfg.num_train_timesteps, E2V_EINVAL, "num_inference_steps out of range");
         E2V_REQUIRE(eta == 0.0f, E2V_EINVAL, "only the deterministic DDIM update (eta = 0) is implemented");
-        const bool cfg_on = guidance > 1.0f;                                     // pipeline_tuneeeg2video.py:281
-        E2V_REQUIRE(!cfg_on || (uncond && (Bu == 1 || Bu == B)), E2V_EINVAL, "uncond must have batch 1 or B");
+        check_loop_uncond(a);
         hipStream_t s = S(c, stream);
-        const int Cl = c->cfg.in_channels, D = c->cfg.cross_attention_dim;
-        const int P = F * h * w;
-        const size_t per = (size_t)P * Cl;
-        const int N = cfg_on ? 2 * B : B;
-
+        const int Cl = c->cfg.in_channels, P = F * h * w;
+        const long long count = (long long)P * Cl * B;
         Act x(c->pool, (int64_t)B * P, Cl);
         ncfhw_to_cl(latents, x.p, B, Cl, Cl, P, 1.0f, s);                        // init_noise_sigma = 1 (:244)
-        Act emb;                                                                 // [uncond ; cond] (:162-172)
-        const float* embp = cond;
-        if (cfg_on) {
-            emb = Act(c->pool, (int64_t)N * T, D);
-            const size_t one = (size_t)T * D;
-            if (Bu == B) E2V_HIP(hipMemcpyAsync(emb.p, uncond, one * B * sizeof(float), hipMemcpyDeviceToDevice, s));
-            else for (int b = 0; b < B; ++b)
-                E2V_HIP(hipMemcpyAsync(emb.p + b * one, uncond, one * sizeof(float), hipMemcpyDeviceToDevice, s));
-            E2V_HIP(hipMemcpyAsync(emb.p + B * one, cond, one * B * sizeof(float), hipMemcpyDeviceToDevice, s));
-            embp = emb.p;
-        }
         std::vector<int64_t> ts(steps);
         e2v_ddim_timesteps(c, steps, ts.data());                                 // :287-288
         const int64_t ratio = c->cfg.num_train_timesteps / steps;
-        // everything that depends only on (t_i, conditioning) is computed once for the whole loop
-        struct CacheGuard {
-            e2v_ctx* c;
-            ~CacheGuard() { c->step_cache_on = false; c->temb_cache.clear(); c->kv_cache.clear(); }
-        } guard{c};
-        // (the family of the UNet passes this call makes, so that the caches do not depend on what an earlier call ran.  No launch in
-        // there is eligible for split-K at the shipped thresholds -- cross-attention K = cross_attention_dim < 2 x 2048, the
-        // time-embedding linears are fp32 rows -- so the caches are the same bits in both families)
-        c->build_step_caches(ts.data(), steps, embp, N, T, unet_small_family(N), s);
-        c->step_cache_on = true;
-        // latent_model_input = cat([latents] * 2) (:313) is not materialised: the UNet is told that its input stands for the
-        // pair, and computes what the two copies share (up to the first cross-attention) once
-        const bool pair = cfg_on && !c->unet.down[0].attn.empty();
-        Act xin;
-        if (cfg_on && !pair) xin = Act(c->pool, (int64_t)N * P, Cl);
-        for (int i = 0; i < steps; ++i) {                                        // :311
-            const float* in = x.p;
-            if (cfg_on && !pair) {
-                E2V_HIP(hipMemcpyAsync(xin.p, x.p, per * B * sizeof(float), hipMemcpyDeviceToDevice, s));
-                E2V_HIP(hipMemcpyAsync(xin.p + per * B, x.p, per * B * sizeof(float), hipMemcpyDeviceToDevice, s));
-                in = xin.p;
+        std::vector<e2v_ctx::EvalTime> ev(steps);
+        for (int i = 0; i < steps; ++i) ev[i] = e2v_ctx::EvalTime{ts[i], (float)ts[i], false};
+        denoise_loop(c, a, ev, s,
+                     [&](int) { return (const float*)x.p; },
+                     [&](int i, const float* eu, const float* ec) {
+                         float co[4];
+                         ddim_coeffs(c, ts[i], ts[i] - ratio, co);
+                         ddim_cfg_step(eu, ec, x.p, x.p, count, guidance, co[0], co[1], co[2], co[3], s);
+                     },
+                     [&] { return (const float*)x.p; });
+    });
+}
+
+// ---- sampler plans (eeg2video_hip.h: e2v_plan_op) ------------------------------------------------------------------------------------
+// Host-only validation: everything e2v_generate_plan / e2v_op_run_plan index memory by.  Throws E2V_EINVAL naming the op.
+static int plan_check(const e2v_ctx* c, const e2v_plan_op* ops, int n_ops, int n_slots, int final_slot, int n_noise) {
+    E2V_REQUIRE(ops && n_ops > 0, E2V_EINVAL, "plan: no ops");
+    E2V_REQUIRE(n_slots >= 1 && n_slots <= E2V_PLAN_MAX_SLOTS, E2V_EINVAL,
+                "plan: n_slots = " + std::to_string(n_slots) + " is outside 1.." + std::to_string(E2V_PLAN_MAX_SLOTS));
+    E2V_REQUIRE(n_noise >= 0, E2V_EINVAL, "plan: negative n_noise");
+    bool written[E2V_PLAN_MAX_SLOTS] = {true};                                   // slot 0 holds the latents on entry
+    int n_unet = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        const e2v_plan_op& op = ops[i];
+        const std::string at = "plan op " + std::to_string(i) + ": ";
+        E2V_REQUIRE(op.kind == E2V_PLAN_UNET || op.kind == E2V_PLAN_LINCOMB, E2V_EINVAL, at + "unknown kind " + std::to_string(op.kind));
+        const int lo = 1, hi = op.kind == E2V_PLAN_UNET ? 1 : E2V_PLAN_MAX_TERMS;
+        E2V_REQUIRE(op.n_src >= lo && op.n_src <= hi, E2V_EINVAL,
+                    at + std::to_string(op.n_src) + " terms (" + (hi == 1 ? "a UNET op reads one slot" : "a LINCOMB op takes 1..5") + ")");
+        E2V_REQUIRE(op.dst >= 0 && op.dst < n_slots, E2V_EINVAL, at + "destination slot " + std::to_string(op.dst) + " out of range");
+        for (int k = 0; k < op.n_src; ++k) {
+            const int src = op.src[k];
+            if (src < 0) {
+                E2V_REQUIRE(op.kind == E2V_PLAN_LINCOMB && -1 - (int64_t)src < n_noise, E2V_EINVAL,
+                            at + "noise tensor " + std::to_string(-1 - (int64_t)src) + " out of range");
+            } else {
+                E2V_REQUIRE(src < n_slots, E2V_EINVAL, at + "source slot " + std::to_string(src) + " out of range");
+                E2V_REQUIRE(written[src], E2V_EINVAL, at + "slot " + std::to_string(src) + " is read before any op wrote it");
+                E2V_REQUIRE(src != op.dst, E2V_EINVAL, at + "writes slot " + std::to_string(src) + ", which it reads");
             }
-            c->step_cache_step = i;
-            Act eps = c->unet_forward_cl(in, &ts[i], 1, embp, N, F, h, w, T, s, pair);  // :317
-            float co[4];
-            ddim_coeffs(c, ts[i], ts[i] - ratio, co);
-            ddim_cfg_step(eps.p, cfg_on ? eps.p + per * B : nullptr, x.p, x.p, (long long)(per * B), guidance, co[0], co[1],
-                          co[2], co[3], s);                                      // :320-325
-            // profiling aid: under rocprofv3 --pmc (ROCm 7.2) rocprofiler-sdk's queue-intercept callback faulted with a whole pass
-            // (~34 000 launches, ~680 per DDIM step) queued behind the GPU (profiles/r02_pmc_async_abort_README.md names the frames);
-            // E2V_SYNC_EACH_STEP=1 drains the stream after every DDIM step.  Read once per process; never set in a timed run
-            static const bool sync_each = [] { const char* e = std::getenv("E2V_SYNC_EACH_STEP"); return e && std::atoi(e) != 0; }();
-            if (sync_each) E2V_HIP(hipStreamSynchronize(s));
+            if (op.kind == E2V_PLAN_LINCOMB)
+                E2V_REQUIRE(std::isfinite(op.coef[k]) && std::isfinite((float)op.coef[k]), E2V_EINVAL, at + "non-finite coefficient");
         }
-        if (latents_out) cl_to_ncfhw(x.p, Cl, latents_out, B, Cl, P, 1.f, 0.f, 0, 0.f, 0.f, s);
-        if (videos) {                                                            // decode_latents (:175-184)
-            Act z(c->pool, (int64_t)B * P, Cl);
-            const float inv = (float)(1.0 / c->cfg.vae_scaling_factor);
-            ncfhw_to_cl(x.p, z.p, 1, 1, 1, (int)(per * B), inv, s);      // z = 1 / 0.18215 * latents (:177), flat scale
-            decode_to_video(c, z.p, B, F, h, w, 1, videos, s);
+        if (op.kind == E2V_PLAN_UNET) {
+            E2V_REQUIRE(std::isfinite(op.timestep) && std::isfinite((float)op.timestep), E2V_EINVAL, at + "non-finite timestep");
+            if (!op.fractional)
+                E2V_REQUIRE(op.timestep == std::floor(op.timestep) && op.timestep >= 0 && op.timestep < c->cfg.num_train_timesteps,
+                            E2V_EINVAL, at + "integral timestep outside [0, num_train_timesteps)");
+            ++n_unet;
         }
+        written[op.dst] = true;
+    }
+    E2V_REQUIRE(n_unet > 0, E2V_EINVAL, "plan: no UNET op");
+    E2V_REQUIRE(final_slot >= 0 && final_slot < n_slots && written[final_slot], E2V_EINVAL,
+                "plan: final_slot " + std::to_string(final_slot) + " is out of range or never written");
+    return n_unet;
+}
+
+static e2v_status plan_checked(e2v_ctx* c, const e2v_plan_op* ops, int n_ops, int n_slots, int final_slot, const float* noise,
+                               int n_noise, int* n_unet) {
+    try {
+        *n_unet = plan_check(c, ops, n_ops, n_slots, final_slot, n_noise);
+        E2V_REQUIRE(n_noise == 0 || noise, E2V_EINVAL, "plan: n_noise > 0 needs the noise array");
+        return E2V_OK;
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+}
+
+// The executor: walks the ops in order with the launchers of the stepped loop (misc.hip: lincomb, cfg_combine), the coefficients cast
+// to float as e2v_lincomb's callers cast them.  Every slot is `count` floats; the layout is whatever the caller's is (the ops are
+// elementwise).
+struct PlanRun {
+    const e2v_plan_op* ops;
+    int n_ops;
+    long long count;
+    float guidance;
+    const float* noise;                                      // [n_noise][count], in the slots' layout
+    hipStream_t s;
+    std::vector<Act> slot;
+    int pc = 0;
+    // run the LINCOMB ops up to the next UNET op (or the end); returns that op, or null
+    const e2v_plan_op* advance() {
+        for (; pc < n_ops && ops[pc].kind == E2V_PLAN_LINCOMB; ++pc) {
+            const e2v_plan_op& op = ops[pc];
+            const float* xs[E2V_PLAN_MAX_TERMS];
+            float cf[E2V_PLAN_MAX_TERMS];
+            for (int k = 0; k < op.n_src; ++k) {
+                xs[k] = op.src[k] >= 0 ? slot[op.src[k]].p : noise + (size_t)(-1 - op.src[k]) * (size_t)count;
+                cf[k] = (float)op.coef[k];
+            }
+            lincomb(op.n_src, xs, cf, slot[op.dst].p, count, s);
+        }
+        return pc < n_ops ? &ops[pc] : nullptr;
+    }
+    // the UNET op at pc: its dst slot receives the guided eps (:320-322), or eps itself
+    void unet_result(const float* eu, const float* ec) {
+        const e2v_plan_op& op = ops[pc++];
+        if (ec) cfg_combine(eu, ec, guidance, slot[op.dst].p, count, s);
+        else E2V_HIP(hipMemcpyAsync(slot[op.dst].p, eu, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, s));
+    }
+};
+
+e2v_status e2v_generate_plan(e2v_ctx* c, const float* latents, const float* cond, const float* uncond, int Bu, int B, int F, int h,
+                             int w, int T, const e2v_plan_op* ops, int n_ops, int n_slots, int final_slot, const float* noise,
+                             int n_noise, float guidance, float* videos, float* latents_out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    int n_unet = 0;
+    const e2v_status st = plan_checked(c, ops, n_ops, n_slots, final_slot, noise, n_noise, &n_unet);
+    if (st != E2V_OK) return st;
+    return guarded(c, [&] {
+        const LoopArgs a{cond, uncond, Bu, B, F, h, w, T, guidance, videos, latents_out};
+        check_loop_args(a, latents);
+        check_loop_uncond(a);
+        hipStream_t s = S(c, stream);
+        const int Cl = c->cfg.in_channels, P = F * h * w;
+        E2V_REQUIRE((int64_t)(n_noise > 0 ? n_noise : 1) * B <= INT32_MAX, E2V_ESHAPE, "n_noise * B does not fit an int");
+        PlanRun run{ops, n_ops, (long long)P * Cl * B, guidance, nullptr, s, {}};
+        for (int k = 0; k < n_slots; ++k) run.slot.emplace_back(c->pool, (int64_t)B * P, Cl);
+        ncfhw_to_cl(latents, run.slot[0].p, B, Cl, Cl, P, 1.0f, s);
+        Act noise_cl;                                        // the noise tensors in the loop's layout (exact: a permutation)
+        if (n_noise > 0) {
+            noise_cl = Act(c->pool, (int64_t)n_noise * B * P, Cl);
+            ncfhw_to_cl(noise, noise_cl.p, n_noise * B, Cl, Cl, P, 1.0f, s);
+            run.noise = noise_cl.p;
+        }
+        std::vector<e2v_ctx::EvalTime> ev;
+        ev.reserve(n_unet);
+        for (int i = 0; i < n_ops; ++i)
+            if (ops[i].kind == E2V_PLAN_UNET)
+                ev.push_back(e2v_ctx::EvalTime{(int64_t)ops[i].timestep, (float)ops[i].timestep, ops[i].fractional != 0});
+        denoise_loop(c, a, ev, s,
+                     [&](int) { return (const float*)run.slot[run.advance()->src[0]].p; },
+                     [&](int, const float* eu, const float* ec) { run.unet_result(eu, ec); },
+                     [&] { run.advance(); return (const float*)run.slot[final_slot].p; });
+    });
+}
+
+// Test aid (eeg2video_hip_ops.h): the executor above with the UNet's results handed in.
+e2v_status e2v_op_run_plan(e2v_ctx* c, const e2v_plan_op* ops, int n_ops, int n_slots, int final_slot, const float* x0,
+                           const float* eps_u, const float* eps_c, int n_unet, const float* noise, int n_noise, float guidance,
+                           float* out, int64_t count, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    int plan_unet = 0;
+    const e2v_status st = plan_checked(c, ops, n_ops, n_slots, final_slot, noise, n_noise, &plan_unet);
+    if (st != E2V_OK) return st;
+    if (plan_unet != n_unet) { c->err = "plan: " + std::to_string(plan_unet) + " UNET ops, eps arrays of " + std::to_string(n_unet); return E2V_EINVAL; }
+    return guarded(c, [&] {
+        const bool cfg_on = guidance > 1.0f;
+        E2V_REQUIRE(x0 && eps_u && out && count > 0 && (!cfg_on || eps_c), E2V_EINVAL, "null argument");
+        hipStream_t s = S(c, stream);
+        PlanRun run{ops, n_ops, (long long)count, guidance, noise, s, {}};
+        for (int k = 0; k < n_slots; ++k) run.slot.emplace_back(c->pool, count, 1);
+        E2V_HIP(hipMemcpyAsync(run.slot[0].p, x0, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, s));
+        for (int k = 0; run.advance(); ++k)
+            run.unet_result(eps_u + (size_t)k * count, cfg_on ? eps_c + (size_t)k * count : nullptr);
+        E2V_HIP(hipMemcpyAsync(out, run.slot[final_slot].p, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, s));
         E2V_HIP(hipGetLastError());
     });
 }
+
+int64_t e2v_plan_op_size(void) { return (int64_t)sizeof(e2v_plan_op); }
 
 // ---- which kernel and tile every launch of a configuration takes, without a GPU -----------------------------------------------------
 // Runs e2v_generate (one DDIM step with guidance + decode) of B clips of [4, F, h, w] latents as a DRY RUN on a host-only ctx: the

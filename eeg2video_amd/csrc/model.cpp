@@ -1126,9 +1126,15 @@ struct Runner {
     // -> SiLU (resnets consume SiLU(emb)); fp32 rows in both modes.  tap(emb) sees linear_2's output (unet.py:345).
     template <class Tap>
     Act time_embedding(int n_t, int rows, int t_is_f32, Tap&& tap) {
-        const int boc0 = c->cfg.block_out_channels[0], temb_dim = boc0 * 4;
+        const int boc0 = c->cfg.block_out_channels[0];
         Act sin(pool(), rows, boc0);
         timestep_sinusoid(reinterpret_cast<const long long*>(c->d_timesteps.blk.data()), n_t, sin.p, rows, boc0, c->cfg.flip_sin_to_cos, c->cfg.freq_shift, s, t_is_f32);
+        return time_mlp(sin, rows, tap);
+    }
+    // ... the part after the sinusoid
+    template <class Tap>
+    Act time_mlp(const Act& sin, int rows, Tap&& tap) {
+        const int boc0 = c->cfg.block_out_channels[0], temb_dim = boc0 * 4;
         Act e1 = linear(c->unet.te1, sin.p, boc0, rows, f32_rows());
         silu(e1.p, e1.p, (long long)rows * temb_dim, s);
         Act emb = linear(c->unet.te2, e1.p, temb_dim, rows, f32_rows());
@@ -1274,16 +1280,35 @@ Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int 
 }
 
 // What a denoising loop can compute once instead of once per step ("precompute all 50 x 22 vectors once per
-// run"): the time-embedding MLP and every resnet's time_emb_proj for all timesteps (one GEMM of `steps` rows per resnet
+// run"): the time-embedding MLP and every resnet's time_emb_proj for all evaluations (one GEMM of `steps` rows per resnet
 // instead of `steps` GEMMs of N identical rows), and to_k / to_v of the conditioning of every cross-attention.  Row-wise
-// the arithmetic is the uncached one, so results are bit-identical.
-void e2v_ctx::build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s) {
+// the arithmetic is the uncached one, so results are bit-identical.  Row i belongs to EVALUATION i (PNDM evaluates one timestep
+// twice); an integral timestep takes the int64 sinusoid path and a fractional one the fp32 path, as e2v_unet_forward /
+// e2v_unet_forward_ft would for that evaluation alone: one sinusoid launch per run of evaluations of one kind (a DDIM / PNDM /
+// DPM-Solver++ schedule is one run; linspace(0, 999, 7)[::-1] = 999, 832.5, 666, ... alternates).
+void e2v_ctx::build_step_caches(const EvalTime* ev, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s) {
     Runner R{this, s, small_family};
     temb_cache.clear();
     kv_cache.clear();
-    const int temb_dim = cfg.block_out_channels[0] * 4;
-    E2V_HIP(hipMemcpyAsync(timesteps(steps, s), ts, sizeof(int64_t) * steps, hipMemcpyHostToDevice, s));
-    Act emb = R.time_embedding(steps, steps, 0, [](const Act&) {});
+    const int boc0 = cfg.block_out_channels[0], temb_dim = boc0 * 4;
+    // the buffer holds `steps` int64 values followed by `steps` floats (entry i of the array its kind names is the one read)
+    std::vector<int64_t> ti(steps);
+    std::vector<float> tf(steps);
+    bool any_frac = false;
+    for (int i = 0; i < steps; ++i) { ti[i] = ev[i].t; tf[i] = ev[i].tf; any_frac = any_frac || ev[i].frac; }
+    long long* d_ti = timesteps(any_frac ? 2 * steps : steps, s);
+    const float* d_tf = reinterpret_cast<const float*>(d_ti + steps);
+    E2V_HIP(hipMemcpyAsync(d_ti, ti.data(), sizeof(int64_t) * steps, hipMemcpyHostToDevice, s));
+    if (any_frac) E2V_HIP(hipMemcpyAsync(const_cast<float*>(d_tf), tf.data(), sizeof(float) * steps, hipMemcpyHostToDevice, s));
+    Act sin(pool, steps, boc0);
+    for (int a = 0; a < steps;) {
+        int b = a + 1;
+        while (b < steps && ev[b].frac == ev[a].frac) ++b;
+        const long long* src = ev[a].frac ? reinterpret_cast<const long long*>(d_tf + a) : d_ti + a;
+        timestep_sinusoid(src, b - a, sin.p + (size_t)a * boc0, b - a, boc0, cfg.flip_sin_to_cos, cfg.freq_shift, s, ev[a].frac ? 1 : 0);
+        a = b;
+    }
+    Act emb = R.time_mlp(sin, steps, [](const Act&) {});
     Act cond16;
     if (R.bf()) {
         cond16 = R.to_act16(cond, cfg.cross_attention_dim, cfg.cross_attention_dim, (int64_t)N * T);

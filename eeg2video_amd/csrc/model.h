@@ -184,7 +184,10 @@ struct e2v_ctx {
     bool step_cache_on = false; int step_cache_step = 0;
     std::vector<e2v::Act> temb_cache, kv_cache;
     long long* timesteps(int n, hipStream_t s) { return static_cast<long long*>(d_timesteps.ensure(sizeof(long long) * n, 0, s)); }
-    void build_step_caches(const int64_t* ts, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s);
+    // the timestep of one UNet evaluation: integral (`t`, the int64 sinusoid path of e2v_unet_forward) or fractional (`tf`, the fp32
+    // path of e2v_unet_forward_ft)
+    struct EvalTime { int64_t t; float tf; bool frac; };
+    void build_step_caches(const EvalTime* ev, int steps, const float* cond, int N, int T, bool small_family, hipStream_t s);
 
     // stream of the previous call (workspace reuse is stream-ordered): see enter_stream
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;

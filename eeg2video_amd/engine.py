@@ -383,6 +383,71 @@ class Engine:
             lat_out.data_ptr() if return_latents else None, _stream()))
         return (videos, lat_out) if return_latents else videos
 
+    def _plan_noise(self, plan, noise, shape) -> Optional[torch.Tensor]:
+        """The ``[n_noise, *shape]`` fp32 device tensor a plan reads (a tensor or a sequence of ``n_noise`` tensors), checked here on
+        the host because the library reads ``n_noise * prod(shape)`` floats whatever the real size."""
+        if plan.n_noise == 0:
+            if noise is not None and len(noise) != 0:
+                raise ValueError("this plan reads no noise tensor")
+            return None
+        if noise is None:
+            raise ValueError(f"this plan reads {plan.n_noise} noise tensors of shape {tuple(shape)}: pass `noise`")
+        if not isinstance(noise, torch.Tensor):
+            noise = torch.stack([self._dev(z, "noise") for z in noise])
+        noise = self._dev(noise, "noise")
+        if tuple(noise.shape) != (plan.n_noise,) + tuple(shape):
+            raise ValueError(f"`noise` must be {(plan.n_noise,) + tuple(shape)}, got {tuple(noise.shape)}")
+        return noise
+
+    def generate_plan(self, latents: torch.Tensor, cond: torch.Tensor, uncond: Optional[torch.Tensor], plan,
+                      guidance_scale: float = 7.5, noise=None, decode: bool = True, return_latents: bool = False):
+        """``generate`` with the per-step update of a ``sampler_plan.SamplerPlan`` (``e2v_generate_plan``): the whole loop of any
+        scheduler mirror on the device.  ``noise``: the ``[plan.n_noise, B, 4, F, h, w]`` N(0, 1) tensors of a stochastic plan, in
+        step order.  Results are written only when every check has passed."""
+        x, cond = self._dev(latents, "latents"), self._dev(cond, "cond")
+        un = self._dev(uncond, "uncond") if uncond is not None else None
+        self._check_loop_inputs(x, cond, un)
+        if guidance_scale > 1.0 and un is None:
+            raise ValueError("classifier-free guidance (guidance_scale > 1) needs `uncond`")
+        z = self._plan_noise(plan, noise, x.shape)
+        b, c, f, h, w = x.shape
+        videos = torch.empty((b, self.vae_cfg.out_channels, f, 8 * h, 8 * w), device=self.device,
+                             dtype=torch.float32) if decode else None
+        lat_out = torch.empty_like(x) if return_latents else None
+        ops = plan.c_ops()
+        self._check(self.lib.e2v_generate_plan(
+            self.ctx, x.data_ptr(), cond.data_ptr(), un.data_ptr() if un is not None else None,
+            un.shape[0] if un is not None else 0, b, f, h, w, cond.shape[1], ops, len(ops), int(plan.n_slots), int(plan.final_slot),
+            z.data_ptr() if z is not None else None, int(plan.n_noise), float(guidance_scale),
+            videos.data_ptr() if decode else None, lat_out.data_ptr() if return_latents else None, _stream()))
+        return (videos, lat_out) if return_latents else videos
+
+    def run_plan_updates(self, plan, x0: torch.Tensor, eps_u, eps_c=None, guidance_scale: float = 1.0, noise=None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Test aid (``e2v_op_run_plan``): the plan's updates with the UNet's results handed in -- ``eps_u`` (and, with guidance on,
+        ``eps_c``) ``[plan.n_unet, *x0.shape]``, UNET op ``k`` taking entry ``k``.  Returns the final slot (``out=``: written there)."""
+        x0 = self._dev(x0, "x0")                             # (a float32 tensor already on the device is used where it is)
+        want = (plan.n_unet,) + tuple(x0.shape)
+
+        def stacked(e, name):
+            e = self._dev(e if isinstance(e, torch.Tensor) else torch.stack([self._dev(t, name) for t in e]), name)
+            if tuple(e.shape) != want:
+                raise ValueError(f"`{name}` must be {want}, got {tuple(e.shape)}")
+            return e
+        eu = stacked(eps_u, "eps_u")
+        cfg = guidance_scale > 1.0
+        if cfg and eps_c is None:
+            raise ValueError("classifier-free guidance (guidance_scale > 1) needs `eps_c`")
+        ec = stacked(eps_c, "eps_c") if cfg else None
+        z = self._plan_noise(plan, noise, x0.shape)
+        out = self._op_out(out, tuple(x0.shape))
+        ops = plan.c_ops()
+        self._check(self.lib.e2v_op_run_plan(self.ctx, ops, len(ops), int(plan.n_slots), int(plan.final_slot), x0.data_ptr(),
+                                             eu.data_ptr(), ec.data_ptr() if ec is not None else None, int(plan.n_unet),
+                                             z.data_ptr() if z is not None else None, int(plan.n_noise), float(guidance_scale),
+                                             out.data_ptr(), x0.numel(), _stream()))
+        return out
+
     # ------------------------------------------------------------------ the steps either side of the path (SURVEY 8(f))
     def semantic_predict(self, eeg: torch.Tensor) -> torch.Tensor:
         x = self._dev(eeg, "eeg")

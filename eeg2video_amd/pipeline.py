@@ -8,9 +8,15 @@ same checks and error types, same output object.  What differs, on purpose:
 * the unconditional embedding is taken from ``negative_prompt`` (a ``[1 or B,77,768]`` tensor) or
   ``self.negative_embeddings`` instead of the hard-coded ``negative.npy`` path of ``:170``, and is
   broadcast to the batch (the reference is only consistent for B = 1; SURVEY G12);
-* when no per-step callback is requested and UNet and VAE share one engine the whole loop runs
-  inside ``e2v_generate`` with no host round trip per step; otherwise the loop below steps through
-  ``e2v_unet_forward`` / ``e2v_ddim_cfg_step`` exactly as the reference's Python loop does.
+* when no per-step callback is requested and UNet and VAE share one engine the whole loop runs on the device with no
+  host round trip per step: deterministic DDIM inside ``e2v_generate``, every other scheduler mirror (PNDM -- what a stock
+  SD-v1-4 directory names --, LMS, Euler, Euler-ancestral, DPM-Solver++, DDIM with ``eta > 0``) inside ``e2v_generate_plan``
+  with the plan ``sampler_plan.trace_plan`` records from the mirror; otherwise the loop below steps through
+  ``e2v_unet_forward`` / ``e2v_ddim_cfg_step`` / ``e2v_lincomb`` exactly as the reference's Python loop does.
+  ``pipe.last_loop`` names the loop that served the latest call: ``"ddim"``, ``"plan"`` or ``"stepped"``.  A stochastic plan
+  (Euler-ancestral, DDIM with ``eta > 0``) has its noise drawn before the call -- one draw per step, in step order, from the
+  caller's ``generator`` on its device, the draws the stepped loop makes -- and held on the device for the call:
+  ``num_inference_steps x B x 4 F h w`` floats, 354 MB at B = 32, F = 6, 36 x 64 latents and 50 steps.
 """
 from __future__ import annotations
 
@@ -21,8 +27,9 @@ from typing import Callable, List, Optional, Union
 import numpy as np
 import torch
 
-from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
-                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, scheduler_from_pretrained)
+from .sampler_plan import trace_plan
+from .scheduler import (SCHEDULERS, DDIMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,  # noqa: F401
+                        EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, _randn_like, scheduler_from_pretrained)
 from .unet import UNet3DConditionModel
 from .vae import AutoencoderKL
 
@@ -49,6 +56,7 @@ class TuneAVideoPipeline:
         if scheduler.engine is None:
             scheduler.bind(unet.engine)
         self._progress = True
+        self.last_loop: Optional[str] = None             # the loop that served the latest call: "ddim", "plan" or "stepped"
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, unet: Optional[UNet3DConditionModel] = None, vae: Optional[AutoencoderKL] = None,
@@ -258,15 +266,31 @@ class TuneAVideoPipeline:
         extra = self.prepare_extra_step_kwargs(generator, eta)                                    # :306
         b = latents.shape[0]
         eng = self.unet.engine
-        # the fused device loop is the deterministic DDIM one; a stochastic update (eta > 0 draws torch noise per step), another
-        # scheduler type or a per-step callback step through the public entry points exactly as the reference's loop does
-        fused = (callback is None and self.vae.engine is eng and isinstance(self.scheduler, DDIMScheduler)
-                 and extra.get("eta", 0.0) == 0.0)
+        # The device loops need no per-step callback and one engine for UNet and VAE.  Deterministic DDIM is e2v_generate's own
+        # update; every other scheduler mirror runs as the plan recorded from it (e2v_generate_plan) -- not with a list of generators,
+        # which the mirrors' own noise draw does not take either.  Anything else (a callback, a scheduler object that is not one of
+        # the mirrors, a generator list) steps through the public entry points exactly as the reference's loop does.
+        device_loop = callback is None and self.vae.engine is eng
+        fused = device_loop and isinstance(self.scheduler, DDIMScheduler) and extra.get("eta", 0.0) == 0.0
+        planned = (device_loop and not fused and type(self.scheduler) in SCHEDULERS.values()
+                   and not isinstance(generator, (list, tuple)))
+        self.last_loop = "ddim" if fused else "plan" if planned else "stepped"
         if fused:
             self.scheduler.bind(eng)      # the fused loop walks the ctx's schedule: make it this scheduler's (table, steps_offset)
             with self.progress_bar(total=num_inference_steps) as bar:
                 video = eng.generate(latents, emb[b:] if do_cfg else emb, emb[:b] if do_cfg else None,
                                      num_inference_steps, guidance_scale, 0.0, decode=True)
+                bar.update(num_inference_steps)
+            video = video.cpu().float().numpy()                                                   # :183
+        elif planned:
+            # A stochastic plan reads one N(0, 1) tensor per step: they are drawn here, before the call, one `_randn_like` draw per
+            # step in step order from the caller's generator on its device -- the sequence of draws the stepped loop makes.  They are
+            # held for the call: n x B x 4 F h w floats (354 MB at B = 32, F = 6, 36 x 64 latents and 50 steps).
+            plan = trace_plan(self.scheduler, num_inference_steps, eta=extra.get("eta", 0.0))
+            noise = torch.stack([_randn_like(latents, generator) for _ in range(plan.n_noise)]) if plan.n_noise else None
+            with self.progress_bar(total=num_inference_steps) as bar:
+                video = eng.generate_plan(latents, emb[b:] if do_cfg else emb, emb[:b] if do_cfg else None, plan,
+                                          guidance_scale, noise=noise, decode=True)
                 bar.update(num_inference_steps)
             video = video.cpu().float().numpy()                                                   # :183
         else:

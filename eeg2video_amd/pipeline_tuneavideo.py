@@ -12,7 +12,8 @@ conditioning enters in one of two ways:
   ``text_encoder/``, and the tokenizer's ids go to it as a host array), or a host-side torch module with the ``transformers`` CLIP
   interface that the caller hands in.  Only the tokenizer (BPE) stays outside the library.
 
-From there on it is the EEG pipeline's loop (``pipeline.py``): the fused device loop for deterministic DDIM, else stepped.
+From there on it is the EEG pipeline's loop (``pipeline.py``): the device loop for deterministic DDIM (``e2v_generate``) and for every
+other scheduler mirror (``e2v_generate_plan``), else stepped; ``pipe.last_loop`` says which.
 """
 from __future__ import annotations
 

@@ -172,6 +172,15 @@ int64_t e2v_op_pool_gets(const e2v_ctx* ctx);
  * none.  E2V_ESTATE while the switch is off.  No reference counterpart. */
 e2v_status e2v_op_pool_guard_selftest(e2v_ctx* ctx, int64_t payload_bytes, int64_t offset, e2v_stream stream);
 
+/* Test aid: the update arithmetic of e2v_generate_plan without a model -- the same executor, the same validation, with the UNet
+ * replaced by the caller's tensors.  Everything is elementwise over `count` floats: slot 0 starts as x0 [count]; UNET op number k
+ * (in plan order) takes eps_u[k] and, with guidance on (guidance_scale > 1), eps_c[k] from device arrays [n_unet][count] (eps_c may
+ * be NULL with guidance off; n_unet must be the plan's number of UNET ops, else E2V_EINVAL); noise: device [n_noise][count]; out
+ * [count] receives the final slot.  Timesteps are validated and otherwise unused.  No reference counterpart. */
+e2v_status e2v_op_run_plan(e2v_ctx* ctx, const e2v_plan_op* ops, int n_ops, int n_slots, int final_slot, const float* x0,
+                           const float* eps_u, const float* eps_c, int n_unet, const float* noise, int n_noise,
+                           float guidance_scale, float* out, int64_t count, e2v_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
