@@ -266,7 +266,7 @@ __device__ __forceinline__ void igemm_tile(const IgemmArgs& p, const int rbg, co
     }
     if (ks < nk) kstep(std::integral_constant<int, 0>{});
 
-    igemm_epilogue<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, reinterpret_cast<float*>(smem));
+    igemm_epilogue_batched<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, reinterpret_cast<float*>(smem));
 }
 
 // =====================================================================================================
@@ -465,7 +465,7 @@ __device__ __forceinline__ void igemm_tile_x3(const IgemmArgs& p, const int rbg,
         kstep(std::integral_constant<int, 1>{});
     }
     if (ks < nk) kstep(std::integral_constant<int, 0>{});
-    igemm_epilogue<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, reinterpret_cast<float*>(smem));
+    igemm_epilogue_batched<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, reinterpret_cast<float*>(smem));
 }
 
 template <int ABLX>
@@ -637,7 +637,7 @@ __device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg
         kstep(std::integral_constant<int, 1>{});
     }
     if (ks < nk) kstep(std::integral_constant<int, 0>{});
-    igemm_epilogue<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, smem);
+    igemm_epilogue_batched<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, smem);
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void igemm_k16_kernel(const IgemmArgs p) {

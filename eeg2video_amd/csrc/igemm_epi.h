@@ -27,6 +27,24 @@ __device__ __forceinline__ float gelu_erf(float x) {
     return 0.5f * x * (1.0f + copysignf(erf_abs, x));
 }
 
+// The same function on a pair: the fma / mul chain as v_pk_fma_f32 / v_pk_mul_f32 (half the vector instructions; on gfx950 they are not
+// hidden behind the fp32 MFMA), v_rcp_f32 and v_exp_f32 per element.  Each element sees exactly the operations of gelu_erf.
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 gelu_erf2(const f32x2 x) {
+    const f32x2 z = __builtin_elementwise_abs(x) * 0.70710678118654752440f;
+    const f32x2 d = __builtin_elementwise_fma(f32x2(0.3275911f), z, f32x2(1.0f));
+    const f32x2 t = {__builtin_amdgcn_rcpf(d[0]), __builtin_amdgcn_rcpf(d[1])};
+    f32x2 p = __builtin_elementwise_fma(f32x2(1.061405429f), t, f32x2(-1.453152027f));
+    p = __builtin_elementwise_fma(p, t, f32x2(1.421413741f));
+    p = __builtin_elementwise_fma(p, t, f32x2(-0.284496736f));
+    p = __builtin_elementwise_fma(p, t, f32x2(0.254829592f));
+    p *= t;
+    const f32x2 a = z * z * -1.44269504088896340736f;
+    const f32x2 e = {__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
+    const f32x2 erf_abs = __builtin_elementwise_fma(-p, e, f32x2(1.0f));
+    return 0.5f * x * (1.0f + __builtin_elementwise_copysign(erf_abs, x));
+}
+
 // The same gate in the bf16-activation mode, where the product value * gelu(gate) is rounded to bf16 (2^-9 relative) on its way out:
 // gelu(x) = x Phi(x) with the normal CDF as a logistic of an odd cubic, Phi(x) ~ 1 / (1 + exp(-(a x + b x^3))), a = 1.60031415,
 // b = 0.06940179 (minimax fit of x Phi(x) over the real line; monotone, so no clamp): |gelu error| <= 2.8e-4 = 1/14 of the rounding
@@ -57,10 +75,57 @@ typedef hx4<__bf16> bf16x4;        // (the split-bf16 fp32 path of igemm.hip nam
 typedef hx8<__bf16> bf16x8;
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// Epilogue shared by the fp32, bf16 and split-bf16 tiles (all use 32x32 MFMA results with the WEIGHT fragment as the A
-// operand): in each 32x32 result a lane holds pixel m = lane & 31 and output channels n = 8 g + 4 (lane >> 5) + e in register
-// r = 4 g + e -- four consecutive channels per register quad, i.e. 16-byte bias / time-embedding / residual loads and 16-byte
-// stores (a short-K layer -- every Winograd-domain GEMM, every attention projection -- spends a tenth of its time here).
+// Buffer descriptor over [ptr, ptr + 2 GB) from a pointer forced into SGPRs: an offset of kEpiOob lies outside the window, so a masked
+// lane's load returns zeros and its store is dropped by the buffer unit -- no branch, and every access of a batch is one basic block.
+constexpr unsigned kEpiOob = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t epi_rsrc(const void* ptr) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(ptr);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+    const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), (short)0, 0x7FFFFFF0, 0x00020000);
+}
+__device__ __forceinline__ f32x4 epi_load(const __amdgpu_buffer_rsrc_t rs, const unsigned off) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 0));
+}
+__device__ __forceinline__ void epi_store(const f32x4 v, const __amdgpu_buffer_rsrc_t rs, const unsigned off) {
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, off, 0, 0);
+}
+
+// Element-wise form of the epilogues below (N, or a stride, not a multiple of 4: the VAE's 3-channel conv_out)
+template <int BM, int TM, int TN, int WM, int WN>
+__device__ __forceinline__ void igemm_epilogue_scalar(const IgemmArgs& p, f32x16 (&acc)[TM][TN], float* __restrict__ out, const int bm,
+                                                      const int n0, const int wm, const int wn, const int lane) {
+    const int mrow = lane & 31;
+    const int nq = (lane >> 5) * 4;
+#pragma unroll
+    for (int mi = 0; mi < TM; ++mi) {
+        const int m = bm * BM + wm * WM + mi * 32 + mrow;
+        if (m >= p.M) continue;
+        const float* rbp = p.rowbias ? p.rowbias + (size_t)(m / p.rows_per_sample) * p.rb_ld : nullptr;
+        const float* rsp = p.resid ? p.resid + (size_t)m * p.ldr : nullptr;
+        float* orow = out + (size_t)m * p.ldc;
+#pragma unroll
+        for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int n = n0 + wn * WN + ni * 32 + 8 * g + nq;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    if (n + e >= p.N) break;
+                    float v = acc[mi][ni][4 * g + e] * p.alpha + (p.bias ? p.bias[n + e] : 0.f);
+                    if (rbp) v += rbp[n + e];
+                    if (rsp) v += rsp[n + e];
+                    if (p.relu) v = fmaxf(v, 0.f);
+                    orow[n + e] = v;
+                }
+            }
+    }
+}
+
+// Epilogue of the 16-bit tiles with fp32 output (bgemm.hip), and the layout it shares with the fp32 tiles' igemm_epilogue_batched
+// below (all use 32x32 MFMA results with the WEIGHT fragment as the A operand): in each 32x32 result a lane holds pixel m = lane & 31
+// and output channels n = 8 g + 4 (lane >> 5) + e in register r = 4 g + e -- four consecutive channels per register quad, i.e. 16-byte
+// bias / time-embedding / residual loads and 16-byte stores.
 template <int BM, int TM, int TN, int WM, int WN>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f32x16 (&acc)[TM][TN], float* __restrict__ out, const int bm,
                                                const int n0, const int wm, const int wn, const int lane, float* stage) {
@@ -143,30 +208,209 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f32x16 (&acc)
         }
         return;
     }
-    // scalar fallback (N, or a stride, not a multiple of 4: the VAE's 3-channel conv_out)
+    igemm_epilogue_scalar<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane);
+}
+
+// The same epilogue for the fp32 and split-bf16 tiles (igemm.hip), whose short-K launches paid a fifth of a tile for it: memory accesses
+// in batches of branch-free buffer loads / stores, the GEGLU gate on packed fp32 pairs.  Per element the floating-point operations
+// and their order are those of igemm_epilogue -- results are bit-identical.  (The 16-bit tiles keep the form above: with this one
+// inlined their kernels fell from three / two waves per SIMD to one.)
+template <int BM, int TM, int TN, int WM, int WN>
+__device__ __forceinline__ void igemm_epilogue_batched(const IgemmArgs& p, f32x16 (&acc)[TM][TN], float* __restrict__ out, const int bm,
+                                                       const int n0, const int wm, const int wn, const int lane, float* stage) {
+    const int mrow = lane & 31;
+    const int nq = (lane >> 5) * 4;
+    const int m_left = p.M - bm * BM;                              // rows of the matrix from the tile's first row on
+    const __amdgpu_buffer_rsrc_t ro = epi_rsrc(out + (size_t)bm * BM * p.ldc);   // stores: offsets relative to the tile's first row
+    if (p.geglu) {
+        if constexpr (TN == 2) {
+            const int nb = n0 + wn * WN;                           // value columns nb .. nb+31, gate columns nb+32 .. nb+63
+            if (nb + 64 <= p.N) {
+                // v * gelu(g) in the accumulator layout, staged per wave as WM x 32 and written row-contiguously (8 lanes = one
+                // 128-byte row segment) like the plain epilogue below
+                constexpr int SLD = 36;
+                float* st = stage + (size_t)(threadIdx.x >> 6) * 32 * SLD;
+                const int col = (lane & 7) * 4;
+                const bool fast = p.a_bf16 == H16_BF16 || (kF16FastGate && p.a_bf16 == H16_FP16);
+                // the wave's eight bias quads, once (they were loaded per 32-row block, inside the element loops)
+                const __amdgpu_buffer_rsrc_t rbs = epi_rsrc(p.bias);
+                f32x4 bv[4], bg[4];
 #pragma unroll
-    for (int mi = 0; mi < TM; ++mi) {
-        const int m = bm * BM + wm * WM + mi * 32 + mrow;
-        if (m >= p.M) continue;
-        const float* rbp = p.rowbias ? p.rowbias + (size_t)(m / p.rows_per_sample) * p.rb_ld : nullptr;
-        const float* rsp = p.resid ? p.resid + (size_t)m * p.ldr : nullptr;
-        float* orow = out + (size_t)m * p.ldc;
+                for (int g = 0; g < 4; ++g) {
+                    bv[g] = epi_load(rbs, p.bias ? (unsigned)(nb + 8 * g + nq) * 4u : kEpiOob);
+                    bg[g] = epi_load(rbs, p.bias ? (unsigned)(nb + 32 + 8 * g + nq) * 4u : kEpiOob);
+                }
+                const f32x2 alpha2 = {p.alpha, p.alpha};
 #pragma unroll
-        for (int ni = 0; ni < TN; ++ni)
+                for (int mi = 0; mi < TM; ++mi) {
+                    if (fast) {                                    // the 16-bit arithmetic modes' gate (no fp32 launch selects it)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int n = n0 + wn * WN + ni * 32 + 8 * g + nq;
+                        for (int g = 0; g < 4; ++g) {
+                            f32x4 y;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    if (n + e >= p.N) break;
-                    float v = acc[mi][ni][4 * g + e] * p.alpha + (p.bias ? p.bias[n + e] : 0.f);
-                    if (rbp) v += rbp[n + e];
-                    if (rsp) v += rsp[n + e];
-                    if (p.relu) v = fmaxf(v, 0.f);
-                    orow[n + e] = v;
+                            for (int e = 0; e < 4; ++e)
+                                y[e] = (acc[mi][0][4 * g + e] * p.alpha + bv[g][e]) * gelu_gate(acc[mi][1][4 * g + e] * p.alpha + bg[g][e], true);
+                            *reinterpret_cast<f32x4*>(st + mrow * SLD + 8 * g + nq) = y;
+                        }
+                    } else {
+                        // erf form on pairs: per element the fma / mul sequence of the scalar code (acc * alpha + bias fused), as
+                        // packed instructions -- 16 pairs per 32-row block instead of 32 trips through a 29-instruction loop body
+#pragma unroll
+                        for (int g = 0; g < 4; ++g) {
+                            f32x4 y;
+#pragma unroll
+                            for (int h = 0; h < 2; ++h) {
+                                const int r = 4 * g + 2 * h;
+                                const f32x2 v = __builtin_elementwise_fma(f32x2{acc[mi][0][r], acc[mi][0][r + 1]}, alpha2, f32x2{bv[g][2 * h], bv[g][2 * h + 1]});
+                                const f32x2 x = __builtin_elementwise_fma(f32x2{acc[mi][1][r], acc[mi][1][r + 1]}, alpha2, f32x2{bg[g][2 * h], bg[g][2 * h + 1]});
+                                const f32x2 o = v * gelu_erf2(x);
+                                y[2 * h] = o[0];
+                                y[2 * h + 1] = o[1];
+                            }
+                            *reinterpret_cast<f32x4*>(st + mrow * SLD + 8 * g + nq) = y;
+                        }
+                    }
+                    f32x4 y[4];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) y[i] = *reinterpret_cast<const f32x4*>(st + ((lane >> 3) + 8 * i) * SLD + col);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int row = wm * WM + mi * 32 + (lane >> 3) + 8 * i;
+                        epi_store(y[i], ro, row < m_left ? (unsigned)(row * p.ldc + nb / 2 + col) * 4u : kEpiOob);
+                    }
                 }
             }
+        }
+        return;
     }
+    const bool vec = ((p.N | p.ldc | p.ldr | p.rb_ld) & 3) == 0;   // strides of absent operands are 0
+    if (vec) {
+        // Row-contiguous epilogue: the wave transposes its accumulators, 32 rows at a time, through LDS (the tile buffers are dead: every
+        // real fragment read precedes the last barrier of the k-loop) so that a 16-byte access instruction covers whole rows --
+        // 64 / (WN / 4) rows x WN floats -- instead of 32 rows x 32 bytes.  Residual reads and stores then move full 128-byte
+        // lines (+5 % on the K = 320 layers, whose output write is a tenth of their time).
+        // Memory accesses come in batches: the residual quads of 16 rows and a block's time-embedding quads are requested half a block
+        // ahead of their use, as buffer loads whose masked lanes (rows >= M, columns >= N, absent operand) carry an out-of-window
+        // offset; adds and stores follow behind counted waits that leave the stores in flight.  (One load, one wait for everything
+        // before it, one store per row group -- 16 memory round trips in a row per wave of a 128 x 128 tile -- was a fifth of a
+        // K = 320 tile.  Whole 32-row requests do not fit 168 registers: the allocator spilled two quads behind a full wait.)
+        constexpr int SLD = WN + 4;                            // padded staging row: conflict-free b128 writes and reads
+        constexpr int LPR = WN / 4;                            // lanes per staged row
+        constexpr int RPI = 64 / LPR;                          // rows per access instruction
+        constexpr int NI = 32 / RPI;                           // access instructions per 32-row block
+        float* st = stage + (size_t)(threadIdx.x >> 6) * 32 * SLD;   // one 32-row staging block per wave, reused per mi
+        const int col = (lane % LPR) * 4;
+        const int rl = lane / LPR;                             // the lane's row within an access instruction
+        const int n = n0 + wn * WN + col;
+        const bool nok = n < p.N;                              // N % 4 == 0: the lane's four columns are in or out together
+        const f32x4 bias4 = epi_load(epi_rsrc(p.bias), ((p.bias != nullptr) & nok) ? (unsigned)n * 4u : kEpiOob);
+        const __amdgpu_buffer_rsrc_t rr = epi_rsrc(p.resid ? p.resid + (size_t)bm * BM * p.ldr : nullptr);
+        const __amdgpu_buffer_rsrc_t rt = epi_rsrc(p.rowbias);
+        const bool rok = (p.resid != nullptr) & nok, tok = (p.rowbias != nullptr) & nok;   // bitwise: selects, not branches
+        const int row0 = wm * WM + rl;                         // the lane's first row within the tile
+        // Time-embedding rows: a 32-row block touches at most two samples when rows_per_sample >= 32 (every map of the full-size
+        // model), so they are two loads per lane and block -- the sample of the block's first row and the next -- requested with the
+        // residual, and a select per row group.  Tiny maps (TINY) load one row per row group instead, and their residual with it, NH
+        // row groups at a time behind the previous stores: a code path of its own, so that the other one has no load between its
+        // stores and no register of its batch is shared with it.
+        constexpr int NH = 2;                                  // row groups finished together (registers: 168 with three waves per SIMD)
+        auto run = [&](auto tiny_c) {
+            constexpr bool TINY = decltype(tiny_c)::value;
+            f32x4 res[TM][NI], tb[TM][2];
+            int split[TM];                                     // rows of block mi below split[mi] belong to its first sample
+            constexpr int HB = NI / 2;                         // a request: the residual of 16 rows; with a block's first, its time-embedding rows
+            auto request = [&](const int mi, const int hh) {
+                if constexpr (TINY) return;
+#pragma unroll
+                for (int i = hh * HB; i < hh * HB + HB; ++i) {
+                    const int row = row0 + mi * 32 + RPI * i;
+                    res[mi][i] = epi_load(rr, (rok & (row < m_left)) ? (unsigned)(row * p.ldr + n) * 4u : kEpiOob);
+                }
+                if (hh != 0) return;
+                const int m0 = __builtin_amdgcn_readfirstlane(bm * BM + wm * WM + mi * 32);   // the block's first row: scalar division
+                const int s_lo = m0 / p.rows_per_sample;
+                split[mi] = (s_lo + 1) * p.rows_per_sample - m0;
+                const int rows = min(p.M - m0, 32);
+                tb[mi][0] = epi_load(rt, (tok & (rows > 0)) ? (unsigned)(s_lo * p.rb_ld + n) * 4u : kEpiOob);
+                tb[mi][1] = epi_load(rt, (tok & (split[mi] < rows)) ? (unsigned)((s_lo + 1) * p.rb_ld + n) * 4u : kEpiOob);
+            };
+            request(0, 0);
+#pragma unroll
+            for (int mi = 0; mi < TM; ++mi) {
+#pragma unroll
+                for (int ni = 0; ni < TN; ++ni)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        f32x4 y;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) y[e] = acc[mi][ni][4 * g + e];
+                        *reinterpret_cast<f32x4*>(st + mrow * SLD + ni * 32 + 8 * g + nq) = y;
+                    }
+                // NH row groups at a time: per element, in this order, (* alpha) + bias + time embedding + residual, relu
+                // -- under wave-uniform conditions -- then their stores back to back
+#pragma unroll
+                for (int h = 0; h < NI / NH; ++h) {
+                    // (requests stay where they are written, half a block ahead: left alone the scheduler issues them all up front)
+                    __builtin_amdgcn_sched_barrier(0);
+                    if ((h * NH) % HB == 0) {
+                        if (h == 0) request(mi, 1);
+                        else if (mi + 1 < TM) request(mi + 1, 0);
+                    }
+                    f32x4 th[NH], rh[NH];
+                    if constexpr (TINY) {
+                        const int m0 = __builtin_amdgcn_readfirstlane(bm * BM + wm * WM + mi * 32);
+                        const int s0 = m0 / p.rows_per_sample, rem = m0 - s0 * p.rows_per_sample;
+                        // sample of row m0 + d = s0 + (rem + d) / rows_per_sample with rem + d < 64, the quotient through a
+                        // reciprocal: (x + 0.5) / r is at least 1 / 64 away from an integer, the product's error below 2^-16
+                        const float inv = __builtin_amdgcn_rcpf((float)p.rows_per_sample);
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) {
+                            const int d = rl + RPI * (h * NH + j);
+                            const int smp = s0 + (int)(((float)(rem + d) + 0.5f) * inv);
+                            const int row = row0 + mi * 32 + d - rl;
+                            th[j] = epi_load(rt, (tok & (row < m_left)) ? (unsigned)(smp * p.rb_ld + n) * 4u : kEpiOob);
+                            rh[j] = epi_load(rr, (rok & (row < m_left)) ? (unsigned)(row * p.ldr + n) * 4u : kEpiOob);
+                        }
+                    }
+                    f32x4 y[NH];
+#pragma unroll
+                    for (int j = 0; j < NH; ++j) y[j] = *reinterpret_cast<const f32x4*>(st + (rl + RPI * (h * NH + j)) * SLD + col);
+                    if (p.alpha != 1.0f) {                     // only the VAE attention scales
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) y[j] *= p.alpha;
+                    }
+#pragma unroll
+                    for (int j = 0; j < NH; ++j) y[j] += bias4;
+                    if (p.rowbias) {
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) {
+                            if constexpr (TINY) y[j] += th[j];
+                            else y[j] += (rl + RPI * (h * NH + j) >= split[mi]) ? tb[mi][1] : tb[mi][0];
+                        }
+                    }
+                    if (p.resid) {
+#pragma unroll
+                        for (int j = 0; j < NH; ++j) y[j] += TINY ? rh[j] : res[mi][h * NH + j];
+                    }
+                    if (p.relu) {
+#pragma unroll
+                        for (int j = 0; j < NH; ++j)
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) y[j][e] = fmaxf(y[j][e], 0.f);
+                    }
+#pragma unroll
+                    for (int j = 0; j < NH; ++j) {
+                        const int row = row0 + mi * 32 + RPI * (h * NH + j);
+                        epi_store(y[j], ro, (nok & (row < m_left)) ? (unsigned)(row * p.ldc + n) * 4u : kEpiOob);
+                    }
+                }
+            }
+        };
+        if (p.rowbias && p.rows_per_sample < 32) run(std::true_type{});
+        else run(std::false_type{});
+        return;
+    }
+    igemm_epilogue_scalar<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane);
 }
 
 
