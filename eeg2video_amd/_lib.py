@@ -48,7 +48,7 @@ E2V_PLAN_MAX_SLOTS, E2V_PLAN_MAX_TERMS = 8, 5
 
 E2V_OK, E2V_EINVAL, E2V_ESHAPE, E2V_ENOWEIGHT, E2V_EHIP, E2V_ESTATE = 0, -1, -2, -3, -4, -5
 E2V_F32, E2V_F16, E2V_BF16, E2V_F32X3 = 0, 1, 2, 3
-#: bits of e2v_op_weight_forms (include/eeg2video_hip_ops.h)
+#: the E2V_FORM_* bits (include/eeg2video_hip.h): the mask of e2v_op_weight_forms, the `form` of e2v_read_tensor
 FORM_BITS = {"fp32": 1, "bf16": 2, "fp16": 4, "x3": 8, "conv_direct32": 16, "wino2": 32, "wino4": 64, "bf16_up2": 128,
              "f16_up2": 256, "wino2_x3": 512, "wino4_x3": 1024}
 
@@ -69,6 +69,7 @@ SIGNATURES = {
     "e2v_expected_key": (C.c_char_p, [_ctx, _i64, c_int64_p, C.POINTER(_i)]),
     "e2v_finalize_weights": (_i, [_ctx, _i]),
     "e2v_update_tensor": (_i, [_ctx, C.c_char_p, _p, _i, _i, c_int64_p, _i, _stream]),
+    "e2v_read_tensor": (_i, [_ctx, C.c_char_p, _i, _p, _i, _i, c_int64_p, _i, _stream]),
     "e2v_ddim_timesteps": (_i, [_ctx, _i, c_int64_p]),
     "e2v_ddim_alphas_cumprod": (_i, [_ctx, C.POINTER(C.c_float)]),
     "e2v_set_alphas_cumprod": (_i, [_ctx, C.POINTER(C.c_float), _i]),

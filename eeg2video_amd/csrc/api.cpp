@@ -258,6 +258,36 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
     });
 }
 
+e2v_status e2v_read_tensor(e2v_ctx* c, const char* key, int form, void* out, e2v_dtype dtype, int on_device, const int64_t* shape,
+                           int ndim, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    if (!key || !out || !shape) { c->err = "null argument"; return E2V_EINVAL; }
+    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
+    try {
+        auto it = c->raw.find(key);
+        E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
+        const WTensor& t = it->second;
+        bool same = (int)t.shape.size() == ndim;
+        for (int d = 0; same && d < ndim; ++d) same = t.shape[d] == shape[d];
+        E2V_REQUIRE(same, E2V_ENOWEIGHT, std::string("shape mismatch for ") + key);
+        E2V_REQUIRE(dtype == E2V_F32 || dtype == E2V_F16 || dtype == E2V_BF16, E2V_EINVAL, "e2v_read_tensor: the destination is fp32, fp16 or bf16");
+        if (form == 0) form = E2V_FORM_F32;
+        E2V_REQUIRE((form & (form - 1)) == 0, E2V_EINVAL, "e2v_read_tensor: `form` names one stored form (one E2V_FORM_* bit)");
+        E2V_REQUIRE(form > 0 && form <= E2V_FORM_WINO4_X3, E2V_EINVAL, "e2v_read_tensor: unknown form bit");
+        E2V_REQUIRE(form == E2V_FORM_F32 || form == E2V_FORM_BF16 || form == E2V_FORM_F16 || form == E2V_FORM_X3, E2V_EINVAL,
+                    "e2v_read_tensor: the conv kernel layouts, the Winograd domains and the UP2 forms have no index-map inverse; read E2V_FORM_F32");
+        updatable(c, key);
+        c->read_source(key, form);
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no weights in a dry run");
+        c->read_tensor(key, form, out, dtype, on_device != 0, S(c, stream));
+    });
+}
+
 e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
     if (!c) return E2V_EINVAL;
     if (!key || !mask) { c->err = "null argument"; return E2V_EINVAL; }

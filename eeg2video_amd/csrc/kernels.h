@@ -265,6 +265,21 @@ struct WeightScatterArgs {
 };
 void weight_scatter(const WeightScatterArgs& a, hipStream_t s);
 
+// Weight read-back (e2v_read_tensor): the inverse of weight_scatter over the same row map.  ONE stored form of a linear is the source --
+// fp32 (src_mode 0), the bf16 or fp16 copy (1 / 2), or the three f32x3 planes (x3 = 1: `src` is plane 0, the others `plane` elements
+// on; the value is (p0 + p1) + p2 in fp32, which is the fp32 weight exactly) -- with row stride `ld` elements, of which the first
+// `in` columns are the tensor's.  Destination row j, dense [rows][in] in dst_mode's type (0 fp32, 1 bf16, 2 fp16: round to nearest
+// even, as to_h16), comes from source row  row_off + j  (half == 0) or from the GEGLU-interleaved row WeightScatterArgs describes.
+// Nothing is read past column `in` of a source row and exactly rows * in destination elements are written; `dst` may have any alignment.
+struct WeightGatherArgs {
+    const void* src = nullptr; int src_mode = 0; int x3 = 0;
+    int ld = 0; long long plane = 0;
+    int rows = 0, in = 0;
+    int row_off = 0, half = 0, blk = 1;
+    void* dst = nullptr; int dst_mode = 0;
+};
+void weight_gather(const WeightGatherArgs& a, hipStream_t s);
+
 // weight-streaming GEMV (gemv.hip): out[b][n] = act(x[b] . W[n] + bias[n]) for B <= 16 rows, x / out fp32 rows, W [N][ldw] fp32 or
 // bf16 (rows zero-padded to ldw); the Semantic Predictor at the reference's batch sizes
 bool gemv_rows_supported(int B, int K, int w_bf16);

@@ -1,6 +1,8 @@
 // Element-wise and layout kernels of the path (all HBM-bound, grid-stride, 16-byte lanes where the
 // layout allows): boundary layout conversion NCFHW <-> channel-last, the fused classifier-free
 // guidance + DDIM update, the timestep sinusoid, SiLU, and a tiled transpose for the VAE attention.
+#include <type_traits>
+
 #include "h16.h"
 #include "kernels.h"
 #include "prof.h"
@@ -380,6 +382,107 @@ void weight_scatter(const WeightScatterArgs& a, hipStream_t s) {
     };
     if (a.src_mode == H16_NONE) launch(float{});
     else h16_dispatch(a.src_mode, launch);
+}
+
+// ---- weight read-back (e2v_read_tensor; kernels.h: WeightGatherArgs) -----------------------------------------------------------------
+// The inverse of weight_scatter_kernel over the same row map: one lane per 8-column piece of a DESTINATION row, read from the one
+// stored form the caller chose (Src = float, __bf16, _Float16; X3: unsigned short planes, summed (p0 + p1) + p2 -- the partial sums
+// fit fp32's 24 bits, so the value is the fp32 weight the planes were split from) and written dense in the requested type (the compiler's
+// round-to-nearest-even casts, as to_h16_kernel).  VEC: 16-byte loads and stores.  VEC = false serves a row length that is no multiple
+// of 8 (22, 310, 4) and a source row or a destination that is not 16-byte aligned: element loads guarded by `in` (the padding columns
+// of a source row are never read), element stores guarded by `in` (rows * in elements are written, no more).
+template <typename Src, typename Dst, bool X3, bool VEC>
+__global__ __launch_bounds__(256) void weight_gather_kernel(const WeightGatherArgs a, int pieces) {
+    const Src* __restrict__ src = static_cast<const Src*>(a.src);
+    Dst* __restrict__ dst = static_cast<Dst*>(a.dst);
+    const size_t total = (size_t)a.rows * pieces;
+    auto plane_val = [](unsigned short p0, unsigned short p1, unsigned short p2) {
+        const float f0 = __builtin_bit_cast(float, (unsigned)p0 << 16), f1 = __builtin_bit_cast(float, (unsigned)p1 << 16),
+                    f2 = __builtin_bit_cast(float, (unsigned)p2 << 16);
+        return (f0 + f1) + f2;
+    };
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int p = (int)(i % pieces);
+        const int r = (int)(i / pieces);
+        const int c0 = p * 8;
+        int sr = r;
+        if (a.half > 0) {
+            const int jj = r % a.half;
+            sr = 2 * a.blk * (jj / a.blk) + jj % a.blk + (r >= a.half ? a.blk : 0);
+        }
+        sr += a.row_off;
+        const Src* sp = src + (size_t)sr * a.ld + c0;
+        float v[8];
+        if constexpr (VEC) {
+            if constexpr (X3) {
+                const hx8<unsigned short> p0 = *reinterpret_cast<const hx8<unsigned short>*>(sp),
+                                          p1 = *reinterpret_cast<const hx8<unsigned short>*>(sp + a.plane),
+                                          p2 = *reinterpret_cast<const hx8<unsigned short>*>(sp + 2 * a.plane);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = plane_val(p0[k], p1[k], p2[k]);
+            } else if constexpr (sizeof(Src) == 4) {
+                const f32x4 lo = *reinterpret_cast<const f32x4*>(sp), hi = *reinterpret_cast<const f32x4*>(sp + 4);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { v[k] = lo[k]; v[4 + k] = hi[k]; }
+            } else {
+                const hx8<Src> q = *reinterpret_cast<const hx8<Src>*>(sp);
+#pragma unroll
+                for (int k = 0; k < 8; ++k) v[k] = (float)q[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                v[k] = 0.f;
+                if (c0 + k < a.in) {
+                    if constexpr (X3) v[k] = plane_val(sp[k], sp[a.plane + k], sp[2 * a.plane + k]);
+                    else v[k] = (float)sp[k];
+                }
+            }
+        }
+        Dst* d = dst + (size_t)r * a.in + c0;
+        if constexpr (VEC) {
+            if constexpr (sizeof(Dst) == 4) {
+                *reinterpret_cast<f32x4*>(d) = f32x4{v[0], v[1], v[2], v[3]};
+                *reinterpret_cast<f32x4*>(d + 4) = f32x4{v[4], v[5], v[6], v[7]};
+            } else {
+                hx8<Dst> o;
+#pragma unroll
+                for (int k = 0; k < 8; ++k) o[k] = (Dst)v[k];
+                *reinterpret_cast<hx8<Dst>*>(d) = o;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) if (c0 + k < a.in) d[k] = (Dst)v[k];
+        }
+    }
+}
+void weight_gather(const WeightGatherArgs& a, hipStream_t s) {
+    if (a.rows <= 0 || a.in <= 0) return;
+    E2V_REQUIRE(a.src && a.dst && a.ld >= a.in && a.row_off >= 0 && a.blk > 0 && (a.half == 0 || (a.rows == 2 * a.half && a.half % a.blk == 0)) &&
+                    (!a.x3 || a.plane >= (long long)(a.row_off + a.rows) * a.ld),
+                E2V_EINVAL, "weight_gather: bad source geometry");
+    const int pieces = (a.in + 7) / 8;
+    const size_t esz = a.x3 || a.src_mode != H16_NONE ? 2 : 4;
+    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    // 16-byte accesses: whole pieces, every source row start (of every plane) and the destination aligned
+    const bool vec = a.in % 8 == 0 && ((size_t)a.ld * esz) % 16 == 0 && al16(static_cast<const char*>(a.src) + (size_t)a.row_off * a.ld * esz) &&
+                     (!a.x3 || a.plane % 8 == 0) && al16(a.dst);
+    const size_t total = (size_t)a.rows * pieces;
+    const dim3 g(grid_for(total)), b(256);
+    auto launch = [&](auto src_tag, auto dst_tag, auto x3_tag) {
+        using Src = decltype(src_tag);
+        using Dst = decltype(dst_tag);
+        constexpr bool X3 = decltype(x3_tag)::value;
+        if (vec) E2V_KLAUNCH((weight_gather_kernel<Src, Dst, X3, true>), g, b, 0, s, a, pieces);
+        else E2V_KLAUNCH((weight_gather_kernel<Src, Dst, X3, false>), g, b, 0, s, a, pieces);
+    };
+    auto with_dst = [&](auto src_tag, auto x3_tag) {
+        if (a.dst_mode == H16_NONE) launch(src_tag, float{}, x3_tag);
+        else h16_dispatch(a.dst_mode, [&](auto dst_tag) { launch(src_tag, dst_tag, x3_tag); });
+    };
+    if (a.x3) with_dst((unsigned short)0, std::true_type{});
+    else if (a.src_mode == H16_NONE) with_dst(float{}, std::false_type{});
+    else h16_dispatch(a.src_mode, [&](auto src_tag) { with_dst(src_tag, std::false_type{}); });
 }
 
 // strided row copy with a storage-type change: out[r][c] = in[r][c] for c < cols, 0 for cols <= c < cols_out

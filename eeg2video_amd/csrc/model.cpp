@@ -741,6 +741,59 @@ void e2v_ctx::update_tensor(const std::string& key, const void* data, e2v_dtype 
     E2V_HIP(hipGetLastError());
 }
 
+// =====================================================================================================
+// weight read-back (e2v_read_tensor): the inverse map of update_tensor
+// =====================================================================================================
+WeightGatherArgs e2v_ctx::read_source(const std::string& key, int form) {
+    auto bi = bind.find(key);
+    E2V_REQUIRE(bi != bind.end(), E2V_ESTATE, "no binding for " + key);
+    const WBind& b = bi->second;
+    E2V_REQUIRE(form == E2V_FORM_F32 || b.kind == WBind::LIN, E2V_EINVAL,
+                "e2v_read_tensor: only the weight of a linear keeps 16-bit copies or f32x3 planes with an inverse; read E2V_FORM_F32 of " + key);
+    E2V_REQUIRE(weight_forms(key) & form, E2V_ESTATE, "form not built for " + key + " (e2v_op_weight_forms says which are)");
+    WeightGatherArgs a;
+    a.rows = b.rows; a.in = b.in; a.row_off = b.row_off; a.half = b.half; a.blk = b.blk;
+    switch (b.kind) {
+        case WBind::RAW:
+            a.src = b.dst; a.ld = b.in; a.row_off = 0;
+            break;
+        case WBind::LIN: {
+            E2V_REQUIRE(b.lin && b.row_off + b.rows <= b.lin->out && b.in <= b.lin->in, E2V_ESTATE, "stale binding for " + key);
+            const LinW& l = *b.lin;
+            if (form == E2V_FORM_F32) { a.src = l.w; a.ld = l.in; }
+            else if (form == E2V_FORM_BF16) { a.src = l.w16; a.src_mode = H16_BF16; a.ld = l.in16; }
+            else if (form == E2V_FORM_F16) { a.src = l.w16h; a.src_mode = H16_FP16; a.ld = l.in16; }
+            else { a.src = l.w3; a.x3 = 1; a.ld = l.in; a.plane = (long long)l.out * l.in; }
+            break;
+        }
+        case WBind::CONV:
+            E2V_REQUIRE(b.conv && (size_t)b.conv->cout * b.conv->cin * 9 == (size_t)b.in, E2V_ESTATE, "stale binding for " + key);
+            a.src = b.conv->raw; a.ld = b.in;
+            break;
+    }
+    return a;
+}
+
+void e2v_ctx::read_tensor(const std::string& key, int form, void* out, e2v_dtype dtype, bool on_device, hipStream_t s) {
+    const WTensor& t = raw.at(key);
+    WeightGatherArgs a = read_source(key, form);
+    E2V_REQUIRE((size_t)a.rows * a.in == t.numel, E2V_ESTATE, "stale binding for " + key);
+    const size_t esz = dtype == E2V_F32 ? 4 : 2;
+    Act stage;
+    if (!on_device) stage = Act(pool, (int64_t)((t.numel * esz + 4095) / 4096), 1024);      // gathered here in `dtype`, then copied out
+    a.dst = on_device ? out : stage.p;
+    a.dst_mode = dtype == E2V_F32 ? H16_NONE : dtype == E2V_BF16 ? H16_BF16 : H16_FP16;
+    if (bind.at(key).kind == WBind::LIN || a.half > 0)
+        weight_gather(a, s);
+    else                                    // conv and RAW tensors with no row map: a type-converting copy
+        cvt_rows(a.src, a.ld, 0, a.dst, a.in, a.dst_mode, a.rows, a.in, a.in, s);
+    E2V_HIP(hipGetLastError());
+    if (!on_device) {
+        E2V_HIP(hipMemcpyAsync(out, stage.p, t.numel * esz, hipMemcpyDeviceToHost, s));
+        E2V_HIP(hipStreamSynchronize(s));
+    }
+}
+
 int e2v_ctx::weight_forms(const std::string& key) {
     auto bi = bind.find(key);
     E2V_REQUIRE(bi != bind.end(), E2V_ESTATE, "no binding for " + key);

@@ -212,6 +212,11 @@ struct e2v_ctx {
     // e2v_update_tensor: overwrite every existing form of `key` on stream s (data: [numel] of dtype, device or host)
     void update_tensor(const std::string& key, const void* data, e2v_dtype dtype, bool on_device, hipStream_t s);
     int weight_forms(const std::string& key);                    // e2v_op_weight_forms
+    // e2v_read_tensor: where `form` (one of E2V_FORM_F32 / BF16 / F16 / X3) of `key` is read from -- chosen from the binding as
+    // update_tensor chooses its destinations; throws for a form the binding kind cannot have or that is not built.  No HIP call.
+    e2v::WeightGatherArgs read_source(const std::string& key, int form);
+    // gather it into `out` ([numel] of dtype, device or host) in the torch layout, on stream s
+    void read_tensor(const std::string& key, int form, void* out, e2v_dtype dtype, bool on_device, hipStream_t s);
 
     float* dev_alloc(size_t floats);
     enum ConvForm { FORM_DIRECT32, FORM_BF16, FORM_WINO2, FORM_WINO4, FORM_BF16_UP2, FORM_F16, FORM_F16_UP2 };

@@ -164,6 +164,67 @@ class Engine:
             ev.record(stream)
             self._pending.append((ev, host_sources))
 
+    def _key_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        if getattr(self, "_shapes", None) is None:
+            self._shapes = self.expected_keys()
+        return self._shapes
+
+    def read_tensor(self, key: str, form: Optional[str] = None, dtype: torch.dtype = torch.float32,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """One tensor of a FINALIZED part, read back in the torch layout of the reference state dict (``e2v_read_tensor``): the inverse
+        of every re-layout finalize makes, on the current stream, with no synchronisation and no allocation inside the library.
+        ``form``: which stored form is read, a name of ``_lib.FORM_BITS`` -- ``None`` / ``'fp32'``: the fp32 values; for the weight of
+        a linear also ``'bf16'`` / ``'fp16'`` (that stored copy, widened exactly) and ``'x3'`` (the three planes summed: the fp32
+        weight exactly).  ``dtype``: float32, bfloat16 or float16 (round to nearest even).  Returns a device tensor; ``out``: a
+        contiguous tensor of that dtype and the key's shape to write instead -- any view of a device buffer, whatever its alignment,
+        or a CPU tensor (then the call returns when the copy has landed; it waits for the current stream only)."""
+        shapes = self._key_shapes()
+        if key not in shapes:
+            raise RuntimeError(f"unexpected state-dict key: {key}")
+        shape = shapes[key]
+        if dtype not in self._UPDATE_DTYPES:
+            raise ValueError(f"read_tensor writes float32, bfloat16 or float16, not {dtype}")
+        if form is not None and form not in _lib.FORM_BITS:
+            raise ValueError(f"form {form!r}: one of {sorted(_lib.FORM_BITS)}")
+        if out is None:
+            out = torch.empty(shape, device=self.device, dtype=dtype)
+        elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() \
+                or out.device not in (self.device, torch.device("cpu")):
+            raise ValueError(f"`out` has to be a contiguous {dtype} tensor of shape {shape} on {self.device} or on the host")
+        stream = torch.cuda.current_stream(self.device)
+        on_device = int(out.device == self.device)
+        if on_device:
+            out.record_stream(stream)
+        cshape = (C.c_int64 * len(shape))(*shape)
+        self._check(self.lib.e2v_read_tensor(self.ctx, key.encode(), _lib.FORM_BITS[form] if form else 0, C.c_void_p(out.data_ptr()),
+                                             self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
+        return out
+
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text."}
+
+    def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
+        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT``) as the device holds it NOW -- after any
+        ``update_state_dict`` --, an ``OrderedDict`` in ``expected_keys()`` order with ``prefix`` (the one ``load_state_dict`` adds:
+        ``'vae.'``, ``'semantic.'``, ``'text.'``) stripped from the names.  ``device``: ``'cuda'`` (tensors on the engine's device) or
+        ``'cpu'``."""
+        from collections import OrderedDict
+        dev = torch.device(device)
+        if dev.type == "cuda":
+            dev = self.device
+        elif dev.type != "cpu":
+            raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
+        own = self._PART_PREFIX.get(part, "")
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT) or prefix not in ("", own):
+            raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
+        foreign = tuple(self._PART_PREFIX.values())
+        out = OrderedDict()
+        for k, shape in self._key_shapes().items():
+            if not (k.startswith(own) if own else not k.startswith(foreign)):
+                continue
+            t = torch.empty(shape, device=dev, dtype=dtype)
+            out[k[len(prefix):]] = self.read_tensor(k, dtype=dtype, out=t)
+        return out
+
     def weight_forms(self, key: str) -> int:
         """Test aid (``e2v_op_weight_forms``): bit mask of the forms of ``key`` that exist on the device (``_lib.FORM_BITS``)."""
         mask = C.c_int(0)

@@ -103,6 +103,37 @@ class TuneAVideoPipeline:
             unet.to(torch_dtype)
         return cls(vae=vae, tokenizer=tokenizer, unet=unet, scheduler=scheduler)
 
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+        """``DiffusionPipeline.save_pretrained`` (``train_finetune_videodiffusion.py:343-350,355-362``: the pipeline built around the
+        trained modules is what the run leaves behind): ``model_index.json``, ``unet/`` and ``vae/`` with the weights the device holds
+        NOW (read back after any ``sync_from``), ``scheduler/scheduler_config.json`` from ``scheduler.config``, ``text_encoder/`` when
+        the pipeline has one that can save itself, ``tokenizer/`` through the tokenizer's own ``save_pretrained`` -- the directory
+        ``from_pretrained`` reads."""
+        import json
+        import os
+        os.makedirs(save_directory, exist_ok=True)
+        index = {"_class_name": type(self).__name__,
+                 "unet": ["eeg2video_amd", type(self.unet).__name__], "vae": ["eeg2video_amd", type(self.vae).__name__],
+                 "scheduler": ["eeg2video_amd", type(self.scheduler).__name__]}
+        self.unet.save_pretrained(os.path.join(save_directory, "unet"), safe_serialization=safe_serialization)
+        self.vae.save_pretrained(os.path.join(save_directory, "vae"), safe_serialization=safe_serialization)
+        os.makedirs(os.path.join(save_directory, "scheduler"), exist_ok=True)
+        sched = {"_class_name": type(self.scheduler).__name__}
+        sched.update({k: list(v) if isinstance(v, tuple) else v for k, v in self.scheduler.config.items()})
+        with open(os.path.join(save_directory, "scheduler", "scheduler_config.json"), "w") as f:
+            json.dump(sched, f, indent=2, sort_keys=True)
+            f.write("\n")
+        text_encoder = getattr(self, "text_encoder", None)
+        if text_encoder is not None and hasattr(text_encoder, "save_pretrained"):
+            text_encoder.save_pretrained(os.path.join(save_directory, "text_encoder"), safe_serialization=safe_serialization)
+            index["text_encoder"] = ["eeg2video_amd" if getattr(text_encoder, "native", False) else "transformers", type(text_encoder).__name__]
+        if self.tokenizer is not None and hasattr(self.tokenizer, "save_pretrained"):
+            self.tokenizer.save_pretrained(os.path.join(save_directory, "tokenizer"))
+            index["tokenizer"] = ["transformers", type(self.tokenizer).__name__]
+        with open(os.path.join(save_directory, "model_index.json"), "w") as f:
+            json.dump(index, f, indent=2, sort_keys=True)
+            f.write("\n")
+
     # -- small API of DiffusionPipeline the callers use ------------------------------------------------
     @property
     def device(self):

@@ -13,7 +13,9 @@ conditioning enters in one of two ways:
   interface that the caller hands in.  Only the tokenizer (BPE) stays outside the library.
 
 From there on it is the EEG pipeline's loop (``pipeline.py``): the device loop for deterministic DDIM (``e2v_generate``) and for every
-other scheduler mirror (``e2v_generate_plan``), else stepped; ``pipe.last_loop`` says which.
+other scheduler mirror (``e2v_generate_plan``), else stepped; ``pipe.last_loop`` says which.  ``save_pretrained(dir)`` is the EEG
+pipeline's too (``train_finetune_videodiffusion.py:343-350``): it writes this pipeline's ``text_encoder/`` next to ``unet/``, ``vae/``
+and ``scheduler/``, which is the directory ``from_pretrained`` above builds the whole pipeline from.
 """
 from __future__ import annotations
 

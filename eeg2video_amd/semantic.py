@@ -45,6 +45,35 @@ class CLIP:
         self.engine.update_state_dict({k: v for k, v in named_tensors(source, only_trainable) if k in spec}, prefix="semantic.")
         return self
 
+    def state_dict(self, dtype: torch.dtype = torch.float32, device="cuda"):
+        """What the built predictor holds now, read back from the device (``Engine.state_dict``): the keys and shapes
+        ``train_semantic_predictor.py:146-147`` saves -- the first layer without the K padding the kernels run it with."""
+        from .unet import _model_state_dict
+        return _model_state_dict(self.engine, Engine.SEMANTIC, "semantic.", self.state_dict_spec(), dtype, device)
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+        """``config.json`` (the ``SemanticConfig`` fields and the embedding width) + ``diffusion_pytorch_model.safetensors``
+        (``safe_serialization=False``: the ``.bin``), the directory ``from_pretrained`` below reads."""
+        from .unet import _save_checkpoint
+        config = {"_class_name": type(self).__name__, "in_features": self.scfg.in_features, "hidden": self.scfg.hidden,
+                  "tokens": self.scfg.tokens, "cross_attention_dim": self.engine.unet_cfg.cross_attention_dim}
+        _save_checkpoint(save_directory, config, self.state_dict(device="cpu"), safe_serialization)
+
+    @classmethod
+    def from_pretrained(cls, pretrained_model_path: str, *, engine: Optional[Engine] = None, device: int = 0):
+        """A directory written by ``save_pretrained`` (local only)."""
+        import json
+        import os
+        from .unet import _load_checkpoint
+        with open(os.path.join(pretrained_model_path, "config.json")) as f:
+            cj = json.load(f)
+        config = SemanticConfig(in_features=cj["in_features"], hidden=cj["hidden"], tokens=cj["tokens"])
+        if engine is None:
+            from .weights import UNetConfig
+            engine = Engine(UNetConfig(cross_attention_dim=cj.get("cross_attention_dim", UNetConfig.cross_attention_dim)),
+                            device=device, sem_cfg=config)
+        return cls(config, engine=engine).load_state_dict(_load_checkpoint(pretrained_model_path))
+
     def init_synthetic(self, seed: int = 44, mode: str = "reference_init"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
 

@@ -99,6 +99,20 @@ class CLIPTextModel:
         self.engine.finalize(Engine.TEXT)
         return self
 
+    def state_dict(self, dtype: torch.dtype = torch.float32, device="cuda"):
+        """What the built text encoder holds, read back from the device (``Engine.state_dict``) under the checkpoint's names
+        (``text_model.``...); q / k / v projections come out of the fused matrix and bias."""
+        from .unet import _model_state_dict
+        return _model_state_dict(self.engine, Engine.TEXT, "text.", self.state_dict_spec(), dtype, device)
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+        """``config.json`` as ``config_from_dir`` reads it + ``model.safetensors`` (``safe_serialization=False``:
+        ``pytorch_model.bin``)."""
+        from .unet import _save_checkpoint
+        config = {"_class_name": type(self).__name__, "architectures": [type(self).__name__], "model_type": "clip_text_model"}
+        config.update(self.config)
+        _save_checkpoint(save_directory, config, self.state_dict(device="cpu"), safe_serialization, SAFETENSORS_NAME, WEIGHTS_NAME)
+
     def init_synthetic(self, seed: int = 44, mode: str = "perturbed"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
 

@@ -33,6 +33,31 @@ def _load_checkpoint(path: str, safetensors_name: str = SAFETENSORS_NAME, weight
     return torch.load(os.path.join(path, weights_name), map_location="cpu", weights_only=True)
 
 
+def _model_state_dict(engine: Engine, part: int, prefix: str, spec, dtype=torch.float32, device="cuda"):
+    """``Engine.state_dict`` of one part in the order of the model's own spec."""
+    from collections import OrderedDict
+    sd = engine.state_dict(part, prefix=prefix, dtype=dtype, device=device)
+    missing = [k for k in spec if k not in sd]
+    if missing or len(sd) != len(spec):
+        raise RuntimeError(f"the engine's key scheme and the model's spec disagree: {missing[:4]}...")
+    return OrderedDict((k, sd[k]) for k in spec)
+
+
+def _save_checkpoint(save_directory: str, config: dict, state_dict, safe_serialization: bool = True,
+                     safetensors_name: str = SAFETENSORS_NAME, weights_name: str = WEIGHTS_NAME) -> None:
+    """``config.json`` + the weights file of a diffusers / transformers model directory, as ``_load_checkpoint`` reads them back."""
+    os.makedirs(save_directory, exist_ok=True)
+    with open(os.path.join(save_directory, "config.json"), "w") as f:
+        json.dump(config, f, indent=2, sort_keys=True)
+        f.write("\n")
+    sd = {k: v.detach().cpu().contiguous() for k, v in state_dict.items()}
+    if safe_serialization:
+        from safetensors.torch import save_file
+        save_file(sd, os.path.join(save_directory, safetensors_name), metadata={"format": "pt"})
+    else:
+        torch.save(sd, os.path.join(save_directory, weights_name))
+
+
 class FrozenDict(dict):
     def __getattr__(self, k):
         try:
@@ -256,6 +281,25 @@ class UNet3DConditionModel:
         sd = self._engine_layout(dict(named_tensors(source, only_trainable)), strict=False)
         self.engine.update_state_dict({k: v for k, v in sd.items() if k in spec})
         return self
+
+    def state_dict(self, dtype: torch.dtype = torch.float32, device="cuda"):
+        """What the built model holds NOW (``Engine.state_dict``: read back from the device, after any ``sync_from``), under the
+        reference's names and in the reference's shapes -- ``_engine_layout`` undone: with ``use_linear_projection`` the ``proj_in`` /
+        ``proj_out`` weights come back 2-D -- so ``torch_module.load_state_dict(hip_unet.state_dict())`` works (``unet.py:445``)."""
+        sd = _model_state_dict(self.engine, Engine.UNET, "", self.state_dict_spec(), dtype, device)
+        if self.use_linear_projection:
+            for k, v in sd.items():
+                if k.endswith(".proj_in.weight") or k.endswith(".proj_out.weight"):
+                    sd[k] = v.reshape(v.shape[0], v.shape[1])
+        return sd
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+        """``ModelMixin.save_pretrained`` (``train_finetune_videodiffusion.py:343-350`` through the pipeline): ``config.json`` as
+        ``from_pretrained`` reads it and the weights as ``diffusion_pytorch_model.safetensors`` (``safe_serialization=False``: the
+        ``.bin``; a ``.safetensors`` file already in the directory would still be the one ``from_pretrained`` prefers)."""
+        config = {"_class_name": type(self).__name__}
+        config.update({k: list(v) if isinstance(v, tuple) else v for k, v in self.config.items()})
+        _save_checkpoint(save_directory, config, self.state_dict(device="cpu"), safe_serialization)
 
     def init_synthetic(self, seed: int = 42, mode: str = "reference_init"):
         """Random-init weights of this architecture from the counter RNG (no checkpoints offline)."""

@@ -108,6 +108,23 @@ class AutoencoderKL:
         self.engine.update_state_dict({k: v for k, v in named_tensors(source, only_trainable) if k in spec}, prefix="vae.")
         return self
 
+    def state_dict(self, dtype: torch.dtype = torch.float32, device="cuda"):
+        """What the built VAE holds now, read back from the device (``Engine.state_dict``) under diffusers' names and shapes."""
+        from .unet import _model_state_dict
+        return _model_state_dict(self.engine, Engine.VAE, "vae.", self.state_dict_spec(), dtype, device)
+
+    def save_pretrained(self, save_directory: str, safe_serialization: bool = True):
+        """``config.json`` as ``config_from_dir`` reads it + ``diffusion_pytorch_model.safetensors`` (``safe_serialization=False``:
+        the ``.bin``)."""
+        from .unet import _save_checkpoint
+        c = self.vcfg
+        config = {"_class_name": type(self).__name__, "in_channels": c.in_channels, "out_channels": c.out_channels,
+                  "latent_channels": c.latent_channels, "block_out_channels": list(c.block_out_channels),
+                  "layers_per_block": c.layers_per_block, "norm_num_groups": c.norm_num_groups, "scaling_factor": c.scaling_factor,
+                  "down_block_types": ["DownEncoderBlock2D"] * len(c.block_out_channels),
+                  "up_block_types": ["UpDecoderBlock2D"] * len(c.block_out_channels), "act_fn": "silu"}
+        _save_checkpoint(save_directory, config, self.state_dict(device="cpu"), safe_serialization)
+
     def init_synthetic(self, seed: int = 43, mode: str = "reference_init"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
 

@@ -141,6 +141,46 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
+/* The stored forms of one tensor of a finalized part, one bit each (the mask e2v_op_weight_forms reports; the `form` of e2v_read_tensor). */
+enum {
+    E2V_FORM_F32 = 1 << 0,
+    E2V_FORM_BF16 = 1 << 1,
+    E2V_FORM_F16 = 1 << 2,
+    E2V_FORM_X3 = 1 << 3,              /* f32x3 planes of a linear */
+    E2V_FORM_CONV_DIRECT32 = 1 << 4,   /* fp32 direct implicit-GEMM layout */
+    E2V_FORM_WINO2 = 1 << 5,           /* Winograd F(2x2,3x3) domain */
+    E2V_FORM_WINO4 = 1 << 6,           /* Winograd F(4x4,3x3) domain */
+    E2V_FORM_BF16_UP2 = 1 << 7,        /* sub-pixel form of resize + conv, bf16 */
+    E2V_FORM_F16_UP2 = 1 << 8,         /* the same as IEEE half */
+    E2V_FORM_WINO2_X3 = 1 << 9,        /* f32x3 planes of the F(2x2) form */
+    E2V_FORM_WINO4_X3 = 1 << 10        /* f32x3 planes of the F(4x4) form */
+};
+/* replaces: model.state_dict() / pipeline.save_pretrained(output_dir) on the live modules (unet.py:445 walks model.state_dict();
+ * train_semantic_predictor.py:146-147 saves it; train_finetune_videodiffusion.py:343-350,355-362 builds a pipeline around the trained
+ * modules and saves it).  The counterpart of e2v_update_tensor: after an update with on_device = 1 the device holds the only current
+ * copy of a weight, and this call reads it back.
+ * Writes one tensor of a FINALIZED part to `out` in the torch layout of the reference state dict -- the inverse of every re-layout
+ * finalize makes: a 3x3 conv [Cout,Cin,3,3] from the torch-layout weight the context keeps, a row range of a fused QKV / KV matrix
+ * (and of its fused bias), the GEGLU row interleave of ff.net.0.proj undone, the K-padded first layer of the Semantic Predictor
+ * without its padding columns, plain linears, 1x1 convs, norm affines and embeddings as they are.
+ * `key`: any expected key (UNet, "vae.", "semantic.", "text.": reading a text tensor is allowed, only updating one is refused).
+ * `form`: which stored form is read -- 0 or E2V_FORM_F32: the fp32 values (every tensor has them).  For the weight of a linear
+ * (or 1x1 conv) also E2V_FORM_BF16 / E2V_FORM_F16: that stored 16-bit copy, widened exactly, and E2V_FORM_X3: (p0 + p1) + p2 of the
+ * three planes in fp32, which is the fp32 weight exactly.  A form e2v_op_weight_forms does not report for the key: E2V_ESTATE ("form
+ * not built").  More than one bit, an unknown bit, a form with no index-map inverse (the conv kernel layouts, the Winograd domains,
+ * the UP2 forms), or a 16-bit / X3 form of anything but a linear's weight: E2V_EINVAL.
+ * `dtype`: the type of `out`, E2V_F32, E2V_BF16 or E2V_F16 (round to nearest even, the casts finalize uses; E2V_F32X3: E2V_EINVAL).
+ * `shape` / `ndim`: the key's expected shape, else E2V_ENOWEIGHT as e2v_load_tensor.
+ * on_device = 1: `out` is a device pointer of ANY alignment on the ctx's device; exactly numel elements are written, on `stream`:
+ * a read queued before an update sees the old values, one queued after it the new.  No synchronisation and no allocation at all.
+ * on_device = 0: `out` is a host pointer; the tensor is gathered into a workspace-pool block in `dtype` and copied out, and the call
+ * returns when the copy has landed.  It waits for `stream` ONLY: work queued on other streams is neither waited for nor ordered.
+ * No allocation once the staging block of that size is cached (e2v_device_bytes does not move).
+ * The argument checks come before anything is enqueued and before the host-only check: null ctx / key / out / shape E2V_EINVAL,
+ * unknown key E2V_ENOWEIGHT, part not finalized E2V_ESTATE; a well-formed call on a host-only context: E2V_ESTATE. */
+e2v_status e2v_read_tensor(e2v_ctx* ctx, const char* key, int form, void* out, e2v_dtype dtype, int on_device,
+                           const int64_t* shape, int ndim, e2v_stream stream);
+
 /* ---- schedule (host, integer-exact) ---------------------------------------------------------------- */
 /* replaces: DDIMScheduler.set_timesteps (call site pipeline_tuneeeg2video.py:287-288).
  * t_i = (i * (T // n))[::-1] + steps_offset, int64; n=50 -> 981, 961, ..., 21, 1. */

@@ -131,20 +131,8 @@ e2v_status e2v_op_last_dispatch(char* buf, int64_t cap);
  * mode builds on first use, the three bf16 planes of the f32x3 mode.  A 3x3 conv weight: F32 = the torch-layout weight, BF16 / F16 = the
  * direct 16-bit layouts, and the remaining bits the layouts built on first use by the kernel that needs them.  Norm affines and biases
  * have the F32 bit only, and so does every tensor of the text encoder ("text." keys: fp32 in every compute mode).  The update tests use it to prove that an update ran against each form.  E2V_ENOWEIGHT for an unknown key,
- * E2V_ESTATE when the key's part is not finalized (and on a host-only context).  No reference counterpart. */
-enum {
-    E2V_FORM_F32 = 1 << 0,
-    E2V_FORM_BF16 = 1 << 1,
-    E2V_FORM_F16 = 1 << 2,
-    E2V_FORM_X3 = 1 << 3,              /* f32x3 planes of a linear */
-    E2V_FORM_CONV_DIRECT32 = 1 << 4,   /* fp32 direct implicit-GEMM layout */
-    E2V_FORM_WINO2 = 1 << 5,           /* Winograd F(2x2,3x3) domain */
-    E2V_FORM_WINO4 = 1 << 6,           /* Winograd F(4x4,3x3) domain */
-    E2V_FORM_BF16_UP2 = 1 << 7,        /* sub-pixel form of resize + conv, bf16 */
-    E2V_FORM_F16_UP2 = 1 << 8,         /* the same as IEEE half */
-    E2V_FORM_WINO2_X3 = 1 << 9,        /* f32x3 planes of the F(2x2) form */
-    E2V_FORM_WINO4_X3 = 1 << 10        /* f32x3 planes of the F(4x4) form */
-};
+ * E2V_ESTATE when the key's part is not finalized (and on a host-only context).  The bits are the E2V_FORM_* values of
+ * eeg2video_hip.h (e2v_read_tensor names one of them as its source).  No reference counterpart. */
 e2v_status e2v_op_weight_forms(e2v_ctx* ctx, const char* key, int* mask);
 
 /* Test aid for the bounds tests: the guarded workspace pool.  While the run-time switch "E2V_POOL_GUARD" (e2v_op_set_knob, or the
