@@ -1,5 +1,6 @@
 """Bit comparison of the fp32 GEMM epilogue between two builds of the library: every case of tests/test_hip_igemm_epilogue.py
-(fenced operands, ragged M / N / K, bias / residual / time-embedding / GEGLU epilogues), one SHA-256 of the output bytes per case.
+(fenced operands, ragged M / N / K, bias / residual / time-embedding / GEGLU epilogues) and of tests/test_hip_igemm_schedule.py (the
+mixed and wide tile schedules of the production graph), one SHA-256 of the output bytes per case.
 
     E2V_LIB_PATH=/path/to/other/libeeg2video_hip.so python tools/igemm_epilogue_bits.py a.json     # one build per process
     python tools/igemm_epilogue_bits.py b.json                                                      # the shipped build
@@ -13,11 +14,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def digests():
     sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
     import test_hip_igemm_epilogue as t
+    import test_hip_igemm_schedule as ts
     eng = t.make_engine()
     out = {}
-    for name, run in t.cases():
-        y, _ = run(eng)
-        out[name] = hashlib.sha256(y.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+    for module in (t, ts):
+        for name, run in module.cases():
+            y, _ = run(eng)
+            out[name] = hashlib.sha256(y.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
     return out
 
 
