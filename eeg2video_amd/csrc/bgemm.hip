@@ -454,35 +454,6 @@ __device__ __forceinline__ void bgemm_tile(const IgemmArgs& p, const int rbg, co
 // slot s takes tiles s, s + slots, ...).  The LDS ring never stops: the last k-stage of tile i issues stage 0 of tile i + 1
 // (whose gather table was built while tile i was being multiplied), the epilogue of tile i stages its accumulators through the
 // stage buffer it has just consumed while that DMA is in flight, and its stores are never waited for.
-struct BgTile {
-    int rbg, n0, wide, valid;
-};
-
-__device__ __forceinline__ BgTile bgemm_decode(const IgemmArgs& p, const int x, const int loc) {
-    BgTile t{0, 0, 0, 0};
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        t.rbg = rb_lo + r;
-        t.wide = j < p.w1;
-        t.n0 = t.wide ? j * 128 : p.w1 * 128 + (j - p.w1) * 64;
-        t.valid = 1;
-    } else {
-        const int q = loc - n1;
-        if (q < tail * p.s2) {
-            const int r = q / p.s2;
-            t.rbg = rb_lo + (nrb - tail) + r;
-            t.n0 = (q - r * p.s2) * 64;
-            t.valid = 1;
-        }
-    }
-    return t;
-}
-
 template <typename H, int BM, int WGM, bool LIN>
 __device__ __forceinline__ void bgemm_pers_body(const IgemmArgs& p, char* smem, const int x, const int slot, const int nslots) {
     constexpr int BKE = 64, ROWB = 128, WGN = 2;
@@ -536,7 +507,7 @@ __device__ __forceinline__ void bgemm_pers_body(const IgemmArgs& p, char* smem, 
 
     // gather table of tile t into table buffer `which` (3x3: all threads take part; the caller orders it against the first use
     // with a barrier)
-    auto build_table = [&](const BgTile t, const int which) {
+    auto build_table = [&](const Tile t, const int which) {
         if constexpr (!LIN) {
             const int z = p.batch > 1 ? t.rbg / p.nbm_per : 0;
             const int bm = t.rbg - z * p.nbm_per;
@@ -570,7 +541,7 @@ __device__ __forceinline__ void bgemm_pers_body(const IgemmArgs& p, char* smem, 
         }
     };
     // point the issue side at tile t, whose table sits in buffer `which`
-    auto aim = [&](const BgTile t, const int which) {
+    auto aim = [&](const Tile t, const int which) {
         const int z = p.batch > 1 ? t.rbg / p.nbm_per : 0;
         const int bm = t.rbg - z * p.nbm_per;
         const H* a0 = reinterpret_cast<const H*>(p.a0) + (size_t)z * p.sa0;
@@ -676,7 +647,7 @@ __device__ __forceinline__ void bgemm_pers_body(const IgemmArgs& p, char* smem, 
     const char* const Afr = smem + (wm * WM + fr) * ROWB;
 
     int loc = slot;
-    BgTile cur = bgemm_decode(p, x, loc);
+    Tile cur = tile_decode(tile_sched(p), x, loc);
     if (!cur.valid) return;
     build_table(cur, 0);
     aim(cur, 0);
@@ -689,7 +660,7 @@ __device__ __forceinline__ void bgemm_pers_body(const IgemmArgs& p, char* smem, 
 
     for (;;) {
         loc += nslots;
-        const BgTile nxt = bgemm_decode(p, x, loc);
+        const Tile nxt = tile_decode(tile_sched(p), x, loc);
         if constexpr (!LIN) {
             // the next tile's table, now: the k-loop's barriers (or the one here, for a single-stage tile) put it in front of
             // its first use at this tile's last stage
@@ -835,21 +806,22 @@ __global__ __launch_bounds__(256, 2) void bgemm_pers_kernel(const IgemmArgs p) {
 template <typename H, bool LIN>
 __global__ __launch_bounds__(256) void bgemm_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_bg[];
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
+    // tile_decode() written out, the 128x64 tile called from the s1 and from the tail branch: with the single call behind
+    // tile_decode() the linear instances spilled more SGPRs (4 -> 8), so this kernel keeps this form.  Same rule, same order.
+    const int loc = blockIdx.x >> 3;
+    const RowBlocks rb = xcd_row_blocks(blockIdx.x & 7, p.nbm);
+    const int tail = min(rb.n, p.tail_rb);
     const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
+    const int n1 = (rb.n - tail) * per1;
     if (loc < n1) {
         const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN>(p, rb_lo + r, j * 128, smem_bg);
-        else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_bg);
+        if (j < p.w1) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN>(p, rb.lo + r, j * 128, smem_bg);
+        else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN>(p, rb.lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_bg);
     } else {
         const int t = loc - n1;
         if (t >= tail * p.s2) return;
         const int r = t / p.s2;
-        bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_bg);
+        bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN>(p, rb.lo + (rb.n - tail) + r, (t - r * p.s2) * 64, smem_bg);
     }
 }
 
@@ -880,14 +852,14 @@ __global__ __launch_bounds__(256) void bgemm_splitk_kernel(const IgemmArgs p) {
     q.w16 = reinterpret_cast<const char*>(p.w16) + kfirst * 2;
     q.out = p.sk_ws + (size_t)run * p.M * p.N; q.ldc = p.N; q.out_f32 = 1;
     q.bias = nullptr; q.rowbias = nullptr; q.resid = nullptr; q.alpha = 1.f; q.relu = 0;
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
+    // (split-K has no tail, whatever the plan's tail_rb: the cut-down decode -- through tile_decode() every instance came out larger)
+    const int loc = blockIdx.x >> 3;
+    const RowBlocks rb = xcd_row_blocks(blockIdx.x & 7, p.nbm);
     const int per_rb = p.w1 + p.s1;
-    if (loc >= nrb * per_rb) return;
+    if (loc >= rb.n * per_rb) return;
     const int r = loc / per_rb, j = loc - r * per_rb;
-    if (j < p.w1) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN, NST, 1>(q, rb_lo + r, j * 128, smem_sk);
-    else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN, NST, 1>(q, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_sk);
+    if (j < p.w1) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN, NST, 1>(q, rb.lo + r, j * 128, smem_sk);
+    else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN, NST, 1>(q, rb.lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_sk);
 }
 
 // out[m][n .. n+3] = epilogue(sum over runs, run 0 first); one thread = four consecutive columns of a row
@@ -936,22 +908,10 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const IgemmArgs p, c
 template <typename H, bool LIN>
 __global__ __launch_bounds__(256) void bgemm_s3_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_bgs3[];
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN, 3, 2>(p, rb_lo + r, j * 128, smem_bgs3);
-        else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN, 3, 2>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_bgs3);
-    } else {
-        const int t = loc - n1;
-        if (t >= tail * p.s2) return;
-        const int r = t / p.s2;
-        bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN, 3, 2>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_bgs3);
-    }
+    const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
+    if (!t.valid) return;
+    if (t.wide) bgemm_tile<H, 128, 128, 2, 2, 128 * 128 * 2, LIN, 3, 2>(p, t.rbg, t.n0, smem_bgs3);
+    else bgemm_tile<H, 128, 64, 2, 2, 128 * 128 * 2, LIN, 3, 2>(p, t.rbg, t.n0, smem_bgs3);
 }
 
 // 256-row tiles: 8 waves (4 x 2, the same 64 x 64 wave tile), 256 x 128 and 256 x 64, 48 KB stages, one workgroup per CU.
@@ -960,22 +920,10 @@ template <typename H, bool LIN>
 __global__ __launch_bounds__(512) void bgemm256_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_bg256[];
     constexpr int ST = (256 + 128) * 128;
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1) bgemm_tile<H, 256, 128, 4, 2, ST, LIN>(p, rb_lo + r, j * 128, smem_bg256);
-        else bgemm_tile<H, 256, 64, 4, 2, ST, LIN>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_bg256);
-    } else {
-        const int t = loc - n1;
-        if (t >= tail * p.s2) return;
-        const int r = t / p.s2;
-        bgemm_tile<H, 256, 64, 4, 2, ST, LIN>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_bg256);
-    }
+    const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
+    if (!t.valid) return;
+    if (t.wide) bgemm_tile<H, 256, 128, 4, 2, ST, LIN>(p, t.rbg, t.n0, smem_bg256);
+    else bgemm_tile<H, 256, 64, 4, 2, ST, LIN>(p, t.rbg, t.n0, smem_bg256);
 }
 #endif
 
@@ -989,22 +937,10 @@ template <typename H, bool LIN>
 __global__ __launch_bounds__(512) void bgemm256s3_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_bg256s3[];
     constexpr int ST = (256 + 128) * 128;
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1) bgemm_tile<H, 256, 128, 4, 2, ST, LIN, 3>(p, rb_lo + r, j * 128, smem_bg256s3);
-        else bgemm_tile<H, 256, 64, 4, 2, ST, LIN, 3>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_bg256s3);
-    } else {
-        const int t = loc - n1;
-        if (t >= tail * p.s2) return;
-        const int r = t / p.s2;
-        bgemm_tile<H, 256, 64, 4, 2, ST, LIN, 3>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_bg256s3);
-    }
+    const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
+    if (!t.valid) return;
+    if (t.wide) bgemm_tile<H, 256, 128, 4, 2, ST, LIN, 3>(p, t.rbg, t.n0, smem_bg256s3);
+    else bgemm_tile<H, 256, 64, 4, 2, ST, LIN, 3>(p, t.rbg, t.n0, smem_bg256s3);
 }
 
 bool bgemm_use_256(const IgemmArgs& a) {
@@ -1036,12 +972,12 @@ bool bgemm_use_256(const IgemmArgs& a) {
 template <typename H, bool LIN>
 __global__ __launch_bounds__(256) void bgemm_n64_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_bg64[];
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    if (loc >= nrb * p.s2) return;
+    // (rb1 == 0, every row block is tail: the cut-down decode -- through tile_decode() the instances changed registers and grew)
+    const int loc = blockIdx.x >> 3;
+    const RowBlocks rb = xcd_row_blocks(blockIdx.x & 7, p.nbm);
+    if (loc >= rb.n * p.s2) return;
     const int r = loc / p.s2;
-    bgemm_tile<H, 128, 64, 2, 2, (128 + 64) * 128, LIN>(p, rb_lo + r, (loc - r * p.s2) * 64, smem_bg64);
+    bgemm_tile<H, 128, 64, 2, 2, (128 + 64) * 128, LIN>(p, rb.lo + r, (loc - r * p.s2) * 64, smem_bg64);
 }
 
 bool bgemm_all_n64(const IgemmArgs& a) {
@@ -1091,19 +1027,10 @@ void bgemm_splitk_launch(const IgemmArgs& a_in, hipStream_t s) {
     if (runs < 2 || !a.sk_ws) throw Error(E2V_EINVAL, "split-K launch without a plan (splitk_plan) or workspace");
     constexpr size_t smem = (size_t)2 * 128 * 128 * 2 + 9 * 128 * sizeof(unsigned);
     const bool lin = a.taps == 1;
-    const double K = (double)a.taps * (a.c0 + a.c1);
-    const double rows_in = a.taps == 1 ? (double)a.M : (double)a.M * a.Hs * a.Ws / ((double)a.Ho * a.Wo);
-    std::string pname = a.a_bf16 == H16_FP16 ? "igemm_fp16" : "igemm_bf16";
-    if (prof_detail())
-        pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) + " t" + std::to_string(a.taps) +
-                 (a.stride > 1 ? " s2" : "") + (a.upsample ? " up" : "") + (a.c1 ? " cat" : "");
-    ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K, 2.0 * rows_in * (a.c0 + a.c1) + 2.0 * a.N * K + (a.out_f32 ? 4.0 : 2.0) * a.M * a.N, s);
-    int per_xcd = 0;
-    for (int x = 0; x < 8; ++x) {
-        const int nrb = (int)(((long)(x + 1) * a.nbm) >> 3) - (int)(((long)x * a.nbm) >> 3);
-        per_xcd = nrb > per_xcd ? nrb : per_xcd;
-    }
-    const dim3 grid(8 * per_xcd * (a.w1 + a.s1), runs, 1);
+    if (a.batch != 1 || a.geglu) throw Error(E2V_EINVAL, "split-K launch: batch == 1 and no GEGLU (splitk_layout)");      // (the profile name and figures below rest on it)
+    const GemmProf pr = gemm_prof(nullptr, a, 2.0, 2.0, a.out_f32 ? 4.0 : 2.0);
+    ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
+    const dim3 grid(sched_grid(TileSched{a.nbm, a.w1, a.s1, a.s2, 0}), runs, 1);      // no tail: every row block is cut into w1 + s1 tiles
     // at most ~one round of workgroups: the three-stage ring (one workgroup per CU, two stages in flight); more: two co-resident
     // two-stage workgroups per CU cover each other's waits
     const bool s3 = (long)grid.x * runs <= 320 && (a.taps == 9 || lin);
@@ -1128,13 +1055,6 @@ void bgemm_launch(const IgemmArgs& a_in, int ntiles, hipStream_t s) {
     constexpr size_t smem = (size_t)2 * 128 * 128 * 2 + 9 * 128 * sizeof(unsigned);     // two stages of (128 + 128) rows + gather table
     static const int* const lean = E2V_AB_KNOB("E2V_BGEMM_LIN", 1);        // 0: linears through the gather path
     const bool lin = a.taps == 1 && *lean;
-    const double K = (double)a.taps * (a.c0 + a.c1);
-    const double rows_in = a.taps == 1 ? (double)a.M : (double)a.M * a.Hs * a.Ws / ((double)a.Ho * a.Wo);
-    std::string pname = a.a_bf16 == H16_FP16 ? "igemm_fp16" : "igemm_bf16";
-    if (prof_detail())
-        pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) + " t" + std::to_string(a.taps) +
-                 (a.stride > 1 ? " s2" : "") + (a.upsample ? " up" : "") + (a.c1 ? " cat" : "") + (a.geglu ? " geglu" : "") +
-                 (a.batch > 1 ? " b" + std::to_string(a.batch) : "");
 #ifdef E2V_ABLATE
     // timing experiments (make EXTRA=-DE2V_ABLATE): drop the output stores / zero the A loads -- the results are WRONG, so the
     // switch does not exist in the shipped build
@@ -1144,21 +1064,15 @@ void bgemm_launch(const IgemmArgs& a_in, int ntiles, hipStream_t s) {
 #else
     a.ablate = 0;
 #endif
-    const double out_b = a.out_f32 ? 4.0 : 2.0;
-    ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K * a.batch,
-                 a.batch * (2.0 * rows_in * (a.c0 + a.c1) + 2.0 * a.N * K + out_b * a.M * (a.geglu ? a.N / 2 : a.N)), s);
+    const GemmProf pr = gemm_prof(nullptr, a, 2.0, 2.0, a.out_f32 ? 4.0 : 2.0);
+    ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
     // E2V_BGEMM_PERS: 0 never, 1 where it measured faster (same-box A/B over every GEMM shape of a B = 32 pass, tools/shape_profile.py:
     // linears with a residual to read, K <= 2560: -3..-20 %; K = 320 and the K = 640 GEGLU without one: -4..-6 %; the wide
     // residual-free projections at K >= 640 and the 3x3 convs that are too small for 256-row tiles: +2..+6 %), 2 wherever it applies
     // launches of at most one round of 128-row tiles: the three-stage ring (bgemm_s3_kernel), one workgroup per CU
     static const int* const s3on = knob("E2V_BGEMM_S3_SMALL", 1);
     if (*s3on && !a.bm256 && (a.taps == 9 || lin)) {
-        long real = 0;                                                                // tiles the grid really holds
-        for (int x = 0; x < 8; ++x) {
-            const int nrb = (int)(((long)(x + 1) * a.nbm) >> 3) - (int)(((long)x * a.nbm) >> 3);
-            const int tail = nrb < a.tail_rb ? nrb : a.tail_rb;
-            real += (long)(nrb - tail) * (a.w1 + a.s1) + (long)tail * a.s2;
-        }
+        const long real = sched_real_tiles(tile_sched(a));                            // tiles the grid really holds
         const int nk = a.taps * ((a.c0 + 63) / 64 + (a.c1 + 63) / 64);
         // (same-process A/B at B = 1, profiles/r05_shape_ab_b1_s3_small.log: 40 tiles -- the 5x8 level -- 24 -> 18 us; 140 tiles +-0 .. +7 %:
         // from there on two co-resident two-stage workgroups per CU cover each other as well)
@@ -1199,13 +1113,8 @@ void bgemm_launch(const IgemmArgs& a_in, int ntiles, hipStream_t s) {
 #endif
     if (a.rb1 == 0 && !a.geglu) {          // every row block is cut into 128 x 64 tiles only
         constexpr size_t smem64 = (size_t)2 * (128 + 64) * 128 + 9 * 128 * sizeof(unsigned);
-        int nt = 0;
-        for (int x = 0; x < 8; ++x) {
-            const int nrb = (int)(((long)(x + 1) * a.nbm) >> 3) - (int)(((long)x * a.nbm) >> 3);
-            nt = nrb * a.s2 > nt ? nrb * a.s2 : nt;
-        }
         dry_tag(" -> bgemm_n64_kernel 128x64");
-        E2V_BG_LAUNCH(bgemm_n64_kernel, dim3(nt * 8, 1, 1), dim3(256), smem64);
+        E2V_BG_LAUNCH(bgemm_n64_kernel, dim3(ntiles, 1, 1), dim3(256), smem64);
         return;
     }
     dry_tag(" -> bgemm_kernel 128x128" + std::string(a.rb1 < a.nbm ? "+128x64" : ""));

@@ -71,9 +71,9 @@ __device__ __forceinline__ void t256_body(const IgemmArgs& p, const int vblock, 
     // (a partial launch -- the tail split of bgemm_t256_launch -- starts at row block rb0 and takes column tiles col_off + k col_stride)
     const int nct = p.nct_l ? p.nct_l : (p.N + BN - 1) / BN;
     const int x = vblock & 7, loc = vblock >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    if (loc >= (rb_hi - rb_lo) * nct) return;
-    const int bm = p.rb0 + rb_lo + loc / nct;
+    const RowBlocks rb = xcd_row_blocks(x, p.nbm);
+    if (loc >= rb.n * nct) return;
+    const int bm = p.rb0 + rb.lo + loc / nct;
     const int n0 = col_off + (loc % nct) * (p.col_stride ? p.col_stride : BN);
 
     const int steps0 = p.c0 >> 6, steps1 = p.c1 >> 6;        // channel counts are multiples of 64 (launcher)
@@ -624,8 +624,8 @@ __global__ __launch_bounds__(512) void bgemm_t256p_kernel(const IgemmArgs p) {
 
     const int nct = p.N / BN;
     const int x = blockIdx.x & 7, slot = blockIdx.x >> 3, nslots = gridDim.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int ntx = (rb_hi - rb_lo) * nct;                   // tiles of this XCD
+    const int rb_lo = xcd_row_blocks(x, p.nbm).lo;
+    const int ntx = xcd_row_blocks(x, p.nbm).n * nct;        // tiles of this XCD
     if (slot >= ntx) return;
     float* const lds_bias = reinterpret_cast<float*>(smem + 2 * (XBYTES + WBYTES));      // behind the operand buffers
     if constexpr (BLDS) {
@@ -1051,11 +1051,7 @@ static int t256_tile_cols(const IgemmArgs& a, const bool force = false) {      /
 static void t256_launch_part(IgemmArgs a, const int cols, const int rb0, const int nbm, const int col_off, const int col_stride, const int nct_l,
                              const int nt, const bool allow_persistent, hipStream_t s) {
     a.nbm = nbm; a.rb0 = rb0; a.col_off = col_off; a.col_stride = col_stride; a.nct_l = nct_l;
-    int per_xcd = 0;
-    for (int x = 0; x < 8; ++x) {
-        const int nrb = (int)(((long)(x + 1) * a.nbm) >> 3) - (int)(((long)x * a.nbm) >> 3);
-        per_xcd = nrb > per_xcd ? nrb : per_xcd;
-    }
+    const int per_xcd = longest_chunk(a.nbm);
     const int nct = nct_l ? nct_l : a.N / cols;
     const int grid = 8 * per_xcd * nct * (nt == 0 ? 2 : 1);
     const size_t smem = (size_t)2 * (256 + 64 * (nt == 0 ? 3 : nt)) * 128;
@@ -1136,16 +1132,9 @@ bool bgemm_t256_launch(const IgemmArgs& a_in, hipStream_t s) {
     const IgemmArgs& a = a_in;
     const int nbm = (a.M + 255) / 256;
     const int nct = a.N / cols;
-    const bool lin = a.taps == 1;
-    const double K = (double)a.taps * (a.c0 + a.c1);
-    const double rows_in = lin ? (double)a.M : (double)a.M * a.Hs * a.Ws / ((double)a.Ho * a.Wo);
-    std::string pname = a.a_bf16 == H16_FP16 ? "igemm_fp16" : "igemm_bf16";
-    if (prof_detail())
-        pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) + " t" + std::to_string(a.taps) +
-                 (a.stride > 1 ? " s2" : "") + (a.c1 ? " cat" : "") + (a.geglu ? " geglu" : "") + " T" + std::to_string(cols);
-    const double out_b = a.out_f32 ? 4.0 : 2.0;
-    ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K,
-                 2.0 * rows_in * (a.c0 + a.c1) + 2.0 * a.N * K + out_b * a.M * (a.geglu ? a.N / 2 : a.N), s);
+    if (a.batch != 1 || a.upsample) throw Error(E2V_EINVAL, "bgemm_t256: batch == 1 and no resize (t256_tile_cols)");     // (the profile name and figures below rest on it)
+    const GemmProf pr = gemm_prof(nullptr, a, 2.0, 2.0, a.out_f32 ? 4.0 : 2.0, " T" + std::to_string(cols));
+    ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
     // Tail split (E2V_BGEMM_T256_TAIL = 1; OFF by default).  256 CUs take whole tiles: a launch of 3.375 rounds (level 2 at B = 32: 216
     // row blocks x 4 column tiles) runs four, the last one three eighths full.  With the switch on, when the last round would be at
     // most half full its row blocks go into a second launch as 256 x 192 and 256 x 128 tiles (the same kernel body with NT = 3 / 2:

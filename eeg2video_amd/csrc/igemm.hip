@@ -23,6 +23,24 @@ namespace e2v {
 static constexpr int BK = 32;
 static constexpr int LDS_LD = 36;
 
+// Profile name, flops and bytes of a GEMM launch (kernels.h): shared by the launchers of this file, bgemm.hip and bgemm256.hip
+GemmProf gemm_prof(const char* cls, const IgemmArgs& a, const double in_b, const double w_b, const double out_b, const std::string& suffix,
+                   const bool terse) {
+    const double K = (double)a.taps * (a.c0 + a.c1);
+    const double rows_in = a.taps == 1 ? (double)a.M : (double)a.M * a.Hs * a.Ws / ((double)a.Ho * a.Wo);
+    GemmProf pr;
+    pr.name = cls ? cls : (a.a_bf16 == H16_FP16 ? "igemm_fp16" : "igemm_bf16");
+    if (prof_detail()) {
+        pr.name += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K);
+        if (!terse)
+            pr.name += " t" + std::to_string(a.taps) + (a.stride > 1 ? " s2" : "") + (a.upsample ? " up" : "") + (a.c1 ? " cat" : "");
+        pr.name += (a.geglu ? " geglu" : "") + (a.batch > 1 ? " b" + std::to_string(a.batch) : "") + suffix;
+    }
+    pr.flops = 2.0 * a.M * a.N * K * a.batch;
+    pr.bytes = a.batch * (in_b * rows_in * (a.c0 + a.c1) + w_b * a.N * K + out_b * a.M * (a.geglu ? a.N / 2 : a.N));
+    return pr;
+}
+
 // fp32 operands, v_mfma_f32_32x32x2_f32, 32 k per stage (the parity configuration).  (The bf16-activation mode has its own
 // kernels: bgemm.hip.)
 template <int BM, int BN, int WGM, int WGN, int ABL, int NBUF>
@@ -471,24 +489,10 @@ __device__ __forceinline__ void igemm_tile_x3(const IgemmArgs& p, const int rbg,
 template <int ABLX>
 __global__ __launch_bounds__(256) void igemm_x3_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) char smem_x3[];
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1)
-            igemm_tile_x3<128, 128, 2, 2, ABLX>(p, rb_lo + r, j * 128, smem_x3);
-        else
-            igemm_tile_x3<128, 64, 2, 2, ABLX>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_x3);
-    } else {
-        const int t = loc - n1;
-        if (t >= tail * p.s2) return;
-        const int r = t / p.s2;
-        igemm_tile_x3<128, 64, 2, 2, ABLX>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_x3);
-    }
+    const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
+    if (!t.valid) return;
+    if (t.wide) igemm_tile_x3<128, 128, 2, 2, ABLX>(p, t.rbg, t.n0, smem_x3);
+    else igemm_tile_x3<128, 64, 2, 2, ABLX>(p, t.rbg, t.n0, smem_x3);
 }
 
 static void launch_igemm_x3(const IgemmArgs& a, int ntiles, hipStream_t s) {
@@ -497,13 +501,8 @@ static void launch_igemm_x3(const IgemmArgs& a, int ntiles, hipStream_t s) {
     E2V_KATTR(&igemm_x3_kernel<0>, smem);
     E2V_KATTR(&igemm_x3_kernel<1>, smem);
     E2V_KATTR(&igemm_x3_kernel<2>, smem);
-    const double K = (double)(a.c0 + a.c1);
-    std::string pname = "igemm_f32x3";
-    if (prof_detail())
-        pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) +
-                 (a.geglu ? " geglu" : "") + (a.batch > 1 ? " b" + std::to_string(a.batch) : "");
-    ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K * a.batch,
-                 4.0 * a.batch * ((double)a.M * K + 1.5 * a.N * K + (double)a.M * (a.geglu ? a.N / 2 : a.N)), s);
+    const GemmProf pr = gemm_prof("igemm_f32x3", a, 4.0, 6.0, 4.0, "", true);       // (weights: three bf16 planes)
+    ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
     if (ablx == 1) E2V_KLAUNCH(igemm_x3_kernel<1>, dim3(ntiles, 1, 1), dim3(256), smem, s, a);
     else if (ablx == 2) E2V_KLAUNCH(igemm_x3_kernel<2>, dim3(ntiles, 1, 1), dim3(256), smem, s, a);
     else E2V_KLAUNCH(igemm_x3_kernel<0>, dim3(ntiles, 1, 1), dim3(256), smem, s, a);
@@ -642,54 +641,41 @@ __device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void igemm_k16_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem_k16[];
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
-    const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
-    if (loc < n1) {
-        const int r = loc / per1, j = loc - r * per1;
-        if (j < p.w1) igemm_tile_k16<128, 128, 2, 2>(p, rb_lo + r, j * 128, smem_k16);
-        else igemm_tile_k16<128, 64, 2, 2>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem_k16);
-    } else {
-        const int t = loc - n1;
-        if (t >= tail * p.s2) return;
-        const int r = t / p.s2;
-        igemm_tile_k16<128, 64, 2, 2>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem_k16);
-    }
+    const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
+    if (!t.valid) return;
+    if (t.wide) igemm_tile_k16<128, 128, 2, 2>(p, t.rbg, t.n0, smem_k16);
+    else igemm_tile_k16<128, 64, 2, 2>(p, t.rbg, t.n0, smem_k16);
 }
 
-// One launch runs a MIX of tile shapes (IgemmArgs::rb1/w1/s1/s2): row blocks [0, rb1) are cut into w1 tiles of
-// 128x128 followed by s1 tiles of 128x64 (N = 320 -> 2 + 1, no wasted columns); row blocks [rb1, nbm) are cut into s2
-// tiles of 128x64 only.  The launcher sizes rb1 so that the 128x128 part fills whole rounds of the 512 resident
-// tiles and the ragged last round runs as half-size tiles (L1: 5 rounds -> 4.5, L2: 3 -> 2.5).
-// XCD-aware order: the 8 XCDs are dealt blocks round-robin; each XCD gets a contiguous run of tiles (columns
-// fastest), so the column tiles that share one gathered A tile hit the same L2.
+// One launch runs a MIX of tile shapes, dealt to the XCDs chunk by chunk: the schedule of gemm_sched.h (tile_decode), which every
+// GEMM kernel of the library walks.  The launcher (plan_tiles) sizes the wide part so that the 128x128 tiles fill whole rounds of
+// the 512 resident tiles and the ragged last round runs as half-size tiles (L1: 5 rounds -> 4.5, L2: 3 -> 2.5).
 template <int ABL>
 __global__ __launch_bounds__(256) void igemm_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    // XCD x = blockIdx % 8 owns the contiguous row blocks [x*nbm/8, (x+1)*nbm/8); the last `tail` of them are cut
-    // into 128x64 tiles only, the others into w1 tiles of 128x128 + s1 of 128x64.  Every XCD therefore ends on
-    // half-size tiles (an even tail), and column tiles sharing one gathered A tile stay on one L2.
-    const int x = blockIdx.x & 7, loc = blockIdx.x >> 3;
-    const int rb_lo = (int)(((long)x * p.nbm) >> 3), rb_hi = (int)(((long)(x + 1) * p.nbm) >> 3);
-    const int nrb = rb_hi - rb_lo;
-    const int tail = min(nrb, p.tail_rb);
+    // tile_decode() written out, the 128x64 tile called from the s1 and from the tail branch: with the single call behind
+    // tile_decode() every instance of this kernel spilled more SGPRs (6 -> 14), so it keeps this form.  Same rule, same order.
+    const int loc = blockIdx.x >> 3;
+    const RowBlocks rb = xcd_row_blocks(blockIdx.x & 7, p.nbm);
+    const int tail = min(rb.n, p.tail_rb);
     const int per1 = p.w1 + p.s1;
-    const int n1 = (nrb - tail) * per1;
+    const int n1 = (rb.n - tail) * per1;
     if (loc < n1) {
         const int r = loc / per1, j = loc - r * per1;
         if (j < p.w1)
-            igemm_tile<128, 128, 2, 2, ABL, 2>(p, rb_lo + r, j * 128, smem);
+            igemm_tile<128, 128, 2, 2, ABL, 2>(p, rb.lo + r, j * 128, smem);
         else
-            igemm_tile<128, 64, 2, 2, ABL, 2>(p, rb_lo + r, p.w1 * 128 + (j - p.w1) * 64, smem);
+            igemm_tile<128, 64, 2, 2, ABL, 2>(p, rb.lo + r, p.w1 * 128 + (j - p.w1) * 64, smem);
     } else {
         const int t = loc - n1;
-        if (t >= tail * p.s2) return;                     // padding block of the 8 x max-chunk grid
+        if (t >= tail * p.s2) return;                     // padding block of the 8 x longest-chunk grid
         const int r = t / p.s2;
-        igemm_tile<128, 64, 2, 2, ABL, 2>(p, rb_lo + (nrb - tail) + r, (t - r * p.s2) * 64, smem);
+        igemm_tile<128, 64, 2, 2, ABL, 2>(p, rb.lo + (rb.n - tail) + r, (t - r * p.s2) * 64, smem);
     }
+}
+
+static std::string sched_suffix(const IgemmArgs& a) {
+    return " rb1=" + std::to_string(a.rb1) + " w" + std::to_string(a.w1) + " s" + std::to_string(a.s1);
 }
 
 template <int ABL>
@@ -697,40 +683,33 @@ static void launch_igemm(const IgemmArgs& a, int ntiles, const char* cls, hipStr
     constexpr size_t smem = (size_t)2 * (128 + 128) * LDS_LD * sizeof(float) + 9 * 128 * sizeof(unsigned);   // tiles + gather table
     E2V_KATTR(&igemm_kernel<ABL>, smem);
     dim3 grid(ntiles, 1, 1);
-    const double K = (double)a.taps * (a.c0 + a.c1);
-    const double rows_in = a.taps == 1 ? (double)a.M : (double)a.M * a.Hs * a.Ws / ((double)a.Ho * a.Wo);
-    std::string pname = cls;
-    if (prof_detail())
-        pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) + " t" +
-                 std::to_string(a.taps) + (a.stride > 1 ? " s2" : "") + (a.upsample ? " up" : "") + (a.c1 ? " cat" : "") +
-                 (a.geglu ? " geglu" : "") + (a.batch > 1 ? " b" + std::to_string(a.batch) : "") + " rb1=" +
-                 std::to_string(a.rb1) + " w" + std::to_string(a.w1) + " s" + std::to_string(a.s1);
-    ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K * a.batch,
-                 4.0 * a.batch * (rows_in * (a.c0 + a.c1) + (double)a.N * K + (double)a.M * (a.geglu ? a.N / 2 : a.N)), s);
+    const GemmProf pr = gemm_prof(cls, a, 4.0, 4.0, 4.0, sched_suffix(a));
+    ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
     dry_tag(" -> igemm_kernel 128x128x32");
     E2V_KLAUNCH((igemm_kernel<ABL>), grid, dim3(256), smem, s, a);
 }
 
-bool igemm_writes_rbsum(const IgemmArgs& a_in) {
-    if (!a_in.rbsum || !a_in.a_bf16 || a_in.M <= 0 || a_in.N <= 0) return false;
+// linear / 1x1: a 1 x M map without padding -- the same gather as the 3x3 case
+static IgemmArgs igemm_normalised(const IgemmArgs& a_in) {
     IgemmArgs a = a_in;
     if (a.taps == 1) {
         a.Ho = a.Hi = a.Hs = 1;
         a.Wo = a.Wi = a.Ws = a.M;
         a.stride = 1; a.pad = 0; a.upsample = 0;
     }
+    return a;
+}
+
+bool igemm_writes_rbsum(const IgemmArgs& a_in) {
+    if (!a_in.rbsum || !a_in.a_bf16 || a_in.M <= 0 || a_in.N <= 0) return false;
+    IgemmArgs a = igemm_normalised(a_in);
     a.ldw = a.ldw16;
     return bgemm_t256_writes_rbsum(a);
 }
 
 void igemm(const IgemmArgs& a_in, hipStream_t s) {
     if (a_in.M <= 0 || a_in.N <= 0) return;
-    IgemmArgs a = a_in;
-    if (a.taps == 1) {      // linear / 1x1: a 1 x M map without padding -- the same gather as the 3x3 case
-        a.Ho = a.Hi = a.Hs = 1;
-        a.Wo = a.Wi = a.Ws = a.M;
-        a.stride = 1; a.pad = 0; a.upsample = 0;
-    }
+    IgemmArgs a = igemm_normalised(a_in);
     // ---- tile schedule ----------------------------------------------------------------------------------
     static const int abl = [] { const char* e = std::getenv("E2V_IGEMM_ABLATE"); return e ? std::atoi(e) : 0; }();
     static const int sched = [] { const char* e = std::getenv("E2V_IGEMM_SCHED"); return e ? std::atoi(e) : 1; }();   // 0: no half-size tails
@@ -741,19 +720,7 @@ void igemm(const IgemmArgs& a_in, hipStream_t s) {
     const bool want_sk = a.a_bf16 && a.sk >= 2 && a.sk_ws && splitk_plan(a, a.sk) >= 2;
     const int BMrows = (a.a_bf16 && !want_sk && bgemm_use_256(a)) ? 256 : 128;
     a.bm256 = BMrows == 256 ? 1 : 0;
-    a.nbm_per = (a.M + BMrows - 1) / BMrows;
-    const int nbm = a.nbm_per * a.batch;                     // batch entries are just more row blocks (dealt to the XCDs together)
     static const int k16 = [] { const char* e = std::getenv("E2V_IGEMM_K16"); return e ? std::atoi(e) : 1; }();   // 0: the 32-k tile for everything
-    // The tail heuristics below size rounds of 512 tiles (2 workgroups per CU).  The 16-k tile runs 3 per CU, but sizing its
-    // rounds at 768 measured worse (level-2 linears 129 -> 116 TFLOP/s, UNet step 272.9 -> 278.9 ms): the third workgroup is
-    // better spent overlapping than being planned for.
-    const int slots = BMrows == 256 ? 256 : 512;
-    a.s2 = (a.N + 63) / 64;
-    a.w1 = a.N / 128;                                        // full 128-wide column tiles
-    const int rem = a.N - a.w1 * 128;
-    a.s1 = rem == 0 ? 0 : (rem <= 64 ? 1 : 0);
-    if (rem > 64) a.w1 += 1;                                 // 65..127 leftover columns: one more (masked) wide tile
-    a.rb1 = nbm;
     constexpr bool use_bf16 = false;
     // split-bf16 fp32 (see igemm_tile_x3): linears / Winograd GEMMs whose K is a multiple of 8 and whose weights were split
     const bool use_x3 = !use_bf16 && a.x3 && a.w3 && a.taps == 1 && !a.relu && a.c0 % 8 == 0 && a.c1 % 8 == 0 && a.ldw % 8 == 0 &&
@@ -766,63 +733,34 @@ void igemm(const IgemmArgs& a_in, hipStream_t s) {
         if (!want_sk && bgemm_t256_launch(a, s)) return;     // 256 x 256 / 256 x 320 deep-pipelined tiles (bgemm256.hip), by layer shape
     }
     const char* cls = "igemm_f32";
-    if (a.geglu) {                                           // the GEGLU epilogue pairs the two 32-column halves of a wave
-        a.w1 = (a.N + 127) / 128; a.s1 = 0;
-    } else if (a.w1 == 0) {                                  // N <= 64
-        a.rb1 = 0;
-    } else if (want_sk) {                                    // full-size tiles: the runs multiply the workgroup count
-    } else if (sched == 1) {
-        // per XCD: 64 resident tiles per round.  Keep whole rounds of full-size tiles; if what is left of the XCD's
-        // chunk is at most half a round, run it as half-size tiles (it then takes about half a round's time).
-        const double per_rb = a.w1 + 0.5 * a.s1;             // cost of one row block in 128x128 units
-        const int nrb = (nbm + 7) / 8;                       // row blocks of the largest chunk
-        const double units = per_rb * nrb;
-        const int xslots = slots / 8;
-        if (units * 8 < slots) {
-            a.rb1 = 0;                                       // less than one round: half-size tiles spread over more CUs
-        } else {
-            const int full = (int)std::floor(units / xslots);
-            const int wide_rb = (int)std::floor(full * xslots / per_rb);
-            const int tail = nrb - wide_rb;
-            if (tail > 0 && tail * per_rb <= 0.5 * xslots) a.rb1 = nbm - 8 * tail < 0 ? 0 : nbm - 8 * tail;
-        }
-    }
+    // The plan (gemm_sched.h) sizes rounds of 512 tiles (2 workgroups per CU; 256-row blocks: 256 tiles, one per CU).  The 16-k tile
+    // runs 3 per CU, but sizing its rounds at 768 measured worse (level-2 linears 129 -> 116 TFLOP/s, UNet step 272.9 -> 278.9 ms):
+    // the third workgroup is better spent overlapping than being planned for.
     // Launches of only a few rounds (the level-2 linears of a B = 8 pass: 1080 tiles of 128 x 128 on 768 slots = 1.4 rounds) leave the
     // chip part idle in their last round.  E2V_IGEMM_HALF_BELOW = r x 100 > 0: a launch of fewer than r rounds of full-size tiles runs
     // ENTIRELY as 128 x 64 tiles (twice the workgroups at half the work: the round granularity halves; same k order per output, so
     // bit-identical).  Same-process A/B: profiles/r04_shape_ab_fp32_tail.log.
     static const int* const half_below = E2V_AB_KNOB("E2V_IGEMM_HALF_BELOW", 0);      // (measured +-0: `make ab` only)
-    if (!a.a_bf16 && *half_below > 0 && !a.geglu && a.w1 > 0 && a.rb1 > 0) {
-        const double per_rb = a.w1 + 0.5 * a.s1;
-        const double rounds = per_rb * ((nbm + 7) / 8) / (slots / 8);
-        if (rounds * 100.0 < (double)*half_below) a.rb1 = 0;
-    }
-    if (a.a_bf16 && bgemm_all_n64(a)) a.rb1 = 0;
-    a.nbm = nbm;
-    a.tail_rb = (nbm - a.rb1 + 7) / 8;                       // per XCD chunk (rb1 == 0: every row block is "tail")
-    if (a.rb1 == 0) a.tail_rb = nbm;
-    int ntiles = 0;                                          // grid = 8 x the largest chunk's tile count
-    for (int x = 0; x < 8; ++x) {
-        const int nrb = (int)(((long)(x + 1) * nbm) >> 3) - (int)(((long)x * nbm) >> 3);
-        const int tail = nrb < a.tail_rb ? nrb : a.tail_rb;
-        const int t = (nrb - tail) * (a.w1 + a.s1) + tail * a.s2;
-        ntiles = t > ntiles ? t : ntiles;
-    }
-    ntiles *= 8;
+    PlanIn in{};
+    in.M = a.M; in.N = a.N; in.batch = a.batch; in.geglu = a.geglu != 0;
+    in.rows = BMrows; in.slots = BMrows == 256 ? 256 : 512;
+    in.all_narrow = a.a_bf16 && bgemm_all_n64(a);
+    in.full_only = want_sk;                                  // full-size tiles: the runs multiply the workgroup count
+    in.sched = sched;
+    in.half_below = a.a_bf16 ? 0 : *half_below;
+    const Plan plan = plan_tiles(in);
+    a.rb1 = plan.rb1; a.w1 = plan.w1; a.s1 = plan.s1; a.s2 = plan.s2;
+    a.nbm = plan.nbm; a.nbm_per = plan.nbm_per; a.tail_rb = plan.tail_rb;
+    const int ntiles = sched_grid(plan.sched());             // 8 x the longest chunk's tile count
     if (want_sk) { bgemm_splitk_launch(a, s); return; }
     if (a.a_bf16) { bgemm_launch(a, ntiles, s); return; }
     if (use_x3) { launch_igemm_x3(a, ntiles, s); return; }
     if (k16 && !use_bf16 && a.taps == 1 && abl == 0) {
         constexpr size_t smem16 = (size_t)2 * (128 + 128) * 20 * sizeof(float);   // 40 KB (epilogue staging: 4 x 32 x 68 floats = 34 KB)
         E2V_KATTR(&igemm_k16_kernel, smem16);
-        const double K = (double)(a.c0 + a.c1);
-        std::string pname = cls;
-        if (prof_detail())
-            pname += " M" + std::to_string(a.M) + " N" + std::to_string(a.N) + " K" + std::to_string((long)K) + " t1" + (a.c1 ? " cat" : "") +
-                     (a.geglu ? " geglu" : "") + (a.batch > 1 ? " b" + std::to_string(a.batch) : "") + " k16";
-        ProfScope ps(pname.c_str(), 2.0 * a.M * a.N * K * a.batch,
-                     4.0 * a.batch * ((double)a.M * K + (double)a.N * K + (double)a.M * (a.geglu ? a.N / 2 : a.N)), s);
-        dry_tag(" rb1=" + std::to_string(a.rb1) + " w" + std::to_string(a.w1) + " s" + std::to_string(a.s1) + " -> igemm_k16_kernel 128x128x16");
+        const GemmProf pr = gemm_prof(cls, a, 4.0, 4.0, 4.0, " k16");
+        ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);
+        dry_tag(sched_suffix(a) + " -> igemm_k16_kernel 128x128x16");
         E2V_KLAUNCH(igemm_k16_kernel, dim3(ntiles, 1, 1), dim3(256), smem16, s, a);
         return;
     }

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <string>
 
+#include "gemm_sched.h"
+
 namespace e2v {
 
 // ---------------------------------------------------------------------------------------
@@ -77,6 +79,17 @@ struct IgemmArgs {
 // The split a launch of `a` would take for a request of `want` runs: 0 = none (the launch is not eligible), else the number of runs
 // actually used (<= want: whole chunks, every run non-empty); the caller then provides sk_ws of that many [M][N] fp32 planes.
 int splitk_plan(const IgemmArgs& a, int want);
+// the tile schedule a launch carries (gemm_sched.h), as the kernels decode it
+E2V_SCHED_HD inline TileSched tile_sched(const IgemmArgs& p) { return TileSched{p.nbm, p.w1, p.s1, p.s2, p.tail_rb}; }
+// Profile name and algorithmic flops / bytes of a GEMM launch, for its ProfScope: `cls` (null: the class of the launch's 16-bit type,
+// "igemm_bf16" / "igemm_fp16") + (detailed profiles and dry runs) the shape tags " M.. N.. K.. t.. s2 up cat geglu b.." + `suffix`.
+// in_b / w_b / out_b: bytes per activation, weight and output element; `terse` leaves out the taps / stride / resize / concat tags
+// (the f32x3 launches never carried them).
+struct GemmProf {
+    std::string name;
+    double flops, bytes;
+};
+GemmProf gemm_prof(const char* cls, const IgemmArgs& a, double in_b, double w_b, double out_b, const std::string& suffix = "", bool terse = false);
 void igemm(const IgemmArgs& a, hipStream_t s);
 bool igemm_writes_rbsum(const IgemmArgs& a);       // will igemm(a) fill a.rbsum?  (same rules as the launch itself)
 // rows per lane pass of the canonical order: the staged epilogue of a 256 x 320 tile finishes 6 rows per pass, of a 256 x 256 tile 8

@@ -851,6 +851,11 @@ _P = {
     "geglu300x320x128": _lin("geglu300x320x128", 300, 320, 128, geglu=True),
     "geglu300x640x256": _lin("geglu300x640x256", 300, 640, 256, geglu=True),
     "lin552x320x192r": _lin("lin552x320x192r", 552, 320, 192, resid=True),
+    # 256-row tiles beyond the narrow schedule (sched256: what igemm_schedule.schedule(rows=256, slots=256) has to say of the launch):
+    # 178 row blocks in unequal chunks, the last two of each chunk as 128x64 tiles only; 254 row blocks, 128x128 + 128x64 everywhere
+    "lin45500x64x192r": dict(_lin("lin45500x64x192r", 45500, 64, 192, resid=True),
+                             sched256=dict(kind="mixed", nbm=178, rb1=162, w1=1, s1=1, s2=3, tail_rb=2, chunks=(22, 22, 22, 23, 22, 22, 22, 23))),
+    "lin65000x64x192r": dict(_lin("lin65000x64x192r", 65000, 64, 192, resid=True), sched256=dict(kind="wide", nbm=254, rb1=254, w1=1, s1=1, s2=3, tail_rb=0)),
     "lin513x640x320r": _lin("lin513x640x320r", 513, 640, 320, resid=True),
     "lin513x640x320": _lin("lin513x640x320", 513, 640, 320),
     "lin300x640x512r": _lin("lin300x640x512r", 300, 640, 512, resid=True),
@@ -898,7 +903,8 @@ GEMM_CASES = (
     _form("pers", {"E2V_BGEMM_S3_SMALL": 0, "E2V_BGEMM_PERS": 2},
           [("lin300x320x192r", _PERS), ("lin8300x64x1024r", _PERS), ("geglu300x320x128", _PERS), ("conv64to128_3x9x16_rps144r", _PERS),
            ("conv64to128_2x7x5_rps35r", _N64, _PERS)]) +          # time-embedding rows of more than two samples under one tile: refused
-    _form("256s3", {"E2V_BGEMM_256": 2, "E2V_BGEMM_T256": 0}, [("lin552x320x192r", "bgemm256s3_kernel"), ("conv64to128_3x8x23_rps184r", "bgemm256s3_kernel")]) +
+    _form("256s3", {"E2V_BGEMM_256": 2, "E2V_BGEMM_T256": 0}, [("lin552x320x192r", "bgemm256s3_kernel"), ("conv64to128_3x8x23_rps184r", "bgemm256s3_kernel"),
+                                                                ("lin45500x64x192r", "bgemm256s3_kernel"), ("lin65000x64x192r", "bgemm256s3_kernel")]) +
     _form("t256", _T256, [("lin513x640x320r", "bgemm_t256_kernel 256x320"), ("lin300x640x512r", "bgemm_t256_kernel 256x256"),
                           ("geglu300x640x256", "bgemm_t256_kernel 256x256"), ("conv128to320_3x9x16_rps144r", "bgemm_t256_kernel 256x320"),
                           ("conv128to256_2x8x12_s2_rps24r", "bgemm_t256_kernel 256x256"), ("conv128+64to320_2x7x5r", "bgemm_t256_kernel 256x320")]) +

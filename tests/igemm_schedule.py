@@ -1,6 +1,7 @@
 """The tile schedule of the fp32 GEMM launcher, restated (pure Python: no torch, no GPU).
 
-``igemm()`` (csrc/igemm.hip, "tile schedule") cuts the ``nbm`` row blocks of 128 rows of a launch -- the row blocks of all batch entries
+``plan_tiles()`` (csrc/gemm_sched.h, the one home of the rule: ``igemm()`` calls it for every GEMM launch, every GEMM kernel decodes its
+result with ``tile_decode()`` of the same header) cuts the ``nbm`` row blocks of 128 rows of a launch -- the row blocks of all batch entries
 together -- into tiles of two shapes: row blocks of the *wide* part into ``w1`` tiles of 128x128 followed by ``s1`` tiles of 128x64,
 row blocks of the *tail* part into ``s2`` tiles of 128x64 only.  ``rb1`` is the number of wide row blocks the rule asks for:
 
@@ -12,7 +13,9 @@ The kernels deal the row blocks to eight XCD chunks, chunk x owning ``[x * nbm /
 tail_rb)`` row blocks of every chunk are its tail, so the seam between wide and tail tiles lies inside every chunk.  The grid is eight
 times the tile count of the longest chunk; the blocks a shorter chunk does not need return at once.
 
-``schedule()`` restates the rule for the fp32 path (128-row blocks, 512 slots, ``E2V_IGEMM_SCHED`` at its default of 1, no split-K),
+``schedule()`` restates the rule for the fp32 path (128-row blocks, 512 slots, ``E2V_IGEMM_SCHED`` at its default of 1, no split-K;
+``rows`` / ``slots``: the same rule for the 256-row blocks of the 16-bit modes), independently of the header -- tests/
+test_gemm_sched_host.py holds the header's planner to it over a sweep of launches --,
 ``klass()`` names the class of a launch, ``region()`` says which tile of the schedule owns an output element of a case of ``CASES`` --
 the launches tests/test_hip_igemm_schedule.py runs, chosen so that every class of the production dispatch table
 (tests/golden/dispatch_sd_v1_4.json) is reached (tests/test_igemm_schedule_host.py).
@@ -23,9 +26,10 @@ SLOTS = 512          # resident tiles the rule sizes a round by (2 workgroups pe
 ROWS = 128           # rows of a row block
 
 
-def schedule(M, N, batch=1, geglu=False):
-    """``M`` rows per batch entry, ``N`` GEMM columns (GEGLU: both halves, 2 x the output width)."""
-    nbm_per = (M + ROWS - 1) // ROWS
+def schedule(M, N, batch=1, geglu=False, rows=ROWS, slots=SLOTS):
+    """``M`` rows per batch entry, ``N`` GEMM columns (GEGLU: both halves, 2 x the output width).  ``rows``, ``slots``: the row-block
+    height and the resident tiles of a round -- 128 and 512, or 256 and 256 for the 256-row tiles of the 16-bit modes."""
+    nbm_per = (M + rows - 1) // rows
     nbm = nbm_per * batch
     s2 = (N + 63) // 64
     w1 = N // 128
@@ -42,8 +46,8 @@ def schedule(M, N, batch=1, geglu=False):
         per2 = 2 * w1 + s1                       # cost of a row block in units of half a 128x128 tile (the source's per_rb, doubled)
         nrb = (nbm + 7) // 8                     # row blocks of the longest chunk
         units2 = per2 * nrb
-        xslots = SLOTS // 8
-        if units2 * 8 < 2 * SLOTS:
+        xslots = slots // 8
+        if units2 * 8 < 2 * slots:
             rb1 = 0                              # less than one round
         else:
             full = units2 // (2 * xslots)        # whole rounds of wide tiles

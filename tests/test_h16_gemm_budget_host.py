@@ -53,6 +53,22 @@ def test_every_form_of_the_table_has_its_cases():
     assert hb.gemm_shape(hb.GEMM_PROBLEM_BY_ID["conv128to256_2x8x12_s2_rps24r"])[0] == 48 and hb.gemm_shape(hb.GEMM_PROBLEM_BY_ID["conv64to128_3x8x23_rps184r"])[0] == 2 * 256 + 40
 
 
+def test_256_row_cases_beyond_the_narrow_schedule():
+    """The two `256s3` cases chosen for the mixed and the wide schedule of 256-row tiles are of that class: the restated rule, generalised
+    to 256-row blocks and 256 slots, says so; the form's other cases are narrow (three row blocks)."""
+    import igemm_schedule as sc
+    kinds = {}
+    for c in hb.GEMM_CASES:
+        if c["form_name"] != "256s3":
+            continue
+        M, N, _ = hb.gemm_shape(c)
+        s = sc.schedule(M, N, rows=256, slots=256)
+        kinds[c["pid"]] = sc.kind_of(s)
+        for k, v in c.get("sched256", {}).items():
+            assert (sc.kind_of(s) if k == "kind" else s[k]) == v, f"{c['id']}: {k} is {s.get(k, sc.kind_of(s))}, the table claims {v}"
+    assert kinds == {"lin552x320x192r": "narrow", "conv64to128_3x8x23_rps184r": "narrow", "lin45500x64x192r": "mixed", "lin65000x64x192r": "wide"}
+
+
 def test_gate_restates_the_kernels_formula():
     """bf16: the logistic form within 2.8e-4 of erf-GELU (the bound the kernel's comment states); fp16: the erf form itself."""
     x = torch.linspace(-8, 8, 4001, dtype=torch.float64)

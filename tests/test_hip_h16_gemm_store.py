@@ -97,6 +97,11 @@ def test_gemm_store(eng, case, ty):
     order."""
     p = _problem(case["pid"], ty)
     what = f"{case['id']} [{ty}]"
+    if "sched256" in case:                     # a case chosen for a tile schedule of 256-row blocks: the restated rule names its class
+        import igemm_schedule as sc
+        s = sc.schedule(p["M"], p["N"], rows=256, slots=256)
+        assert sc.kind_of(s) == case["sched256"]["kind"], f"{what}: the launch is {sc.kind_of(s)}, chosen as {case['sched256']['kind']}"
+        what += f" ({sc.kind_of(s)} schedule: rb1={s['rb1']} w{s['w1']} s{s['s1']} s2={s['s2']} tail_rb={s['tail_rb']})"
     with form_of(eng, ty, case["form"]) as e:
         y = run(e, p).cpu()
         tags = _served_by(e, case, what)

@@ -1,6 +1,7 @@
 """Bit comparison of the fp32 GEMM epilogue between two builds of the library: every case of tests/test_hip_igemm_epilogue.py
 (fenced operands, ragged M / N / K, bias / residual / time-embedding / GEGLU epilogues) and of tests/test_hip_igemm_schedule.py (the
-mixed and wide tile schedules of the production graph), one SHA-256 of the output bytes per case.
+mixed and wide tile schedules of the production graph), and every case of the 16-bit GEMM table (``GEMM_CASES`` of tests/h16_budget.py:
+each in bf16 and in fp16, under the switches of its form, stored in 16 bits as the graph stores it), one SHA-256 of the output bytes per case.
 
     E2V_LIB_PATH=/path/to/other/libeeg2video_hip.so python tools/igemm_epilogue_bits.py a.json     # one build per process
     python tools/igemm_epilogue_bits.py b.json                                                      # the shipped build
@@ -20,8 +21,23 @@ def digests():
     for module in (t, ts):
         for name, run in module.cases():
             y, _ = run(eng)
-            out[name] = hashlib.sha256(y.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+            out[name] = _sha(y)
+    import h16_budget as hb
+    import test_hip_h16_gemm_store as tg
+    eng.set_knob("E2V_OP_IO16", 1)
+    try:
+        for ty in tg.TYPES:
+            for case in sorted(hb.GEMM_CASES, key=lambda c: c["pid"]):           # (forms of one problem back to back: its operands are cached)
+                with tg.form_of(eng, ty, case["form"]) as e:
+                    out[f"h16 {case['id']} [{ty}]"] = _sha(tg.run(e, tg._problem(case["pid"], ty)))
+    finally:
+        eng.set_knob("E2V_OP_IO16", 0)
     return out
+
+
+def _sha(y):
+    import torch
+    return hashlib.sha256(y.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
 
 
 def main(argv):
