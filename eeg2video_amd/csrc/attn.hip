@@ -1377,19 +1377,6 @@ __global__ __launch_bounds__(128) void temporal_attn_lds_kernel(const T* __restr
 // softmax of its head and the P V product of its own 8 channels.  LH = lanes per head = D / 8 rounded up to a power of two (D = 40:
 // 5 of 8 lanes carry data, the loads of the other 3 are masked); the staged kernel below spent its time alternating a load phase
 // and a compute phase in which 24 of a block's 128 threads worked (1.6 TB/s at level 0).
-template <int LH>
-__device__ __forceinline__ float head_allreduce(float x) {
-    auto dpp = [](float v, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    x += dpp(x, std::integral_constant<int, 0xB1>{});                       // quad_perm [1,0,3,2]
-    x += dpp(x, std::integral_constant<int, 0x4E>{});                       // quad_perm [2,3,0,1]
-    if constexpr (LH >= 8) x += dpp(x, std::integral_constant<int, 0x141>{});   // row_half_mirror: the other quad of the 8
-    if constexpr (LH >= 16) x += dpp(x, std::integral_constant<int, 0x140>{});  // row_mirror: the other 8 of the 16
-    if constexpr (LH >= 32) x += __shfl_xor(x, 16);
-    return x;
-}
-
 template <typename T, int F, int D>
 __global__ __launch_bounds__(256) void temporal_attn_wave_kernel(const T* __restrict__ qkv, int ld, T* __restrict__ out, int ldo, int HW,
                                                                  long npix, int heads, float scale) {
@@ -1468,7 +1455,7 @@ __global__ __launch_bounds__(256) void temporal_attn_wave_kernel(const T* __rest
         float m = -INFINITY;
 #pragma unroll
         for (int j = 0; j < F; ++j) {
-            s[i][j] = head_allreduce<LH>(s[i][j]) * scale;
+            s[i][j] = lanes_allreduce<LH>(s[i][j]) * scale;
             m = fmaxf(m, s[i][j]);
         }
         float l = 0.f;

@@ -11,6 +11,7 @@
 #include "h16.h"
 #include "kernels.h"
 #include "prof.h"
+#include "runtime.h"
 #include "act_io.h"
 #ifdef E2V_AB
 #include <hip/hip_cooperative_groups.h>      // gn_coop_kernel (measured, not adopted)
@@ -26,56 +27,75 @@ static constexpr int GN_ROWS_PER_CHUNK = 64;      // granularity of the partial-
 
 int groupnorm_chunks(int P) { return (P + GN_ROWS_PER_CHUNK - 1) / GN_ROWS_PER_CHUNK; }
 
-// largest divisor of cq that is <= 64
-static int quad_tile(int cq) {
+// columns (quads or octets) a workgroup handles side by side: the largest divisor of n that is <= 64
+static int col_tile(int n) {
     int best = 1;
-    for (int d = 1; d <= 64 && d <= cq; ++d)
-        if (cq % d == 0) best = d;
+    for (int d = 1; d <= 64 && d <= n; ++d)
+        if (n % d == 0) best = d;
     return best;
 }
 
-// grid (chunks, slabs); part[((slab*chunks + chunk)*Ctot + coff + c)*2 + {0,1}]
-template <typename T>
+// A 16-bit source whose channels and row stride are multiples of 8 takes the 8-channel (16-byte) statistics kernel; a call whose two
+// sources and output all qualify takes the 8-channel apply pass.  The launches AND the tags read these two.
+static bool gn_source_wide(const GroupNormArgs& a, int C, int ld) { return a.bf16 && C % 8 == 0 && ld % 8 == 0; }
+static bool gn_apply_wide(const GroupNormArgs& a) {
+    return gn_source_wide(a, a.c0, a.ld0) && gn_source_wide(a, a.c1, a.ld1) && a.ldo % 8 == 0;
+}
+
+// Statistics pass, VE = 4 or 8 channels per lane (RowVec: act_io.h; 8 = one 16-byte access of a 16-bit row -- at 8 bytes per
+// instruction the 16-bit passes ran at 2.2-2.9 TB/s effective).  The arithmetic does not depend on VE: fp32 sums of <= 64 values per
+// thread, fp64 fold, fp32 affine.  grid (chunks, slabs); part[((slab*chunks + chunk)*Ctot + coff + c)*2 + {0,1}]; TILE = columns of VE
+// channels handled side by side (divides C / VE, <= 64)
+template <typename T, int VE>
 __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x, int ld, int C, int P, int chunks,
-                                                         float* __restrict__ part, int Ctot, int coff, int QT, int chunk_rows) {
-    __shared__ f32x4 red[2][256];
+                                                         float* __restrict__ part, int Ctot, int coff, int TILE, int chunk_rows) {
+    using V = RowVec<T, VE>;
+    constexpr int NQ = VE / 4;
+    __shared__ f32x4 red[2 * NQ][256];
     const int chunk = blockIdx.x, slab = blockIdx.y;
-    const int R = 256 / QT;
-    const int q = threadIdx.x % QT, r = threadIdx.x / QT;
+    const int R = 256 / TILE;
+    const int q = threadIdx.x % TILE, r = threadIdx.x / TILE;
     const int p0 = chunk * chunk_rows;
     const int p1 = min(P, p0 + chunk_rows);
     const T* base = x + (size_t)slab * P * ld;
     float* dst = part + ((size_t)(slab * chunks + chunk) * Ctot + coff) * 2;
-    const int CQ = C / 4;
-    for (int q0 = 0; q0 < CQ; q0 += QT) {
-        f32x4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};
+    const int CV = C / VE;
+    for (int q0 = 0; q0 < CV; q0 += TILE) {
+        // sums of the NQ quads, then their sums of squares (the rows of `red`).  Keep ALL sums before ALL squares in the loops below: with
+        // sum and square interleaved per quad the 8-channel instance scheduled differently and ran 1 % slower at level 0 (0.321 -> 0.324 ms).
+        f32x4 acc[2 * NQ];
+#pragma unroll
+        for (int i = 0; i < 2 * NQ; ++i) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (r < R) {
-            const T* col = base + (q0 + q) * 4;
+            const T* col = base + (q0 + q) * VE;
             int pr = p0 + r;
             for (; pr + 3 * R < p1; pr += 4 * R) {          // four rows in flight per thread
-                const f32x4 v0 = ld4(col + (size_t)pr * ld);
-                const f32x4 v1 = ld4(col + (size_t)(pr + R) * ld);
-                const f32x4 v2 = ld4(col + (size_t)(pr + 2 * R) * ld);
-                const f32x4 v3 = ld4(col + (size_t)(pr + 3 * R) * ld);
-                s += (v0 + v1) + (v2 + v3);
-                ss += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
+                const V a = V::load(col + (size_t)pr * ld), b = V::load(col + (size_t)(pr + R) * ld);
+                const V c = V::load(col + (size_t)(pr + 2 * R) * ld), d = V::load(col + (size_t)(pr + 3 * R) * ld);
+#pragma unroll
+                for (int h = 0; h < NQ; ++h) acc[h] += (a.q[h] + b.q[h]) + (c.q[h] + d.q[h]);
+#pragma unroll
+                for (int h = 0; h < NQ; ++h) acc[NQ + h] += (a.q[h] * a.q[h] + b.q[h] * b.q[h]) + (c.q[h] * c.q[h] + d.q[h] * d.q[h]);
             }
             for (; pr < p1; pr += R) {
-                const f32x4 v = ld4(col + (size_t)pr * ld);
-                s += v;
-                ss += v * v;
+                const V a = V::load(col + (size_t)pr * ld);
+#pragma unroll
+                for (int h = 0; h < NQ; ++h) acc[h] += a.q[h];
+#pragma unroll
+                for (int h = 0; h < NQ; ++h) acc[NQ + h] += a.q[h] * a.q[h];
             }
         }
-        red[0][threadIdx.x] = s;
-        red[1][threadIdx.x] = ss;
+#pragma unroll
+        for (int i = 0; i < 2 * NQ; ++i) red[i][threadIdx.x] = acc[i];
         __syncthreads();
-        if (threadIdx.x < QT) {
+        if (threadIdx.x < NQ * TILE) {                      // thread (half, column): channels 4 half .. + 3 of the column's VE
+            const int o = NQ > 1 ? threadIdx.x % TILE : threadIdx.x, half = NQ > 1 ? threadIdx.x / TILE : 0;
             f32x4 ts = {0.f, 0.f, 0.f, 0.f}, tss = {0.f, 0.f, 0.f, 0.f};
             for (int k = 0; k < R; ++k) {
-                ts += red[0][k * QT + threadIdx.x];
-                tss += red[1][k * QT + threadIdx.x];
+                ts += red[half][k * TILE + o];
+                tss += red[NQ + half][k * TILE + o];
             }
-            float* d = dst + (size_t)(q0 + threadIdx.x) * 8;
+            float* d = dst + ((size_t)(q0 + o) * VE + 4 * half) * 2;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 d[2 * e] = ts[e];
@@ -83,6 +103,29 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const T* __restrict__ x
             }
         }
         __syncthreads();
+    }
+}
+
+// The tail of a (slab, group) fold: the wave's fp64 lane sums reduced, mean, variance (clamped at 0), rstd, and the group's channels'
+// (scale, shift) = (rstd gamma, beta - mean rstd gamma) written out
+__device__ __forceinline__ void gn_fold_tail(double s, double ss, const int cpg, const int Ctot, const int P, const float eps,
+                                             const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ scsh,
+                                             const int g, const int slab, const int lane) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        s += __shfl_xor(s, off);
+        ss += __shfl_xor(ss, off);
+    }
+    const double cnt = (double)cpg * (double)P;
+    const double mean = s / cnt;
+    double var = ss / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    const double rstd = 1.0 / sqrt(var + (double)eps);
+    for (int c = g * cpg + lane; c < (g + 1) * cpg; c += 64) {
+        const double ga = (double)gamma[c];
+        float* o = scsh + ((size_t)slab * Ctot + c) * 2;
+        o[0] = (float)(rstd * ga);
+        o[1] = (float)((double)beta[c] - mean * rstd * ga);
     }
 }
 
@@ -109,22 +152,7 @@ __device__ __forceinline__ void gn_finalize_unit(const float* __restrict__ part,
         for (int u = 0; u < 8; ++u)
             if (i0 + 64 * u < total) { s += (double)e[u][0]; ss += (double)e[u][1]; }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_xor(s, off);
-        ss += __shfl_xor(ss, off);
-    }
-    const double cnt = (double)cpg * (double)P;
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    for (int c = g * cpg + lane; c < (g + 1) * cpg; c += 64) {
-        const double ga = (double)gamma[c];
-        float* o = scsh + ((size_t)slab * Ctot + c) * 2;
-        o[0] = (float)(rstd * ga);
-        o[1] = (float)((double)beta[c] - mean * rstd * ga);
-    }
+    gn_fold_tail(s, ss, cpg, Ctot, P, eps, gamma, beta, scsh, g, slab, lane);
 }
 
 // grid (groups, slabs), one wave each
@@ -144,120 +172,41 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x0,
     const int CQ = Ctot / 4;
     const size_t total = rows * CQ;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    auto one = [&](size_t i, f32x4& v, f32x4& a, f32x4& b, size_t& row, int& c) {
+    using V = RowVec<T, 4>;
+    auto one = [&](size_t i, V& v, typename V::ScSh& t, size_t& row, int& c) {
         row = i / CQ;
         c = (int)(i - row * CQ) * 4;
         const int slab = (int)(row / P);
-        v = (c < c0) ? ld4(x0 + row * ld0 + c) : ld4(x1 + row * ld1 + (c - c0));
-        const float* sc = scsh + ((size_t)slab * Ctot + c) * 2;
-        a = *reinterpret_cast<const f32x4*>(sc);
-        b = *reinterpret_cast<const f32x4*>(sc + 4);
+        v = (c < c0) ? V::load(x0 + row * ld0 + c) : V::load(x1 + row * ld1 + (c - c0));
+        t = V::load_scsh(scsh + ((size_t)slab * Ctot + c) * 2);
     };
-    auto fin = [&](const f32x4& v, const f32x4& a, const f32x4& b, size_t row, int c) {
-        f32x4 y;
-        y[0] = v[0] * a[0] + a[1];
-        y[1] = v[1] * a[2] + a[3];
-        y[2] = v[2] * b[0] + b[1];
-        y[3] = v[3] * b[2] + b[3];
-        if (act) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = silu_f(y[e]);
-        }
-        st4(out + row * ldo + c, y);
+    auto fin = [&](const V& v, const typename V::ScSh& t, size_t row, int c) {
+        V y = v.gn_affine(t);
+        if (act) y.apply([](float f) { return silu_f(f); });
+        y.store(out + row * ldo + c);
     };
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     for (; i + stride < total; i += 2 * stride) {           // two elements in flight per thread
-        f32x4 v0, a0, b0, v1, a1, b1;
+        V v0, v1;
+        typename V::ScSh t0, t1;
         size_t r0, r1;
         int cc0, cc1;
-        one(i, v0, a0, b0, r0, cc0);
-        one(i + stride, v1, a1, b1, r1, cc1);
-        fin(v0, a0, b0, r0, cc0);
-        fin(v1, a1, b1, r1, cc1);
+        one(i, v0, t0, r0, cc0);
+        one(i + stride, v1, t1, r1, cc1);
+        fin(v0, t0, r0, cc0);
+        fin(v1, t1, r1, cc1);
     }
     if (i < total) {
-        f32x4 v, a, b;
+        V v;
+        typename V::ScSh t;
         size_t r;
         int cc;
-        one(i, v, a, b, r, cc);
-        fin(v, a, b, r, cc);
+        one(i, v, t, r, cc);
+        fin(v, t, r, cc);
     }
 }
 
-// ---- bf16 activations: 16-byte (8-channel) accesses ---------------------------------------------------------------------
-// The templated kernels above move 4 channels per lane: 16 bytes of fp32 but only 8 of bf16, and at half the bytes per
-// instruction the bf16 passes ran at 2.2-2.9 TB/s effective.  These variants give every lane 8 channels (one 16-byte load /
-// store), the arithmetic is unchanged (fp32 sums of <= 64 values per thread, fp64 fold, fp32 affine).
-struct F8 { f32x4 lo, hi; };
-typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
-template <typename H>      // H: bf16 / fp16 (h16.h)
-__device__ __forceinline__ F8 ld8(const H* p) {
-    const hx8<H> v = *reinterpret_cast<const hx8<H>*>(p);
-    F8 r;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { r.lo[e] = (float)v[e]; r.hi[e] = (float)v[4 + e]; }
-    return r;
-}
-template <typename H>
-__device__ __forceinline__ void st8(H* p, const f32x4& lo, const f32x4& hi) {
-    hx8<H> v;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { v[e] = (H)lo[e]; v[4 + e] = (H)hi[e]; }
-    *reinterpret_cast<hx8<H>*>(p) = v;
-}
-
-// grid (chunks, slabs); same partial layout as gn_partial_kernel; OT = octets handled side by side (divides C / 8, <= 64)
-template <typename H>
-__global__ __launch_bounds__(256) void gn_partial8_kernel(const H* __restrict__ x, int ld, int C, int P, int chunks,
-                                                          float* __restrict__ part, int Ctot, int coff, int OT, int chunk_rows) {
-    __shared__ f32x4 red[4][256];
-    const int chunk = blockIdx.x, slab = blockIdx.y;
-    const int R = 256 / OT;
-    const int q = threadIdx.x % OT, r = threadIdx.x / OT;
-    const int p0 = chunk * chunk_rows;
-    const int p1 = min(P, p0 + chunk_rows);
-    const H* base = x + (size_t)slab * P * ld;
-    float* dst = part + ((size_t)(slab * chunks + chunk) * Ctot + coff) * 2;
-    const int CO = C / 8;
-    for (int q0 = 0; q0 < CO; q0 += OT) {
-        f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, ss0 = s0, ss1 = s0;
-        if (r < R) {
-            const H* col = base + (q0 + q) * 8;
-            int pr = p0 + r;
-            for (; pr + 3 * R < p1; pr += 4 * R) {          // four rows in flight per thread
-                const F8 a = ld8(col + (size_t)pr * ld), b = ld8(col + (size_t)(pr + R) * ld);
-                const F8 c = ld8(col + (size_t)(pr + 2 * R) * ld), d = ld8(col + (size_t)(pr + 3 * R) * ld);
-                s0 += (a.lo + b.lo) + (c.lo + d.lo);
-                s1 += (a.hi + b.hi) + (c.hi + d.hi);
-                ss0 += (a.lo * a.lo + b.lo * b.lo) + (c.lo * c.lo + d.lo * d.lo);
-                ss1 += (a.hi * a.hi + b.hi * b.hi) + (c.hi * c.hi + d.hi * d.hi);
-            }
-            for (; pr < p1; pr += R) {
-                const F8 a = ld8(col + (size_t)pr * ld);
-                s0 += a.lo; s1 += a.hi;
-                ss0 += a.lo * a.lo; ss1 += a.hi * a.hi;
-            }
-        }
-        red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1; red[2][threadIdx.x] = ss0; red[3][threadIdx.x] = ss1;
-        __syncthreads();
-        if (threadIdx.x < 2 * OT) {                       // thread (half, octet): channels 4 half .. + 3 of the octet
-            const int o = threadIdx.x % OT, half = threadIdx.x / OT;
-            f32x4 ts = {0.f, 0.f, 0.f, 0.f}, tss = ts;
-            for (int k = 0; k < R; ++k) {
-                ts += red[half][k * OT + o];
-                tss += red[2 + half][k * OT + o];
-            }
-            float* d = dst + ((size_t)(q0 + o) * 8 + 4 * half) * 2;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                d[2 * e] = ts[e];
-                d[2 * e + 1] = tss[e];
-            }
-        }
-        __syncthreads();
-    }
-}
-
+// ---- 16-bit activations: the apply pass at 8 channels (one 16-byte access) per lane ------------------------------------------
 #ifdef E2V_AB          // the flat-index apply pass (E2V_GN_ROWS = 0): the other arm of the A/B that adopted the row-tiled one
 template <typename H>
 __global__ __launch_bounds__(256) void gn_apply8_kernel(const H* __restrict__ x0, const H* __restrict__ x1, int c0, int c1,
@@ -267,22 +216,15 @@ __global__ __launch_bounds__(256) void gn_apply8_kernel(const H* __restrict__ x0
     const int CO = Ctot / 8;
     const size_t total = rows * CO;
     const size_t stride = (size_t)gridDim.x * blockDim.x;
+    using V = RowVec<H, 8>;
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < total; i += stride) {
         const size_t row = i / CO;
         const int c = (int)(i - row * CO) * 8;
         const int slab = (int)(row / P);
-        const F8 v = (c < c0) ? ld8(x0 + row * ld0 + c) : ld8(x1 + row * ld1 + (c - c0));
-        const float* sc = scsh + ((size_t)slab * Ctot + c) * 2;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(sc), b = *reinterpret_cast<const f32x4*>(sc + 4);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(sc + 8), e = *reinterpret_cast<const f32x4*>(sc + 12);
-        f32x4 lo, hi;
-        lo[0] = v.lo[0] * a[0] + a[1]; lo[1] = v.lo[1] * a[2] + a[3]; lo[2] = v.lo[2] * b[0] + b[1]; lo[3] = v.lo[3] * b[2] + b[3];
-        hi[0] = v.hi[0] * d[0] + d[1]; hi[1] = v.hi[1] * d[2] + d[3]; hi[2] = v.hi[2] * e[0] + e[1]; hi[3] = v.hi[3] * e[2] + e[3];
-        if (act) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { lo[k] = silu_f(lo[k]); hi[k] = silu_f(hi[k]); }
-        }
-        st8(out + row * ldo + c, lo, hi);
+        const V v = (c < c0) ? V::load(x0 + row * ld0 + c) : V::load(x1 + row * ld1 + (c - c0));
+        V y = v.gn_affine(V::load_scsh(scsh + ((size_t)slab * Ctot + c) * 2));
+        if (act) y.apply([](float f) { return silu_f(f); });
+        y.store(out + row * ldo + c);
     }
 }
 #endif
@@ -298,6 +240,7 @@ template <typename H, bool ACT>
 __global__ __launch_bounds__(256) void gn_apply8_rows_kernel(const H* __restrict__ x0, const H* __restrict__ x1, int c0, int c1,
                                                              int ld0, int ld1, const float* __restrict__ scsh, H* __restrict__ out,
                                                              int ldo, int P, int OT, int chunk_rows) {
+    using V = RowVec<H, 8>;
     const int chunk = blockIdx.x, slab = blockIdx.y;
     const int R = 256 / OT;
     const int q = threadIdx.x % OT, r = threadIdx.x / OT;
@@ -312,34 +255,20 @@ __global__ __launch_bounds__(256) void gn_apply8_rows_kernel(const H* __restrict
         const H* col = c < c0 ? x0 + row0 * ld0 + c : x1 + row0 * ld1 + (c - c0);
         const int ld = c < c0 ? ld0 : ld1;
         H* dst = out + row0 * ldo + c;
-        const float* sc = scb + (size_t)c * 2;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(sc), b = *reinterpret_cast<const f32x4*>(sc + 4);
-        const f32x4 d = *reinterpret_cast<const f32x4*>(sc + 8), e = *reinterpret_cast<const f32x4*>(sc + 12);
-        auto fin = [&](const F8& v, const int pr) {
-            f32x4 lo, hi;
-            lo[0] = v.lo[0] * a[0] + a[1]; lo[1] = v.lo[1] * a[2] + a[3]; lo[2] = v.lo[2] * b[0] + b[1]; lo[3] = v.lo[3] * b[2] + b[3];
-            hi[0] = v.hi[0] * d[0] + d[1]; hi[1] = v.hi[1] * d[2] + d[3]; hi[2] = v.hi[2] * e[0] + e[1]; hi[3] = v.hi[3] * e[2] + e[3];
-            if constexpr (ACT) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { lo[k] = silu_fast(lo[k]); hi[k] = silu_fast(hi[k]); }
-            }
-            st8(dst + (size_t)pr * ldo, lo, hi);
+        const typename V::ScSh t = V::load_scsh(scb + (size_t)c * 2);
+        auto fin = [&](const V& v, const int pr) {
+            V y = v.gn_affine(t);
+            if constexpr (ACT) y.apply([](float f) { return silu_fast(f); });
+            y.store(dst + (size_t)pr * ldo);
         };
         int pr = p0 + r;
         for (; pr + 3 * R < p1; pr += 4 * R) {
-            const F8 v0 = ld8(col + (size_t)pr * ld), v1 = ld8(col + (size_t)(pr + R) * ld);
-            const F8 v2 = ld8(col + (size_t)(pr + 2 * R) * ld), v3 = ld8(col + (size_t)(pr + 3 * R) * ld);
+            const V v0 = V::load(col + (size_t)pr * ld), v1 = V::load(col + (size_t)(pr + R) * ld);
+            const V v2 = V::load(col + (size_t)(pr + 2 * R) * ld), v3 = V::load(col + (size_t)(pr + 3 * R) * ld);
             fin(v0, pr); fin(v1, pr + R); fin(v2, pr + 2 * R); fin(v3, pr + 3 * R);
         }
-        for (; pr < p1; pr += R) fin(ld8(col + (size_t)pr * ld), pr);
+        for (; pr < p1; pr += R) fin(V::load(col + (size_t)pr * ld), pr);
     }
-}
-
-static int oct_tile(int co) {
-    int best = 1;
-    for (int d = 1; d <= 64 && d <= co; ++d)
-        if (co % d == 0) best = d;
-    return best;
 }
 
 // Rows per workgroup of the statistics / apply passes, a multiple of GN_ROWS_PER_CHUNK chosen from the SAMPLE's size only (never
@@ -373,11 +302,11 @@ __global__ __launch_bounds__(256) void rowblock_sums_kernel(const __bf16* __rest
         for (int c = 0; c < 2; ++c) {
             f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = s0, q0 = s0, q1 = s0;
             for (int r = j; r < 32; r += rpp) {
-                const F8 v = ld8(x + (row0 + 32 * c + r) * ld + q * 8);
+                const RowVec<__bf16, 8> v = RowVec<__bf16, 8>::load(x + (row0 + 32 * c + r) * ld + q * 8);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    s0[e] += v.lo[e]; s1[e] += v.hi[e];
-                    q0[e] = __builtin_fmaf(v.lo[e], v.lo[e], q0[e]); q1[e] = __builtin_fmaf(v.hi[e], v.hi[e], q1[e]);
+                    s0[e] += v.q[0][e]; s1[e] += v.q[1][e];
+                    q0[e] = __builtin_fmaf(v.q[0][e], v.q[0][e], q0[e]); q1[e] = __builtin_fmaf(v.q[1][e], v.q[1][e], q1[e]);
                 }
             }
             acc[c][0] = s0; acc[c][1] = s1; acc[c][2] = q0; acc[c][3] = q1;
@@ -433,22 +362,7 @@ __global__ __launch_bounds__(64) void gn_finalize_mixed_kernel(const float* __re
             ss += (double)e[1];
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        s += __shfl_xor(s, off);
-        ss += __shfl_xor(ss, off);
-    }
-    const double cnt = (double)cpg * (double)P;
-    const double mean = s / cnt;
-    double var = ss / cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const double rstd = 1.0 / sqrt(var + (double)eps);
-    for (int c = g * cpg + lane; c < (g + 1) * cpg; c += 64) {
-        const double ga = (double)gamma[c];
-        float* o = scsh + ((size_t)slab * Ctot + c) * 2;
-        o[0] = (float)(rstd * ga);
-        o[1] = (float)((double)beta[c] - mean * rstd * ga);
-    }
+    gn_fold_tail(s, ss, cpg, Ctot, P, eps, gamma, beta, scsh, g, slab, lane);
 }
 
 // ---- one kernel for a small (sample, group): the small-batch family ---------------------------------------------------------------
@@ -532,7 +446,7 @@ static bool gn_fused_small_applies(const GroupNormArgs& a) {
 // Two samples at level 0 are 17.7 MB (35 MB with a concatenated skip): 69-138 KB per CU.  The three-launch path reads that tensor twice
 // and spends most of its 37 us in the ramp and drain of three dependent launches of ~100 workgroups.  Here the tensor is read ONCE into
 // the LDS of <= 256 co-resident workgroups (cooperative launch: the runtime refuses a grid that is not resident as a whole), each owning
-// a run of rows of one sample: statistics per channel from LDS (partials in the layout of gn_partial8_kernel), grid barrier, the fold of
+// a run of rows of one sample: statistics per channel from LDS (partials in the layout of gn_partial_kernel), grid barrier, the fold of
 // every (sample, group) by one wave (gn_finalize_unit: the same fp64 fold), grid barrier, the affine (+ SiLU) applied from LDS.  Another
 // grouping of the partial sums than the chunked path (rows per workgroup instead of 64-row chunks), so the small-batch family picks it.
 // BUILT, PARITY-TESTED, MEASURED AND NOT ADOPTED (`make ab`, E2V_GN_COOP = 1; profiles/r05_shape_ab_b1_gn_cooperative.log): the
@@ -544,6 +458,7 @@ __global__ __launch_bounds__(1024) void gn_coop_kernel(const H* __restrict__ x0,
                                                       int P, int groups, float eps, int wps, int rows_per_wg, int RS, float* __restrict__ part,
                                                       float* __restrict__ scsh) {
     extern __shared__ __attribute__((aligned(16))) char gnc_lds[];
+    typedef unsigned u32x4g __attribute__((ext_vector_type(4)));
     namespace cg = cooperative_groups;
     cg::grid_group grid = cg::this_grid();
     const int tid = threadIdx.x;
@@ -602,17 +517,10 @@ __global__ __launch_bounds__(1024) void gn_coop_kernel(const H* __restrict__ x0,
     __syncthreads();
     for (int i = tid; i < pieces; i += 1024) {
         const int r = i / CO, q = i - r * CO, c = q * 8;
-        const hx8<H> v = __builtin_bit_cast(hx8<H>, tile[i]);
-        const f32x4* sc = reinterpret_cast<const f32x4*>(scratch + (size_t)c * 2);
-        const f32x4 a = sc[0], b = sc[1], d = sc[2], e = sc[3];
-        f32x4 lo, hi;
-        lo[0] = (float)v[0] * a[0] + a[1]; lo[1] = (float)v[1] * a[2] + a[3]; lo[2] = (float)v[2] * b[0] + b[1]; lo[3] = (float)v[3] * b[2] + b[3];
-        hi[0] = (float)v[4] * d[0] + d[1]; hi[1] = (float)v[5] * d[2] + d[3]; hi[2] = (float)v[6] * e[0] + e[1]; hi[3] = (float)v[7] * e[2] + e[3];
-        if (ACT) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { lo[k] = silu_f(lo[k]); hi[k] = silu_f(hi[k]); }
-        }
-        st8(out + (row0 + r) * ldo + c, lo, hi);
+        using V = RowVec<H, 8>;
+        V y = V::load(reinterpret_cast<const H*>(tile + i)).gn_affine(V::load_scsh(scratch + (size_t)c * 2));
+        if (ACT) y.apply([](float f) { return silu_f(f); });
+        y.store(out + (row0 + r) * ldo + c);
     }
 }
 
@@ -651,31 +559,27 @@ static void groupnorm_stats_launch(const GroupNormArgs& a, hipStream_t s) {
     const int crows = gn_chunk_rows(a.P, a.small_chunks != 0);
     const int chunks = (a.P + crows - 1) / crows;
     auto part = [&](const float* x, int ld, int C, int coff) {
-        const int qt = quad_tile(C / 4);
-        if (a.bf16) {
-            h16_dispatch(a.bf16, [&](auto h16_tag) {
-                using H = decltype(h16_tag);
-                if (C % 8 == 0 && ld % 8 == 0)
-                    E2V_KLAUNCH(gn_partial8_kernel<H>, dim3(chunks, a.samples), dim3(256), 0, s, reinterpret_cast<const H*>(x), ld, C, a.P,
-                                chunks, a.ws_part, Ctot, coff, oct_tile(C / 8), crows);
-                else
-                    E2V_KLAUNCH(gn_partial_kernel<H>, dim3(chunks, a.samples), dim3(256), 0, s, reinterpret_cast<const H*>(x), ld, C,
-                                a.P, chunks, a.ws_part, Ctot, coff, qt, crows);
-            });
-        }
-        else
-            E2V_KLAUNCH(gn_partial_kernel<float>, dim3(chunks, a.samples), dim3(256), 0, s, x, ld, C, a.P, chunks, a.ws_part, Ctot,
-                               coff, qt, crows);
+        auto go = [&](auto kern, auto* xs, const int ve) {
+            E2V_KLAUNCH(kern, dim3(chunks, a.samples), dim3(256), 0, s, xs, ld, C, a.P, chunks, a.ws_part, Ctot, coff, col_tile(C / ve), crows);
+        };
+        if (!a.bf16) return go(gn_partial_kernel<float, 4>, x, 4);
+        h16_dispatch(a.bf16, [&](auto h16_tag) {
+            using H = decltype(h16_tag);
+            if (gn_source_wide(a, C, ld)) go(gn_partial_kernel<H, 8>, reinterpret_cast<const H*>(x), 8);
+            else go(gn_partial_kernel<H, 4>, reinterpret_cast<const H*>(x), 4);
+        });
     };
     // sources that came with their row-block sums skip the statistics pass
     const bool use_rb = a.bf16 && a.P % 64 == 0 && (a.rb0 || (a.c1 > 0 && a.rb1));
     const bool rb0 = use_rb && a.rb0, rb1 = use_rb && a.c1 > 0 && a.rb1;
-    if (dry_run()) {
-        const std::string pk = std::string(a.bf16 && a.c0 % 8 == 0 && a.c1 % 8 == 0 && ((a.ld0 | a.ld1) & 7) == 0 ? "gn_partial8_kernel" : "gn_partial_kernel") + " rows" + std::to_string(crows);
+    if (dry_run() || op_recording()) {      // (recorded for e2v_op_last_dispatch too: tests read which kernel served each source)
+        // (the tags keep the names the two statistics kernels had before they became one template: gn_partial8_kernel is its VE = 8)
+        auto pk = [&](int C, int ld) {
+            return std::string(gn_source_wide(a, C, ld) ? " gn_partial8_kernel" : " gn_partial_kernel") + " rows" + std::to_string(crows);
+        };
         std::string t = " ->";
-        if (!rb0) t += " " + pk + (a.c1 > 0 ? "[0]" : "");
-        if (rb0) t += " sums-from-producer[0]";
-        if (a.c1 > 0) t += rb1 ? " sums-from-producer[1]" : " " + pk + "[1]";
+        t += rb0 ? " sums-from-producer[0]" : pk(a.c0, a.ld0) + (a.c1 > 0 ? "[0]" : "");
+        if (a.c1 > 0) t += rb1 ? " sums-from-producer[1]" : pk(a.c1, a.ld1) + "[1]";
         dry_tag(t + (use_rb ? " + gn_finalize_mixed_kernel" : " + gn_finalize_kernel"));
     }
     // timing experiment (make ab): E2V_GN_SKIP_PARTIAL = 1 drops the statistics pass over the tensor -- RESULTS ARE WRONG -- to measure
@@ -714,7 +618,7 @@ static void groupnorm_bf16_launch(const GroupNormArgs& a, hipStream_t s) {
     const int Ctot = a.c0 + a.c1;
     const size_t rows = (size_t)a.samples * a.P;
     if (*rowsp) {
-        const int ot = oct_tile(a.c1 > 0 ? gcd_int(a.c0 / 8, a.c1 / 8) : a.c0 / 8);
+        const int ot = col_tile(a.c1 > 0 ? gcd_int(a.c0 / 8, a.c1 / 8) : a.c0 / 8);
         const int crows = gn_chunk_rows(a.P, a.small_chunks != 0);
         const dim3 grid((a.P + crows - 1) / crows, a.samples);
         dry_tag(" + gn_apply8_rows_kernel rows" + std::to_string(crows));
@@ -791,7 +695,7 @@ void groupnorm(const GroupNormArgs& a, hipStream_t s) {
     const size_t rows = (size_t)a.samples * a.P;
     const size_t total = rows * (Ctot / 4);
     const int blocks = (int)((total + 511) / 512 < 16384 ? (total + 511) / 512 : 16384);
-    if (a.bf16 && a.c0 % 8 == 0 && a.c1 % 8 == 0 && ((a.ld0 | a.ld1 | a.ldo) & 7) == 0) {
+    if (gn_apply_wide(a)) {
         // The tensor is read twice (statistics, then the affine), and a B = 32 pass normalises 566 MB .. 1.7 GB tensors: the second
         // read finds nothing in the 256 MiB Infinity Cache.  E2V_GN_GROUP_MB > 0 sends runs of samples of that size through
         // statistics -> apply one after the other, so that a run's apply pass re-reads what its statistics pass has just brought
@@ -834,90 +738,40 @@ void groupnorm(const GroupNormArgs& a, hipStream_t s) {
                            a.ldo, a.P, rows, a.silu);
 }
 
-// ---- LayerNorm: one wave per row, row held in registers (C <= 64*4*NV) ------------------------------
-template <int NV, typename T>
-__global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, T* __restrict__ out, int ldo,
-                                                        int rows, int C, float eps) {
-    const int lane = threadIdx.x & 63;
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= rows) return;
-    const int CQ = C / 4;
-    const T* xr = x + (size_t)row * ldx;
-    f32x4 v[NV];
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int q = lane + 64 * k;
-        if (q < CQ) {
-            v[k] = ld4(xr + q * 4);
-            s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
-        } else {
-            v[k] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    const float mean = s / (float)C;
-    float ss = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int q = lane + 64 * k;
-        if (q < CQ) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d = v[k][e] - mean;
-                ss += d * d;
-            }
-        }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) ss += __shfl_xor(ss, off);
-    const float rstd = rsqrtf(ss / (float)C + eps);
-    T* orow = out + (size_t)row * ldo;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const int q = lane + 64 * k;
-        if (q < CQ) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + q * 4);
-            const f32x4 b = *reinterpret_cast<const f32x4*>(beta + q * 4);
-            f32x4 y;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = (v[k][e] - mean) * rstd * g[e] + b[e];
-            st4(orow + q * 4, y);
-        }
-    }
-}
-
-// bf16 rows: 8 channels (16 bytes) per lane and R rows per wave, all loads of the R rows issued before the first reduction
-// (a wave that owns one 640-byte row spends its life on launch, two shuffle chains and a store: 2.9 TB/s effective)
-template <typename H, int NV, int R>
-__global__ __launch_bounds__(256) void layernorm_bf16_kernel(const H* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, H* __restrict__ out, int ldo,
+// ---- LayerNorm -------------------------------------------------------------------------------------------------------------------
+// Kernels over RowVec<T, VE> (act_io.h), in two dispatch families whose mean / rstd arithmetic differs ON PURPOSE (the bits of
+// every earlier build): the wave-per-row kernel divides by (float)C, a runtime width; the sub-wave kernel multiplies by the
+// compile-time 1.0f / C.
+//
+// One wave per R rows, a row held in registers (C <= 64 VE NV), all loads of the R rows issued before the first reduction (a wave
+// that owns one 640-byte row spends its life on launch, two shuffle chains and a store: 2.9 TB/s effective).  fp32 rows and 16-bit
+// rows that are no multiple of 8 wide: VE = 4, R = 1; 16-bit rows of 8-channel pieces: VE = 8, R = 4.
+template <typename T, int VE, int NV, int R>
+__global__ __launch_bounds__(256) void layernorm_wave_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, T* __restrict__ out, int ldo,
                                                              int rows, int C, float eps) {
+    using V = RowVec<T, VE>;
     const int lane = threadIdx.x & 63;
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
     if (row0 >= rows) return;
-    const int CO = C / 8;
-    F8 v[R][NV];
+    const int CV = C / VE;
+    V v[R][NV];
     float s[R], ss[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int row = min(row0 + r, rows - 1);
-        const H* xr = x + (size_t)row * ldx;
+        const T* xr = x + (size_t)row * ldx;
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
             const int q = lane + 64 * k;
-            if (q < CO) v[r][k] = ld8(xr + q * 8);
-            else { v[r][k].lo = f32x4{0.f, 0.f, 0.f, 0.f}; v[r][k].hi = v[r][k].lo; }
+            v[r][k] = q < CV ? V::load(xr + q * VE) : V::zero();
         }
     }
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < NV; ++k)
-            t += ((v[r][k].lo[0] + v[r][k].lo[1]) + (v[r][k].lo[2] + v[r][k].lo[3])) + ((v[r][k].hi[0] + v[r][k].hi[1]) + (v[r][k].hi[2] + v[r][k].hi[3]));
+        for (int k = 0; k < NV; ++k) t += v[r][k].sum();
         s[r] = t;
     }
 #pragma unroll
@@ -929,15 +783,8 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const H* __restrict
         const float mean = s[r] / (float)C;
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            if (lane + 64 * k < CO) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float d0 = v[r][k].lo[e] - mean, d1 = v[r][k].hi[e] - mean;
-                    t += d0 * d0 + d1 * d1;
-                }
-            }
-        }
+        for (int k = 0; k < NV; ++k)
+            if (lane + 64 * k < CV) v[r][k].add_sqdev(t, mean);
         ss[r] = t;
         s[r] = mean;
     }
@@ -948,79 +795,52 @@ __global__ __launch_bounds__(256) void layernorm_bf16_kernel(const H* __restrict
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
         const int q = lane + 64 * k;
-        if (q < CO) {
-            const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + q * 8), g1 = *reinterpret_cast<const f32x4*>(gamma + q * 8 + 4);
-            const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + q * 8), b1 = *reinterpret_cast<const f32x4*>(beta + q * 8 + 4);
+        if (q < CV) {
+            const V g = V::load_f32(gamma + q * VE), b = V::load_f32(beta + q * VE);
 #pragma unroll
-            for (int r = 0; r < R; ++r) {
-                if (row0 + r < rows) {
-                    const float rstd = rsqrtf(ss[r] / (float)C + eps);
-                    f32x4 lo, hi;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        lo[e] = (v[r][k].lo[e] - s[r]) * rstd * g0[e] + b0[e];
-                        hi[e] = (v[r][k].hi[e] - s[r]) * rstd * g1[e] + b1[e];
-                    }
-                    st8(out + (size_t)(row0 + r) * ldo + q * 8, lo, hi);
-                }
-            }
+            for (int r = 0; r < R; ++r)
+                if (row0 + r < rows)
+                    v[r][k].ln_affine(s[r], rsqrtf(ss[r] / (float)C + eps), g, b).store(out + (size_t)(row0 + r) * ldo + q * VE);
         }
     }
 }
 
-// Sub-wave rows: C = 320 / 640 / 1280 are 40 / 80 / 160 octets -- LPR = 8 / 16 / 32 lanes share a row (five 16-byte octets each, at a lane
-// stride of LPR octets: every load instruction of the wave covers 128 contiguous bytes of 64 / LPR rows), all 64 lanes carry data
-// (the wave-per-row form above: 40 of 64 at C = 320), the two reductions are 3-5 DPP adds inside the row's lanes instead of six
-// wave-wide shuffles, and a wave keeps G row groups in flight.
-template <int LPR>
-__device__ __forceinline__ float rowlanes_allreduce(float x) {
-    auto dpp = [](float v, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    x += dpp(x, std::integral_constant<int, 0xB1>{});                       // quad_perm [1,0,3,2]
-    x += dpp(x, std::integral_constant<int, 0x4E>{});                       // quad_perm [2,3,0,1]
-    x += dpp(x, std::integral_constant<int, 0x141>{});                      // row_half_mirror: the other quad of the 8
-    if constexpr (LPR >= 16) x += dpp(x, std::integral_constant<int, 0x140>{});  // row_mirror: the other 8 of the 16
-    if constexpr (LPR >= 32) x += __shfl_xor(x, 16);
-    return x;
-}
+// Sub-wave rows: C = 320 / 640 / 1280 are five 16-byte pieces for each of LPR lanes (16-bit rows: 40 / 80 / 160 octets, LPR = 8 / 16 /
+// 32), at a lane stride of LPR pieces: every load instruction of the wave covers contiguous runs of 64 / LPR rows, all 64 lanes carry
+// data (the wave-per-row form above: 40 of 64 at C = 320), the two reductions are 3-5 DPP adds inside the row's lanes instead of six
+// wave-wide shuffles, and a wave keeps G row groups in flight.  16-bit rows; fp32 rows: layernorm_f32_rows_kernel below.
 template <typename H, int LPR, int G>
-__global__ __launch_bounds__(256) void layernorm_bf16_rows_kernel(const H* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                                  const float* __restrict__ beta, H* __restrict__ out, int ldo,
-                                                                  int rows, float eps, int stats_only) {
-    constexpr int NV = 5, RW = 64 / LPR, C = LPR * NV * 8;
+__global__ __launch_bounds__(256) void layernorm_rows_kernel(const H* __restrict__ x, int ldx, const float* __restrict__ gamma,
+                                                             const float* __restrict__ beta, H* __restrict__ out, int ldo,
+                                                             int rows, float eps, int stats_only) {
+    constexpr int VE = 8, NV = 5, RW = 64 / LPR, C = LPR * NV * VE;
+    using V = RowVec<H, VE>;
     const int lane = threadIdx.x & 63;
     const int c = lane % LPR, rl = lane / LPR;
     const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * (RW * G) + rl;
     if (row0 - rl >= rows) return;
-    F8 v[G][NV];
+    V v[G][NV];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         const int row = min(row0 + g * RW, rows - 1);
-        const H* xr = x + (size_t)row * ldx + c * 8;
+        const H* xr = x + (size_t)row * ldx + c * VE;
 #pragma unroll
-        for (int k = 0; k < NV; ++k) v[g][k] = ld8(xr + k * LPR * 8);
+        for (int k = 0; k < NV; ++k) v[g][k] = V::load(xr + k * LPR * VE);
     }
     float mean[G], rstd[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < NV; ++k)
-            t += ((v[g][k].lo[0] + v[g][k].lo[1]) + (v[g][k].lo[2] + v[g][k].lo[3])) + ((v[g][k].hi[0] + v[g][k].hi[1]) + (v[g][k].hi[2] + v[g][k].hi[3]));
-        mean[g] = rowlanes_allreduce<LPR>(t) * (1.0f / (float)C);
+        for (int k = 0; k < NV; ++k) t += v[g][k].sum();
+        mean[g] = lanes_allreduce<LPR>(t) * (1.0f / (float)C);
     }
 #pragma unroll
     for (int g = 0; g < G; ++g) {
         float t = 0.f;
 #pragma unroll
-        for (int k = 0; k < NV; ++k)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float d0 = v[g][k].lo[e] - mean[g], d1 = v[g][k].hi[e] - mean[g];
-                t += d0 * d0 + d1 * d1;
-            }
-        rstd[g] = rsqrtf(rowlanes_allreduce<LPR>(t) * (1.0f / (float)C) + eps);
+        for (int k = 0; k < NV; ++k) v[g][k].add_sqdev(t, mean[g]);
+        rstd[g] = rsqrtf(lanes_allreduce<LPR>(t) * (1.0f / (float)C) + eps);
     }
     if (stats_only) {      // TIMING EXPERIMENT (`make ab`, E2V_LN_STATS_ONLY = 1; results are wrong): what a statistics-only pass would cost --
 #pragma unroll             // the ceiling of folding LayerNorm into its consumer GEMM: 8 bytes per row instead of the row
@@ -1033,25 +853,19 @@ __global__ __launch_bounds__(256) void layernorm_bf16_rows_kernel(const H* __res
     }
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        const int ch = (c + k * LPR) * 8;
-        const f32x4 g0 = *reinterpret_cast<const f32x4*>(gamma + ch), g1 = *reinterpret_cast<const f32x4*>(gamma + ch + 4);
-        const f32x4 b0 = *reinterpret_cast<const f32x4*>(beta + ch), b1 = *reinterpret_cast<const f32x4*>(beta + ch + 4);
+        const int ch = (c + k * LPR) * VE;
+        const V g0 = V::load_f32(gamma + ch), b0 = V::load_f32(beta + ch);
 #pragma unroll
-        for (int g = 0; g < G; ++g) {
-            if (row0 + g * RW < rows) {
-                f32x4 lo, hi;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    lo[e] = (v[g][k].lo[e] - mean[g]) * rstd[g] * g0[e] + b0[e];
-                    hi[e] = (v[g][k].hi[e] - mean[g]) * rstd[g] * g1[e] + b1[e];
-                }
-                st8(out + (size_t)(row0 + g * RW) * ldo + ch, lo, hi);
-            }
-        }
+        for (int g = 0; g < G; ++g)
+            if (row0 + g * RW < rows) v[g][k].ln_affine(mean[g], rstd[g], g0, b0).store(out + (size_t)(row0 + g * RW) * ldo + ch);
     }
 }
 
-// fp32 rows, same scheme: C = 320 / 640 / 1280 are 80 / 160 / 320 float4 quads = five per lane of 16 / 32 / 64 lanes
+// fp32 rows, same scheme (80 / 160 / 320 quads = five per lane of 16 / 32 / 64 lanes; 64 IS the wave: the shuffle chain).  WRITTEN OUT on
+// plain f32x4, both ways tried and measured against the earlier build's code: as the (float, 4) instance of the kernel above the
+// compiler contracts the first two squared deviations of a row into the other FMA (d1 d1 + (d0 d0) for d0 d0 + (d1 d1)) and rows change
+// in their last bit; on RowVec's load / sum / affine / store alone (squared deviations as here) the bits hold but the schedule moves
+// (379 -> 426 instructions at LPR = 16).  As it stands the code is the earlier build's, instruction for instruction.
 template <int LPR, int G>
 __global__ __launch_bounds__(256) void layernorm_f32_rows_kernel(const float* __restrict__ x, int ldx, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, float* __restrict__ out, int ldo,
@@ -1075,7 +889,7 @@ __global__ __launch_bounds__(256) void layernorm_f32_rows_kernel(const float* __
             for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off);
             return t;
         } else {
-            return rowlanes_allreduce<LPR>(t);
+            return lanes_allreduce<LPR>(t);
         }
     };
     float mean[G], rstd[G];
@@ -1114,16 +928,55 @@ __global__ __launch_bounds__(256) void layernorm_f32_rows_kernel(const float* __
     }
 }
 
-template <typename T>
-static void layernorm_launch(const T* x, int ldx, const float* gamma, const float* beta, T* out, int ldo, int rows, int C, float eps,
-                             hipStream_t s) {
-    const int blocks = (rows + 3) / 4;
-    if (C <= 256)
-        E2V_KLAUNCH((layernorm_kernel<1, T>), dim3(blocks), dim3(256), 0, s, x, ldx, gamma, beta, out, ldo, rows, C, eps);
-    else if (C <= 768)
-        E2V_KLAUNCH((layernorm_kernel<3, T>), dim3(blocks), dim3(256), 0, s, x, ldx, gamma, beta, out, ldo, rows, C, eps);
-    else
-        E2V_KLAUNCH((layernorm_kernel<5, T>), dim3(blocks), dim3(256), 0, s, x, ldx, gamma, beta, out, ldo, rows, C, eps);
+// The kernel a LayerNorm call takes, chosen ONCE: the dry-run tag and the launch both read it.  n: NV of the wave-per-row kernel,
+// lanes per row of the sub-wave one.  (The tags keep the names the kernels had before fp32 and 16-bit rows shared their text.)
+struct LnChoice { bool sub_wave; int ve, n, rows_per_wave; const char* tag; };
+static LnChoice ln_choose(int C, int ldx, int ldo, int bf16) {
+    static const int* const rowsp = knob("E2V_LN_ROWS", 1);         // 0: one wave per row group of four rows
+    const int ve = bf16 ? 8 : 4;                                    // channels of a 16-byte access
+    if (*rowsp && (C == 320 || C == 640 || C == 1280) && ldx % ve == 0 && ldo % ve == 0) {
+        const int lpr = C / (5 * ve);
+        return {true, ve, lpr, 2 * (64 / lpr), bf16 ? "layernorm_bf16_rows_kernel" : "layernorm_f32_rows_kernel"};
+    }
+    if (bf16 && C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && C <= 1536) return {false, 8, C <= 512 ? 1 : C <= 1024 ? 2 : 3, 4, "layernorm_bf16_kernel"};
+    return {false, 4, C <= 256 ? 1 : C <= 768 ? 3 : 5, 1, "layernorm_kernel"};
+}
+
+template <typename T, int VE>
+static void layernorm_launch(const LnChoice& k, const T* x, int ldx, const float* gamma, const float* beta, T* out, int ldo, int rows, int C,
+                             float eps, hipStream_t s) {
+    const int blocks = (rows + 4 * k.rows_per_wave - 1) / (4 * k.rows_per_wave);
+    auto go = [&](auto kern, auto... tail) { E2V_KLAUNCH(kern, dim3(blocks), dim3(256), 0, s, x, ldx, gamma, beta, out, ldo, rows, tail...); };
+    constexpr bool f32 = std::is_same<T, float>::value;
+    if (k.sub_wave) {                                               // k.n: lanes per row
+        if constexpr (VE == 8) {
+            static const int* const stats_only = E2V_AB_KNOB("E2V_LN_STATS_ONLY", 0);      // (timing experiment, see the kernel)
+            switch (k.n) {
+                case 8: return go(layernorm_rows_kernel<T, 8, 2>, eps, *stats_only);
+                case 16: return go(layernorm_rows_kernel<T, 16, 2>, eps, *stats_only);
+                case 32: return go(layernorm_rows_kernel<T, 32, 2>, eps, *stats_only);
+            }
+        } else if constexpr (f32) {
+            switch (k.n) {
+                case 16: return go(layernorm_f32_rows_kernel<16, 2>, eps);
+                case 32: return go(layernorm_f32_rows_kernel<32, 2>, eps);
+                case 64: return go(layernorm_f32_rows_kernel<64, 2>, eps);
+            }
+        }
+    } else if constexpr (VE == 8) {                                 // k.n: octets per lane (C <= 512 / 1024 / 1536), four rows per wave
+        switch (k.n) {
+            case 1: return go(layernorm_wave_kernel<T, 8, 1, 4>, C, eps);
+            case 2: return go(layernorm_wave_kernel<T, 8, 2, 4>, C, eps);
+            case 3: return go(layernorm_wave_kernel<T, 8, 3, 4>, C, eps);
+        }
+    } else {                                                        // k.n: quads per lane (C <= 256 / 768 / 1280), one row per wave
+        switch (k.n) {
+            case 1: return go(layernorm_wave_kernel<T, 4, 1, 1>, C, eps);
+            case 3: return go(layernorm_wave_kernel<T, 4, 3, 1>, C, eps);
+            case 5: return go(layernorm_wave_kernel<T, 4, 5, 1>, C, eps);
+        }
+    }
+    E2V_REQUIRE(false, E2V_EINVAL, "layernorm: no kernel for this choice");      // (ln_choose and the instances above have to agree)
 }
 
 void layernorm(const float* x, int ldx, const float* gamma, const float* beta, float* out, int ldo, int rows, int C,
@@ -1131,47 +984,16 @@ void layernorm(const float* x, int ldx, const float* gamma, const float* beta, f
     std::string pname = "layernorm";
     if (prof_detail()) pname += " rows" + std::to_string(rows) + " C" + std::to_string(C);
     ProfScope ps(pname.c_str(), 8.0 * rows * C, 2.0 * (bf16 ? 2.0 : 4.0) * rows * C, s);
-    static const int* const rowsp = knob("E2V_LN_ROWS", 1);         // 0: one wave per row group of four rows
-    if (dry_run()) {
-        const bool shared = *rowsp && (C == 320 || C == 640 || C == 1280) && ldx % (bf16 ? 8 : 4) == 0 && ldo % (bf16 ? 8 : 4) == 0;
-        dry_tag(std::string(" -> ") + (shared ? (bf16 ? "layernorm_bf16_rows_kernel" : "layernorm_f32_rows_kernel")
-                                       : (bf16 && C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && C <= 1536 ? "layernorm_bf16_kernel" : "layernorm_kernel")));
-    }
-    if (bf16) {
-        h16_dispatch(bf16, [&](auto h16_tag) {
-            using H = decltype(h16_tag);
-            const H* xi = reinterpret_cast<const H*>(x);
-            H* xo = reinterpret_cast<H*>(out);
-            if (*rowsp && (C == 320 || C == 640 || C == 1280) && ldx % 8 == 0 && ldo % 8 == 0) {
-                auto go = [&](auto kern, const int rows_per_wave) {
-                    const int blocks = (rows + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
-                    static const int* const stats_only = E2V_AB_KNOB("E2V_LN_STATS_ONLY", 0);      // (timing experiment, see the kernel)
-                    E2V_KLAUNCH(kern, dim3(blocks), dim3(256), 0, s, xi, ldx, gamma, beta, xo, ldo, rows, eps, *stats_only);
-                };
-                if (C == 320) go(layernorm_bf16_rows_kernel<H, 8, 2>, 16);
-                else if (C == 640) go(layernorm_bf16_rows_kernel<H, 16, 2>, 8);
-                else go(layernorm_bf16_rows_kernel<H, 32, 2>, 4);
-            } else if (C % 8 == 0 && ldx % 8 == 0 && ldo % 8 == 0 && C <= 1536) {
-                constexpr int R = 4;
-                const int blocks = (rows + 4 * R - 1) / (4 * R);
-                if (C <= 512) E2V_KLAUNCH((layernorm_bf16_kernel<H, 1, R>), dim3(blocks), dim3(256), 0, s, xi, ldx, gamma, beta, xo, ldo, rows, C, eps);
-                else if (C <= 1024) E2V_KLAUNCH((layernorm_bf16_kernel<H, 2, R>), dim3(blocks), dim3(256), 0, s, xi, ldx, gamma, beta, xo, ldo, rows, C, eps);
-                else E2V_KLAUNCH((layernorm_bf16_kernel<H, 3, R>), dim3(blocks), dim3(256), 0, s, xi, ldx, gamma, beta, xo, ldo, rows, C, eps);
-            } else {
-                layernorm_launch(xi, ldx, gamma, beta, xo, ldo, rows, C, eps, s);
-            }
-        });
-    }
-    else if (*rowsp && (C == 320 || C == 640 || C == 1280) && ldx % 4 == 0 && ldo % 4 == 0) {
-        auto go = [&](auto kern, const int rows_per_wave) {
-            const int blocks = (rows + 4 * rows_per_wave - 1) / (4 * rows_per_wave);
-            E2V_KLAUNCH(kern, dim3(blocks), dim3(256), 0, s, x, ldx, gamma, beta, out, ldo, rows, eps);
-        };
-        if (C == 320) go(layernorm_f32_rows_kernel<16, 2>, 8);
-        else if (C == 640) go(layernorm_f32_rows_kernel<32, 2>, 4);
-        else go(layernorm_f32_rows_kernel<64, 2>, 2);
-    } else
-        layernorm_launch(x, ldx, gamma, beta, out, ldo, rows, C, eps, s);
+    const LnChoice k = ln_choose(C, ldx, ldo, bf16);
+    if (dry_run() || op_recording()) dry_tag(std::string(" -> ") + k.tag);
+    if (!bf16) return layernorm_launch<float, 4>(k, x, ldx, gamma, beta, out, ldo, rows, C, eps, s);
+    h16_dispatch(bf16, [&](auto h16_tag) {
+        using H = decltype(h16_tag);
+        const H* xi = reinterpret_cast<const H*>(x);
+        H* xo = reinterpret_cast<H*>(out);
+        if (k.ve == 8) layernorm_launch<H, 8>(k, xi, ldx, gamma, beta, xo, ldo, rows, C, eps, s);
+        else layernorm_launch<H, 4>(k, xi, ldx, gamma, beta, xo, ldo, rows, C, eps, s);
+    });
 }
 
 }  // namespace e2v

@@ -332,6 +332,10 @@ GN_CASES = [
     dict(id="one_chunk", samples=2, P=64, c0=128, c1=0, groups=32, silu=True),
     dict(id="real_seam_cpg60", samples=2, P=240, c0=1280, c1=640, groups=32, silu=True),
     dict(id="constant_group", samples=3, P=50, c0=64, c1=32, groups=8, silu=True, constant_group=2),
+    # one source of each kind: 8-channel statistics for 64, 4-channel for 36 and for the 100-wide apply pass; group 6 straddles the seam
+    # (c0 = 60, c1 = 36, groups = 8 -- 4 channels per lane on both sources -- is in tests/test_hip_ops.py: with no seam group and
+    # 12 x 70 values per group its variance-over-N-1 mutant reaches 3.9 x this budget in bf16, short of MUTANT_FACTOR)
+    dict(id="mixed_alignment", samples=2, P=70, c0=64, c1=36, groups=10, silu=True),
 ]
 
 
@@ -383,6 +387,9 @@ LN_FORMS = [{"E2V_LN_ROWS": 1}, {"E2V_LN_ROWS": 0}]
 LN_DEFAULTS = {"E2V_LN_ROWS": 1}
 LN_MAX_WIDTH = 1280                # e2v_op_layernorm takes no wider row (the kernels behind it hold 1280 / 1536 columns in registers)
 LN_CASES = [dict(id=f"C{c}_rows{rows}", C=c, rows=rows) for c in (320, 640, 1280, 64, 1544) for rows in (1, 17)]
+# the wave-per-row kernel's other instances: C = 324 is no multiple of 8 (4 channels per lane on 16-bit rows; its last piece of 8 for
+# the mutants and sentinels is columns 312 .. 319, and 316 / 323 carry the sentinels), C = 768 / 1032 are two / three octets per lane
+LN_CASES += [dict(id=f"C{c}_rows{rows}", C=c, rows=rows) for c, rows in ((324, 9), (768, 17), (1032, 5))]
 
 
 def ln_inputs(case):

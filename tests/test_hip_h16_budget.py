@@ -75,7 +75,8 @@ def _gn_ref(case_id, ty):
 @pytest.mark.parametrize("ty", TYPES)
 @pytest.mark.parametrize("case,form", _params(hb.GN_CASES, hb.GN_FORMS + hb.GN_FORMS_AB))
 def test_groupnorm(eng, case, form, ty):
-    """Default: gn_partial8_kernel + gn_finalize_kernel + gn_apply8_rows_kernel; FUSED_SMALL = 2: gn_fused_small_kernel; in AB builds
+    """Default: gn_partial_kernel at 8 channels per lane + gn_finalize_kernel + gn_apply8_rows_kernel (widths that are no multiple of 8:
+    gn_partial_kernel and gn_apply_kernel at 4); FUSED_SMALL = 2: gn_fused_small_kernel; in AB builds
     GN_ROWS = 0: the flat apply pass, GN_COOP = 2: gn_coop_kernel.  One lost, doubled or foreign row, a wrong count or a seam group read
     from one source is at least 4 x over this budget in every sample it touches (host test)."""
     if form in hb.GN_FORMS_AB and not ab_build(eng):
@@ -87,6 +88,28 @@ def test_groupnorm(eng, case, form, ty):
                            silu=case["silu"], x1=s.cuda() if s is not None else None)
     what = f"groupnorm {case['id']} [{ty}, {hb.form_id(form)}]"
     _report(what, hb.assert_within_budget(y, ref, budget, what, hb.where_groupnorm(case)))
+
+
+@pytest.mark.parametrize("ty", TYPES)
+def test_groupnorm_mixed_alignment_dispatch(eng, ty):
+    """c0 = 64 takes the 8-channel statistics kernel, c1 = 36 the 4-channel one, the 100-wide output the 4-channel apply pass: every
+    element within its budget AND the recorded dispatch (``e2v_op_last_dispatch``) names, source by source, the kernels that ran."""
+    case = next(c for c in hb.GN_CASES if c["id"] == "mixed_alignment")
+    a, s, gamma, beta = hb.gn_inputs(case)
+    ref, budget = _gn_ref(case["id"], ty)
+    eng.set_knob("E2V_OP_RECORD", 1)
+    try:
+        with form_of(eng, ty, {}, hb.GN_DEFAULTS) as e:
+            y = e.op_groupnorm(a.cuda(), gamma.cuda(), beta.cuda(), samples=case["samples"], P=case["P"], groups=case["groups"], eps=1e-5,
+                               silu=case["silu"], x1=s.cuda())
+            tags = e.last_dispatch()
+    finally:
+        eng.set_knob("E2V_OP_RECORD", 0)
+    what = f"groupnorm {case['id']} [{ty}, recorded]"
+    _report(what, hb.assert_within_budget(y, ref, budget, what, hb.where_groupnorm(case)))
+    for needle in ("gn_partial8_kernel rows64[0]", "gn_partial_kernel rows64[1]", "gn_finalize_kernel", "gn_apply_kernel"):
+        assert needle in tags, f"{what}: `{needle}` is not in the recorded dispatch `{tags}`"
+    assert "gn_apply8" not in tags and "gn_fused_small" not in tags, f"{what}: the recorded dispatch is `{tags}`"
 
 
 # ------------------------------------------------------------------ LayerNorm
@@ -101,8 +124,9 @@ def _ln_ref(case_id, ty):
 @pytest.mark.parametrize("ty", TYPES)
 @pytest.mark.parametrize("case,form", _params(hb.LN_CASES, hb.LN_FORMS))
 def test_layernorm(eng, case, form, ty):
-    """C = 320 / 640 / 1280 at 8 / 16 / 32 lanes per row (layernorm_bf16_rows_kernel) and, with LN_ROWS = 0, one wave per four rows
-    (layernorm_bf16_kernel, which C = 64 takes either way); one row and a ragged 17.  No kernel holds a row wider than 1536 columns, and
+    """C = 320 / 640 / 1280 at 8 / 16 / 32 lanes per row (layernorm_rows_kernel) and, with LN_ROWS = 0, one wave per four rows
+    (layernorm_wave_kernel at 8 channels per lane, which C = 64, 768 and 1032 take either way -- one, two and three octets per lane --
+    and C = 324 at 4 channels per lane); one row and ragged 5, 9, 17.  No kernel holds a row wider than 1536 columns, and
     the entry point takes none wider than 1280: C = 1544 has to be REFUSED -- the wave-per-row kernels would leave the columns past
     their registers unread and unwritten -- and the output buffer left alone."""
     x, gamma, beta = hb.ln_inputs(case)

@@ -191,7 +191,7 @@ def test_groupnorm_concat_group_straddles_seam(eng):
     close(y.reshape(n, p, 1, c0 + c1).permute(0, 3, 1, 2), ref)
 
 
-@pytest.mark.parametrize("c", [64, 320, 640, 1280])
+@pytest.mark.parametrize("c", [64, 320, 640, 1280, 768, 1032])       # (768 / 1032: the wave-per-row kernel at 3 / 5 quads per lane)
 def test_layernorm(eng, c):
     x, g, b = rnd(777, c, seed=40) * 3 + 1, rnd(c, seed=41) * 0.2 + 1, rnd(c, seed=42) * 0.2
     close(eng.op_layernorm(x.cuda(), g.cuda(), b.cuda()), F.layer_norm(x, (c,), g, b, 1e-5))
@@ -454,6 +454,18 @@ def test_bf16_norms_and_temporal_attention(bf):
     ref = _unheads(_ref_attn(_heads(q, heads), _heads(k, heads), _heads(v, heads), d ** -0.5), heads)
     ref = ref.reshape(n, hw, f, c).permute(0, 2, 1, 3).reshape(n * f * hw, c)
     y = bf.op_temporal_attention(qkv.cuda(), n=n, F=f, HW=hw, heads=heads, D=d, scale=d ** -0.5)
+    close(y, ref, rtol=tol16(8e-3), atol=tol16(8e-3))
+
+
+def test_bf16_groupnorm_four_channels_per_lane(bf):
+    """Widths that are no multiple of 8 (c0 = 60, c1 = 36): gn_partial_kernel and gn_apply_kernel at 4 channels per lane on 16-bit rows,
+    both sources, two row chunks (P = 70): against torch on rounded inputs, to one rounding of the output."""
+    samples, P, c0, c1, groups = 2, 70, 60, 36, 8
+    a, s = rnd(samples * P, c0, seed=150), rnd(samples * P, c1, seed=151)
+    g, be = rnd(c0 + c1, seed=152), rnd(c0 + c1, seed=153)
+    xin = torch.cat([rb(a), rb(s)], 1).reshape(samples, P, c0 + c1).permute(0, 2, 1)
+    ref = F.silu(F.group_norm(xin, groups, g, be, 1e-5)).permute(0, 2, 1).reshape(samples * P, c0 + c1)
+    y = bf.op_groupnorm(a.cuda(), g.cuda(), be.cuda(), samples=samples, P=P, groups=groups, eps=1e-5, silu=True, x1=s.cuda())
     close(y, ref, rtol=tol16(8e-3), atol=tol16(8e-3))
 
 
