@@ -9,6 +9,7 @@ Layout (only what the path needs):
   constructor accepts, ``TuneAVideoPipeline.__call__`` / ``.from_pretrained``)
 * ``text_encoder`` / ``pipeline_tuneavideo``   ``transformers``' ``CLIPTextModel`` on the library and the text-prompt twin of the pipeline
 * ``semantic`` / ``util``   the steps either side of the path: Semantic Predictor, DDIM inversion, ``save_videos_grid``
+* ``metrics``   the frame metrics of the reference's scoring script on the device: per-frame SSIM / MSE (``ssim_score_only`` ...)
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
 * ``dist``       sharding of clips over ranks and the all-gather of decoded frames

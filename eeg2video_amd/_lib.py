@@ -52,6 +52,9 @@ E2V_F32, E2V_F16, E2V_BF16, E2V_F32X3 = 0, 1, 2, 3
 FORM_BITS = {"fp32": 1, "bf16": 2, "fp16": 4, "x3": 8, "conv_direct32": 16, "wino2": 32, "wino4": 64, "bf16_up2": 128,
              "f16_up2": 256, "wino2_x3": 512, "wino4_x3": 1024}
 
+#: `kind` of an input of e2v_frame_metrics: type | layout bit
+E2V_FRAMES_F32, E2V_FRAMES_U8, E2V_FRAMES_CHANNELS_LAST = 0, 1, 2
+
 _ctx = C.c_void_p
 _stream = C.c_void_p
 _i, _f, _i64, _p = C.c_int, C.c_float, C.c_int64, C.c_void_p
@@ -86,6 +89,7 @@ SIGNATURES = {
     "e2v_text_encode": (_i, [_ctx, c_int64_p, _i, _i, _p, _stream]),
     "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
+    "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
     "e2v_cfg_combine": (_i, [_ctx, _p, _p, _f, _p, _i64, _stream]),
     "e2v_lincomb": (_i, [_ctx, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _p, _i64, _stream]),
     "e2v_ddim_next_step": (_i, [_ctx, _p, _p, _p, _i64, _i64, _i, _stream]),

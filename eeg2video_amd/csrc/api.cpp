@@ -440,6 +440,33 @@ e2v_status e2v_frames_to_uint8(e2v_ctx* c, const float* videos, uint8_t* out, in
     });
 }
 
+e2v_status e2v_frame_metrics(e2v_ctx* c, const void* a, int a_kind, const void* b, int b_kind, int n, int F, int C, int H, int W,
+                             float* ssim, float* mse, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
+    try {
+        const int known = E2V_FRAMES_U8 | E2V_FRAMES_CHANNELS_LAST;
+        E2V_REQUIRE(a && b, E2V_EINVAL, "e2v_frame_metrics: null argument");
+        E2V_REQUIRE(ssim || mse, E2V_EINVAL, "e2v_frame_metrics: ssim and mse are both NULL");
+        E2V_REQUIRE((a_kind & ~known) == 0 && (b_kind & ~known) == 0, E2V_EINVAL, "e2v_frame_metrics: unknown bits in a kind");
+        E2V_REQUIRE(n > 0 && F > 0, E2V_ESHAPE, "e2v_frame_metrics: non-positive clip or frame count");
+        E2V_REQUIRE(C >= 1 && C <= 4, E2V_ESHAPE, "e2v_frame_metrics: 1 to 4 channels");
+        E2V_REQUIRE(H >= 7 && W >= 7, E2V_ESHAPE, "e2v_frame_metrics: the 7x7 window exceeds the image");
+        E2V_REQUIRE((double)n * F * (double)frame_metrics_tiles(H, W) < 2147483648.0, E2V_ESHAPE, "e2v_frame_metrics: too many tiles for one call");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        Act partials(c->pool, (int64_t)(frame_metrics_partials_bytes(n, F, H, W) / 4), 1);
+        const FrameSrc sa{a, (a_kind & E2V_FRAMES_U8) == 0, (a_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc sb{b, (b_kind & E2V_FRAMES_U8) == 0, (b_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        frame_metrics(sa, sb, n, F, C, H, W, partials.p, ssim, mse, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
 e2v_status e2v_profile_begin(e2v_ctx* c) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] { E2V_HIP(hipDeviceSynchronize()); profiler().begin(); });

@@ -262,6 +262,18 @@ void dana_noise(const float* x0, const float* eps_div, const float* eps_same, co
 void frames_to_u8(const float* in, unsigned char* out, long long count, hipStream_t s);
 void pad_cols(const float* in, int cols, float* out, int cols_pad, long long rows, hipStream_t s, int out_bf16 = 0);   // fp32 in; out fp32 or bf16
 
+// Frame metrics (metrics.hip; e2v_frame_metrics): per-image SSIM (skimage's defaults at data_range = 255, exact integer window moments)
+// and MSE of two clips of n * F images with C channels.  Each input is fp32 in [0,1] (quantised to bytes once, at load) or uint8, planar
+// [n,C,F,H,W] or channels-last [n,F,H,W,C], of any alignment its type allows.  One workgroup scores kCols x kRows window positions of
+// one image and leaves one partial in `partials` (frame_metrics_partials_bytes, caller-owned); a second kernel sums them per image in
+// index order into ssim / mse [n * F] (either may be null).  H, W >= 7, 1 <= C <= 4, n * F * frame_metrics_tiles(H, W) < 2^31.
+struct FrameMetricsTile { static constexpr int kCols = 256, kRows = 32; };
+struct FrameSrc { const void* p = nullptr; int f32 = 0; int channels_last = 0; };
+long long frame_metrics_tiles(int H, int W);
+size_t frame_metrics_partials_bytes(int n, int F, int H, int W);
+void frame_metrics(const FrameSrc& a, const FrameSrc& b, int n, int F, int C, int H, int W, void* partials, float* ssim, float* mse,
+                   hipStream_t s);
+
 // In-place weight update (e2v_update_tensor): one pass over a [rows][in] source (fp32, bf16 or fp16; src_mode as the h16.h flags:
 // 0 / 1 / 2) that writes every form a finalized linear keeps of it -- the fp32 matrix, the bf16 and fp16 copies (rows zero-padded
 // to ld16, a multiple of 8) and the three f32x3 planes -- with the roundings of to_h16 / split_bf16x3, so the bits equal a fresh

@@ -559,6 +559,37 @@ class Engine:
         self._check(self.lib.e2v_frames_to_uint8(self.ctx, v.data_ptr(), out.data_ptr(), v.numel(), _stream()))
         return out
 
+    def frame_metrics(self, a: torch.Tensor, b: torch.Tensor, a_channels_last: bool = False,
+                      b_channels_last: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Per-frame SSIM and MSE of two clips (``e2v_frame_metrics``; the reference's ``ssim_metric`` / ``mse_metric``,
+        ``40_class_run_metrics.py:229-233``) -> ``(ssim, mse)``, fp32 ``[n,F]`` each on the engine's device.  ``a`` / ``b``: uint8, or
+        float32 in ``[0,1]`` (quantised as ``frames_to_uint8`` does), planar ``[n,C,F,H,W]`` (``[C,F,H,W]``: one clip) or, with the
+        input's ``*_channels_last`` flag, ``[n,F,H,W,C]`` (``[F,H,W,C]``); host tensors are copied over.  The two inputs choose type
+        and layout independently; a non-contiguous view is made contiguous, a contiguous slice at any offset is read in place."""
+        views = []
+        for t, cl, name in ((a, a_channels_last, "a"), (b, b_channels_last, "b")):
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"`{name}` has to be of type `torch.Tensor` but is {type(t)}")
+            if t.dtype not in (torch.uint8, torch.float32):
+                raise ValueError(f"`{name}` has to be uint8 or float32, not {t.dtype}")
+            if t.dim() == 4:
+                t = t[None]
+            if t.dim() != 5:
+                raise ValueError(f"`{name}`: expected a 4-D clip or a 5-D batch of clips, got shape {tuple(t.shape)}")
+            t = t.to(self.device).contiguous()
+            n, c, f, h, w = (t.shape[0], t.shape[4], t.shape[1], t.shape[2], t.shape[3]) if cl else tuple(t.shape)
+            kind = (_lib.E2V_FRAMES_U8 if t.dtype == torch.uint8 else _lib.E2V_FRAMES_F32) | (_lib.E2V_FRAMES_CHANNELS_LAST if cl else 0)
+            views.append((t, kind, (n, f, c, h, w)))
+        (ta, ka, dims), (tb, kb, dims_b) = views
+        if dims != dims_b:
+            raise ValueError(f"clips differ: (n, F, C, H, W) = {dims} against {dims_b}")
+        n, f, c, h, w = dims
+        ssim = torch.empty((n, f), device=self.device, dtype=torch.float32)
+        mse = torch.empty((n, f), device=self.device, dtype=torch.float32)
+        self._check(self.lib.e2v_frame_metrics(self.ctx, ta.data_ptr(), ka, tb.data_ptr(), kb, n, f, c, h, w, ssim.data_ptr(),
+                                               mse.data_ptr(), _stream()))
+        return ssim, mse
+
     # ------------------------------------------------------------------ the one exchange of the path (SURVEY 8(e))
     def comm_init(self, group=None) -> int:
         """Open the library's own RCCL communicator over the ranks of the (already initialised) ``torch.distributed`` group:

@@ -9,6 +9,9 @@ latents of EEG2Video_New) over 40 concepts x 5 clips, batched and shardable over
 
 Synthetic EEG and random-init weights throughout (no datasets / checkpoints offline).  Prints one JSON line: clips/s of the
 whole flow and the share of each stage.  ``--tiny`` runs the same code on the tiny test configuration in seconds.
+``--score-against DIR`` scores every clip against ``DIR/<concept>_<k>.npy`` (or ``.gif``) as the reference's
+``40_class_run_metrics.py:284-298`` does -- per-frame SSIM and MSE (``e2v_frame_metrics``), on the device while the batch's frames
+are still there -- and adds ``ssim_mean``, ``ssim_std``, ``mse_mean`` and a ``score`` stage to the line.
 
     python examples/run_sweep.py --dtype bf16 --batch 32            # 200 clips on one GPU
     python -m torch.distributed.run --nproc-per-node 8 examples/run_sweep.py   # concepts sharded over ranks, frames gathered
@@ -18,6 +21,19 @@ import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
+
+
+def load_clip(stem):
+    """``stem + '.npy'`` or ``stem + '.gif'`` as ``save_videos_grid`` wrote it -> uint8 ``[F,H,W,3]``"""
+    if os.path.isfile(stem + ".npy"):
+        a = np.load(stem + ".npy")
+    else:
+        from PIL import Image, ImageSequence
+        with Image.open(stem + ".gif") as im:
+            a = np.stack([np.asarray(fr.convert("RGB")) for fr in ImageSequence.Iterator(im)])
+    if a.ndim != 4 or a.dtype != np.uint8:
+        raise ValueError(f"{stem}: expected uint8 frames [F,H,W,3], got {a.dtype} {a.shape}")
+    return a
 
 
 def main(argv=None, engine=None):
@@ -31,6 +47,8 @@ def main(argv=None, engine=None):
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
     ap.add_argument("--out", default="", help="directory for <concept>_<k>.gif (empty: frames are produced but not written)")
     ap.add_argument("--npy", action="store_true", help="write .npy instead of .gif")
+    ap.add_argument("--score-against", default="", metavar="DIR",
+                    help="directory of ground-truth clips named as --out names them (.npy or .gif): per-frame SSIM / MSE on the device")
     args = ap.parse_args(argv)
 
     import torch.distributed as dist
@@ -74,7 +92,9 @@ def main(argv=None, engine=None):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     neg = t(counter_normal(2, "neg", (1, scfg.tokens, ucfg.cross_attention_dim))).to(dev)
     stage = {"glmnet": 0.0, "seq2seq": 0.0, "semantic": 0.0, "dana": 0.0, "generate": 0.0, "uint8_d2h": 0.0, "write": 0.0}
-    mine = []
+    mine, scores = [], []
+    if args.score_against:
+        stage["score"] = 0.0
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0)) - 2)))
     pending = []
@@ -118,6 +138,12 @@ def main(argv=None, engine=None):
         t0 = time.perf_counter()
         frames = eng.generate(lat, cond, neg, args.steps, 12.5, 0.0, decode=True)
         tick("generate", t0)
+        if args.score_against:
+            names = [f"{k // args.per_concept:02d}_{k % args.per_concept}" for k in ids]
+            gt = torch.from_numpy(np.stack([load_clip(os.path.join(args.score_against, nm)) for nm in names])).to(dev)   # [B,F,H,W,3] uint8
+            t0 = time.perf_counter()
+            scores.append(eng.frame_metrics(frames, gt, b_channels_last=True))
+            tick("score", t0)
         t0 = time.perf_counter()
         u8 = eng.frames_to_uint8(frames).cpu()
         tick("uint8_d2h", t0)
@@ -136,6 +162,16 @@ def main(argv=None, engine=None):
     pool.shutdown()
     elapsed = time.perf_counter() - t_all
     u8_all = torch.cat(mine) if mine else torch.zeros((0, 3, F, 8 * h, 8 * w), dtype=torch.uint8)
+    score_keys = {}
+    if args.score_against:
+        ssim = torch.cat([s for s, _ in scores]).cpu() if scores else torch.zeros((0, F))
+        mse = torch.cat([m for _, m in scores]).cpu() if scores else torch.zeros((0, F))
+        if world > 1:                                               # per-frame scores of every rank, in clip order
+            parts = [None] * world
+            dist.all_gather_object(parts, (ssim, mse))
+            ssim, mse = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        ssim, mse = ssim.double().numpy(), mse.double().numpy()
+        score_keys = {"ssim_mean": float(np.mean(ssim)), "ssim_std": float(np.std(ssim)), "mse_mean": float(np.mean(mse))}
     if world > 1:
         u8_all = all_gather_frames(u8_all.to(dev).float() / 255.0, as_uint8=True).cpu()
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -147,7 +183,7 @@ def main(argv=None, engine=None):
         print(json.dumps({"workload": f"{args.concepts} concepts x {args.per_concept} clips, {args.steps}-step DDIM, CFG 12.5, {F}x{8 * h}x{8 * w}, {args.dtype}, batch {args.batch}",
                           "clips": total, "n_gpus": world, "seconds": elapsed, "clips_per_s": total / elapsed, "setup_s": t_setup,
                           "stage_seconds_rank0": stage, "host_model_share": host / max(elapsed, 1e-9),
-                          "generate_share": stage["generate"] / max(elapsed, 1e-9), "uint8_checksum": int(u8_all.long().sum())}))
+                          "generate_share": stage["generate"] / max(elapsed, 1e-9), "uint8_checksum": int(u8_all.long().sum()), **score_keys}))
     if world > 1:
         dist.destroy_process_group()
     return u8_all

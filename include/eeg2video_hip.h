@@ -337,6 +337,35 @@ e2v_status e2v_dana_noise(e2v_ctx* ctx, const float* x0, const float* eps_div, c
  * util.py:29) on the device, so that frames cross xGMI / PCIe as 1 byte per sample: videos in [0,1] -> uint8. */
 e2v_status e2v_frames_to_uint8(e2v_ctx* ctx, const float* videos, uint8_t* out, int64_t count, e2v_stream stream);
 
+/* rank 5 -- replaces ssim_metric / mse_metric and the per-frame loops ssim_score_only / mse_score_only around them
+ * (EEG2Video/40_class_run_metrics.py:201-233: skimage.metrics.structural_similarity(img1, img2, data_range=255, channel_axis=-1)
+ * and mse_loss(img1 / 255, img2 / 255) of each generated frame against its ground-truth frame), on the device, where the frames are.
+ * a, b: two batches of n clips, n * F images with C channels, H x W.  `kind` = type | layout bit, chosen per input: E2V_FRAMES_F32 (fp32,
+ * 4-byte aligned) or E2V_FRAMES_U8 (bytes of ANY alignment: slices of a gathered buffer, odd W * C); layout bit clear: planar
+ * [n,C,F,H,W], the library's `videos`; E2V_FRAMES_CHANNELS_LAST: [n,F,H,W,C], what imageio.mimread and the reference stack.
+ * ssim, mse: device [n,F] fp32 each, entry (i, f) = the score of image f of clip i; either may be NULL, not both.
+ * Quantisation: a u8 input is used as it is; an fp32 input is quantised once at load, q = (uint8)(min(max(x, 0), 1) * 255.f)
+ * (truncation: the bytes of e2v_frames_to_uint8 on [0,1]; NaN -> 0).  Everything after that is defined on the bytes.
+ * SSIM per image and channel, skimage's defaults as the reference calls it: 7x7 uniform window, sample covariance (NP / (NP - 1)),
+ * K1 = 0.01, K2 = 0.03, L = 255, the map cropped by 3 on every side (only windows fully inside the image count: no border rule),
+ * the mean over the (H-6)(W-6) map per channel, then over the channels.  Window moments are exact integers: with N = 49 and
+ * Sx, Sy, Sxx, Syy, Sxy over the window,
+ *   A1 = 2 Sx Sy / N^2 + C1,  A2 = 2 (N Sxy - Sx Sy) / (N (N-1)) + C2,  B1 = (Sx^2 + Sy^2) / N^2 + C1,
+ *   B2 = (N (Sxx + Syy) - Sx^2 - Sy^2) / (N (N-1)) + C2,  S = A1 A2 / (B1 B2),  C1 = 6.5025, C2 = 58.5225;
+ * every integer fits int32; the four terms and S are fp32, S is summed in double and rounded to fp32 once, after the division by the
+ * count.  Identical inputs give exactly 1; the result is symmetric in (a, b) bit for bit.
+ * MSE per image: sum (qa - qb)^2 / (65025 C H W) over ALL pixels, the border included; the integer sum is exact (64-bit), divided in
+ * double and rounded to fp32 once -- the reference's mse_loss without its per-element fp32 roundings.
+ * Fixed reduction order: per-workgroup partials in a workspace-pool block, summed per image in index order by a second kernel, no
+ * atomics -- an image's result does not depend on n or on its position in the batch and is bit-identical from run to run.
+ * Stream-ordered, does not synchronise, allocates nothing once the partials block of a shape is cached (e2v_device_bytes does not move).
+ * The argument checks come before anything is enqueued and before the host-only check: null ctx / a / b, both outputs NULL or unknown
+ * bits in a kind E2V_EINVAL; n or F <= 0 E2V_ESHAPE; C outside 1..4 E2V_ESHAPE; H or W < 7 E2V_ESHAPE ("window exceeds the image",
+ * where skimage raises); a well-formed call on a host-only context: E2V_ESTATE. */
+enum { E2V_FRAMES_F32 = 0, E2V_FRAMES_U8 = 1, E2V_FRAMES_CHANNELS_LAST = 2 };   /* kind = type | layout bit */
+e2v_status e2v_frame_metrics(e2v_ctx* ctx, const void* a, int a_kind, const void* b, int b_kind,
+                             int n, int F, int C, int H, int W, float* ssim, float* mse, e2v_stream stream);
+
 /* ---- multi-GPU: the one exchange of the path ------------------------------------------------------------------
  * replaces: nothing in the reference (it generates its 200 clips serially on one GPU, inference_eeg2video.py:90); clips shard
  * over one process per GPU with no data-path exchange, and the decoded frames of all ranks are gathered at the end.  The
