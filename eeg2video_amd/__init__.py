@@ -9,16 +9,18 @@ Layout (only what the path needs):
   constructor accepts, ``TuneAVideoPipeline.__call__`` / ``.from_pretrained``)
 * ``text_encoder`` / ``pipeline_tuneavideo``   ``transformers``' ``CLIPTextModel`` on the library and the text-prompt twin of the pipeline
 * ``semantic`` / ``util``   the steps either side of the path: Semantic Predictor, DDIM inversion, ``save_videos_grid``
-* ``metrics``   the frame metrics of the reference's scoring script on the device: per-frame SSIM / MSE (``ssim_score_only`` ...)
+* ``metrics``   the reference's scoring script on the device: per-frame SSIM / MSE (``ssim_score_only`` ...) and the image N-way
+  accuracy (``img_classify_metric``) over ``image_classifier``, ``transformers``' ``ViTForImageClassification`` on the library
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
 * ``dist``       sharding of clips over ranks and the all-gather of decoded frames
 
 The compute path has no CPU fallback: without the built library or without a GPU it raises.
 """
-from .weights import TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, SemanticConfig, TextConfig, UNetConfig, VAEConfig  # noqa: F401
+from .weights import (TINY_IMAGE, TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, ImageConfig, SemanticConfig, TextConfig,  # noqa: F401
+                      UNetConfig, VAEConfig)
 
-__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig",
+__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig", "ViTForImageClassification", "ImageConfig",
            "DDIMScheduler", "PNDMScheduler", "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler",
            "DPMSolverMultistepScheduler", "TuneAVideoPipeline", "build_pipeline", "save_videos_grid"]
 
@@ -33,6 +35,9 @@ def __getattr__(name):          # lazy: importing the package must not need torc
     if name == "CLIPTextModel":
         from .text_encoder import CLIPTextModel
         return CLIPTextModel
+    if name == "ViTForImageClassification":
+        from .image_classifier import ViTForImageClassification
+        return ViTForImageClassification
     if name == "AutoencoderKL":
         from .vae import AutoencoderKL
         return AutoencoderKL

@@ -32,6 +32,9 @@ class E2VConfig(C.Structure):
         ("attention_heads_per_block", C.c_int * 4),
         ("text_vocab_size", C.c_int), ("text_hidden", C.c_int), ("text_heads", C.c_int), ("text_layers", C.c_int),
         ("text_intermediate", C.c_int), ("text_max_positions", C.c_int), ("text_act", C.c_int), ("text_norm_eps", C.c_float),
+        ("vit_hidden", C.c_int), ("vit_heads", C.c_int), ("vit_layers", C.c_int), ("vit_intermediate", C.c_int),
+        ("vit_image_size", C.c_int), ("vit_patch_size", C.c_int), ("vit_num_labels", C.c_int), ("vit_norm_eps", C.c_float),
+        ("vit_rescale", C.c_double), ("vit_mean", C.c_float * 3), ("vit_std", C.c_float * 3),
     ]
 
 
@@ -90,6 +93,7 @@ SIGNATURES = {
     "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
     "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
+    "e2v_image_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
     "e2v_cfg_combine": (_i, [_ctx, _p, _p, _f, _p, _i64, _stream]),
     "e2v_lincomb": (_i, [_ctx, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _p, _i64, _stream]),
     "e2v_ddim_next_step": (_i, [_ctx, _p, _p, _p, _i64, _i64, _i, _stream]),
@@ -115,6 +119,9 @@ SIGNATURES = {
     "e2v_op_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _stream]),
     "e2v_op_temporal_attention": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _i, _f, _stream]),
     "e2v_op_causal_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
+    "e2v_image_resize_table": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),
+    "e2v_op_image_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
+    "e2v_op_image_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
     "e2v_op_set_knob": (_i, [C.c_char_p, _i]),

@@ -150,9 +150,29 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
             E2V_REQUIRE(cfg->text_max_positions >= 1 && cfg->text_max_positions <= kTextAttnMaxT, E2V_EINVAL,
                         "text_max_positions must be in 1 .. " + std::to_string(kTextAttnMaxT) + ": the text attention kernel keeps K and V of a prompt in LDS");
         }
+        if (cfg->vit_layers != 0) {                      // (all zero: no image classifier)
+            E2V_REQUIRE(cfg->vit_layers > 0 && cfg->vit_heads > 0 && cfg->vit_intermediate > 0 && cfg->vit_intermediate % 4 == 0 &&
+                            cfg->vit_image_size > 0 && cfg->vit_patch_size > 0 && cfg->vit_num_labels >= 3 && cfg->vit_norm_eps > 0.f,
+                        E2V_EINVAL, "bad image classifier config (sizes must be positive, vit_intermediate a multiple of 4, vit_num_labels at least 3)");
+            E2V_REQUIRE(cfg->vit_hidden == 64 * cfg->vit_heads, E2V_EINVAL,
+                        "vit_hidden must be 64 * vit_heads: 64 is the head dim of the image attention kernel's only instance");
+            E2V_REQUIRE(cfg->vit_hidden % 4 == 0 && cfg->vit_hidden <= 1280, E2V_EINVAL, "vit_hidden must be a multiple of 4, at most 1280 (the LayerNorm kernel's limit)");
+            E2V_REQUIRE(cfg->vit_image_size % cfg->vit_patch_size == 0 && (3 * cfg->vit_patch_size * cfg->vit_patch_size) % 4 == 0, E2V_EINVAL,
+                        "vit_image_size must be a multiple of vit_patch_size, and 3 * vit_patch_size^2 a multiple of 4");
+            const long long grid = cfg->vit_image_size / cfg->vit_patch_size;
+            E2V_REQUIRE(grid * grid + 1 <= kImageAttnMaxT, E2V_EINVAL,
+                        "(vit_image_size / vit_patch_size)^2 + 1 tokens must be at most " + std::to_string(kImageAttnMaxT) +
+                            ": the image attention kernel keeps K and V of an image's head in LDS");
+            for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(cfg->vit_std[ch] != 0.f, E2V_EINVAL, "vit_std must be non-zero");
+        }
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
+        for (int ch = 0; ch < 3 && cfg->vit_layers > 0; ++ch)      // ViTImageProcessor: rescale in double, rounded to fp32; normalise in fp32
+            for (int b = 0; b < 256; ++b) {
+                const float x = (float)((double)b * cfg->vit_rescale);
+                c->image_lut[ch * 256 + b] = (x - cfg->vit_mean[ch]) / cfg->vit_std[ch];
+            }
         c->expected_keys();
         make_alphas(c);
         if (const char* e = std::getenv("E2V_CONV_ALGO")) c->conv_algo = std::atoi(e);
@@ -231,7 +251,7 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
     const int part = e2v_ctx::key_part(k);
-    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : c->unet_ready;
+    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : c->unet_ready;
     E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
@@ -246,6 +266,10 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
     if (dtype != E2V_F32 && dtype != E2V_F16 && dtype != E2V_BF16) { c->err = "e2v_update_tensor: the source is fp32, fp16 or bf16"; return E2V_EINVAL; }
     if (e2v_ctx::key_part(key) == 8) {
         c->err = "e2v_update_tensor: the text encoder is frozen on this path (train_finetune_videodiffusion.py:115); load a new one with e2v_load_tensor + e2v_finalize_weights";
+        return E2V_EINVAL;
+    }
+    if (e2v_ctx::key_part(key) == 16) {
+        c->err = "e2v_update_tensor: the image classifier is a frozen yardstick (40_class_run_metrics.py:88-90); load a new one with e2v_load_tensor + e2v_finalize_weights";
         return E2V_EINVAL;
     }
     return guarded(c, [&] {
@@ -300,7 +324,7 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(which >= 1 && which <= 15, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder");
+        E2V_REQUIRE(which >= 1 && which <= 31, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier");
         c->finalize(which);
     });
 }
@@ -463,6 +487,109 @@ e2v_status e2v_frame_metrics(e2v_ctx* c, const void* a, int a_kind, const void* 
         const FrameSrc sa{a, (a_kind & E2V_FRAMES_U8) == 0, (a_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
         const FrameSrc sb{b, (b_kind & E2V_FRAMES_U8) == 0, (b_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
         frame_metrics(sa, sb, n, F, C, H, W, partials.p, ssim, mse, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+}  // extern "C"
+
+namespace {
+// the argument checks e2v_image_classify and e2v_op_image_preprocess share (no HIP call)
+void check_frames(const char* who, const void* frames, int kind, int n, int F, int H, int W) {
+    const int known = E2V_FRAMES_U8 | E2V_FRAMES_CHANNELS_LAST;
+    const std::string w(who);
+    E2V_REQUIRE(frames, E2V_EINVAL, w + ": null frames");
+    E2V_REQUIRE((kind & ~known) == 0, E2V_EINVAL, w + ": unknown bits in kind");
+    E2V_REQUIRE((kind & E2V_FRAMES_U8) || (reinterpret_cast<uintptr_t>(frames) & 3) == 0, E2V_EINVAL, w + ": fp32 frames must be 4-byte aligned");
+    E2V_REQUIRE(n >= 1, E2V_EINVAL, w + ": n < 1");
+    E2V_REQUIRE(F >= 1 && H >= 1 && W >= 1, E2V_ESHAPE, w + ": F, H and W must be at least 1");
+    E2V_REQUIRE((double)n * F < 2147483648.0, E2V_ESHAPE, w + ": too many images for one call");
+}
+}  // namespace
+
+extern "C" {
+
+// ViTImageProcessor + ViTForImageClassification + softmax + top 3 of every frame (img_classify_metric's classifier half)
+e2v_status e2v_image_classify(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* logits, float* probs,
+                              int32_t* top3, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
+    try {
+        check_frames("e2v_image_classify", frames, kind, n, F, H, W);
+        E2V_REQUIRE(logits || probs || top3, E2V_EINVAL, "e2v_image_classify: logits, probs and top3 are all NULL");
+        E2V_REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(top3)) & 3) == 0,
+                    E2V_EINVAL, "e2v_image_classify: misaligned output (4 bytes)");
+        E2V_REQUIRE(c->cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
+        E2V_REQUIRE(c->prep_plan(H, W).band >= 1, E2V_ESHAPE,
+                    "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
+        E2V_REQUIRE(c->image_ready, E2V_ESTATE, "image classifier weights are not finalized");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->image_classify(src, n, F, H, W, logits, probs, top3, S(c, stream));
+    });
+}
+
+e2v_status e2v_image_resize_table(int in_size, int out_size, int* first, int* count, int32_t* coeff, int* ksize) {
+    if (!ksize || in_size < 1 || out_size < 1) return E2V_EINVAL;
+    const ResizeAxis t = resize_axis(in_size, out_size);
+    *ksize = t.ksize;
+    if (first) std::memcpy(first, t.first.data(), t.first.size() * sizeof(int));
+    if (count) std::memcpy(count, t.count.data(), t.count.size() * sizeof(int));
+    if (coeff) std::memcpy(coeff, t.coeff.data(), t.coeff.size() * sizeof(int32_t));
+    return E2V_OK;
+}
+
+// the preprocess of e2v_image_classify on its own, at any (S, P) and with the caller's pixel table
+e2v_status e2v_op_image_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch,
+                                   const float* host_lut, float* rows, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    ImagePrepPlan plan;
+    try {
+        check_frames("e2v_op_image_preprocess", frames, kind, n, F, H, W);
+        E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_image_preprocess: null or misaligned rows");
+        E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0, E2V_ESHAPE, "e2v_op_image_preprocess: 1 <= S <= 4096, a multiple of P >= 1");
+        E2V_REQUIRE(host_lut || c->cfg.vit_layers > 0, E2V_ESTATE, "e2v_op_image_preprocess: no pixel table given and the config has no image classifier");
+        plan = image_prep_plan(H, W, size, patch, host_lut ? host_lut : c->image_lut);
+        E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_image_preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        Act tables(c->pool, (int64_t)plan.words.size(), 1);
+        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
+        for (long long i0 = 0; i0 < total; i0 += 4096) {
+            const int ni = (int)std::min<long long>(4096, total - i0);
+            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
+        }
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// fp32 in every compute mode, as e2v_image_classify runs it
+e2v_status e2v_op_image_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
+        E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && T <= kImageAttnMaxT, E2V_ESHAPE, "image attention: B, heads >= 1 and 1 <= T <= " + std::to_string(kImageAttnMaxT));
+        E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldqkv % 4 == 0 && ldo >= heads * 64 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                    E2V_EINVAL, "image attention: qkv rows of q | k | v (16-byte aligned, ldqkv a multiple of 4), out rows of heads * 64 columns");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        OpRecord rec;
+        image_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
         E2V_HIP(hipGetLastError());
     });
 }

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "gemm_sched.h"
 
@@ -229,6 +230,42 @@ constexpr int kTextAttnMaxT = 128;      // 2 x 128 rows x 272 bytes = 68 KiB of 
 void text_causal_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
 // in place: act 0 = quick-GELU x sigmoid(1.702 x), 1 = erf GELU; count a multiple of 4
 void text_activation(float* x, long long count, int act, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// ViT image classifier (vit.hip; e2v_image_classify): fp32 in every compute mode.  LayerNorm, the linears and the GELU are
+// norm.hip's, igemm.hip's and text.hip's.
+// ---------------------------------------------------------------------------------------
+struct FrameSrc;                            // (below: the input description e2v_frame_metrics shares)
+// One axis of Pillow's antialiased BILINEAR resize as a table (host arithmetic; e2v_image_resize_table)
+struct ResizeAxis {
+    int in = 0, out = 0, ksize = 0;
+    std::vector<int> first, count;          // [out]
+    std::vector<int> coeff;                 // [out][ksize], 22-bit fixed point
+};
+ResizeAxis resize_axis(int in_size, int out_size);
+// The tables of one (H, W) -> S x S resize and the pixel table, as the preprocess kernel reads them: one block of 32-bit words,
+// [hfirst S | hcount S | vfirst S | vcount S | hcoeff S * kh | vcoeff S * kv | lut 3 * 256 floats]
+struct ImagePrepPlan {
+    int H = 0, W = 0, S = 0, kh = 0, kv = 0;
+    bool vfirst = false;                    // Pillow resizes an image more than 100 times as tall as wide vertically first
+    int band = 0, band_rows = 0;            // output rows per workgroup and the most source rows such a band reads (0: does not fit)
+    std::vector<int> words;
+};
+constexpr int kImagePrepLdsBytes = 48 * 1024;     // the band of horizontally resized rows a workgroup keeps
+ImagePrepPlan image_prep_plan(int H, int W, int S, int P, const float* lut768);
+// frames (FrameSrc: fp32 quantised at load or bytes, planar [n,3,F,H,W] or channels-last [n,F,H,W,3]) -> rows [n*F*(S/P)^2][3*P*P];
+// `plan_dev`: plan.words on the device
+void image_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const ImagePrepPlan& plan, const int* plan_dev, int P,
+                      float* rows, hipStream_t s);
+// x[i][0][:] = cls + pos[0], x[i][1 + p][:] = patches[i * (T - 1) + p][:] + pos[1 + p]   (C a multiple of 4)
+void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s);
+// non-causal self-attention over each of B images of T tokens, head dim 64, scale 64^-0.5; layouts as text_causal_attention.
+// K and V of an (image, head) live in LDS at the 68-float stride, which bounds T:
+constexpr int kImageAttnMaxT = 288;     // 2 x 288 rows x 272 bytes = 153 KiB of the CU's 160; up to five keys per lane
+void image_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
+// one wave per image over logits [nimg][ld] (L <= ld columns used): logits_out [nimg][L] (copy), probs = softmax(logits), top3 = the
+// three largest by (value, index) in ascending order; any of the three may be null.  L >= 3.
+void image_head(const float* logits, int ld, int L, int nimg, float* logits_out, float* probs, int* top3, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)

@@ -153,6 +153,24 @@ void e2v_ctx::expected_keys() {
         }
         s.norm(m + "final_layer_norm", C);
     }
+
+    // ---- ViT image classifier ("image." prefix; the keys of the google/vit-base-patch16-224 checkpoint, ViTForImageClassification) ----
+    if (cfg.vit_layers > 0) {
+        const int C = cfg.vit_hidden, I = cfg.vit_intermediate, P = cfg.vit_patch_size;
+        const std::string m = "image.vit.";
+        s.add(m + "embeddings.cls_token", {1, 1, C});
+        s.add(m + "embeddings.position_embeddings", {1, image_tokens(), C});
+        s.conv(m + "embeddings.patch_embeddings.projection", C, 3, P);
+        for (int i = 0; i < cfg.vit_layers; ++i) {
+            const std::string l = m + "encoder.layer." + std::to_string(i);
+            for (const char* n : {"query", "key", "value"}) s.lin(l + ".attention.attention." + n, C, C);
+            s.lin(l + ".attention.output.dense", C, C);
+            s.lin(l + ".intermediate.dense", I, C); s.lin(l + ".output.dense", C, I);
+            s.norm(l + ".layernorm_before", C); s.norm(l + ".layernorm_after", C);
+        }
+        s.norm(m + "layernorm", C);
+        s.lin("image.classifier", cfg.vit_num_labels, C);
+    }
 }
 
 // a block of a weight layout, owned by the part its caller selected (AllocPart); guarded, and its payload poisoned before the first
@@ -486,6 +504,7 @@ void e2v_ctx::finalize(int which) {
     // everything that can refuse the call is checked BEFORE a part is freed: a failed finalize leaves the context as it was
     E2V_REQUIRE(!(which & 4) || (cfg.sem_in_features > 0 && cfg.sem_hidden > 0), E2V_ESTATE, "the config has no semantic predictor");
     E2V_REQUIRE(!(which & 8) || cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
+    E2V_REQUIRE(!(which & 16) || cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
     for (const auto& k : keys)
         if (which & key_part(k)) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
@@ -600,6 +619,53 @@ void e2v_ctx::finalize(int which) {
         P.f32_only = false;
         text = std::move(t);
     }
+    if (which & 16) {
+        free_part(4);
+        alloc_part = 4;
+        P.f32_only = true;
+        ImageW v;
+        const std::string m = "image.vit.";
+        const int C = cfg.vit_hidden, T = image_tokens(), K = 3 * cfg.vit_patch_size * cfg.vit_patch_size, L = cfg.vit_num_labels;
+        const WTensor& cls = P.t(m + "embeddings.cls_token");
+        const WTensor& pos = P.t(m + "embeddings.position_embeddings");
+        v.cls = cls.d(); v.pos = pos.d();
+        P.bind_raw(m + "embeddings.cls_token", cls.d(), 1, C);
+        P.bind_raw(m + "embeddings.position_embeddings", pos.d(), T, C);
+        {   // the patch convolution [C][3][P][P] is the linear [C][3 P P] over the patch rows as it stands
+            const std::string n = m + "embeddings.patch_embeddings.projection";
+            const WTensor& w = P.t(n + ".weight");
+            P.bind_raw(n + ".weight", w.d(), C, K);
+            P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
+            v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
+        }
+        for (int i = 0; i < cfg.vit_layers; ++i) {
+            const std::string l = m + "encoder.layer." + std::to_string(i);
+            TextLayerW w;
+            w.ln1 = P.norm(l + ".layernorm_before"); w.ln2 = P.norm(l + ".layernorm_after");
+            w.qkv = P.fuse_rows({l + ".attention.attention.query", l + ".attention.attention.key", l + ".attention.attention.value"}, true);
+            w.out = P.lin(l + ".attention.output.dense");
+            w.fc1 = P.lin(l + ".intermediate.dense"); w.fc2 = P.lin(l + ".output.dense");
+            v.layers.push_back(w);
+        }
+        v.ln_f = P.norm(m + "layernorm");
+        if (L % 4 == 0) {
+            v.head = P.lin("image.classifier");
+        } else {                                             // rows of zeros up to a multiple of 4: the linear kernels store quads
+            const int Lp = (L + 3) / 4 * 4;
+            const WTensor& w = P.t("image.classifier.weight");
+            float* d = dev_alloc((size_t)Lp * C);
+            float* b = dev_alloc(Lp);
+            E2V_HIP(hipMemsetAsync(d, 0, (size_t)Lp * C * sizeof(float), P.s));
+            E2V_HIP(hipMemsetAsync(b, 0, (size_t)Lp * sizeof(float), P.s));
+            copy_rows(w.d(), C, d, C, L, C, P.s);
+            copy_rows(P.t("image.classifier.bias").d(), L, b, L, 1, L, P.s);
+            P.bind_lin("image.classifier.weight", d, 0);
+            P.bind_raw("image.classifier.bias", b, 1, L);
+            v.head = P.mk_lin(d, b, C, Lp);
+        }
+        P.f32_only = false;
+        image = std::move(v);
+    }
     alloc_part = -1;
     resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
@@ -624,6 +690,10 @@ void e2v_ctx::finalize(int which) {
             if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
             continue;
         }
+        if (part == 16) {                        // the same for query / key / value, and for a classifier that was padded
+            if (k.find(".attention.attention.") != std::string::npos || (k.rfind("image.classifier.", 0) == 0 && cfg.vit_num_labels % 4 != 0)) drop(k);
+            continue;
+        }
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
@@ -635,6 +705,7 @@ void e2v_ctx::finalize(int which) {
     if (which & 2) vae_ready = true;
     if (which & 4) sem_ready = true;
     if (which & 8) text_ready = true;
+    if (which & 16) image_ready = true;
 }
 
 // =====================================================================================================
@@ -681,6 +752,8 @@ void e2v_ctx::resolve_bindings() {
     visit(vae, fl, fc);
     for (auto& l : sem) fl(l);
     for (auto& l : text.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
+    for (auto& l : image.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
+    fl(image.patch); fl(image.head);
     for (auto& kv : bind) {
         WBind& b = kv.second;
         if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
@@ -1485,5 +1558,69 @@ void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t 
         x = R.linear(l.fc2, f.p, I, M, plus(x));
     }
     ln(text.ln_f, x.p, out);
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// ViTImageProcessor + ViTForImageClassification.forward(pixel_values).logits (transformers: ViTEmbeddings -- patch convolution,
+// class token, position embeddings --, pre-LN encoder layers without a mask, the final LayerNorm, the classifier on the class row),
+// then the softmax and the top-3 indices img_classify_metric takes from it (40_class_run_metrics.py:95-98).  fp32 rows and fp32
+// arithmetic whatever the context's compute mode, as text_encode.  Images are walked in chunks of E2V_VIT_CHUNK (64): every kernel
+// here computes a row from that row's image alone and in an order that does not depend on the row count, so the chunking does not
+// show in the result.
+// -----------------------------------------------------------------------------------------------------
+const ImagePrepPlan& e2v_ctx::prep_plan(int H, int W) {
+    const std::array<int, 2> key{H, W};
+    auto it = prep_plans.find(key);
+    if (it == prep_plans.end()) {
+        if (prep_plans.size() >= 64) prep_plans.clear();
+        it = prep_plans.emplace(key, image_prep_plan(H, W, cfg.vit_image_size, cfg.vit_patch_size, image_lut)).first;
+    }
+    return it->second;
+}
+
+void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, float* logits, float* probs, int* top3, hipStream_t s) {
+    E2V_REQUIRE(image_ready, E2V_ESTATE, "image classifier weights are not finalized");
+    Runner R{this, s, false};
+    const int C = cfg.vit_hidden, I = cfg.vit_intermediate, P = cfg.vit_patch_size, L = cfg.vit_num_labels;
+    const int T = image_tokens(), K = 3 * P * P;
+    const float eps = cfg.vit_norm_eps;
+    const ImagePrepPlan& plan = prep_plan(H, W);
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
+    Act tables(pool, (int64_t)plan.words.size(), 1);
+    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
+    static const int* const chunk_knob = knob("E2V_VIT_CHUNK", 64);
+    const int chunk = std::min(std::max(*chunk_knob, 1), 4096);
+    const long long total = (long long)n * F;
+    for (long long i0 = 0; i0 < total; i0 += chunk) {
+        const int ni = (int)std::min<long long>(chunk, total - i0);
+        const int64_t M = (int64_t)ni * T;
+        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
+        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
+        Act x(pool, M, C);
+        {
+            Act rows(pool, (int64_t)ni * (T - 1), K);
+            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
+            Act patches = R.linear(image.patch, rows.p, K, (int64_t)ni * (T - 1), R.f32_rows());
+            image_embed(patches.p, image.cls, image.pos, x.p, ni, T, C, s);
+        }
+        for (const TextLayerW& l : image.layers) {
+            Act h(pool, M, C);
+            ln(l.ln1, x.p, h.p);
+            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
+            Act a(pool, M, C);
+            image_attention(qkv.p, 3 * C, a.p, C, ni, T, cfg.vit_heads, s);
+            x = R.linear(l.out, a.p, C, M, plus(x));
+            ln(l.ln2, x.p, h.p);
+            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
+            text_activation(f.p, M * I, 1, s);
+            x = R.linear(l.fc2, f.p, I, M, plus(x));
+        }
+        Act cls(pool, ni, C);                                   // the final LayerNorm on the class rows only (row stride T * C)
+        layernorm(x.p, T * C, image.ln_f.g, image.ln_f.b, cls.p, C, ni, C, eps, s);
+        Act lg = R.linear(image.head, cls.p, C, ni, R.f32_rows());
+        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
+                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+    }
     E2V_HIP(hipGetLastError());
 }

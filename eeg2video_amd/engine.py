@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import TEXT_ACTS, SemanticConfig, TextConfig, UNetConfig, VAEConfig
+from .weights import TEXT_ACTS, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -29,17 +29,19 @@ def _stream() -> int:
 
 class Engine:
     """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
-    the ``CLIPTextModel`` one."""
+    the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one."""
 
-    UNET, VAE, SEMANTIC, TEXT = 1, 2, 4, 8
+    UNET, VAE, SEMANTIC, TEXT, IMAGE = 1, 2, 4, 8, 16
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
-                 sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None):
+                 sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None,
+                 image_cfg: Optional[ImageConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
         self.lib = _lib.load()
         self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
+        self.image_cfg = image_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -67,6 +69,8 @@ class Engine:
         cfg.sem_in_features, cfg.sem_hidden, cfg.sem_tokens = sem_cfg.in_features, sem_cfg.hidden, sem_cfg.tokens
         if text_cfg is not None:
             fill_text_config(cfg, text_cfg)
+        if image_cfg is not None:
+            fill_image_config(cfg, image_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
         st = self.lib.e2v_create(C.byref(cfg), device, C.byref(ctx))
@@ -200,10 +204,10 @@ class Engine:
                                              self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
         return out
 
-    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text."}
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image."}
 
     def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
-        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT``) as the device holds it NOW -- after any
+        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE``) as the device holds it NOW -- after any
         ``update_state_dict`` --, an ``OrderedDict`` in ``expected_keys()`` order with ``prefix`` (the one ``load_state_dict`` adds:
         ``'vae.'``, ``'semantic.'``, ``'text.'``) stripped from the names.  ``device``: ``'cuda'`` (tensors on the engine's device) or
         ``'cpu'``."""
@@ -214,7 +218,7 @@ class Engine:
         elif dev.type != "cpu":
             raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
         own = self._PART_PREFIX.get(part, "")
-        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT) or prefix not in ("", own):
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE) or prefix not in ("", own):
             raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
         foreign = tuple(self._PART_PREFIX.values())
         out = OrderedDict()
@@ -590,6 +594,40 @@ class Engine:
                                                mse.data_ptr(), _stream()))
         return ssim, mse
 
+    def _frames_arg(self, frames: torch.Tensor, channels_last: bool, name: str = "frames"):
+        """A batch of RGB clips as the C ABI takes it: ``(tensor on the device, kind, (n, F, H, W))``"""
+        t = frames
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"`{name}` has to be of type `torch.Tensor` but is {type(t)}")
+        if t.dtype not in (torch.uint8, torch.float32):
+            raise ValueError(f"`{name}` has to be uint8 or float32, not {t.dtype}")
+        if t.dim() == 4:
+            t = t[None]
+        if t.dim() != 5 or t.shape[4 if channels_last else 1] != 3:
+            raise ValueError(f"`{name}`: expected RGB clips [n,3,F,H,W] (channels_last: [n,F,H,W,3]) or one clip, got shape {tuple(frames.shape)}")
+        t = t.to(self.device).contiguous()
+        n, f, h, w = (t.shape[0], t.shape[1], t.shape[2], t.shape[3]) if channels_last else (t.shape[0], t.shape[2], t.shape[3], t.shape[4])
+        kind = (_lib.E2V_FRAMES_U8 if t.dtype == torch.uint8 else _lib.E2V_FRAMES_F32) | (_lib.E2V_FRAMES_CHANNELS_LAST if channels_last else 0)
+        return t, kind, (n, f, h, w)
+
+    def classify_frames(self, frames: torch.Tensor, channels_last: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``ViTImageProcessor`` + ``ViTForImageClassification`` over every frame (``e2v_image_classify``; the classifier half of the
+        reference's ``img_classify_metric``, ``40_class_run_metrics.py:86-98``) -> ``(logits, probs, top3)``: fp32 ``[n*F, labels]``
+        twice and int32 ``[n*F, 3]``, the indices of the three largest logits in ascending order (``argsort(-1)[-3:]``), on the engine's
+        device, frame ``f`` of clip ``i`` at row ``i*F + f``.  ``frames``: uint8, or float32 in ``[0,1]`` (quantised as
+        ``frames_to_uint8`` does), planar ``[n,3,F,H,W]`` (``[3,F,H,W]``: one clip) or, with ``channels_last``, ``[n,F,H,W,3]``; host
+        tensors are copied over.  fp32 arithmetic whatever the engine's compute dtype."""
+        if self.image_cfg is None:
+            raise RuntimeError("this engine was built without an image classifier (Engine(..., image_cfg=ImageConfig()))")
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        labels = self.image_cfg.num_labels
+        logits = torch.empty((n * f, labels), device=self.device, dtype=torch.float32)
+        probs = torch.empty((n * f, labels), device=self.device, dtype=torch.float32)
+        top3 = torch.empty((n * f, 3), device=self.device, dtype=torch.int32)
+        self._check(self.lib.e2v_image_classify(self.ctx, t.data_ptr(), kind, n, f, h, w, logits.data_ptr(), probs.data_ptr(),
+                                                top3.data_ptr(), _stream()))
+        return logits, probs, top3
+
     # ------------------------------------------------------------------ the one exchange of the path (SURVEY 8(e))
     def comm_init(self, group=None) -> int:
         """Open the library's own RCCL communicator over the ranks of the (already initialised) ``torch.distributed`` group:
@@ -744,6 +782,28 @@ class Engine:
                                                      heads, _stream()))
         return out
 
+    def op_image_preprocess(self, frames, *, size, patch, lut=None, channels_last=False, out=None):
+        """``e2v_op_image_preprocess``: clips -> the patch rows ``[n*F*(size/patch)^2, 3*patch^2]`` of the classifier's preprocess.
+        ``lut``: ``[3,256]`` fp32 pixel values of a byte per channel (``None``: the engine's image config)."""
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        lut_p = None
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(3, 256))
+            lut_p = lut.ctypes.data_as(C.POINTER(C.c_float))
+        out = self._op_out(out, (n * f * (size // patch) ** 2, 3 * patch * patch))
+        self._check(self.lib.e2v_op_image_preprocess(self.ctx, t.data_ptr(), kind, n, f, h, w, size, patch, lut_p, out.data_ptr(), _stream()))
+        return out
+
+    def op_image_attention(self, qkv, *, B, T, heads, out=None):
+        """``e2v_op_image_attention``: ``qkv`` ``[B*T, 3*64*heads]`` -> ``[B*T, 64*heads]``, non-causal, fp32 in every mode."""
+        qkv = self._dev(qkv, "qkv")
+        if qkv.dim() != 2 or qkv.shape[0] != B * T or qkv.shape[1] != 3 * 64 * heads:
+            raise ValueError(f"expected qkv [B*T, 3*64*heads] = [{B * T}, {3 * 64 * heads}], got {tuple(qkv.shape)}")
+        out = self._op_out(out, (B * T, 64 * heads), strided=True)
+        self._check(self.lib.e2v_op_image_attention(self.ctx, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B, T, heads,
+                                                    _stream()))
+        return out
+
     def op_to_channels_last(self, x, *, Cpad=None, out=None):
         """``[n, C, FHW]`` -> channel-last rows ``[n * FHW, Cpad]`` (``e2v_op_to_channels_last``; columns C.. are written as zeros)."""
         n, c, fhw = x.shape
@@ -785,6 +845,29 @@ def fill_text_config(cfg: "_lib.E2VConfig", text_cfg: TextConfig) -> None:
     cfg.text_vocab_size, cfg.text_hidden, cfg.text_heads = text_cfg.vocab_size, text_cfg.hidden, text_cfg.heads
     cfg.text_layers, cfg.text_intermediate, cfg.text_max_positions = text_cfg.layers, text_cfg.intermediate, text_cfg.max_positions
     cfg.text_act, cfg.text_norm_eps = TEXT_ACTS[text_cfg.hidden_act], text_cfg.layer_norm_eps
+
+
+def fill_image_config(cfg: "_lib.E2VConfig", image_cfg: ImageConfig) -> None:
+    """The ``vit_*`` fields of an ``e2v_config`` from an ``ImageConfig``."""
+    cfg.vit_hidden, cfg.vit_heads, cfg.vit_layers = image_cfg.hidden, image_cfg.heads, image_cfg.layers
+    cfg.vit_intermediate, cfg.vit_image_size, cfg.vit_patch_size = image_cfg.intermediate, image_cfg.image_size, image_cfg.patch_size
+    cfg.vit_num_labels, cfg.vit_norm_eps, cfg.vit_rescale = image_cfg.num_labels, image_cfg.layer_norm_eps, float(image_cfg.rescale_factor)
+    cfg.vit_mean = (C.c_float * 3)(*[float(v) for v in image_cfg.image_mean])
+    cfg.vit_std = (C.c_float * 3)(*[float(v) for v in image_cfg.image_std])
+
+
+def image_resize_table(in_size: int, out_size: int):
+    """One axis of Pillow's antialiased BILINEAR resize (``e2v_image_resize_table``; host arithmetic, no GPU): ``(first, count, coeff)``
+    -- ``first``, ``count`` int32 ``[out_size]``, ``coeff`` int32 ``[out_size, ksize]`` in 22-bit fixed point."""
+    lib = _lib.load()
+    ksize = C.c_int(0)
+    if lib.e2v_image_resize_table(in_size, out_size, None, None, None, C.byref(ksize)) != _lib.E2V_OK:
+        raise ValueError(f"image_resize_table({in_size}, {out_size}): sizes must be at least 1")
+    first, count = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
+    coeff = np.zeros((out_size, ksize.value), dtype=np.int32)
+    lib.e2v_image_resize_table(in_size, out_size, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
+                               coeff.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ksize))
+    return first, count, coeff
 
 
 def named_tensors(source, only_trainable: bool = False):

@@ -1,14 +1,18 @@
 """Frame metrics of the reference's scoring script (``EEG2Video/40_class_run_metrics.py:190-233``) on the device: the same names and
 signatures -- ``channel_last``, ``ssim_metric``, ``mse_metric``, ``ssim_score_only``, ``mse_score_only`` -- over ``Engine.frame_metrics``
 (``e2v_frame_metrics``: skimage's ``structural_similarity(data_range=255, channel_axis=-1)`` and ``mse_loss(img1 / 255, img2 / 255)``,
-one launch per clip instead of one host call per frame).  The classifier metrics of that script (``img_classify_metric``,
-``video_classify_metric``, CLIP score) need hub models and are not here.
+one launch per clip instead of one host call per frame) -- and its image N-way accuracy, ``n_way_top_k_acc`` and
+``img_classify_metric`` (``:57-105``), over ``Engine.classify_frames`` (``e2v_image_classify``: the ViT classifier of every frame of a
+clip in one call, fp32, instead of one fp16 forward per image).  ``video_classify_metric`` (VideoMAE) and the CLIP score are not here.
 
-Every function takes an ``engine=`` keyword; by default one ``Engine()`` without weights is made on first use and kept.
+The frame metrics take an ``engine=`` keyword; by default one ``Engine()`` without weights is made on first use and kept.
+``img_classify_metric`` takes a built classifier (``model=``) or a LOCAL checkpoint directory (``cache_dir=``).
 """
 from __future__ import annotations
 
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple, Union
+
+import os
 
 import numpy as np
 import torch
@@ -73,3 +77,58 @@ def mse_score_only(pred_videos, gt_videos, engine=None, **kwargs) -> Tuple[float
     """``[f,h,w,3]`` or ``[f,c,h,w]`` uint8 clips -> (mean, std) of the per-frame MSE of the pixel values / 255"""
     s = _scores(channel_last(np.asarray(pred_videos)), channel_last(np.asarray(gt_videos)), engine)[1]
     return np.mean(s), np.std(s)
+
+
+def n_way_top_k_acc(pred, class_id, n_way: int, num_trials: int = 40, top_k: int = 1) -> Tuple[float, float]:
+    """``40_class_run_metrics.py:57-70``: ``num_trials`` times, ``n_way - 1`` distractor classes are drawn and the trial counts as
+    correct when a ground-truth class is among the ``top_k`` of the picked ``pred`` values -> ``(accuracy, its binomial std)``.
+    ``pred``: ``[classes]`` scores (tensor or array); ``class_id``: one id or several (the trial is correct if ANY of them is).
+    The ``np.random.choice`` calls are the reference's, in its order, so a seeded run draws the same distractors; everything else is
+    vectorised over the trials.  A ground truth is in the top ``top_k`` when fewer than ``top_k`` picked values are >= its own."""
+    if isinstance(class_id, (int, np.integer)):
+        class_id = [int(class_id)]
+    p = np.asarray(pred.detach().cpu() if isinstance(pred, torch.Tensor) else pred).reshape(-1)
+    ids = [int(i) for i in (class_id.detach().cpu().reshape(-1).tolist() if isinstance(class_id, torch.Tensor) else class_id)]
+    pick_range = [i for i in np.arange(len(p)) if i not in ids]
+    picked = np.stack([np.random.choice(pick_range, n_way - 1, replace=False) for _ in range(num_trials)])      # [trials, n_way - 1]
+    beaten = (p[picked][:, None, :] >= p[ids][None, :, None]).sum(-1)                                           # [trials, ids]
+    corrects = int((beaten < top_k).any(-1).sum())
+    acc = corrects / num_trials
+    return acc, np.sqrt(acc * (1 - acc) / num_trials)
+
+
+_classifiers = {}
+
+
+def _classifier(cache_dir: str, device):
+    key = os.path.abspath(cache_dir)
+    if key not in _classifiers:
+        from .image_classifier import ViTForImageClassification
+        index = torch.device(device).index if device is not None else None
+        _classifiers[key] = ViTForImageClassification.from_pretrained(cache_dir, device=index or 0)
+    return _classifiers[key]
+
+
+def img_classify_metric(pred_videos, gt_videos, n_way: int = 50, num_trials: int = 100, top_k: int = 1, cache_dir: str = ".cache",
+                        device: Optional[str] = "cuda", return_std: bool = False,
+                        model=None) -> Union[List[float], Tuple[List[float], List[float]]]:
+    """``40_class_run_metrics.py:72-105``: per frame, the N-way top-k accuracy of the generated frame's class probabilities against the
+    three most likely classes of the ground-truth frame -> the list of accuracies (``return_std``: and the list of their stds).
+    ``pred_videos`` / ``gt_videos``: ``[f,h,w,3]`` pixel values 0..255 (arrays or tensors, on the device or not).  ``model``: a built
+    ``eeg2video_amd.image_classifier.ViTForImageClassification``; else ``cache_dir`` must be a LOCAL checkpoint directory of one (the
+    reference names the hub model there; nothing is fetched here), loaded once per directory.  Each clip goes through the device in
+    ONE ``classify_frames`` call -- not one forward per frame -- and only the probabilities and the top-3 indices come back."""
+    assert n_way > top_k
+    clf = model if model is not None else _classifier(cache_dir, device)
+    pred = clf.classify(_frames(pred_videos), channels_last=True)[1].cpu().numpy()
+    gt_ids = clf.classify(_frames(gt_videos), channels_last=True)[2].cpu().numpy()
+    if len(pred) != len(gt_ids):
+        raise ValueError(f"clips differ: {len(pred)} generated frames against {len(gt_ids)} ground-truth frames")
+    acc_list, std_list = [], []
+    for p, ids in zip(pred, gt_ids):
+        acc, std = n_way_top_k_acc(p, [int(i) for i in ids], n_way, num_trials, top_k)
+        acc_list.append(acc)
+        std_list.append(std)
+    if return_std:
+        return acc_list, std_list
+    return acc_list

@@ -173,6 +173,74 @@ def text_param_spec(cfg: TextConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     return spec
 
 
+@dataclass(frozen=True)
+class ImageConfig:
+    """``ViTForImageClassification`` (``transformers`` ``ViTConfig``: ``hidden_size``, ``num_attention_heads``, ``num_hidden_layers``,
+    ``intermediate_size``, ``image_size``, ``patch_size``, the number of labels, ``layer_norm_eps``) with its ``ViTImageProcessor``
+    (``preprocessor_config.json``: ``rescale_factor``, ``image_mean``, ``image_std``; the resize is Pillow's BILINEAR to
+    ``image_size`` x ``image_size``); defaults are ``google/vit-base-patch16-224``, the classifier of the reference's
+    ``img_classify_metric``.  The head dim is 64 (``hidden == 64 * heads``), the activation the erf GELU."""
+    hidden: int = 768
+    heads: int = 12
+    layers: int = 12
+    intermediate: int = 3072
+    image_size: int = 224
+    patch_size: int = 16
+    num_labels: int = 1000
+    layer_norm_eps: float = 1e-12
+    rescale_factor: float = 1 / 255
+    image_mean: Tuple[float, float, float] = (0.5, 0.5, 0.5)
+    image_std: Tuple[float, float, float] = (0.5, 0.5, 0.5)
+
+    @property
+    def tokens(self) -> int:
+        return (self.image_size // self.patch_size) ** 2 + 1
+
+
+#: 197 tokens -- the production count -- for a few hundred thousand parameters (tests/golden/vit_tiny.npz)
+TINY_IMAGE = ImageConfig(hidden=128, heads=2, layers=2, intermediate=256, image_size=112, patch_size=8, num_labels=50)
+
+
+def image_param_spec(cfg: ImageConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of the ``ViTForImageClassification`` state dict as the ``google/vit-base-patch16-224`` checkpoint keys it; the
+    engine holds them under ``image.``."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c = cfg.hidden
+    spec["vit.embeddings.cls_token"] = (1, 1, c)
+    spec["vit.embeddings.position_embeddings"] = (1, cfg.tokens, c)
+    _conv(spec, "vit.embeddings.patch_embeddings.projection", c, 3, cfg.patch_size)
+    for i in range(cfg.layers):
+        p = f"vit.encoder.layer.{i}"
+        for n in ("query", "key", "value"):
+            _lin(spec, f"{p}.attention.attention.{n}", c, c)
+        _lin(spec, f"{p}.attention.output.dense", c, c)
+        _lin(spec, f"{p}.intermediate.dense", cfg.intermediate, c)
+        _lin(spec, f"{p}.output.dense", c, cfg.intermediate)
+        _norm(spec, f"{p}.layernorm_before", c)
+        _norm(spec, f"{p}.layernorm_after", c)
+    _norm(spec, "vit.layernorm", c)
+    _lin(spec, "classifier", cfg.num_labels, c)
+    return spec
+
+
+#: how ``transformers`` 5 spells the per-layer tensors of the same model (``vit.layers.{i}.`` instead of ``vit.encoder.layer.{i}.``)
+_VIT_V5_NAMES = (("attention.q_proj.", "attention.attention.query."), ("attention.k_proj.", "attention.attention.key."),
+                 ("attention.v_proj.", "attention.attention.value."), ("attention.o_proj.", "attention.output.dense."),
+                 ("mlp.fc1.", "intermediate.dense."), ("mlp.fc2.", "output.dense."))
+
+
+def image_checkpoint_key(name: str) -> str:
+    """A ``ViTForImageClassification`` state-dict name in either spelling -> the checkpoint's (``image_param_spec``)."""
+    if name.startswith("vit.layers."):
+        rest = name[len("vit.layers."):]
+        for new, old in _VIT_V5_NAMES:
+            if new in rest:
+                rest = rest.replace(new, old)
+                break
+        return "vit.encoder.layer." + rest
+    return name
+
+
 #: tiny configs used by the parity tests (oracle finishes in well under a second).
 TINY_UNET = UNetConfig(sample_size=8, block_out_channels=(64, 128, 256, 256), cross_attention_dim=64)
 TINY_VAE = VAEConfig(block_out_channels=(32, 64, 64, 64), norm_num_groups=8)

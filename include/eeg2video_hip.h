@@ -85,6 +85,19 @@ typedef struct {
     int text_vocab_size, text_hidden, text_heads, text_layers, text_intermediate, text_max_positions;
     int text_act;                           /* 0 = quick_gelu (x sigmoid(1.702 x)), 1 = gelu (erf) */
     float text_norm_eps;
+    /* ViT image classifier (transformers ViTForImageClassification, config.json of google/vit-base-patch16-224: hidden_size,
+     * num_attention_heads, num_hidden_layers, intermediate_size, image_size, patch_size, the number of labels, layer_norm_eps: 768, 12,
+     * 12, 3072, 224, 16, 1000, 1e-12; erf GELU, biased q / k / v) and its ViTImageProcessor (preprocessor_config.json: rescale_factor
+     * 1 / 255, image_mean, image_std 0.5 each; the resize is Pillow's BILINEAR to image_size x image_size).  All zero (the default):
+     * the context has no classifier and expects none of its keys.  vit_layers > 0: vit_hidden must be 64 * vit_heads, a multiple of 4
+     * and at most 1280 (the LayerNorm kernel), vit_intermediate a multiple of 4, vit_image_size a multiple of vit_patch_size,
+     * 3 * vit_patch_size^2 a multiple of 4, (vit_image_size / vit_patch_size)^2 + 1 tokens at most 288 (the attention kernel keeps K and
+     * V of an image's head in LDS), vit_num_labels at least 3 (the top-3 head), every vit_std non-zero.  Appended after the text encoder:
+     * e2v_config_size() tells a binding which layout a library has. */
+    int vit_hidden, vit_heads, vit_layers, vit_intermediate, vit_image_size, vit_patch_size, vit_num_labels;
+    float vit_norm_eps;
+    double vit_rescale;                     /* pixel value of a byte b: ((float)(b * vit_rescale) - vit_mean[c]) / vit_std[c], in fp32 */
+    float vit_mean[3], vit_std[3];
 } e2v_config;
 
 void e2v_default_config(e2v_config* cfg);
@@ -121,6 +134,11 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * "self_attn.{q,k,v,out}_proj.{weight,bias}", "layer_norm{1,2}.{weight,bias}", "mlp.fc{1,2}.{weight,bias}", and
  * "text.text_model.final_layer_norm.{weight,bias}"; q / k / v become one [3C][C] matrix with its [3C] bias).  The text part keeps
  * fp32 matrices only, in every compute mode (E2V_F32X3 included).
+ * bit 4 (16) = ViT image classifier (config with vit_layers > 0; the keys of the google/vit-base-patch16-224 checkpoint under the
+ * prefix "image.": "image.vit.embeddings.{cls_token,position_embeddings}", "image.vit.embeddings.patch_embeddings.projection.{weight,bias}",
+ * per layer "image.vit.encoder.layer.{i}." "attention.attention.{query,key,value}.{weight,bias}", "attention.output.dense.*",
+ * "layernorm_{before,after}.*", "intermediate.dense.*", "output.dense.*", and "image.vit.layernorm.*", "image.classifier.*";
+ * query / key / value become one [3C][C] matrix with its [3C] bias).  fp32 matrices only, as the text part.
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -137,7 +155,9 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * the new; no device synchronisation, and no allocation once the workspace of such a call is cached (e2v_device_bytes does not move).
  * Part not finalized: E2V_ESTATE (use e2v_load_tensor); unknown key / shape mismatch: E2V_ENOWEIGHT as e2v_load_tensor.
  * A "text." key: E2V_EINVAL -- the text encoder is frozen on this path (train_finetune_videodiffusion.py:115
- * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8). */
+ * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8).
+ * An "image." key: E2V_EINVAL as well -- the classifier is a frozen yardstick (40_class_run_metrics.py:70-72 loads it and only
+ * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16). */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
@@ -163,7 +183,7 @@ enum {
  * finalize makes: a 3x3 conv [Cout,Cin,3,3] from the torch-layout weight the context keeps, a row range of a fused QKV / KV matrix
  * (and of its fused bias), the GEGLU row interleave of ff.net.0.proj undone, the K-padded first layer of the Semantic Predictor
  * without its padding columns, plain linears, 1x1 convs, norm affines and embeddings as they are.
- * `key`: any expected key (UNet, "vae.", "semantic.", "text.": reading a text tensor is allowed, only updating one is refused).
+ * `key`: any expected key (UNet, "vae.", "semantic.", "text.", "image.": reading a text or classifier tensor is allowed, only updating one is refused).
  * `form`: which stored form is read -- 0 or E2V_FORM_F32: the fp32 values (every tensor has them).  For the weight of a linear
  * (or 1x1 conv) also E2V_FORM_BF16 / E2V_FORM_F16: that stored 16-bit copy, widened exactly, and E2V_FORM_X3: (p0 + p1) + p2 of the
  * three planes in fp32, which is the fp32 weight exactly.  A form e2v_op_weight_forms does not report for the key: E2V_ESTATE ("form
@@ -365,6 +385,33 @@ e2v_status e2v_frames_to_uint8(e2v_ctx* ctx, const float* videos, uint8_t* out, 
 enum { E2V_FRAMES_F32 = 0, E2V_FRAMES_U8 = 1, E2V_FRAMES_CHANNELS_LAST = 2 };   /* kind = type | layout bit */
 e2v_status e2v_frame_metrics(e2v_ctx* ctx, const void* a, int a_kind, const void* b, int b_kind,
                              int n, int F, int C, int H, int W, float* ssim, float* mse, e2v_stream stream);
+
+/* rank 6 -- replaces the classifier half of img_classify_metric (EEG2Video/40_class_run_metrics.py:86-98, called per clip at :302-328):
+ * ViTImageProcessor(images=frame) and ViTForImageClassification(...).logits of every frame, its softmax and the indices of the three
+ * largest logits (`.argsort(-1)[-3:]`, :97), on the device, where the frames are -- one call for a whole batch of clips instead of one
+ * fp16 forward per image.  The N-way trial loop on top of it (n_way_top_k_acc, :57-70) stays on the host: eeg2video_amd/metrics.py.
+ * frames, kind: as e2v_frame_metrics -- E2V_FRAMES_F32 (4-byte aligned) or E2V_FRAMES_U8 (bytes of ANY alignment), planar [n,3,F,H,W]
+ * or, with E2V_FRAMES_CHANNELS_LAST, [n,F,H,W,3].  An fp32 input is quantised to the bytes of e2v_frames_to_uint8 first (clamped to
+ * [0,1], NaN -> 0); everything after that is defined on bytes.
+ * Preprocess: Pillow's Image.resize((S, S), BILINEAR) with S = vit_image_size -- the two-pass antialiased triangle filter in 22-bit
+ * fixed point, horizontal pass first, the intermediate rounded to bytes (e2v_image_resize_table of eeg2video_hip_ops.h is one axis of
+ * it) -- then the pixel value of the config (vit_rescale, vit_mean, vit_std), bit-identical to ViTImageProcessor on Pillow 12.
+ * Model: patch embedding, class token, position embeddings, vit_layers pre-LN encoder layers (non-causal attention, head dim 64,
+ * erf GELU), the final LayerNorm on the class row, the classifier.  ARITHMETIC IS FP32 IN EVERY COMPUTE MODE, as e2v_text_encode:
+ * the same frames give the same bits under E2V_F32, E2V_BF16, E2V_F16 and E2V_F32X3 contexts.  (The reference runs the model in fp16.)
+ * Outputs, per image in n * F order (image f of clip i at i * F + f), device, 4-byte aligned, any two may be NULL but not all three:
+ *   logits [n*F][vit_num_labels];  probs [n*F][vit_num_labels], the fp32 softmax of the logits;
+ *   top3 [n*F][3] int32, the indices of the three largest logits in ASCENDING order of logit -- what argsort(-1)[-3:] gives; equal
+ *   logits rank as a stable ascending sort ranks them (the larger index counts as larger; -0 equals +0).
+ * Large n * F is walked in chunks of images; the result of an image does not depend on the chunking, on n or on its neighbours, and is
+ * bit-identical from run to run.  Stream-ordered, does not synchronise, allocates nothing outside the workspace pool (and nothing
+ * once the blocks of a shape are cached: e2v_device_bytes does not move).
+ * The argument checks come before anything is enqueued and before the state checks: null ctx / frames, all three outputs NULL, a
+ * misaligned output, unknown bits in kind, n < 1: E2V_EINVAL; F, H or W < 1, or a downscale so strong that one output row's source
+ * rows do not fit the preprocess kernel's LDS band (48 KiB: H / S beyond about 100 at S = 224): E2V_ESHAPE.  Then: no classifier in
+ * the config (vit_layers = 0), the part not finalized, or a host-only context: E2V_ESTATE. */
+e2v_status e2v_image_classify(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W,
+                              float* logits, float* probs, int32_t* top3, e2v_stream stream);
 
 /* ---- multi-GPU: the one exchange of the path ------------------------------------------------------------------
  * replaces: nothing in the reference (it generates its 200 clips serially on one GPU, inference_eeg2video.py:90); clips shard

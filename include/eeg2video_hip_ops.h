@@ -85,6 +85,29 @@ e2v_status e2v_op_temporal_attention(e2v_ctx* ctx, const float* qkv, float* out,
 e2v_status e2v_op_causal_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
                                    e2v_stream stream);
 
+/* One axis of Pillow's antialiased BILINEAR resize (src/libImaging/Resample.c: precompute_coeffs + normalize_coeffs_8bpc), as
+ * e2v_image_classify applies it: output sample xx of out_size reads count[xx] <= *ksize input samples starting at first[xx], with the
+ * 22-bit fixed-point weights coeff[xx * *ksize + k] (the rest of a row is zero):
+ *   out[xx] = clip8((2^21 + sum_k coeff[xx * ksize + k] * in[first[xx] + k]) >> 22).
+ * A two-pass resize applies the table of the width to every row, rounds to bytes, then the table of the height to every column.
+ * HOST-ONLY: plain arithmetic, no context, no GPU.  first, count: out_size ints each; coeff: out_size * ksize entries; all three may be
+ * NULL to ask for *ksize = 2 * ceil(max(in_size / out_size, 1)) + 1 alone.  E2V_EINVAL for a null ksize or a size below 1. */
+e2v_status e2v_image_resize_table(int in_size, int out_size, int* first, int* count, int32_t* coeff, int* ksize);
+
+/* The preprocess of e2v_image_classify on its own: n * F images of H x W (frames / kind as there) -> Pillow's bytes at S x S -> the
+ * patch-row matrix rows [n*F*(S/P)^2][3*P*P] fp32 (device, 4-byte aligned), patch (py, px) of image i at row (i*(S/P) + py)*(S/P) + px,
+ * column c*P*P + y*P + x (the flatten of the patch convolution's weight), value host_lut[c * 256 + byte].  host_lut: HOST [3][256]
+ * floats, or NULL for the table of the context's config (E2V_ESTATE if it has no classifier).  S a multiple of P.  Needs no weights. */
+e2v_status e2v_op_image_preprocess(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W, int S, int P,
+                                   const float* host_lut, float* rows, e2v_stream stream);
+
+/* ViTSelfAttention (transformers modeling_vit.py, as e2v_image_classify runs it): NON-causal self-attention over each of B images of
+ * T tokens, head dim 64, scale 64^-0.5, fp32 scores and softmax.  qkv [B*T][ldqkv]: q | k | v, heads * 64 columns each (16-byte
+ * aligned, ldqkv a multiple of 4); out [B*T][ldo], columns 0 .. heads * 64 - 1 written.  1 <= T <= 288 (E2V_ESHAPE): K and V of an
+ * (image, head) live in LDS.  fp32 in every compute mode. */
+e2v_status e2v_op_image_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
+                                  e2v_stream stream);
+
 /* layout conversion at the boundary: [n][C][FHW] <-> [n][FHW][Cpad] */
 e2v_status e2v_op_to_channels_last(e2v_ctx* ctx, const float* in, float* out, int n, int C, int Cpad, int FHW,
                                    e2v_stream stream);
