@@ -35,6 +35,10 @@ class E2VConfig(C.Structure):
         ("vit_hidden", C.c_int), ("vit_heads", C.c_int), ("vit_layers", C.c_int), ("vit_intermediate", C.c_int),
         ("vit_image_size", C.c_int), ("vit_patch_size", C.c_int), ("vit_num_labels", C.c_int), ("vit_norm_eps", C.c_float),
         ("vit_rescale", C.c_double), ("vit_mean", C.c_float * 3), ("vit_std", C.c_float * 3),
+        ("vmae_hidden", C.c_int), ("vmae_heads", C.c_int), ("vmae_layers", C.c_int), ("vmae_intermediate", C.c_int),
+        ("vmae_image_size", C.c_int), ("vmae_patch_size", C.c_int), ("vmae_tubelet_size", C.c_int), ("vmae_num_frames", C.c_int),
+        ("vmae_num_labels", C.c_int), ("vmae_norm_eps", C.c_float), ("vmae_resize_edge", C.c_int),
+        ("vmae_rescale", C.c_double), ("vmae_mean", C.c_float * 3), ("vmae_std", C.c_float * 3),
     ]
 
 
@@ -94,6 +98,7 @@ SIGNATURES = {
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
     "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
     "e2v_image_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
+    "e2v_video_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
     "e2v_cfg_combine": (_i, [_ctx, _p, _p, _f, _p, _i64, _stream]),
     "e2v_lincomb": (_i, [_ctx, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _p, _i64, _stream]),
     "e2v_ddim_next_step": (_i, [_ctx, _p, _p, _p, _i64, _i64, _i, _stream]),
@@ -122,6 +127,8 @@ SIGNATURES = {
     "e2v_image_resize_table": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),
     "e2v_op_image_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
     "e2v_op_image_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
+    "e2v_op_video_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
+    "e2v_op_token_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
     "e2v_op_set_knob": (_i, [C.c_char_p, _i]),

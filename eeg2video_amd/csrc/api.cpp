@@ -165,9 +165,34 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
                             ": the image attention kernel keeps K and V of an image's head in LDS");
             for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(cfg->vit_std[ch] != 0.f, E2V_EINVAL, "vit_std must be non-zero");
         }
+        if (cfg->vmae_layers != 0) {                     // (all zero: no video classifier)
+            E2V_REQUIRE(cfg->vmae_layers > 0 && cfg->vmae_heads > 0 && cfg->vmae_intermediate > 0 && cfg->vmae_intermediate % 4 == 0 &&
+                            cfg->vmae_image_size > 0 && cfg->vmae_patch_size > 0 && cfg->vmae_tubelet_size > 0 && cfg->vmae_num_frames > 0 &&
+                            cfg->vmae_norm_eps > 0.f,
+                        E2V_EINVAL, "bad video classifier config (sizes must be positive, vmae_intermediate a multiple of 4)");
+            E2V_REQUIRE(cfg->vmae_num_labels >= 3, E2V_EINVAL, "vmae_num_labels must be at least 3 (the top-3 head)");
+            E2V_REQUIRE(cfg->vmae_hidden == 64 * cfg->vmae_heads, E2V_EINVAL,
+                        "vmae_hidden must be 64 * vmae_heads: 64 is the head dim of the token attention kernel's only instance");
+            E2V_REQUIRE(cfg->vmae_hidden % 4 == 0 && cfg->vmae_hidden <= 1280, E2V_EINVAL, "vmae_hidden must be a multiple of 4, at most 1280 (the LayerNorm kernel's limit)");
+            E2V_REQUIRE(cfg->vmae_num_frames % cfg->vmae_tubelet_size == 0, E2V_EINVAL, "vmae_num_frames must be a multiple of vmae_tubelet_size");
+            E2V_REQUIRE(cfg->vmae_image_size % cfg->vmae_patch_size == 0 &&
+                            (3 * cfg->vmae_tubelet_size * cfg->vmae_patch_size * cfg->vmae_patch_size) % 4 == 0, E2V_EINVAL,
+                        "vmae_image_size must be a multiple of vmae_patch_size, and 3 * vmae_tubelet_size * vmae_patch_size^2 a multiple of 4");
+            E2V_REQUIRE(cfg->vmae_resize_edge >= cfg->vmae_image_size && cfg->vmae_resize_edge <= 4096, E2V_EINVAL,
+                        "vmae_resize_edge must be at least vmae_image_size (the centre crop is taken from the resized frame) and at most 4096");
+            const long long tokens = (long long)(cfg->vmae_num_frames / cfg->vmae_tubelet_size) * (cfg->vmae_image_size / cfg->vmae_patch_size) *
+                                     (cfg->vmae_image_size / cfg->vmae_patch_size);
+            E2V_REQUIRE(tokens <= (1 << 20), E2V_EINVAL, "the video classifier's token count must be at most 2^20");
+            for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(cfg->vmae_std[ch] != 0.f, E2V_EINVAL, "vmae_std must be non-zero");
+        }
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
+        for (int ch = 0; ch < 3 && cfg->vmae_layers > 0; ++ch)     // VideoMAEImageProcessor: as the image processor's table
+            for (int b = 0; b < 256; ++b) {
+                const float x = (float)((double)b * cfg->vmae_rescale);
+                c->video_lut[ch * 256 + b] = (x - cfg->vmae_mean[ch]) / cfg->vmae_std[ch];
+            }
         for (int ch = 0; ch < 3 && cfg->vit_layers > 0; ++ch)      // ViTImageProcessor: rescale in double, rounded to fp32; normalise in fp32
             for (int b = 0; b < 256; ++b) {
                 const float x = (float)((double)b * cfg->vit_rescale);
@@ -251,7 +276,7 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
     const int part = e2v_ctx::key_part(k);
-    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : c->unet_ready;
+    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : c->unet_ready;
     E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
@@ -270,6 +295,10 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
     }
     if (e2v_ctx::key_part(key) == 16) {
         c->err = "e2v_update_tensor: the image classifier is a frozen yardstick (40_class_run_metrics.py:88-90); load a new one with e2v_load_tensor + e2v_finalize_weights";
+        return E2V_EINVAL;
+    }
+    if (e2v_ctx::key_part(key) == 32) {
+        c->err = "e2v_update_tensor: the video classifier is a frozen yardstick (40_class_run_metrics.py:113-118); load a new one with e2v_load_tensor + e2v_finalize_weights";
         return E2V_EINVAL;
     }
     return guarded(c, [&] {
@@ -324,7 +353,7 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(which >= 1 && which <= 31, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier");
+        E2V_REQUIRE(which >= 1 && which <= 63, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier");
         c->finalize(which);
     });
 }
@@ -590,6 +619,86 @@ e2v_status e2v_op_image_attention(e2v_ctx* c, const float* qkv, int ldqkv, float
     return guarded(c, [&] {
         OpRecord rec;
         image_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// VideoMAEImageProcessor + VideoMAEForVideoClassification + softmax + top 3 of every clip (video_classify_metric's classifier half)
+e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* logits, float* probs,
+                              int32_t* top3, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        check_frames("e2v_video_classify", frames, kind, n, F, H, W);
+        E2V_REQUIRE(logits || probs || top3, E2V_EINVAL, "e2v_video_classify: logits, probs and top3 are all NULL");
+        E2V_REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(top3)) & 3) == 0,
+                    E2V_EINVAL, "e2v_video_classify: misaligned output (4 bytes)");
+        if (c->cfg.vmae_layers > 0) {
+            E2V_REQUIRE(F == c->cfg.vmae_num_frames, E2V_ESHAPE,
+                        "e2v_video_classify: F = " + std::to_string(F) + " frames per clip, the model takes vmae_num_frames = " +
+                            std::to_string(c->cfg.vmae_num_frames) + " (the position table and the token count are sized by it)");
+            E2V_REQUIRE(c->video_prep_plan(H, W).band >= 1, E2V_ESHAPE,
+                        "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
+        }
+        E2V_REQUIRE(c->cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
+        E2V_REQUIRE(c->video_ready, E2V_ESTATE, "video classifier weights are not finalized");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->video_classify(src, n, F, H, W, logits, probs, top3, S(c, stream));
+    });
+}
+
+// the preprocess of e2v_video_classify on its own, at any (S, P, ts, edge) and with the caller's pixel table
+e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int ts, int edge,
+                                   const float* host_lut, float* rows, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    VideoPrepPlan plan;
+    try {
+        check_frames("e2v_op_video_preprocess", frames, kind, n, F, H, W);
+        E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_video_preprocess: null or misaligned rows");
+        E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0 && edge >= size && edge <= 4096, E2V_ESHAPE,
+                    "e2v_op_video_preprocess: 1 <= S <= edge <= 4096, S a multiple of P >= 1");
+        E2V_REQUIRE(ts >= 1 && F % ts == 0 && F <= 4096, E2V_ESHAPE, "e2v_op_video_preprocess: F must be a multiple of ts >= 1, at most 4096");
+        E2V_REQUIRE(host_lut || c->cfg.vmae_layers > 0, E2V_ESTATE, "e2v_op_video_preprocess: no pixel table given and the config has no video classifier");
+        plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->video_lut);
+        E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_video_preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        Act tables(c->pool, (int64_t)plan.words.size(), 1);
+        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const long long per = (long long)(F / ts) * (size / patch) * (size / patch) * 3 * ts * patch * patch;
+        const int step = std::max(1, 4096 / F);
+        for (int i0 = 0; i0 < n; i0 += step)
+            video_preprocess(src, n, F, ts, i0, std::min(step, n - i0), plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// fp32 in every compute mode, as e2v_video_classify runs it
+e2v_status e2v_op_token_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
+        E2V_REQUIRE(B > 0 && heads > 0 && T >= 1, E2V_ESHAPE, "token attention: B, heads, T >= 1");
+        E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldqkv % 4 == 0 && ldo >= heads * 64 && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 &&
+                        (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+                    E2V_EINVAL, "token attention: qkv rows of q | k | v, out rows of heads * 64 columns, both 16-byte aligned with strides that are multiples of 4");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        OpRecord rec;
+        token_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
         E2V_HIP(hipGetLastError());
     });
 }

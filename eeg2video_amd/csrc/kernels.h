@@ -268,6 +268,33 @@ void image_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, in
 void image_head(const float* logits, int ld, int L, int nimg, float* logits_out, float* probs, int* top3, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
+// VideoMAE video classifier (video.hip; e2v_video_classify): fp32 in every compute mode.  The encoder layers are the image
+// classifier's; the head's softmax / top 3 is image_head.
+// ---------------------------------------------------------------------------------------
+// VideoMAEImageProcessor's geometry: the shortest edge resized to `edge` with the aspect ratio kept, then the centre crop of S x S
+struct VideoCrop { int nh = 0, nw = 0, top = 0, left = 0; };
+VideoCrop video_crop(int H, int W, int edge, int S);
+// The tables of the (H, W) -> (nh, nw) resize restricted to the crop window, in ImagePrepPlan's layout (S entries per axis, `first`
+// in source coordinates), and the source columns [c0, c0 + cw) the window's horizontal taps read (the vertical-first order keeps
+// only those).  band = 0: does not fit.
+struct VideoPrepPlan : ImagePrepPlan {
+    VideoCrop crop;
+    int c0 = 0, cw = 0;
+};
+VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768);
+// clips clip0 .. clip0 + nclips - 1 of `src` ([n][F] frames of plan.H x plan.W) -> rows [nclips*(F/ts)*(S/P)^2][3*ts*P*P]: frame
+// ts*t + dt of a clip writes columns ((c*ts + dt)*P + y)*P + x of the clip's token rows (t, py, px)
+void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
+                      int P, float* rows, hipStream_t s);
+// x[b*T + t][:] = patches[b*T + t][:] + pos[t][:]   (C a multiple of 4; no class row)
+void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s);
+// non-causal self-attention over each of B sequences of T tokens (any T >= 1), head dim 64, scale 64^-0.5; q | k | v in one row matrix
+// as image_attention takes them (16-byte aligned rows, strides multiples of 4).  K and V are read per key tile, never resident.
+void token_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
+// out[b][:] = (sum over t of x[b*T + t][:], t ascending) / T   (x rows of C columns, contiguous)
+void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)
 // ---------------------------------------------------------------------------------------
 void ncfhw_to_cl(const float* in, float* out, int n, int C, int Cpad, int FHW, float scale, hipStream_t s, int out_bf16 = 0);

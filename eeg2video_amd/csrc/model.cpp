@@ -171,6 +171,24 @@ void e2v_ctx::expected_keys() {
         s.norm(m + "layernorm", C);
         s.lin("image.classifier", cfg.vit_num_labels, C);
     }
+
+    // ---- VideoMAE video classifier ("video." prefix; the names of transformers' VideoMAEForVideoClassification state dict, and the
+    // fixed position table -- a buffer transformers builds at construction -- as a key of our own) ----
+    if (cfg.vmae_layers > 0) {
+        const int C = cfg.vmae_hidden, I = cfg.vmae_intermediate, P = cfg.vmae_patch_size;
+        const std::string m = "video.videomae.";
+        s.add(m + "embeddings.position_embeddings", {video_tokens(), C});
+        s.conv(m + "embeddings.patch_embeddings.projection", C, 3 * cfg.vmae_tubelet_size, P);      // Conv3d [C][3][ts][P][P], axes 1 and 2 merged
+        for (int i = 0; i < cfg.vmae_layers; ++i) {
+            const std::string l = m + "encoder.layer." + std::to_string(i);
+            for (const char* n : {"query", "key", "value"}) s.lin(l + ".attention.attention." + n, C, C);
+            s.lin(l + ".attention.output.dense", C, C);
+            s.lin(l + ".intermediate.dense", I, C); s.lin(l + ".output.dense", C, I);
+            s.norm(l + ".layernorm_before", C); s.norm(l + ".layernorm_after", C);
+        }
+        s.norm("video.fc_norm", C);
+        s.lin("video.classifier", cfg.vmae_num_labels, C);
+    }
 }
 
 // a block of a weight layout, owned by the part its caller selected (AllocPart); guarded, and its payload poisoned before the first
@@ -505,6 +523,7 @@ void e2v_ctx::finalize(int which) {
     E2V_REQUIRE(!(which & 4) || (cfg.sem_in_features > 0 && cfg.sem_hidden > 0), E2V_ESTATE, "the config has no semantic predictor");
     E2V_REQUIRE(!(which & 8) || cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
     E2V_REQUIRE(!(which & 16) || cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
+    E2V_REQUIRE(!(which & 32) || cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
     for (const auto& k : keys)
         if (which & key_part(k)) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
@@ -619,6 +638,30 @@ void e2v_ctx::finalize(int which) {
         P.f32_only = false;
         text = std::move(t);
     }
+    // what the two classifiers (parts 16 and 32) share: a transformers encoder layer in the text tower's packing, and the classifier
+    // [L][C] as a linear whose row count is a multiple of 4 -- rows of zeros appended: the linear kernels store quads
+    auto encoder_layer = [&](const std::string& l) {
+        TextLayerW w;
+        w.ln1 = P.norm(l + ".layernorm_before"); w.ln2 = P.norm(l + ".layernorm_after");
+        w.qkv = P.fuse_rows({l + ".attention.attention.query", l + ".attention.attention.key", l + ".attention.attention.value"}, true);
+        w.out = P.lin(l + ".attention.output.dense");
+        w.fc1 = P.lin(l + ".intermediate.dense"); w.fc2 = P.lin(l + ".output.dense");
+        return w;
+    };
+    auto classifier_head = [&](const std::string& n, int L, int C) {
+        if (L % 4 == 0) return P.lin(n);
+        const int Lp = (L + 3) / 4 * 4;
+        const WTensor& w = P.t(n + ".weight");
+        float* d = dev_alloc((size_t)Lp * C);
+        float* b = dev_alloc(Lp);
+        E2V_HIP(hipMemsetAsync(d, 0, (size_t)Lp * C * sizeof(float), P.s));
+        E2V_HIP(hipMemsetAsync(b, 0, (size_t)Lp * sizeof(float), P.s));
+        copy_rows(w.d(), C, d, C, L, C, P.s);
+        copy_rows(P.t(n + ".bias").d(), L, b, L, 1, L, P.s);
+        P.bind_lin(n + ".weight", d, 0);
+        P.bind_raw(n + ".bias", b, 1, L);
+        return P.mk_lin(d, b, C, Lp);
+    };
     if (which & 16) {
         free_part(4);
         alloc_part = 4;
@@ -639,32 +682,38 @@ void e2v_ctx::finalize(int which) {
             v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
         }
         for (int i = 0; i < cfg.vit_layers; ++i) {
-            const std::string l = m + "encoder.layer." + std::to_string(i);
-            TextLayerW w;
-            w.ln1 = P.norm(l + ".layernorm_before"); w.ln2 = P.norm(l + ".layernorm_after");
-            w.qkv = P.fuse_rows({l + ".attention.attention.query", l + ".attention.attention.key", l + ".attention.attention.value"}, true);
-            w.out = P.lin(l + ".attention.output.dense");
-            w.fc1 = P.lin(l + ".intermediate.dense"); w.fc2 = P.lin(l + ".output.dense");
-            v.layers.push_back(w);
+            v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
         }
         v.ln_f = P.norm(m + "layernorm");
-        if (L % 4 == 0) {
-            v.head = P.lin("image.classifier");
-        } else {                                             // rows of zeros up to a multiple of 4: the linear kernels store quads
-            const int Lp = (L + 3) / 4 * 4;
-            const WTensor& w = P.t("image.classifier.weight");
-            float* d = dev_alloc((size_t)Lp * C);
-            float* b = dev_alloc(Lp);
-            E2V_HIP(hipMemsetAsync(d, 0, (size_t)Lp * C * sizeof(float), P.s));
-            E2V_HIP(hipMemsetAsync(b, 0, (size_t)Lp * sizeof(float), P.s));
-            copy_rows(w.d(), C, d, C, L, C, P.s);
-            copy_rows(P.t("image.classifier.bias").d(), L, b, L, 1, L, P.s);
-            P.bind_lin("image.classifier.weight", d, 0);
-            P.bind_raw("image.classifier.bias", b, 1, L);
-            v.head = P.mk_lin(d, b, C, Lp);
-        }
+        v.head = classifier_head("image.classifier", L, C);
         P.f32_only = false;
         image = std::move(v);
+    }
+    if (which & 32) {
+        free_part(5);
+        alloc_part = 5;
+        P.f32_only = true;
+        VideoW v;
+        const std::string m = "video.videomae.";
+        const int C = cfg.vmae_hidden, T = video_tokens(), L = cfg.vmae_num_labels;
+        const int K = 3 * cfg.vmae_tubelet_size * cfg.vmae_patch_size * cfg.vmae_patch_size;
+        const WTensor& pos = P.t(m + "embeddings.position_embeddings");
+        v.pos = pos.d();
+        P.bind_raw(m + "embeddings.position_embeddings", pos.d(), T, C);
+        {   // the tubelet convolution [C][3][ts][P][P] is the linear [C][3 ts P P] over the patch rows as it stands
+            const std::string n = m + "embeddings.patch_embeddings.projection";
+            const WTensor& w = P.t(n + ".weight");
+            P.bind_raw(n + ".weight", w.d(), C, K);
+            P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
+            v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
+        }
+        for (int i = 0; i < cfg.vmae_layers; ++i) {
+            v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
+        }
+        v.fc_norm = P.norm("video.fc_norm");
+        v.head = classifier_head("video.classifier", L, C);
+        P.f32_only = false;
+        video = std::move(v);
     }
     alloc_part = -1;
     resolve_bindings();
@@ -694,6 +743,10 @@ void e2v_ctx::finalize(int which) {
             if (k.find(".attention.attention.") != std::string::npos || (k.rfind("image.classifier.", 0) == 0 && cfg.vit_num_labels % 4 != 0)) drop(k);
             continue;
         }
+        if (part == 32) {
+            if (k.find(".attention.attention.") != std::string::npos || (k.rfind("video.classifier.", 0) == 0 && cfg.vmae_num_labels % 4 != 0)) drop(k);
+            continue;
+        }
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
@@ -706,6 +759,7 @@ void e2v_ctx::finalize(int which) {
     if (which & 4) sem_ready = true;
     if (which & 8) text_ready = true;
     if (which & 16) image_ready = true;
+    if (which & 32) video_ready = true;
 }
 
 // =====================================================================================================
@@ -754,6 +808,8 @@ void e2v_ctx::resolve_bindings() {
     for (auto& l : text.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
     for (auto& l : image.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
     fl(image.patch); fl(image.head);
+    for (auto& l : video.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
+    fl(video.patch); fl(video.head);
     for (auto& kv : bind) {
         WBind& b = kv.second;
         if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
@@ -1619,6 +1675,71 @@ void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, fl
         Act cls(pool, ni, C);                                   // the final LayerNorm on the class rows only (row stride T * C)
         layernorm(x.p, T * C, image.ln_f.g, image.ln_f.b, cls.p, C, ni, C, eps, s);
         Act lg = R.linear(image.head, cls.p, C, ni, R.f32_rows());
+        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
+                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// VideoMAEImageProcessor + VideoMAEForVideoClassification.forward(pixel_values).logits (transformers: VideoMAEEmbeddings -- the
+// tubelet convolution and the fixed sinusoid table --, pre-LN encoder layers without a mask, no final LayerNorm under
+// use_mean_pooling, the mean over the tokens, fc_norm at nn.LayerNorm's default eps, the classifier), then the softmax and the top-3
+// indices video_classify_metric takes from it (40_class_run_metrics.py:128-139).  fp32 rows and arithmetic whatever the compute mode.
+// Clips are walked in chunks of E2V_VMAE_CHUNK (16): every kernel here computes a row from that row's clip alone and in an order
+// that does not depend on the row count, so the chunking does not show in the result.
+// -----------------------------------------------------------------------------------------------------
+const VideoPrepPlan& e2v_ctx::video_prep_plan(int H, int W) {
+    const std::array<int, 2> key{H, W};
+    auto it = video_prep_plans.find(key);
+    if (it == video_prep_plans.end()) {
+        if (video_prep_plans.size() >= 64) video_prep_plans.clear();
+        it = video_prep_plans.emplace(key, e2v::video_prep_plan(H, W, cfg.vmae_resize_edge, cfg.vmae_image_size, cfg.vmae_patch_size, video_lut)).first;
+    }
+    return it->second;
+}
+
+void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, float* logits, float* probs, int* top3, hipStream_t s) {
+    E2V_REQUIRE(video_ready, E2V_ESTATE, "video classifier weights are not finalized");
+    E2V_REQUIRE(F == cfg.vmae_num_frames, E2V_ESHAPE, "e2v_video_classify: F must be vmae_num_frames");
+    Runner R{this, s, false};
+    const int C = cfg.vmae_hidden, I = cfg.vmae_intermediate, P = cfg.vmae_patch_size, ts = cfg.vmae_tubelet_size, L = cfg.vmae_num_labels;
+    const int T = video_tokens(), K = 3 * ts * P * P;
+    const float eps = cfg.vmae_norm_eps;
+    const VideoPrepPlan& plan = video_prep_plan(H, W);
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
+    Act tables(pool, (int64_t)plan.words.size(), 1);
+    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
+    static const int* const chunk_knob = knob("E2V_VMAE_CHUNK", 16);
+    const int chunk = std::min(std::min(std::max(*chunk_knob, 1), 4096), 65535 / F);
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int ni = std::min(chunk, n - i0);
+        const int64_t M = (int64_t)ni * T;
+        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
+        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
+        Act x(pool, M, C);
+        {
+            Act rows(pool, M, K);
+            video_preprocess(src, n, F, ts, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
+            Act patches = R.linear(video.patch, rows.p, K, M, R.f32_rows());
+            video_embed(patches.p, video.pos, x.p, ni, T, C, s);
+        }
+        for (const TextLayerW& l : video.layers) {
+            Act h(pool, M, C);
+            ln(l.ln1, x.p, h.p);
+            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
+            Act a(pool, M, C);
+            token_attention(qkv.p, 3 * C, a.p, C, ni, T, cfg.vmae_heads, s);
+            x = R.linear(l.out, a.p, C, M, plus(x));
+            ln(l.ln2, x.p, h.p);
+            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
+            text_activation(f.p, M * I, 1, s);
+            x = R.linear(l.fc2, f.p, I, M, plus(x));
+        }
+        Act mean(pool, ni, C), pooled(pool, ni, C);
+        token_mean(x.p, mean.p, ni, T, C, s);
+        layernorm(mean.p, C, video.fc_norm.g, video.fc_norm.b, pooled.p, C, ni, C, 1e-5f, s);       // fc_norm = nn.LayerNorm(hidden): the default eps
+        Act lg = R.linear(video.head, pooled.p, C, ni, R.f32_rows());
         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
                    top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
     }

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "image_prep.h"
 #include "kernels.h"
 #include "prof.h"
 #include "runtime.h"
@@ -94,19 +95,6 @@ ImagePrepPlan image_prep_plan(int H, int W, int S, int P, const float* lut768) {
 
 namespace {
 
-struct PrepView {
-    const void* p;
-    long long s_n, s_img, s_c, s_y, s_x;         // clip, frame, channel, row, column -- in elements
-};
-
-__device__ __forceinline__ int prep_quantise(float x) {      // the bytes of frames_to_u8 on [0, 1]; NaN -> 0 (metrics.hip: quantise)
-    x = x > 0.f ? x : 0.f;
-    x = x < 1.f ? x : 1.f;
-    return (int)(x * 255.f);
-}
-
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
-
 // One workgroup: `band` output rows of one channel of one image.
 //   1. horizontal pass over the source rows the band reads -> bytes in LDS ([rows][S]; staging in LDS instead of a byte buffer in
 //      the pool: the intermediate of a band is consumed by the workgroup that made it, 5 KB at 288 x 512 -> 224, and never visits HBM);
@@ -114,11 +102,6 @@ __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : v > 255 ? 255 :
 // Integer arithmetic as Pillow's: 32-bit accumulators starting at 2^21, >> 22, clipped to a byte.
 // VFIRST (Pillow's order for very tall images): 1. vertical pass of the band's rows at the source width W -> bytes in LDS ([band][W]);
 // 2. horizontal pass over them.
-template <bool F32>
-__device__ __forceinline__ int prep_load(const PrepView& v, long long off) {
-    return F32 ? prep_quantise(static_cast<const float*>(v.p)[off]) : (int)static_cast<const unsigned char*>(v.p)[off];
-}
-
 template <bool F32, bool VFIRST>
 __global__ __launch_bounds__(256) void image_prep_kernel(PrepView v, int F, long long img0, int W, int S, int P, int kh, int kv, int band,
                                                          const int* __restrict__ plan, float* __restrict__ rows) {

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import TEXT_ACTS, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig
+from .weights import TEXT_ACTS, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -29,19 +29,20 @@ def _stream() -> int:
 
 class Engine:
     """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
-    the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one."""
+    the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one, ``video_cfg``
+    (``None``: no video classifier) the ``VideoMAEForVideoClassification`` one."""
 
-    UNET, VAE, SEMANTIC, TEXT, IMAGE = 1, 2, 4, 8, 16
+    UNET, VAE, SEMANTIC, TEXT, IMAGE, VIDEO = 1, 2, 4, 8, 16, 32
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
                  sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None,
-                 image_cfg: Optional[ImageConfig] = None):
+                 image_cfg: Optional[ImageConfig] = None, video_cfg: Optional[VideoConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
         self.lib = _lib.load()
         self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
-        self.image_cfg = image_cfg
+        self.image_cfg, self.video_cfg = image_cfg, video_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -71,6 +72,8 @@ class Engine:
             fill_text_config(cfg, text_cfg)
         if image_cfg is not None:
             fill_image_config(cfg, image_cfg)
+        if video_cfg is not None:
+            fill_video_config(cfg, video_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
         st = self.lib.e2v_create(C.byref(cfg), device, C.byref(ctx))
@@ -204,10 +207,10 @@ class Engine:
                                              self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
         return out
 
-    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image."}
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video."}
 
     def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
-        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE``) as the device holds it NOW -- after any
+        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE`` / ``VIDEO``) as the device holds it NOW -- after any
         ``update_state_dict`` --, an ``OrderedDict`` in ``expected_keys()`` order with ``prefix`` (the one ``load_state_dict`` adds:
         ``'vae.'``, ``'semantic.'``, ``'text.'``) stripped from the names.  ``device``: ``'cuda'`` (tensors on the engine's device) or
         ``'cpu'``."""
@@ -218,7 +221,7 @@ class Engine:
         elif dev.type != "cpu":
             raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
         own = self._PART_PREFIX.get(part, "")
-        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE) or prefix not in ("", own):
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO) or prefix not in ("", own):
             raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
         foreign = tuple(self._PART_PREFIX.values())
         out = OrderedDict()
@@ -628,6 +631,23 @@ class Engine:
                                                 top3.data_ptr(), _stream()))
         return logits, probs, top3
 
+    def classify_clips(self, frames: torch.Tensor, channels_last: bool = False) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``VideoMAEImageProcessor`` + ``VideoMAEForVideoClassification`` over every clip (``e2v_video_classify``; the classifier half
+        of the reference's ``video_classify_metric``, ``40_class_run_metrics.py:108-142``) -> ``(logits, probs, top3)``: fp32
+        ``[n, labels]`` twice and int32 ``[n, 3]``, the indices of the three largest logits in ascending order, on the engine's device.
+        ``frames``: as ``classify_frames`` takes them, with exactly ``video_cfg.num_frames`` frames per clip.  fp32 arithmetic whatever
+        the engine's compute dtype."""
+        if self.video_cfg is None:
+            raise RuntimeError("this engine was built without a video classifier (Engine(..., video_cfg=VideoConfig()))")
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        labels = self.video_cfg.num_labels
+        logits = torch.empty((n, labels), device=self.device, dtype=torch.float32)
+        probs = torch.empty((n, labels), device=self.device, dtype=torch.float32)
+        top3 = torch.empty((n, 3), device=self.device, dtype=torch.int32)
+        self._check(self.lib.e2v_video_classify(self.ctx, t.data_ptr(), kind, n, f, h, w, logits.data_ptr(), probs.data_ptr(),
+                                                top3.data_ptr(), _stream()))
+        return logits, probs, top3
+
     # ------------------------------------------------------------------ the one exchange of the path (SURVEY 8(e))
     def comm_init(self, group=None) -> int:
         """Open the library's own RCCL communicator over the ranks of the (already initialised) ``torch.distributed`` group:
@@ -804,6 +824,33 @@ class Engine:
                                                     _stream()))
         return out
 
+    def op_video_preprocess(self, frames, *, size, patch, tubelet, edge, lut=None, channels_last=False, out=None):
+        """``e2v_op_video_preprocess``: clips -> the tubelet patch rows ``[n*(F/tubelet)*(size/patch)^2, 3*tubelet*patch^2]`` of the video
+        classifier's preprocess (shortest edge resized to ``edge``, centre crop of ``size``).  ``lut``: ``[3,256]`` fp32 pixel values
+        of a byte per channel (``None``: the engine's video config)."""
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        lut_p = None
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(3, 256))
+            lut_p = lut.ctypes.data_as(C.POINTER(C.c_float))
+        out = self._op_out(out, (n * (f // max(tubelet, 1)) * (size // patch) ** 2, 3 * tubelet * patch * patch))
+        self._check(self.lib.e2v_op_video_preprocess(self.ctx, t.data_ptr(), kind, n, f, h, w, size, patch, tubelet, edge, lut_p,
+                                                     out.data_ptr(), _stream()))
+        return out
+
+    def op_token_attention(self, qkv, *, B, T, heads, out=None):
+        """``e2v_op_token_attention``: ``qkv`` ``[B*T, 3*64*heads]`` (a 2-D view with unit column stride is read where it is) ->
+        ``[B*T, 64*heads]``, non-causal, any ``T``, fp32 in every mode."""
+        if not (isinstance(qkv, torch.Tensor) and qkv.device == self.device and qkv.dtype == torch.float32 and qkv.dim() == 2
+                and qkv.stride(1) == 1):
+            qkv = self._dev(qkv, "qkv")
+        if qkv.dim() != 2 or qkv.shape[0] != B * T or qkv.shape[1] != 3 * 64 * heads:
+            raise ValueError(f"expected qkv [B*T, 3*64*heads] = [{B * T}, {3 * 64 * heads}], got {tuple(qkv.shape)}")
+        out = self._op_out(out, (B * T, 64 * heads), strided=True)
+        self._check(self.lib.e2v_op_token_attention(self.ctx, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B, T, heads,
+                                                    _stream()))
+        return out
+
     def op_to_channels_last(self, x, *, Cpad=None, out=None):
         """``[n, C, FHW]`` -> channel-last rows ``[n * FHW, Cpad]`` (``e2v_op_to_channels_last``; columns C.. are written as zeros)."""
         n, c, fhw = x.shape
@@ -854,6 +901,16 @@ def fill_image_config(cfg: "_lib.E2VConfig", image_cfg: ImageConfig) -> None:
     cfg.vit_num_labels, cfg.vit_norm_eps, cfg.vit_rescale = image_cfg.num_labels, image_cfg.layer_norm_eps, float(image_cfg.rescale_factor)
     cfg.vit_mean = (C.c_float * 3)(*[float(v) for v in image_cfg.image_mean])
     cfg.vit_std = (C.c_float * 3)(*[float(v) for v in image_cfg.image_std])
+
+
+def fill_video_config(cfg: "_lib.E2VConfig", video_cfg: VideoConfig) -> None:
+    """The ``vmae_*`` fields of an ``e2v_config`` from a ``VideoConfig``."""
+    cfg.vmae_hidden, cfg.vmae_heads, cfg.vmae_layers = video_cfg.hidden, video_cfg.heads, video_cfg.layers
+    cfg.vmae_intermediate, cfg.vmae_image_size, cfg.vmae_patch_size = video_cfg.intermediate, video_cfg.image_size, video_cfg.patch_size
+    cfg.vmae_tubelet_size, cfg.vmae_num_frames, cfg.vmae_num_labels = video_cfg.tubelet_size, video_cfg.num_frames, video_cfg.num_labels
+    cfg.vmae_norm_eps, cfg.vmae_resize_edge, cfg.vmae_rescale = video_cfg.layer_norm_eps, video_cfg.resize_edge, float(video_cfg.rescale_factor)
+    cfg.vmae_mean = (C.c_float * 3)(*[float(v) for v in video_cfg.image_mean])
+    cfg.vmae_std = (C.c_float * 3)(*[float(v) for v in video_cfg.image_std])
 
 
 def image_resize_table(in_size: int, out_size: int):

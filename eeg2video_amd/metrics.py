@@ -3,10 +3,13 @@ signatures -- ``channel_last``, ``ssim_metric``, ``mse_metric``, ``ssim_score_on
 (``e2v_frame_metrics``: skimage's ``structural_similarity(data_range=255, channel_axis=-1)`` and ``mse_loss(img1 / 255, img2 / 255)``,
 one launch per clip instead of one host call per frame) -- and its image N-way accuracy, ``n_way_top_k_acc`` and
 ``img_classify_metric`` (``:57-105``), over ``Engine.classify_frames`` (``e2v_image_classify``: the ViT classifier of every frame of a
-clip in one call, fp32, instead of one fp16 forward per image).  ``video_classify_metric`` (VideoMAE) and the CLIP score are not here.
+clip in one call, fp32, instead of one fp16 forward per image), and its video N-way accuracy, ``video_classify_metric``
+(``:108-142``), over ``Engine.classify_clips`` (``e2v_video_classify``: the VideoMAE classifier of all clips in one call).  The CLIP
+score is not here.
 
 The frame metrics take an ``engine=`` keyword; by default one ``Engine()`` without weights is made on first use and kept.
-``img_classify_metric`` takes a built classifier (``model=``) or a LOCAL checkpoint directory (``cache_dir=``).
+``img_classify_metric`` and ``video_classify_metric`` take a built classifier (``model=``) or a LOCAL checkpoint directory
+(``cache_dir=``).
 """
 from __future__ import annotations
 
@@ -124,6 +127,59 @@ def img_classify_metric(pred_videos, gt_videos, n_way: int = 50, num_trials: int
     gt_ids = clf.classify(_frames(gt_videos), channels_last=True)[2].cpu().numpy()
     if len(pred) != len(gt_ids):
         raise ValueError(f"clips differ: {len(pred)} generated frames against {len(gt_ids)} ground-truth frames")
+    acc_list, std_list = [], []
+    for p, ids in zip(pred, gt_ids):
+        acc, std = n_way_top_k_acc(p, [int(i) for i in ids], n_way, num_trials, top_k)
+        acc_list.append(acc)
+        std_list.append(std)
+    if return_std:
+        return acc_list, std_list
+    return acc_list
+
+
+_video_classifiers = {}
+
+
+def _video_classifier(cache_dir: str, num_frames: int, device):
+    key = (os.path.abspath(cache_dir), int(num_frames))
+    if key not in _video_classifiers:
+        from .video_classifier import VideoMAEForVideoClassification
+        index = torch.device(device).index if device is not None else None
+        _video_classifiers[key] = VideoMAEForVideoClassification.from_pretrained(cache_dir, num_frames=num_frames, device=index or 0)
+    return _video_classifiers[key]
+
+
+def _clips(x) -> torch.Tensor:
+    """``[n,f,h,w,c]`` (or one clip ``[f,h,w,c]``) pixel values 0..255 -> a uint8 tensor ``[n,f,h,w,c]``"""
+    a = np.asarray(x.detach().cpu() if isinstance(x, torch.Tensor) else x)
+    if a.ndim == 4:
+        a = a[None]
+    if a.ndim != 5:
+        raise ValueError(f"expected [n,f,h,w,c] clips or one [f,h,w,c] clip, got shape {a.shape}")
+    if a.dtype != np.uint8:
+        a = a.astype(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(a))
+
+
+def video_classify_metric(pred_videos, gt_videos, n_way: int = 50, num_trials: int = 100, top_k: int = 1, num_frames: int = 6,
+                          cache_dir: str = ".cache", device: Optional[str] = "cuda", return_std: bool = False,
+                          model=None) -> Union[List[float], Tuple[List[float], List[float]]]:
+    """``40_class_run_metrics.py:108-142``: per clip, the N-way top-k accuracy of the generated clip's class probabilities against the
+    three most likely classes of the ground-truth clip -> the list of accuracies (``return_std``: and the list of their stds).
+    ``pred_videos`` / ``gt_videos``: ``[n,f,h,w,3]`` pixel values 0..255 with ``f == num_frames`` (arrays or tensors, on the device or
+    not).  ``model``: a built ``eeg2video_amd.video_classifier.VideoMAEForVideoClassification`` (its ``num_frames`` must be this call's);
+    else ``cache_dir`` must be a LOCAL checkpoint directory of one (the reference names the hub model there; nothing is fetched here),
+    loaded once per (directory, ``num_frames``).  All clips of a side go through the device in ONE ``classify_clips`` call; the trial
+    loop then runs per clip in the reference's order -- ground truth's top 3, prediction's softmax, ``n_way_top_k_acc`` -- so a seeded
+    run draws the reference's distractors."""
+    assert n_way > top_k
+    clf = model if model is not None else _video_classifier(cache_dir, num_frames, device)
+    if clf.vcfg.num_frames != num_frames:
+        raise ValueError(f"the classifier was built for num_frames={clf.vcfg.num_frames}, this call says {num_frames}")
+    pred = clf.classify(_clips(pred_videos), channels_last=True)[1].cpu().numpy()
+    gt_ids = clf.classify(_clips(gt_videos), channels_last=True)[2].cpu().numpy()
+    if len(pred) != len(gt_ids):
+        raise ValueError(f"{len(pred)} generated clips against {len(gt_ids)} ground-truth clips")
     acc_list, std_list = [], []
     for p, ids in zip(pred, gt_ids):
         acc, std = n_way_top_k_acc(p, [int(i) for i in ids], n_way, num_trials, top_k)

@@ -241,6 +241,121 @@ def image_checkpoint_key(name: str) -> str:
     return name
 
 
+@dataclass(frozen=True)
+class VideoConfig:
+    """``VideoMAEForVideoClassification`` (``transformers`` ``VideoMAEConfig``: ``hidden_size``, ``num_attention_heads``,
+    ``num_hidden_layers``, ``intermediate_size``, ``image_size``, ``patch_size``, ``tubelet_size``, ``num_frames``, the number of
+    labels, ``layer_norm_eps``; ``use_mean_pooling``, erf GELU, biased q / k / v as ``transformers`` 5 builds them) with its
+    ``VideoMAEImageProcessor`` (``preprocessor_config.json``: ``size.shortest_edge`` = ``resize_edge``, a centre crop of
+    ``image_size``, ``rescale_factor``, ``image_mean``, ``image_std``).  The defaults are ``MCG-NJU/videomae-base-finetuned-kinetics``
+    as the reference's ``video_classify_metric`` loads it: ``num_frames=6``.  The head dim is 64."""
+    hidden: int = 768
+    heads: int = 12
+    layers: int = 12
+    intermediate: int = 3072
+    image_size: int = 224
+    patch_size: int = 16
+    tubelet_size: int = 2
+    num_frames: int = 6
+    num_labels: int = 400
+    layer_norm_eps: float = 1e-12
+    resize_edge: int = 224
+    rescale_factor: float = 1 / 255
+    image_mean: Tuple[float, float, float] = (0.485, 0.456, 0.406)
+    image_std: Tuple[float, float, float] = (0.229, 0.224, 0.225)
+
+    @property
+    def tokens(self) -> int:
+        return (self.num_frames // self.tubelet_size) * (self.image_size // self.patch_size) ** 2
+
+
+#: 147 tokens: 4.6 key tiles of 32, 2.3 of 64, 1.15 query blocks of 128 -- every ragged edge of the attention kernel
+#: (tests/golden/videomae_tiny.npz)
+TINY_VIDEO = VideoConfig(hidden=128, heads=2, layers=2, intermediate=256, image_size=56, patch_size=8, tubelet_size=2, num_frames=6,
+                         resize_edge=56, num_labels=50)
+
+#: the one key of the video part that no checkpoint holds: the fixed position table, a buffer ``transformers`` builds at construction
+VIDEO_POSITION_KEY = "videomae.embeddings.position_embeddings"
+
+
+def video_param_spec(cfg: VideoConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of the video part as the engine holds it under ``video.``: ``VideoMAEForVideoClassification.state_dict()`` of
+    the installed ``transformers`` -- with the ``Conv3d`` weight ``[C,3,ts,P,P]`` as ``[C,3*ts,P,P]`` (``video_engine_shape``: the
+    library's key shapes have at most four axes; a reshape, the bytes are the same) -- plus ``VIDEO_POSITION_KEY`` ``[T,C]``."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c = cfg.hidden
+    spec[VIDEO_POSITION_KEY] = (cfg.tokens, c)
+    _conv(spec, "videomae.embeddings.patch_embeddings.projection", c, 3 * cfg.tubelet_size, cfg.patch_size)
+    for i in range(cfg.layers):
+        p = f"videomae.encoder.layer.{i}"
+        for n in ("query", "key", "value"):
+            _lin(spec, f"{p}.attention.attention.{n}", c, c)
+        _lin(spec, f"{p}.attention.output.dense", c, c)
+        _lin(spec, f"{p}.intermediate.dense", cfg.intermediate, c)
+        _lin(spec, f"{p}.output.dense", c, cfg.intermediate)
+        _norm(spec, f"{p}.layernorm_before", c)
+        _norm(spec, f"{p}.layernorm_after", c)
+    _norm(spec, "fc_norm", c)
+    _lin(spec, "classifier", cfg.num_labels, c)
+    return spec
+
+
+def video_engine_shape(shape) -> Tuple[int, ...]:
+    """A tensor shape of ``transformers``' state dict -> the engine's: the 5-D ``Conv3d`` weight with axes 1 and 2 merged."""
+    shape = tuple(int(d) for d in shape)
+    return (shape[0], shape[1] * shape[2]) + shape[3:] if len(shape) == 5 else shape
+
+
+def video_checkpoint_spec(cfg: VideoConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of ``VideoMAEForVideoClassification.state_dict()`` itself: ``video_param_spec`` without the position table and
+    with the ``Conv3d`` weight in its own five axes."""
+    spec = video_param_spec(cfg)
+    del spec[VIDEO_POSITION_KEY]
+    k = "videomae.embeddings.patch_embeddings.projection.weight"
+    spec[k] = (cfg.hidden, 3, cfg.tubelet_size, cfg.patch_size, cfg.patch_size)
+    return spec
+
+
+def video_position_table(n_position: int, d_hid: int):
+    """``transformers.models.videomae.modeling_videomae.get_sinusoid_encoding_table``, its numpy formula line by line (float64
+    ``np.power`` / ``np.sin`` / ``np.cos``, rounded to fp32 once at the end as ``torch.FloatTensor`` does), so that the table holds
+    ``transformers``' own bits and not another libm's -> fp32 ``[n_position, d_hid]``."""
+    def get_position_angle_vec(position):
+        return [position / np.power(10000, 2 * (hid_j // 2) / d_hid) for hid_j in range(d_hid)]
+
+    table = np.array([get_position_angle_vec(pos_i) for pos_i in range(n_position)])
+    table[:, 0::2] = np.sin(table[:, 0::2])
+    table[:, 1::2] = np.cos(table[:, 1::2])
+    return table.astype(np.float32)
+
+
+def video_checkpoint_key(name: str) -> str:
+    """A ``VideoMAEForVideoClassification`` tensor name in the ORIGINAL checkpoint's spelling (the hub file: bias-free query / key /
+    value projections and ``...attention.attention.q_bias`` / ``v_bias`` beside them) or in the installed ``transformers``' -> the
+    installed one's (``video_checkpoint_spec``): ``q_bias`` is ``query.bias``, ``v_bias`` is ``value.bias``.  The key projection has no
+    bias there; ``video_checkpoint_rename`` supplies zeros."""
+    for old, new in ((".attention.attention.q_bias", ".attention.attention.query.bias"),
+                     (".attention.attention.v_bias", ".attention.attention.value.bias")):
+        if name.endswith(old):
+            return name[:-len(old)] + new
+    return name
+
+
+def video_checkpoint_rename(state_dict):
+    """A state dict in either spelling -> the installed spelling, with a zero ``key.bias`` wherever the original spelling has none.
+    (``transformers`` 5.15 itself has no rename for the original spelling: ``from_pretrained`` reports ``q_bias`` / ``v_bias`` as
+    unexpected and initialises the three biases afresh, which drops trained values; that is not followed here.  ``transformers`` 4
+    added ``q_bias`` and ``v_bias`` to the query and value projections and no bias to the key projection, which is this mapping.)"""
+    out = OrderedDict((video_checkpoint_key(k), v) for k, v in state_dict.items())
+    for k in list(out):
+        if k.endswith(".attention.attention.key.weight"):
+            b = k[:-len("weight")] + "bias"
+            if b not in out:
+                w = out[k]
+                out[b] = w.new_zeros(w.shape[0]) if hasattr(w, "new_zeros") else np.zeros(w.shape[0], dtype=np.asarray(w).dtype)
+    return out
+
+
 #: tiny configs used by the parity tests (oracle finishes in well under a second).
 TINY_UNET = UNetConfig(sample_size=8, block_out_channels=(64, 128, 256, 256), cross_attention_dim=64)
 TINY_VAE = VAEConfig(block_out_channels=(32, 64, 64, 64), norm_num_groups=8)

@@ -15,6 +15,9 @@ are still there -- and adds ``ssim_mean``, ``ssim_std``, ``mse_mean`` and a ``sc
 ``--classifier DIR`` (with ``--score-against``; a LOCAL ``google/vit-base-patch16-224`` checkpoint directory) adds that script's image
 accuracy (``:302-328``: ``img_classify_metric`` at 2 and 40 ways, 100 trials, seeded here) as ``image_2way_acc`` / ``image_40way_acc``:
 the ViT classifier of every generated and ground-truth frame runs in the score stage (``e2v_image_classify``).
+``--video-classifier DIR`` (with ``--score-against``; a LOCAL ``MCG-NJU/videomae-base-finetuned-kinetics`` checkpoint directory) adds
+its video accuracy (``:332-374``: ``video_classify_metric`` at 2 and 40 ways) as ``video_2way_acc`` / ``video_40way_acc``: the VideoMAE
+classifier of every generated and ground-truth clip, built for the sweep's frame count, runs next to it (``e2v_video_classify``).
 
     python examples/run_sweep.py --dtype bf16 --batch 32            # 200 clips on one GPU
     python -m torch.distributed.run --nproc-per-node 8 examples/run_sweep.py   # concepts sharded over ranks, frames gathered
@@ -54,9 +57,13 @@ def main(argv=None, engine=None):
                     help="directory of ground-truth clips named as --out names them (.npy or .gif): per-frame SSIM / MSE on the device")
     ap.add_argument("--classifier", default="", metavar="DIR",
                     help="with --score-against: local ViTForImageClassification checkpoint directory -> image_{2,40}way_acc")
+    ap.add_argument("--video-classifier", default="", metavar="DIR",
+                    help="with --score-against: local VideoMAEForVideoClassification checkpoint directory -> video_{2,40}way_acc")
     args = ap.parse_args(argv)
     if args.classifier and not args.score_against:
         ap.error("--classifier scores against ground truth: give --score-against DIR too")
+    if args.video_classifier and not args.score_against:
+        ap.error("--video-classifier scores against ground truth: give --score-against DIR too")
 
     import torch.distributed as dist
     from eeg2video_amd.dist import all_gather_frames, shard_range
@@ -99,13 +106,17 @@ def main(argv=None, engine=None):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     neg = t(counter_normal(2, "neg", (1, scfg.tokens, ucfg.cross_attention_dim))).to(dev)
     stage = {"glmnet": 0.0, "seq2seq": 0.0, "semantic": 0.0, "dana": 0.0, "generate": 0.0, "uint8_d2h": 0.0, "write": 0.0}
-    mine, scores, classes = [], [], []
+    mine, scores, classes, video_classes = [], [], [], []
     if args.score_against:
         stage["score"] = 0.0
     vit = None
     if args.classifier:
         from eeg2video_amd.image_classifier import ViTForImageClassification
         vit = ViTForImageClassification.from_pretrained(args.classifier, device=local)      # its own context, fp32 in every mode
+    vmae = None
+    if args.video_classifier:                                       # built for the sweep's frame count, as the reference passes num_frames
+        from eeg2video_amd.video_classifier import VideoMAEForVideoClassification
+        vmae = VideoMAEForVideoClassification.from_pretrained(args.video_classifier, num_frames=F, device=local)
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0)) - 2)))
     pending = []
@@ -156,6 +167,8 @@ def main(argv=None, engine=None):
             scores.append(eng.frame_metrics(frames, gt, b_channels_last=True))
             if vit is not None:                                     # probabilities of the generated frames, top 3 of the ground truth
                 classes.append((vit.classify(frames, channels_last=False)[1], vit.classify(gt, channels_last=True)[2]))
+            if vmae is not None:                                    # the same per clip
+                video_classes.append((vmae.classify(frames, channels_last=False)[1], vmae.classify(gt, channels_last=True)[2]))
             tick("score", t0)
         t0 = time.perf_counter()
         u8 = eng.frames_to_uint8(frames).cpu()
@@ -185,18 +198,20 @@ def main(argv=None, engine=None):
             ssim, mse = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         ssim, mse = ssim.double().numpy(), mse.double().numpy()
         score_keys = {"ssim_mean": float(np.mean(ssim)), "ssim_std": float(np.std(ssim)), "mse_mean": float(np.mean(mse))}
-        if vit is not None:
+        for what, clf, pairs in (("image", vit, classes), ("video", vmae, video_classes)):
+            if clf is None:
+                continue
             from eeg2video_amd.metrics import n_way_top_k_acc
-            probs = torch.cat([p for p, _ in classes]).cpu() if classes else torch.zeros((0, vit.icfg.num_labels))
-            top3 = torch.cat([g for _, g in classes]).cpu() if classes else torch.zeros((0, 3), dtype=torch.int32)
+            probs = torch.cat([p for p, _ in pairs]).cpu() if pairs else torch.zeros((0, clf.config.num_labels))
+            top3 = torch.cat([g for _, g in pairs]).cpu() if pairs else torch.zeros((0, 3), dtype=torch.int32)
             if world > 1:
                 parts = [None] * world
                 dist.all_gather_object(parts, (probs, top3))
                 probs, top3 = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
-            for n_way in (2, 40):                                   # 40_class_run_metrics.py:302-328: 100 trials, top 1, per frame
+            for n_way in (2, 40):                                   # 40_class_run_metrics.py:302-374: 100 trials, top 1, per frame / per clip
                 np.random.seed(n_way)
                 acc = [n_way_top_k_acc(p, [int(i) for i in g], n_way, 100, 1)[0] for p, g in zip(probs.numpy(), top3.numpy())]
-                score_keys[f"image_{n_way}way_acc"] = float(np.mean(acc)) if acc else float("nan")
+                score_keys[f"{what}_{n_way}way_acc"] = float(np.mean(acc)) if acc else float("nan")
     if world > 1:
         u8_all = all_gather_frames(u8_all.to(dev).float() / 255.0, as_uint8=True).cpu()
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)

@@ -98,6 +98,22 @@ typedef struct {
     float vit_norm_eps;
     double vit_rescale;                     /* pixel value of a byte b: ((float)(b * vit_rescale) - vit_mean[c]) / vit_std[c], in fp32 */
     float vit_mean[3], vit_std[3];
+    /* VideoMAE video classifier (transformers VideoMAEForVideoClassification, config.json of MCG-NJU/videomae-base-finetuned-kinetics:
+     * hidden_size, num_attention_heads, num_hidden_layers, intermediate_size, image_size, patch_size, tubelet_size, num_frames, the
+     * number of labels, layer_norm_eps: 768, 12, 12, 3072, 224, 16, 2, 16 (the reference loads it with num_frames = 6), 400, 1e-12; erf
+     * GELU, use_mean_pooling) and its VideoMAEImageProcessor (preprocessor_config.json: size.shortest_edge 224 = vmae_resize_edge,
+     * then a centre crop of image_size x image_size, rescale_factor 1 / 255, the ImageNet mean and std).  All zero (the default): the
+     * context has no video classifier and expects none of its keys.  vmae_layers > 0: vmae_hidden must be 64 * vmae_heads, a
+     * multiple of 4 and at most 1280 (the LayerNorm kernel), vmae_intermediate a multiple of 4, vmae_num_frames a multiple of
+     * vmae_tubelet_size, vmae_image_size a multiple of vmae_patch_size, 3 * vmae_tubelet_size * vmae_patch_size^2 a multiple of 4,
+     * vmae_resize_edge >= vmae_image_size, vmae_num_labels at least 3, every vmae_std non-zero.  The token count
+     * (num_frames / tubelet_size) * (image_size / patch_size)^2 has no kernel limit.  Appended after the image classifier. */
+    int vmae_hidden, vmae_heads, vmae_layers, vmae_intermediate, vmae_image_size, vmae_patch_size, vmae_tubelet_size, vmae_num_frames;
+    int vmae_num_labels;
+    float vmae_norm_eps;                    /* the encoder layers' LayerNorms; fc_norm is nn.LayerNorm's default 1e-5 whatever this says */
+    int vmae_resize_edge;                   /* the processor's shortest_edge */
+    double vmae_rescale;                    /* pixel value of a byte b: ((float)(b * vmae_rescale) - vmae_mean[c]) / vmae_std[c], in fp32 */
+    float vmae_mean[3], vmae_std[3];
 } e2v_config;
 
 void e2v_default_config(e2v_config* cfg);
@@ -139,6 +155,13 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * per layer "image.vit.encoder.layer.{i}." "attention.attention.{query,key,value}.{weight,bias}", "attention.output.dense.*",
  * "layernorm_{before,after}.*", "intermediate.dense.*", "output.dense.*", and "image.vit.layernorm.*", "image.classifier.*";
  * query / key / value become one [3C][C] matrix with its [3C] bias).  fp32 matrices only, as the text part.
+ * bit 5 (32) = VideoMAE video classifier (config with vmae_layers > 0; the names of transformers' VideoMAEForVideoClassification
+ * state dict under the prefix "video.": "video.videomae.embeddings.patch_embeddings.projection.{weight,bias}" -- the Conv3d weight
+ * [C][3][ts][P][P] with its channel and tubelet axes merged, [C][3 * ts][P][P]: expected-key shapes have at most four axes --, per layer
+ * "video.videomae.encoder.layer.{i}." "attention.attention.{query,key,value}.{weight,bias}", "attention.output.dense.*",
+ * "layernorm_{before,after}.*", "intermediate.dense.*", "output.dense.*", then "video.fc_norm.*", "video.classifier.*", and one key
+ * that is not in a checkpoint: "video.videomae.embeddings.position_embeddings" [T][C], the fixed sinusoid transformers computes at
+ * construction for the model's num_frames, supplied by the caller).  fp32 matrices only.
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -157,7 +180,7 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * A "text." key: E2V_EINVAL -- the text encoder is frozen on this path (train_finetune_videodiffusion.py:115
  * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8).
  * An "image." key: E2V_EINVAL as well -- the classifier is a frozen yardstick (40_class_run_metrics.py:70-72 loads it and only
- * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16). */
+ * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32). */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
@@ -183,7 +206,7 @@ enum {
  * finalize makes: a 3x3 conv [Cout,Cin,3,3] from the torch-layout weight the context keeps, a row range of a fused QKV / KV matrix
  * (and of its fused bias), the GEGLU row interleave of ff.net.0.proj undone, the K-padded first layer of the Semantic Predictor
  * without its padding columns, plain linears, 1x1 convs, norm affines and embeddings as they are.
- * `key`: any expected key (UNet, "vae.", "semantic.", "text.", "image.": reading a text or classifier tensor is allowed, only updating one is refused).
+ * `key`: any expected key (UNet, "vae.", "semantic.", "text.", "image.", "video.": reading a text or classifier tensor is allowed, only updating one is refused).
  * `form`: which stored form is read -- 0 or E2V_FORM_F32: the fp32 values (every tensor has them).  For the weight of a linear
  * (or 1x1 conv) also E2V_FORM_BF16 / E2V_FORM_F16: that stored 16-bit copy, widened exactly, and E2V_FORM_X3: (p0 + p1) + p2 of the
  * three planes in fp32, which is the fp32 weight exactly.  A form e2v_op_weight_forms does not report for the key: E2V_ESTATE ("form
@@ -411,6 +434,27 @@ e2v_status e2v_frame_metrics(e2v_ctx* ctx, const void* a, int a_kind, const void
  * rows do not fit the preprocess kernel's LDS band (48 KiB: H / S beyond about 100 at S = 224): E2V_ESHAPE.  Then: no classifier in
  * the config (vit_layers = 0), the part not finalized, or a host-only context: E2V_ESTATE. */
 e2v_status e2v_image_classify(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W,
+                              float* logits, float* probs, int32_t* top3, e2v_stream stream);
+
+/* rank 7 -- replaces the classifier half of video_classify_metric (EEG2Video/40_class_run_metrics.py:108-142, called per clip at
+ * :332-374): VideoMAEImageProcessor(list of frames) and VideoMAEForVideoClassification(...).logits of every CLIP, its softmax and the
+ * indices of the three largest logits, on the device -- one call for a batch of clips instead of one fp16 forward per clip.
+ * frames, kind: as e2v_image_classify.  F must equal vmae_num_frames.
+ * Preprocess: Pillow's Image.resize((nw, nh), BILINEAR) with the SHORTEST edge at vmae_resize_edge = E and the aspect ratio kept --
+ * (nh, nw) = (E, int(E * W / H)) for H <= W, else (int(E * H / W), E) --, of which only the centre crop of S x S (S = vmae_image_size;
+ * rows top .. top + S - 1, top = (nh - S) / 2, columns left = (nw - S) / 2 likewise) is computed, then the pixel value of the config;
+ * bit-identical to VideoMAEImageProcessor on Pillow 12.
+ * Model: the tubelet embedding (a Conv3d of kernel and stride (ts, P, P): frames 2t and 2t + 1 of a clip feed token (t, py, px)), the
+ * caller's position table added, vmae_layers pre-LN encoder layers (non-causal attention over all T tokens of a clip, head dim 64, erf
+ * GELU), the mean over the tokens, fc_norm (eps 1e-5), the classifier.  FP32 IN EVERY COMPUTE MODE.
+ * Outputs, per CLIP, device, 4-byte aligned, any two may be NULL but not all three: logits, probs [n][vmae_num_labels], top3 [n][3]
+ * int32 (ascending order of logit, ties as a stable sort: as e2v_image_classify).
+ * Clips are walked in chunks; a clip's result does not depend on the chunking, on n, on its position, on the compute mode or on the
+ * run.  Stream-ordered, does not synchronise, allocates nothing outside the workspace pool (nothing once a shape's blocks are cached).
+ * Errors, in this order: null ctx / frames, all outputs NULL, misaligned, unknown bits in kind, n < 1: E2V_EINVAL; F !=
+ * vmae_num_frames (with a video config), H or W < 1, or a downscale whose band does not fit the preprocess kernel's LDS: E2V_ESHAPE;
+ * no video classifier in the config, the part not finalized, or a host-only context: E2V_ESTATE. */
+e2v_status e2v_video_classify(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W,
                               float* logits, float* probs, int32_t* top3, e2v_stream stream);
 
 /* ---- multi-GPU: the one exchange of the path ------------------------------------------------------------------

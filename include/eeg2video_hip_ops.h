@@ -108,6 +108,22 @@ e2v_status e2v_op_image_preprocess(e2v_ctx* ctx, const void* frames, int kind, i
 e2v_status e2v_op_image_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
                                   e2v_stream stream);
 
+/* The preprocess of e2v_video_classify on its own: n clips of F frames of H x W (frames / kind as there; F a multiple of ts) ->
+ * Pillow's bytes of the shortest-edge resize to `edge`, centre-cropped to S x S -> the tubelet patch-row matrix
+ * rows [n*(F/ts)*(S/P)^2][3*ts*P*P] fp32 (device, 4-byte aligned): frame f = ts*t + dt of clip i writes patch (py, px) into row
+ * ((i*(F/ts) + t)*(S/P) + py)*(S/P) + px, column ((c*ts + dt)*P + y)*P + x (the flatten of the Conv3d weight), value
+ * host_lut[c * 256 + byte].  host_lut: HOST [3][256] floats, or NULL for the table of the context's video config (E2V_ESTATE if it
+ * has none).  S a multiple of P, edge >= S.  Needs no weights. */
+e2v_status e2v_op_video_preprocess(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W, int S, int P, int ts,
+                                   int edge, const float* host_lut, float* rows, e2v_stream stream);
+
+/* Non-causal self-attention over each of B sequences of T tokens, ANY T >= 1, head dim 64, scale 64^-0.5, fp32 (exact fp32 matrix
+ * instructions, online softmax over key tiles; K and V are read per tile and never resident).  qkv [B*T][ldqkv]: q | k | v, heads * 64
+ * columns each (16-byte aligned, ldqkv a multiple of 4); out [B*T][ldo] (16-byte aligned, ldo a multiple of 4), columns
+ * 0 .. heads * 64 - 1 written.  The order of a row's sums depends on T alone.  fp32 in every compute mode. */
+e2v_status e2v_op_token_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
+                                  e2v_stream stream);
+
 /* layout conversion at the boundary: [n][C][FHW] <-> [n][FHW][Cpad] */
 e2v_status e2v_op_to_channels_last(e2v_ctx* ctx, const float* in, float* out, int n, int C, int Cpad, int FHW,
                                    e2v_stream stream);
