@@ -11,17 +11,18 @@ Layout (only what the path needs):
 * ``semantic`` / ``util``   the steps either side of the path: Semantic Predictor, DDIM inversion, ``save_videos_grid``
 * ``metrics``   the reference's scoring script on the device: per-frame SSIM / MSE (``ssim_score_only`` ...), the image N-way
   accuracy (``img_classify_metric``) over ``image_classifier``, ``transformers``' ``ViTForImageClassification`` on the library, and
-  the video N-way accuracy (``video_classify_metric``) over ``video_classifier``, its ``VideoMAEForVideoClassification``
+  the video N-way accuracy (``video_classify_metric``) over ``video_classifier``, its ``VideoMAEForVideoClassification``, and the
+  CLIP score (``clip_score``, ``clip_score_only``, ``n_way_scores``) over ``clip_vision``, its ``CLIPVisionModelWithProjection``
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
 * ``dist``       sharding of clips over ranks and the all-gather of decoded frames
 
 The compute path has no CPU fallback: without the built library or without a GPU it raises.
 """
-from .weights import (TINY_IMAGE, TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO, ImageConfig, SemanticConfig,  # noqa: F401
-                      TextConfig, UNetConfig, VAEConfig, VideoConfig)
+from .weights import (TINY_CLIP_VISION, TINY_IMAGE, TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO, ClipVisionConfig,  # noqa: F401
+                      ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig)
 
-__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig", "ViTForImageClassification", "ImageConfig", "VideoMAEForVideoClassification", "VideoConfig",
+__all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig", "ViTForImageClassification", "ImageConfig", "VideoMAEForVideoClassification", "VideoConfig", "CLIPVisionModelWithProjection", "ClipVisionConfig",
            "DDIMScheduler", "PNDMScheduler", "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler",
            "DPMSolverMultistepScheduler", "TuneAVideoPipeline", "build_pipeline", "save_videos_grid"]
 
@@ -42,6 +43,9 @@ def __getattr__(name):          # lazy: importing the package must not need torc
     if name == "VideoMAEForVideoClassification":
         from .video_classifier import VideoMAEForVideoClassification
         return VideoMAEForVideoClassification
+    if name == "CLIPVisionModelWithProjection":
+        from .clip_vision import CLIPVisionModelWithProjection
+        return CLIPVisionModelWithProjection
     if name == "AutoencoderKL":
         from .vae import AutoencoderKL
         return AutoencoderKL

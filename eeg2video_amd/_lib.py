@@ -42,6 +42,17 @@ class E2VConfig(C.Structure):
     ]
 
 
+class E2VClipVConfig(C.Structure):
+    """``e2v_clipv_config`` of include/eeg2video_hip.h (field order is the ABI): the CLIP vision tower, handed to
+    ``e2v_create_clip_vision`` beside the ``e2v_config``."""
+    _fields_ = [
+        ("clipv_hidden", C.c_int), ("clipv_heads", C.c_int), ("clipv_layers", C.c_int), ("clipv_intermediate", C.c_int),
+        ("clipv_image_size", C.c_int), ("clipv_patch_size", C.c_int), ("clipv_projection_dim", C.c_int), ("clipv_act", C.c_int),
+        ("clipv_norm_eps", C.c_float), ("clipv_resize_edge", C.c_int), ("clipv_resample", C.c_int),
+        ("clipv_rescale", C.c_double), ("clipv_mean", C.c_float * 3), ("clipv_std", C.c_float * 3),
+    ]
+
+
 class E2VPlanOp(C.Structure):
     """``e2v_plan_op`` of include/eeg2video_hip.h (field order is the ABI)."""
     _fields_ = [
@@ -72,6 +83,8 @@ SIGNATURES = {
     "e2v_config_size": (_i64, []),
     "e2v_version": (C.c_char_p, []),
     "e2v_create": (_i, [C.POINTER(E2VConfig), _i, C.POINTER(_ctx)]),
+    "e2v_clipv_config_size": (_i64, []),
+    "e2v_create_clip_vision": (_i, [C.POINTER(E2VConfig), C.POINTER(E2VClipVConfig), _i, C.POINTER(_ctx)]),
     "e2v_destroy": (None, [_ctx]),
     "e2v_last_error": (C.c_char_p, [_ctx]),
     "e2v_load_tensor": (_i, [_ctx, C.c_char_p, _p, _i, c_int64_p, _i]),
@@ -99,6 +112,8 @@ SIGNATURES = {
     "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
     "e2v_image_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
     "e2v_video_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
+    "e2v_clip_embed": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _stream]),
+    "e2v_clip_similarity": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _p, _stream]),
     "e2v_cfg_combine": (_i, [_ctx, _p, _p, _f, _p, _i64, _stream]),
     "e2v_lincomb": (_i, [_ctx, _i, C.POINTER(C.c_void_p), C.POINTER(C.c_float), _p, _i64, _stream]),
     "e2v_ddim_next_step": (_i, [_ctx, _p, _p, _p, _i64, _i64, _i, _stream]),
@@ -125,6 +140,8 @@ SIGNATURES = {
     "e2v_op_temporal_attention": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _i, _f, _stream]),
     "e2v_op_causal_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_image_resize_table": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),
+    "e2v_image_resize_table_filter": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),
+    "e2v_op_clip_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
     "e2v_op_image_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
     "e2v_op_image_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_video_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
@@ -168,6 +185,9 @@ def load() -> C.CDLL:
     if lib.e2v_config_size() != C.sizeof(E2VConfig):
         raise ImportError(f"{LIB_PATH}: e2v_config is {lib.e2v_config_size()} bytes in the library, {C.sizeof(E2VConfig)} in this binding "
                           "(include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
+    if lib.e2v_clipv_config_size() != C.sizeof(E2VClipVConfig):
+        raise ImportError(f"{LIB_PATH}: e2v_clipv_config is {lib.e2v_clipv_config_size()} bytes in the library, {C.sizeof(E2VClipVConfig)} in "
+                          "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     if lib.e2v_plan_op_size() != C.sizeof(E2VPlanOp):
         raise ImportError(f"{LIB_PATH}: e2v_plan_op is {lib.e2v_plan_op_size()} bytes in the library, {C.sizeof(E2VPlanOp)} in this binding "
                           "(include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")

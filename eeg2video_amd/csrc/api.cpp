@@ -111,11 +111,45 @@ void e2v_default_config(e2v_config* c) {
     c->sem_in_features = 310; c->sem_hidden = 10000; c->sem_tokens = 77;
 }
 
+}  // extern "C"
+
+namespace {
+// what e2v_create_clip_vision refuses (clipv_layers != 0), as the vit_* fields are checked
+void check_clipv_config(const e2v_clipv_config* v) {
+    E2V_REQUIRE(v->clipv_layers > 0 && v->clipv_heads > 0 && v->clipv_intermediate > 0 && v->clipv_intermediate % 4 == 0 &&
+                    v->clipv_image_size > 0 && v->clipv_patch_size > 0 && v->clipv_projection_dim > 0 &&
+                    v->clipv_projection_dim % 4 == 0 && (v->clipv_act == 0 || v->clipv_act == 1) && v->clipv_norm_eps > 0.f,
+                E2V_EINVAL, "bad CLIP vision tower config (sizes must be positive, clipv_intermediate and clipv_projection_dim multiples of 4, "
+                            "clipv_act 0 = quick_gelu or 1 = gelu)");
+    E2V_REQUIRE(v->clipv_hidden == 64 * v->clipv_heads, E2V_EINVAL,
+                "clipv_hidden must be 64 * clipv_heads: 64 is the head dim of the image attention kernel's only instance");
+    E2V_REQUIRE(v->clipv_hidden % 4 == 0 && v->clipv_hidden <= 1280, E2V_EINVAL, "clipv_hidden must be a multiple of 4, at most 1280 (the LayerNorm kernel's limit)");
+    E2V_REQUIRE(v->clipv_image_size % v->clipv_patch_size == 0 && (3 * v->clipv_patch_size * v->clipv_patch_size) % 4 == 0, E2V_EINVAL,
+                "clipv_image_size must be a multiple of clipv_patch_size, and 3 * clipv_patch_size^2 a multiple of 4");
+    const long long grid = v->clipv_image_size / v->clipv_patch_size;
+    E2V_REQUIRE(grid * grid + 1 <= kImageAttnMaxT, E2V_EINVAL,
+                "(clipv_image_size / clipv_patch_size)^2 + 1 tokens must be at most " + std::to_string(kImageAttnMaxT) +
+                    ": the image attention kernel keeps K and V of an image's head in LDS");
+    E2V_REQUIRE(v->clipv_resize_edge >= v->clipv_image_size && v->clipv_resize_edge <= 4096, E2V_EINVAL,
+                "clipv_resize_edge must be at least clipv_image_size (the centre crop is taken from the resized frame) and at most 4096");
+    E2V_REQUIRE(v->clipv_resample == kResizeBilinear || v->clipv_resample == kResizeBicubic, E2V_EINVAL,
+                "clipv_resample must be 2 (BILINEAR) or 3 (BICUBIC), Pillow's codes");
+    for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(v->clipv_std[ch] != 0.f, E2V_EINVAL, "clipv_std must be non-zero");
+}
+}  // namespace
+
+extern "C" {
+
 int64_t e2v_config_size(void) { return (int64_t)sizeof(e2v_config); }
 
 const char* e2v_version(void) { return "eeg2video_hip 0.1 (gfx950, fp32 MFMA)"; }
 
-e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
+e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) { return e2v_create_clip_vision(cfg, nullptr, device, out); }
+
+int64_t e2v_clipv_config_size(void) { return (int64_t)sizeof(e2v_clipv_config); }
+
+e2v_status e2v_create_clip_vision(const e2v_config* cfg, const e2v_clipv_config* clipv, int device, e2v_ctx** out) {
+    if (clipv && clipv->clipv_layers == 0) clipv = nullptr;      // (all zero: no tower)
     if (!cfg || !out) { g_create_error = "null argument"; return E2V_EINVAL; }
     *out = nullptr;
     e2v_ctx* c = nullptr;
@@ -185,9 +219,16 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) {
             E2V_REQUIRE(tokens <= (1 << 20), E2V_EINVAL, "the video classifier's token count must be at most 2^20");
             for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(cfg->vmae_std[ch] != 0.f, E2V_EINVAL, "vmae_std must be non-zero");
         }
+        if (clipv) check_clipv_config(clipv);
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
+        if (clipv) c->vcfg = *clipv;
+        for (int ch = 0; ch < 3 && c->vcfg.clipv_layers > 0; ++ch) // CLIPImageProcessor: as the image processor's table
+            for (int b = 0; b < 256; ++b) {
+                const float x = (float)((double)b * c->vcfg.clipv_rescale);
+                c->clipv_lut[ch * 256 + b] = (x - c->vcfg.clipv_mean[ch]) / c->vcfg.clipv_std[ch];
+            }
         for (int ch = 0; ch < 3 && cfg->vmae_layers > 0; ++ch)     // VideoMAEImageProcessor: as the image processor's table
             for (int b = 0; b < 256; ++b) {
                 const float x = (float)((double)b * cfg->vmae_rescale);
@@ -276,7 +317,7 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
     const int part = e2v_ctx::key_part(k);
-    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : c->unet_ready;
+    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : part == 64 ? c->clipv_ready : c->unet_ready;
     E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
@@ -353,7 +394,8 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(which >= 1 && which <= 63, E2V_EINVAL, "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier");
+        E2V_REQUIRE(which >= 1 && which <= 127, E2V_EINVAL,
+                    "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier, 64 CLIP vision tower");
         c->finalize(which);
     });
 }
@@ -572,6 +614,20 @@ e2v_status e2v_image_resize_table(int in_size, int out_size, int* first, int* co
     return E2V_OK;
 }
 
+e2v_status e2v_image_resize_table_filter(int in_size, int out_size, int filter, int* first, int* count, int32_t* coeff, int* ksize) {
+    if (!ksize || in_size < 1 || out_size < 1 || (filter != kResizeBilinear && filter != kResizeBicubic)) return E2V_EINVAL;
+    try {
+        const ResizeAxis t = resize_axis(in_size, out_size, filter);
+        *ksize = t.ksize;
+        if (first) std::memcpy(first, t.first.data(), t.first.size() * sizeof(int));
+        if (count) std::memcpy(count, t.count.data(), t.count.size() * sizeof(int));
+        if (coeff) std::memcpy(coeff, t.coeff.data(), t.coeff.size() * sizeof(int32_t));
+    } catch (const Error& e) {
+        return e.code;
+    }
+    return E2V_OK;
+}
+
 // the preprocess of e2v_image_classify on its own, at any (S, P) and with the caller's pixel table
 e2v_status e2v_op_image_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch,
                                    const float* host_lut, float* rows, e2v_stream stream) {
@@ -679,6 +735,81 @@ e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int
         const int step = std::max(1, 4096 / F);
         for (int i0 = 0; i0 < n; i0 += step)
             video_preprocess(src, n, F, ts, i0, std::min(step, n - i0), plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// CLIPImageProcessor + CLIPVisionModelWithProjection.image_embeds of every frame (the model half of clip_score)
+e2v_status e2v_clip_embed(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* embeds, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        check_frames("e2v_clip_embed", frames, kind, n, F, H, W);
+        E2V_REQUIRE(embeds && (reinterpret_cast<uintptr_t>(embeds) & 3) == 0, E2V_EINVAL, "e2v_clip_embed: null or misaligned embeds (4 bytes)");
+        E2V_REQUIRE(c->vcfg.clipv_layers > 0, E2V_ESTATE, "the context has no CLIP vision tower (e2v_create_clip_vision)");
+        E2V_REQUIRE(c->clipv_prep_plan(H, W).band >= 1, E2V_ESHAPE,
+                    "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
+        E2V_REQUIRE(c->clipv_ready, E2V_ESTATE, "CLIP vision tower weights are not finalized");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->clip_embed(src, n, F, H, W, embeds, S(c, stream));
+    });
+}
+
+// torch.nn.functional.cosine_similarity(a, b, dim=-1, eps=1e-8) of rows, pairwise or as a matrix
+e2v_status e2v_clip_similarity(e2v_ctx* c, const float* a, int na, const float* b, int nb, int D, int matrix, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        E2V_REQUIRE(a && b && out, E2V_EINVAL, "e2v_clip_similarity: null argument");
+        E2V_REQUIRE(matrix == 0 || matrix == 1, E2V_EINVAL, "e2v_clip_similarity: matrix is 0 (pairs) or 1");
+        E2V_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
+                    E2V_EINVAL, "e2v_clip_similarity: a and b must be 16-byte aligned, out 4-byte aligned");
+        E2V_REQUIRE(na >= 1 && nb >= 1 && D >= 4 && D % 4 == 0, E2V_ESHAPE, "e2v_clip_similarity: na, nb >= 1 and D a positive multiple of 4");
+        E2V_REQUIRE(matrix || na == nb, E2V_ESHAPE, "e2v_clip_similarity: the pair form takes as many rows of a as of b");
+        E2V_REQUIRE(!matrix || (na + 15) / 16 <= 65535, E2V_ESHAPE, "e2v_clip_similarity: at most 65535 * 16 rows of a in the matrix form");
+        E2V_REQUIRE(c->device >= 0, E2V_ESTATE, "e2v_clip_similarity: a host-only context has no device");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        clip_similarity(a, na, b, nb, D, matrix != 0, 1e-8f, out, S(c, stream));
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// the preprocess of e2v_clip_embed on its own, at any (S, P, edge, filter) and with the caller's pixel table
+e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int edge,
+                                  int filter, const float* host_lut, float* rows, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    VideoPrepPlan plan;
+    try {
+        check_frames("e2v_op_clip_preprocess", frames, kind, n, F, H, W);
+        E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_clip_preprocess: null or misaligned rows");
+        E2V_REQUIRE(filter == kResizeBilinear || filter == kResizeBicubic, E2V_EINVAL, "e2v_op_clip_preprocess: filter 2 (BILINEAR) or 3 (BICUBIC)");
+        E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0 && edge >= size && edge <= 4096, E2V_ESHAPE,
+                    "e2v_op_clip_preprocess: 1 <= S <= edge <= 4096, S a multiple of P >= 1");
+        E2V_REQUIRE(host_lut || c->vcfg.clipv_layers > 0, E2V_ESTATE, "e2v_op_clip_preprocess: no pixel table given and the context has no CLIP vision tower");
+        plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->clipv_lut, filter);
+        E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_clip_preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        Act tables(c->pool, (int64_t)plan.words.size(), 1);
+        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
+        for (long long i0 = 0; i0 < total; i0 += 4096) {
+            const int ni = (int)std::min<long long>(4096, total - i0);
+            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
+        }
         E2V_HIP(hipGetLastError());
     });
 }

@@ -236,13 +236,15 @@ void text_activation(float* x, long long count, int act, hipStream_t s);
 // norm.hip's, igemm.hip's and text.hip's.
 // ---------------------------------------------------------------------------------------
 struct FrameSrc;                            // (below: the input description e2v_frame_metrics shares)
-// One axis of Pillow's antialiased BILINEAR resize as a table (host arithmetic; e2v_image_resize_table)
+// One axis of Pillow's antialiased resize as a table (host arithmetic; e2v_image_resize_table, e2v_image_resize_table_filter).
+// The filter in Pillow's codes: 2 BILINEAR (the triangle, support 1), 3 BICUBIC (a = -0.5, support 2: negative coefficients).
+constexpr int kResizeBilinear = 2, kResizeBicubic = 3;
 struct ResizeAxis {
     int in = 0, out = 0, ksize = 0;
     std::vector<int> first, count;          // [out]
     std::vector<int> coeff;                 // [out][ksize], 22-bit fixed point
 };
-ResizeAxis resize_axis(int in_size, int out_size);
+ResizeAxis resize_axis(int in_size, int out_size, int filter = kResizeBilinear);
 // The tables of one (H, W) -> S x S resize and the pixel table, as the preprocess kernel reads them: one block of 32-bit words,
 // [hfirst S | hcount S | vfirst S | vcount S | hcoeff S * kh | vcoeff S * kv | lut 3 * 256 floats]
 struct ImagePrepPlan {
@@ -281,11 +283,15 @@ struct VideoPrepPlan : ImagePrepPlan {
     VideoCrop crop;
     int c0 = 0, cw = 0;
 };
-VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768);
+VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768, int filter = kResizeBilinear);
 // clips clip0 .. clip0 + nclips - 1 of `src` ([n][F] frames of plan.H x plan.W) -> rows [nclips*(F/ts)*(S/P)^2][3*ts*P*P]: frame
 // ts*t + dt of a clip writes columns ((c*ts + dt)*P + y)*P + x of the clip's token rows (t, py, px)
 void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
                       int P, float* rows, hipStream_t s);
+// the same at ts = 1 for frames img0 .. img0 + nimg - 1 of the [n][F] source, every frame an image of its own (a range may start
+// and end inside a clip) -> rows [nimg*(S/P)^2][3*P*P]: the patch layout of image_preprocess
+void frame_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
+                      float* rows, hipStream_t s);
 // x[b*T + t][:] = patches[b*T + t][:] + pos[t][:]   (C a multiple of 4; no class row)
 void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s);
 // non-causal self-attention over each of B sequences of T tokens (any T >= 1), head dim 64, scale 64^-0.5; q | k | v in one row matrix
@@ -293,6 +299,17 @@ void video_embed(const float* patches, const float* pos, float* x, int B, int T,
 void token_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
 // out[b][:] = (sum over t of x[b*T + t][:], t ascending) / T   (x rows of C columns, contiguous)
 void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
+// CLIP vision tower and CLIP score (clip.hip; e2v_clip_embed, e2v_clip_similarity): fp32 in every compute mode.  The processor is
+// video_preprocess at ts = 1 over a bicubic plan (every frame its own image: rows [images * patches][3 P P]); the token rows, the
+// attention and the layers are the image classifier's.
+// ---------------------------------------------------------------------------------------
+// torch.nn.functional.cosine_similarity(a, b, dim=-1, eps): dot(a, b) / (max(|a|, eps) * max(|b|, eps)).  a [na][D], b [nb][D],
+// contiguous, 16-byte aligned, D a multiple of 4.  matrix = false: na == nb, out[i] = cos(a[i], b[i]); true: out[i][j] = cos(a[i],
+// b[j]).  Every output runs the same sums in the same order (four strided partial sums over d ascending, joined at the end: a
+// function of D alone), so out[i][j] of the matrix form carries the bits of the pair form on (a[i], b[j]).
+void clip_similarity(const float* a, int na, const float* b, int nb, int D, bool matrix, float eps, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)

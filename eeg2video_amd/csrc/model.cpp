@@ -189,6 +189,25 @@ void e2v_ctx::expected_keys() {
         s.norm("video.fc_norm", C);
         s.lin("video.classifier", cfg.vmae_num_labels, C);
     }
+
+    // ---- CLIP vision tower ("clipv." prefix; the keys of a CLIPVisionModelWithProjection checkpoint -- "pre_layrnorm" is the
+    // checkpoint's own spelling; the position_ids buffer of older checkpoints is not a weight) ----
+    if (vcfg.clipv_layers > 0) {
+        const int C = vcfg.clipv_hidden, I = vcfg.clipv_intermediate, P = vcfg.clipv_patch_size;
+        const std::string m = "clipv.vision_model.";
+        s.add(m + "embeddings.class_embedding", {C});
+        s.add(m + "embeddings.patch_embedding.weight", {C, 3, P, P});
+        s.add(m + "embeddings.position_embedding.weight", {clipv_tokens(), C});
+        s.norm(m + "pre_layrnorm", C);
+        for (int i = 0; i < vcfg.clipv_layers; ++i) {
+            const std::string l = m + "encoder.layers." + std::to_string(i);
+            for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) s.lin(l + ".self_attn." + n, C, C);
+            s.norm(l + ".layer_norm1", C); s.norm(l + ".layer_norm2", C);
+            s.lin(l + ".mlp.fc1", I, C); s.lin(l + ".mlp.fc2", C, I);
+        }
+        s.norm(m + "post_layernorm", C);
+        s.lin("clipv.visual_projection", vcfg.clipv_projection_dim, C, false);
+    }
 }
 
 // a block of a weight layout, owned by the part its caller selected (AllocPart); guarded, and its payload poisoned before the first
@@ -524,6 +543,7 @@ void e2v_ctx::finalize(int which) {
     E2V_REQUIRE(!(which & 8) || cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
     E2V_REQUIRE(!(which & 16) || cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
     E2V_REQUIRE(!(which & 32) || cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
+    E2V_REQUIRE(!(which & 64) || vcfg.clipv_layers > 0, E2V_ESTATE, "the context has no CLIP vision tower (e2v_create_clip_vision)");
     for (const auto& k : keys)
         if (which & key_part(k)) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
@@ -614,6 +634,15 @@ void e2v_ctx::finalize(int which) {
             }
         }
     }
+    // a CLIPEncoderLayer under its checkpoint names: the text tower's (part 8) and the vision tower's (part 64)
+    auto clip_layer = [&](const std::string& l) {
+        TextLayerW w;
+        w.ln1 = P.norm(l + ".layer_norm1"); w.ln2 = P.norm(l + ".layer_norm2");
+        w.qkv = P.fuse_rows({l + ".self_attn.q_proj", l + ".self_attn.k_proj", l + ".self_attn.v_proj"}, true);
+        w.out = P.lin(l + ".self_attn.out_proj");
+        w.fc1 = P.lin(l + ".mlp.fc1"); w.fc2 = P.lin(l + ".mlp.fc2");
+        return w;
+    };
     if (which & 8) {
         free_part(3);
         alloc_part = 3;
@@ -625,15 +654,7 @@ void e2v_ctx::finalize(int which) {
         t.tok = tok.d(); t.pos = pos.d();
         P.bind_raw(m + "embeddings.token_embedding.weight", tok.d(), (int)tok.shape[0], (int)tok.shape[1]);
         P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), (int)pos.shape[0], (int)pos.shape[1]);
-        for (int i = 0; i < cfg.text_layers; ++i) {
-            const std::string l = m + "encoder.layers." + std::to_string(i);
-            TextLayerW w;
-            w.ln1 = P.norm(l + ".layer_norm1"); w.ln2 = P.norm(l + ".layer_norm2");
-            w.qkv = P.fuse_rows({l + ".self_attn.q_proj", l + ".self_attn.k_proj", l + ".self_attn.v_proj"}, true);
-            w.out = P.lin(l + ".self_attn.out_proj");
-            w.fc1 = P.lin(l + ".mlp.fc1"); w.fc2 = P.lin(l + ".mlp.fc2");
-            t.layers.push_back(w);
-        }
+        for (int i = 0; i < cfg.text_layers; ++i) t.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
         t.ln_f = P.norm(m + "final_layer_norm");
         P.f32_only = false;
         text = std::move(t);
@@ -715,6 +736,30 @@ void e2v_ctx::finalize(int which) {
         P.f32_only = false;
         video = std::move(v);
     }
+    if (which & 64) {
+        free_part(6);
+        alloc_part = 6;
+        P.f32_only = true;
+        ClipVW v;
+        const std::string m = "clipv.vision_model.";
+        const int C = vcfg.clipv_hidden, T = clipv_tokens(), K = 3 * vcfg.clipv_patch_size * vcfg.clipv_patch_size;
+        const WTensor& cls = P.t(m + "embeddings.class_embedding");
+        const WTensor& pos = P.t(m + "embeddings.position_embedding.weight");
+        v.cls = cls.d(); v.pos = pos.d();
+        P.bind_raw(m + "embeddings.class_embedding", cls.d(), 1, C);
+        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), T, C);
+        {   // the patch convolution [C][3][P][P] (no bias) is the linear [C][3 P P] over the patch rows as it stands
+            const WTensor& w = P.t(m + "embeddings.patch_embedding.weight");
+            P.bind_raw(m + "embeddings.patch_embedding.weight", w.d(), C, K);
+            v.patch = P.mk_lin(w.d(), nullptr, K, C);
+        }
+        v.pre_ln = P.norm(m + "pre_layrnorm");
+        for (int i = 0; i < vcfg.clipv_layers; ++i) v.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
+        v.post_ln = P.norm(m + "post_layernorm");
+        v.proj = P.lin("clipv.visual_projection", false);
+        P.f32_only = false;
+        clipv = std::move(v);
+    }
     alloc_part = -1;
     resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
@@ -747,6 +792,10 @@ void e2v_ctx::finalize(int which) {
             if (k.find(".attention.attention.") != std::string::npos || (k.rfind("video.classifier.", 0) == 0 && cfg.vmae_num_labels % 4 != 0)) drop(k);
             continue;
         }
+        if (part == 64) {                        // as the text tower
+            if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
+            continue;
+        }
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
@@ -760,6 +809,7 @@ void e2v_ctx::finalize(int which) {
     if (which & 8) text_ready = true;
     if (which & 16) image_ready = true;
     if (which & 32) video_ready = true;
+    if (which & 64) clipv_ready = true;
 }
 
 // =====================================================================================================
@@ -810,6 +860,8 @@ void e2v_ctx::resolve_bindings() {
     fl(image.patch); fl(image.head);
     for (auto& l : video.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
     fl(video.patch); fl(video.head);
+    for (auto& l : clipv.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
+    fl(clipv.patch); fl(clipv.proj);
     for (auto& kv : bind) {
         WBind& b = kv.second;
         if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
@@ -1742,6 +1794,74 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
         Act lg = R.linear(video.head, pooled.p, C, ni, R.f32_rows());
         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
                    top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// CLIPImageProcessor + CLIPVisionModelWithProjection.forward(pixel_values).image_embeds (transformers: CLIPVisionEmbeddings -- the
+// patch convolution without bias, the class embedding, position embeddings --, pre_layrnorm over every token row, pre-LN encoder
+// layers without a mask, post_layernorm on the class row, visual_projection without bias): what the reference's clip_score
+// (40_class_run_metrics.py:20-55) normalises and multiplies.  The processor is the video classifier's crop-window preprocess with
+// bicubic tables and one frame per image; the rest is image_classify with a LayerNorm in front of the layers and clipv_act.  fp32 rows
+// and arithmetic whatever the compute mode.  Images are walked in chunks of E2V_CLIPV_CHUNK (256: at B/32's 50 tokens an image a
+// GEMM then sees 12800 rows, about the 64 x 197 = 12608 of the image classifier's chunk); every kernel here computes a row from
+// that row's image alone and in an order that does not depend on the row count, so the chunking does not show in the result.
+// -----------------------------------------------------------------------------------------------------
+const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
+    const std::array<int, 2> key{H, W};
+    auto it = clipv_prep_plans.find(key);
+    if (it == clipv_prep_plans.end()) {
+        if (clipv_prep_plans.size() >= 64) clipv_prep_plans.clear();
+        it = clipv_prep_plans.emplace(key, e2v::video_prep_plan(H, W, vcfg.clipv_resize_edge, vcfg.clipv_image_size, vcfg.clipv_patch_size, clipv_lut,
+                                                                vcfg.clipv_resample)).first;
+    }
+    return it->second;
+}
+
+void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float* embeds, hipStream_t s) {
+    E2V_REQUIRE(clipv_ready, E2V_ESTATE, "CLIP vision tower weights are not finalized");
+    Runner R{this, s, false};
+    const int C = vcfg.clipv_hidden, I = vcfg.clipv_intermediate, P = vcfg.clipv_patch_size, E = vcfg.clipv_projection_dim;
+    const int T = clipv_tokens(), K = 3 * P * P;
+    const float eps = vcfg.clipv_norm_eps;
+    const VideoPrepPlan& plan = clipv_prep_plan(H, W);
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band");
+    Act tables(pool, (int64_t)plan.words.size(), 1);
+    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
+    static const int* const chunk_knob = knob("E2V_CLIPV_CHUNK", 256);
+    const int chunk = std::min(std::max(*chunk_knob, 1), 4096);
+    const long long total = (long long)n * F;
+    for (long long i0 = 0; i0 < total; i0 += chunk) {
+        const int ni = (int)std::min<long long>(chunk, total - i0);
+        const int64_t M = (int64_t)ni * T;
+        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
+        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
+        Act x(pool, M, C);
+        {
+            Act rows(pool, (int64_t)ni * (T - 1), K);
+            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
+            Act patches = R.linear(clipv.patch, rows.p, K, (int64_t)ni * (T - 1), R.f32_rows());
+            Act tok(pool, M, C);
+            image_embed(patches.p, clipv.cls, clipv.pos, tok.p, ni, T, C, s);
+            ln(clipv.pre_ln, tok.p, x.p);
+        }
+        for (const TextLayerW& l : clipv.layers) {
+            Act h(pool, M, C);
+            ln(l.ln1, x.p, h.p);
+            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
+            Act a(pool, M, C);
+            image_attention(qkv.p, 3 * C, a.p, C, ni, T, vcfg.clipv_heads, s);
+            x = R.linear(l.out, a.p, C, M, plus(x));
+            ln(l.ln2, x.p, h.p);
+            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
+            text_activation(f.p, M * I, vcfg.clipv_act, s);
+            x = R.linear(l.fc2, f.p, I, M, plus(x));
+        }
+        Act cls(pool, ni, C);                                   // post_layernorm on the class rows only (row stride T * C)
+        layernorm(x.p, T * C, clipv.post_ln.g, clipv.post_ln.b, cls.p, C, ni, C, eps, s);
+        Act emb = R.linear(clipv.proj, cls.p, C, ni, R.f32_rows());
+        copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s);
     }
     E2V_HIP(hipGetLastError());
 }

@@ -121,6 +121,18 @@ struct VideoW {
     LinW head;                                                       // [labels rounded up to 4][C]
 };
 
+// CLIPVisionModelWithProjection (transformers; keys "clipv.vision_model....", "clipv.visual_projection.weight"): the image
+// classifier's token rows and layers with a LayerNorm in front of the layers, a patch embedding without bias, and a projection
+// without bias in place of the classifier
+struct ClipVW {
+    const float* cls = nullptr;                                      // [C]
+    const float* pos = nullptr;                                      // [T][C]
+    LinW patch;                                                      // the patch convolution as [C][3 P P], no bias
+    NormW pre_ln, post_ln;
+    std::vector<TextLayerW> layers;
+    LinW proj;                                                       // [projection_dim][C], no bias
+};
+
 // Where one raw state-dict tensor lives in the packed world of a finalized part (recorded by finalize(), used by e2v_update_tensor):
 //   RAW   the fp32 block the kernels read -- norm affines, plain biases (the uploaded block itself), a slice of a fused bias, the
 //         GEGLU bias (32-element groups interleaved);
@@ -188,13 +200,19 @@ struct e2v_ctx {
     e2v::TextW text;
     e2v::ImageW image;
     e2v::VideoW video;
+    e2v::ClipVW clipv;
     bool unet_ready = false, vae_ready = false, sem_ready = false, text_ready = false, image_ready = false, video_ready = false;
+    bool clipv_ready = false;
     float image_lut[3 * 256] = {};                               // the processor's pixel value of a byte, per channel (e2v_create)
     std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W)
     const e2v::ImagePrepPlan& prep_plan(int H, int W);
     float video_lut[3 * 256] = {};                               // the same two for the video classifier
     std::map<std::array<int, 2>, e2v::VideoPrepPlan> video_prep_plans;
     const e2v::VideoPrepPlan& video_prep_plan(int H, int W);
+    e2v_clipv_config vcfg = {};                                  // the CLIP vision tower's config (e2v_create_clip_vision); all zero: none
+    float clipv_lut[3 * 256] = {};                               // and for the CLIP vision tower's processor (bicubic tables)
+    std::map<std::array<int, 2>, e2v::VideoPrepPlan> clipv_prep_plans;
+    const e2v::VideoPrepPlan& clipv_prep_plan(int H, int W);
     int conv_algo = 0;                                           // e2v_set_conv_algo: 0 auto, 1 direct, 2 / 3 Winograd F(2x2) / F(4x4) wherever it applies
     bool wino_f4 = true;                                         // auto: F(4x4,3x3) where min(Cin, Cout) >= wino4_min_c and the map, padded to
     int wino4_min_c = 128;                                       //   multiples of 4, grows by <= wino_f4_pad (E2V_WINO_F4 / _F4_MIN_C / _F4_PAD)
@@ -224,7 +242,7 @@ struct e2v_ctx {
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
     void enter_stream(hipStream_t s);
     // device blocks made by dev_alloc, per part (bit index of `which`), so that finalizing a part again frees what it replaces
-    std::vector<e2v::DevBlock> owned_part[6];
+    std::vector<e2v::DevBlock> owned_part[7];
     size_t weight_bytes() const;                                 // what the uploaded tensors and the parts' blocks hold (e2v_device_bytes)
     void* comm = nullptr; int comm_rank = 0, comm_world = 0;     // RCCL communicator of e2v_comm_init (comm.cpp)
     // e2v_op_unet_forward_taps (test aid): while set, unet_forward_cl copies the tensors the oracle exposes (emb, down0..3, mid,
@@ -278,9 +296,14 @@ struct e2v_ctx {
         const int g = cfg.vmae_patch_size > 0 ? cfg.vmae_image_size / cfg.vmae_patch_size : 0;
         return (cfg.vmae_tubelet_size > 0 ? cfg.vmae_num_frames / cfg.vmae_tubelet_size : 0) * g * g;
     }
-    // which finalize() part owns a state-dict key: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier
+    // CLIPImageProcessor + CLIPVisionModelWithProjection over the n * F frames of `src`, walked in chunks of images;
+    // embeds [n*F][clipv_projection_dim]: image_embeds, not normalised
+    void clip_embed(const e2v::FrameSrc& src, int n, int F, int H, int W, float* embeds, hipStream_t s);
+    int clipv_tokens() const { const int g = vcfg.clipv_patch_size > 0 ? vcfg.clipv_image_size / vcfg.clipv_patch_size : 0; return g * g + 1; }
+    // which finalize() part owns a state-dict key: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video
+    // classifier, 64 CLIP vision tower
     static int key_part(const std::string& k) {
         return k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : k.rfind("text.", 0) == 0 ? 8 : k.rfind("image.", 0) == 0 ? 16 :
-               k.rfind("video.", 0) == 0 ? 32 : 1;
+               k.rfind("video.", 0) == 0 ? 32 : k.rfind("clipv.", 0) == 0 ? 64 : 1;
     }
 };

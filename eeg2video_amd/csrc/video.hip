@@ -31,11 +31,12 @@ VideoCrop video_crop(int H, int W, int edge, int S) {
 // row top + yy of the (H -> nh) table, output column xx is column left + xx of the (W -> nw) table.  Pillow computes the whole
 // resized image and the crop discards the rest; a sample inside the window depends on its own taps only, so the window's bytes are
 // Pillow's.  The vertical-first exception (PIL/Image.py) is decided by the source and the resize target, as there.
-VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768) {
+// `filter`: the processor's resample code (VideoMAE's is bilinear; the CLIP processor calls this with bicubic).
+VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768, int filter) {
     VideoPrepPlan p;
     p.H = H; p.W = W; p.S = S;
     p.crop = video_crop(H, W, edge, S);
-    const ResizeAxis hf = resize_axis(W, p.crop.nw), vf = resize_axis(H, p.crop.nh);
+    const ResizeAxis hf = resize_axis(W, p.crop.nw, filter), vf = resize_axis(H, p.crop.nh, filter);
     p.kh = hf.ksize; p.kv = vf.ksize;
     p.vfirst = (long long)H > 100LL * W && p.crop.nh < H;
     const int top = p.crop.top, left = p.crop.left;
@@ -79,9 +80,10 @@ namespace {
 // image_prep_kernel (vit.hip) with the window's tables and the tubelet layout: one workgroup takes `band` output rows of one channel
 // of one frame; the horizontally resized source rows of the band stay in LDS as bytes ([rows][S]); VFIRST: the vertically resized
 // rows of the band over the source columns [c0, c0 + cw) the window reads ([band][cw]).  Frame f = ts t + dt of a clip writes column
-// ((c ts + dt) P + y) P + x of token row (t, py, px).
+// ((c ts + dt) P + y) P + x of token row (t, py, px).  The launch covers frames img0 .. of the [n][F] source; a launch of whole clips
+// starts at a multiple of F, one at ts = 1 (the CLIP processor: every frame an image of its own) anywhere.
 template <bool F32, bool VFIRST>
-__global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int ts, long long clip0, int S, int P, int kh, int kv, int band,
+__global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int ts, long long img0, int S, int P, int kh, int kv, int band,
                                                          int c0, int cw, const int* __restrict__ plan, float* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vprep_tmp[];
     const int* hfirst = plan;
@@ -93,12 +95,13 @@ __global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int 
     const float* lut = reinterpret_cast<const float*>(vco + (size_t)S * kv);
     const int y0 = blockIdx.x * band, y1 = min(y0 + band, S);
     const int c = blockIdx.y;
-    const int lclip = blockIdx.z / F, f = blockIdx.z - lclip * F;
-    const int t = f / ts, dt = f - t * ts;
-    const long long base = (clip0 + lclip) * v.s_n + (long long)f * v.s_img + c * v.s_c;
+    const long long gimg = img0 + blockIdx.z;
+    const long long clip = gimg / F, f = gimg - clip * F;
+    const int t = blockIdx.z / ts, dt = blockIdx.z - t * ts;                 // (t counts the launch's tubelets: F is a multiple of ts)
+    const long long base = clip * v.s_n + f * v.s_img + c * v.s_c;
     const int np = S / P;
     const size_t K = (size_t)3 * ts * P * P;
-    const size_t row0 = ((size_t)lclip * (F / ts) + t) * np * np;
+    const size_t row0 = (size_t)t * np * np;
     const size_t col0 = (size_t)(c * ts + dt) * P * P;
     auto put = [&](int yy, int xx, int byte) {
         const int py = yy / P, px = xx / P;
@@ -144,27 +147,42 @@ __global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int 
 
 }  // namespace
 
-void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
-                      int P, float* rows, hipStream_t s) {
+namespace {
+
+void prep_launch(const FrameSrc& src, int F, int ts, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
+                 float* rows, hipStream_t s) {
     const int S = plan.S;
-    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "video preprocess: the source rows of one output row do not fit the kernel's LDS band");
-    E2V_REQUIRE(ts >= 1 && F % ts == 0 && nclips >= 1 && (long long)nclips * F <= 65535 && clip0 >= 0 && clip0 + nclips <= n, E2V_EINVAL,
-                "video preprocess: bad clip range");
     const long long HW = (long long)plan.H * plan.W;
     PrepView v;
     v.p = src.p;
     if (src.channels_last) { v.s_n = (long long)F * HW * 3; v.s_img = HW * 3; v.s_c = 1; v.s_y = (long long)plan.W * 3; v.s_x = 3; }
     else { v.s_n = 3LL * F * HW; v.s_img = HW; v.s_c = (long long)F * HW; v.s_y = plan.W; v.s_x = 1; }
     const size_t smem = (size_t)plan.band_rows * (plan.vfirst ? plan.cw : S);
-    const dim3 grid((S + plan.band - 1) / plan.band, 3, nclips * F);
-    const double nimg = (double)nclips * F;
+    const dim3 grid((S + plan.band - 1) / plan.band, 3, nimg);
     ProfScope ps("video_preprocess", 2.0 * nimg * 3 * S * ((double)plan.band_rows * (S / plan.band + 1) * plan.kh + (double)S * plan.kv),
-                 nimg * 3 * ((double)S * plan.W * (src.f32 ? 4.0 : 1.0) + 4.0 * S * S), s);
+                 (double)nimg * 3 * ((double)S * plan.W * (src.f32 ? 4.0 : 1.0) + 4.0 * S * S), s);
     auto launch = [&](auto kernel) {
-        E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, ts, clip0, S, P, plan.kh, plan.kv, plan.band, plan.c0, plan.cw, plan_dev, rows);
+        E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, ts, img0, S, P, plan.kh, plan.kv, plan.band, plan.c0, plan.cw, plan_dev, rows);
     };
     if (plan.vfirst) { if (src.f32) launch(video_prep_kernel<true, true>); else launch(video_prep_kernel<false, true>); }
     else { if (src.f32) launch(video_prep_kernel<true, false>); else launch(video_prep_kernel<false, false>); }
+}
+
+}  // namespace
+
+void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
+                      int P, float* rows, hipStream_t s) {
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "video preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    E2V_REQUIRE(ts >= 1 && F % ts == 0 && nclips >= 1 && (long long)nclips * F <= 65535 && clip0 >= 0 && clip0 + nclips <= n, E2V_EINVAL,
+                "video preprocess: bad clip range");
+    prep_launch(src, F, ts, clip0 * F, nclips * F, plan, plan_dev, P, rows, s);
+}
+
+void frame_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
+                      float* rows, hipStream_t s) {
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "frame preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    E2V_REQUIRE(nimg >= 1 && nimg <= 65535 && img0 >= 0 && img0 + nimg <= (long long)n * F, E2V_EINVAL, "frame preprocess: bad image range");
+    prep_launch(src, F, 1, img0, nimg, plan, plan_dev, P, rows, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -16,17 +16,40 @@ namespace e2v {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---------------------------------------------------------------------------------------------------------------------------
-// Pillow's Image.resize(BILINEAR) (src/libImaging/Resample.c, ImagingResampleInner for 8-bit images): per axis a table of
-// normalised triangle-filter weights in double (precompute_coeffs), rounded to 22-bit fixed point (normalize_coeffs_8bpc); the
+// Pillow's Image.resize(BILINEAR / BICUBIC) (src/libImaging/Resample.c, ImagingResampleInner for 8-bit images): per axis a table of
+// normalised filter weights in double (precompute_coeffs), rounded to 22-bit fixed point (normalize_coeffs_8bpc); the
 // horizontal pass runs first and its result is rounded to bytes before the vertical pass reads it -- except for an image more than
 // 100 times as tall as it is wide that is being shrunk vertically, which Image.resize (PIL/Image.py) resizes vertically first.
+// The filters are Resample.c's bilinear_filter (support 1) and bicubic_filter (a = -0.5, support 2); the bicubic one has negative
+// lobes, so coefficients may be negative and a sum may leave [0, 255]: the kernels' arithmetic >> 22 and clip8 are Pillow's.
+// The 22 bits leave the 32-bit accumulator room: it starts at 2^21 and the positive (negative) coefficients of an output add at most
+// 255 times their sum; both bounds are checked here for every output, so no table that would overflow reaches a kernel.
 // ---------------------------------------------------------------------------------------------------------------------------
-ResizeAxis resize_axis(int in_size, int out_size) {
+namespace {
+
+double bilinear_filter(double x) {
+    if (x < 0.0) x = -x;
+    return x < 1.0 ? 1.0 - x : 0.0;
+}
+
+double bicubic_filter(double x) {                                               // Resample.c: `#define a -0.5`
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+}  // namespace
+
+ResizeAxis resize_axis(int in_size, int out_size, int filter) {
+    E2V_REQUIRE(filter == kResizeBilinear || filter == kResizeBicubic, E2V_EINVAL, "resize filter: 2 (bilinear) or 3 (bicubic), Pillow's codes");
+    const bool cubic = filter == kResizeBicubic;
     ResizeAxis t;
     t.in = in_size; t.out = out_size;
     const double scale = (double)in_size / (double)out_size;
     const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 1.0 * filterscale;                                   // the bilinear filter's support is 1
+    const double support = (cubic ? 2.0 : 1.0) * filterscale;
     t.ksize = (int)std::ceil(support) * 2 + 1;
     t.first.assign(out_size, 0);
     t.count.assign(out_size, 0);
@@ -42,16 +65,20 @@ ResizeAxis resize_axis(int in_size, int out_size) {
         xmax -= xmin;
         double ww = 0.0;
         for (int x = 0; x < xmax; ++x) {
-            double a = (x + xmin - center + 0.5) * ss;
-            if (a < 0.0) a = -a;
-            const double w = a < 1.0 ? 1.0 - a : 0.0;
+            const double arg = (x + xmin - center + 0.5) * ss;
+            const double w = cubic ? bicubic_filter(arg) : bilinear_filter(arg);
             k[x] = w;
             ww += w;
         }
+        long long pos = 0, neg = 0;
         for (int x = 0; x < xmax; ++x) {
             if (ww != 0.0) k[x] /= ww;
-            t.coeff[(size_t)xx * t.ksize + x] = k[x] < 0 ? (int)(-0.5 + k[x] * (1 << 22)) : (int)(0.5 + k[x] * (1 << 22));
+            const int q = k[x] < 0 ? (int)(-0.5 + k[x] * (1 << 22)) : (int)(0.5 + k[x] * (1 << 22));
+            t.coeff[(size_t)xx * t.ksize + x] = q;
+            (q < 0 ? neg : pos) += q;
         }
+        E2V_REQUIRE((1LL << 21) + 255 * pos <= 2147483647LL && (1LL << 21) + 255 * neg >= -2147483648LL, E2V_ESHAPE,
+                    "resize table: an output's coefficients could overflow the 32-bit accumulator");
         t.first[xx] = xmin;
         t.count[xx] = xmax;
     }

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import TEXT_ACTS, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig
+from .weights import TEXT_ACTS, ClipVisionConfig, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -30,19 +30,21 @@ def _stream() -> int:
 class Engine:
     """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
     the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one, ``video_cfg``
-    (``None``: no video classifier) the ``VideoMAEForVideoClassification`` one."""
+    (``None``: no video classifier) the ``VideoMAEForVideoClassification`` one, ``clip_vision_cfg`` (``None``: no CLIP vision tower)
+    the ``CLIPVisionModelWithProjection`` one."""
 
-    UNET, VAE, SEMANTIC, TEXT, IMAGE, VIDEO = 1, 2, 4, 8, 16, 32
+    UNET, VAE, SEMANTIC, TEXT, IMAGE, VIDEO, CLIP_VISION = 1, 2, 4, 8, 16, 32, 64
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
                  sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None,
-                 image_cfg: Optional[ImageConfig] = None, video_cfg: Optional[VideoConfig] = None):
+                 image_cfg: Optional[ImageConfig] = None, video_cfg: Optional[VideoConfig] = None,
+                 clip_vision_cfg: Optional[ClipVisionConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
         self.lib = _lib.load()
         self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
-        self.image_cfg, self.video_cfg = image_cfg, video_cfg
+        self.image_cfg, self.video_cfg, self.clip_vision_cfg = image_cfg, video_cfg, clip_vision_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -76,7 +78,11 @@ class Engine:
             fill_video_config(cfg, video_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
-        st = self.lib.e2v_create(C.byref(cfg), device, C.byref(ctx))
+        if clip_vision_cfg is not None:                       # the tower's config is a struct of its own beside the e2v_config
+            self._clipv_cfg = clip_vision_config(clip_vision_cfg)
+            st = self.lib.e2v_create_clip_vision(C.byref(cfg), C.byref(self._clipv_cfg), device, C.byref(ctx))
+        else:
+            st = self.lib.e2v_create(C.byref(cfg), device, C.byref(ctx))
         if st != _lib.E2V_OK:
             raise _ERRORS.get(st, RuntimeError)(self.lib.e2v_last_error(None).decode())
         self.ctx = ctx
@@ -207,10 +213,10 @@ class Engine:
                                              self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
         return out
 
-    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video."}
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video.", 64: "clipv."}
 
     def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
-        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE`` / ``VIDEO``) as the device holds it NOW -- after any
+        """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE`` / ``VIDEO`` / ``CLIP_VISION``) as the device holds it NOW -- after any
         ``update_state_dict`` --, an ``OrderedDict`` in ``expected_keys()`` order with ``prefix`` (the one ``load_state_dict`` adds:
         ``'vae.'``, ``'semantic.'``, ``'text.'``) stripped from the names.  ``device``: ``'cuda'`` (tensors on the engine's device) or
         ``'cpu'``."""
@@ -221,7 +227,7 @@ class Engine:
         elif dev.type != "cpu":
             raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
         own = self._PART_PREFIX.get(part, "")
-        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO) or prefix not in ("", own):
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO, self.CLIP_VISION) or prefix not in ("", own):
             raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
         foreign = tuple(self._PART_PREFIX.values())
         out = OrderedDict()
@@ -648,6 +654,32 @@ class Engine:
                                                 top3.data_ptr(), _stream()))
         return logits, probs, top3
 
+    def clip_embed(self, frames: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
+        """``CLIPImageProcessor`` + ``CLIPVisionModelWithProjection`` over every frame (``e2v_clip_embed``; the model half of the
+        reference's ``clip_score``, ``40_class_run_metrics.py:20-55``) -> ``image_embeds`` fp32 ``[n*F, projection_dim]`` on the
+        engine's device, NOT normalised, frame ``f`` of clip ``i`` at row ``i*F + f``.  ``frames``: as ``classify_frames`` takes them.
+        fp32 arithmetic whatever the engine's compute dtype."""
+        if self.clip_vision_cfg is None:
+            raise RuntimeError("this engine was built without a CLIP vision tower (Engine(..., clip_vision_cfg=ClipVisionConfig()))")
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        out = torch.empty((n * f, self.clip_vision_cfg.projection_dim), device=self.device, dtype=torch.float32)
+        self._check(self.lib.e2v_clip_embed(self.ctx, t.data_ptr(), kind, n, f, h, w, out.data_ptr(), _stream()))
+        return out
+
+    def clip_similarity(self, a: torch.Tensor, b: torch.Tensor, matrix: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``torch.nn.functional.cosine_similarity(a, b, dim=-1)`` (eps 1e-8) of fp32 rows on the device (``e2v_clip_similarity``):
+        ``a`` ``[na, D]``, ``b`` ``[nb, D]`` -> ``[na]`` (pairs, ``na == nb``) or, with ``matrix``, ``[na, nb]`` over every pair of
+        rows.  Element ``(i, j)`` of the matrix carries the bits of the pair form on ``(a[i], b[j])``.  Needs no vision tower."""
+        a, b = self._dev(a, "a"), self._dev(b, "b")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError(f"clip_similarity: expected a [na, D] and b [nb, D], got {tuple(a.shape)} and {tuple(b.shape)}")
+        shape = (a.shape[0], b.shape[0]) if matrix else (a.shape[0],)
+        if out is None:
+            out = torch.empty(shape, device=self.device, dtype=torch.float32)
+        self._check(self.lib.e2v_clip_similarity(self.ctx, a.data_ptr(), a.shape[0], b.data_ptr(), b.shape[0], a.shape[1], int(bool(matrix)),
+                                                 out.data_ptr(), _stream()))
+        return out
+
     # ------------------------------------------------------------------ the one exchange of the path (SURVEY 8(e))
     def comm_init(self, group=None) -> int:
         """Open the library's own RCCL communicator over the ranks of the (already initialised) ``torch.distributed`` group:
@@ -838,6 +870,20 @@ class Engine:
                                                      out.data_ptr(), _stream()))
         return out
 
+    def op_clip_preprocess(self, frames, *, size, patch, edge, filter=3, lut=None, channels_last=False, out=None):
+        """``e2v_op_clip_preprocess``: frames -> the patch rows ``[n*F*(size/patch)^2, 3*patch^2]`` of the CLIP processor (shortest edge
+        resized to ``edge`` with Pillow's ``filter`` -- 2 BILINEAR, 3 BICUBIC --, centre crop of ``size``).  ``lut``: ``[3,256]`` fp32
+        pixel values of a byte per channel (``None``: the engine's CLIP vision config)."""
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        lut_p = None
+        if lut is not None:
+            lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(3, 256))
+            lut_p = lut.ctypes.data_as(C.POINTER(C.c_float))
+        out = self._op_out(out, (n * f * (size // patch) ** 2, 3 * patch * patch))
+        self._check(self.lib.e2v_op_clip_preprocess(self.ctx, t.data_ptr(), kind, n, f, h, w, size, patch, edge, filter, lut_p,
+                                                    out.data_ptr(), _stream()))
+        return out
+
     def op_token_attention(self, qkv, *, B, T, heads, out=None):
         """``e2v_op_token_attention``: ``qkv`` ``[B*T, 3*64*heads]`` (a 2-D view with unit column stride is read where it is) ->
         ``[B*T, 64*heads]``, non-causal, any ``T``, fp32 in every mode."""
@@ -913,17 +959,36 @@ def fill_video_config(cfg: "_lib.E2VConfig", video_cfg: VideoConfig) -> None:
     cfg.vmae_std = (C.c_float * 3)(*[float(v) for v in video_cfg.image_std])
 
 
-def image_resize_table(in_size: int, out_size: int):
-    """One axis of Pillow's antialiased BILINEAR resize (``e2v_image_resize_table``; host arithmetic, no GPU): ``(first, count, coeff)``
-    -- ``first``, ``count`` int32 ``[out_size]``, ``coeff`` int32 ``[out_size, ksize]`` in 22-bit fixed point."""
+def clip_vision_config(cv: ClipVisionConfig) -> "_lib.E2VClipVConfig":
+    """The ``e2v_clipv_config`` of a ``ClipVisionConfig`` (``e2v_create_clip_vision``)."""
+    cfg = _lib.E2VClipVConfig()
+    if cv.hidden_act not in TEXT_ACTS:
+        raise ValueError(f"clip vision hidden_act {cv.hidden_act!r}: the library has {sorted(TEXT_ACTS)}")
+    cfg.clipv_hidden, cfg.clipv_heads, cfg.clipv_layers, cfg.clipv_intermediate = cv.hidden, cv.heads, cv.layers, cv.intermediate
+    cfg.clipv_image_size, cfg.clipv_patch_size, cfg.clipv_projection_dim = cv.image_size, cv.patch_size, cv.projection_dim
+    cfg.clipv_act, cfg.clipv_norm_eps = TEXT_ACTS[cv.hidden_act], cv.layer_norm_eps
+    cfg.clipv_resize_edge, cfg.clipv_resample, cfg.clipv_rescale = cv.resize_edge, cv.resample, float(cv.rescale_factor)
+    cfg.clipv_mean = (C.c_float * 3)(*[float(v) for v in cv.image_mean])
+    cfg.clipv_std = (C.c_float * 3)(*[float(v) for v in cv.image_std])
+    return cfg
+
+
+def image_resize_table(in_size: int, out_size: int, filter: Optional[int] = None):
+    """One axis of Pillow's antialiased resize (host arithmetic, no GPU): ``(first, count, coeff)`` -- ``first``, ``count`` int32
+    ``[out_size]``, ``coeff`` int32 ``[out_size, ksize]`` in 22-bit fixed point.  ``filter``: ``None`` -- BILINEAR through
+    ``e2v_image_resize_table`` --, or Pillow's code through ``e2v_image_resize_table_filter``: 2 BILINEAR, 3 BICUBIC."""
     lib = _lib.load()
     ksize = C.c_int(0)
-    if lib.e2v_image_resize_table(in_size, out_size, None, None, None, C.byref(ksize)) != _lib.E2V_OK:
-        raise ValueError(f"image_resize_table({in_size}, {out_size}): sizes must be at least 1")
+    if filter is None:
+        call = lambda *a: lib.e2v_image_resize_table(in_size, out_size, *a)
+    else:
+        call = lambda *a: lib.e2v_image_resize_table_filter(in_size, out_size, int(filter), *a)
+    if call(None, None, None, C.byref(ksize)) != _lib.E2V_OK:
+        raise ValueError(f"image_resize_table({in_size}, {out_size}, filter={filter}): sizes must be at least 1, the filter 2 or 3")
     first, count = np.zeros(out_size, dtype=np.int32), np.zeros(out_size, dtype=np.int32)
     coeff = np.zeros((out_size, ksize.value), dtype=np.int32)
-    lib.e2v_image_resize_table(in_size, out_size, first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)),
-                               coeff.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(ksize))
+    call(first.ctypes.data_as(C.POINTER(C.c_int)), count.ctypes.data_as(C.POINTER(C.c_int)), coeff.ctypes.data_as(C.POINTER(C.c_int32)),
+         C.byref(ksize))
     return first, count, coeff
 
 

@@ -4,12 +4,14 @@ signatures -- ``channel_last``, ``ssim_metric``, ``mse_metric``, ``ssim_score_on
 one launch per clip instead of one host call per frame) -- and its image N-way accuracy, ``n_way_top_k_acc`` and
 ``img_classify_metric`` (``:57-105``), over ``Engine.classify_frames`` (``e2v_image_classify``: the ViT classifier of every frame of a
 clip in one call, fp32, instead of one fp16 forward per image), and its video N-way accuracy, ``video_classify_metric``
-(``:108-142``), over ``Engine.classify_clips`` (``e2v_video_classify``: the VideoMAE classifier of all clips in one call).  The CLIP
-score is not here.
+(``:108-142``), over ``Engine.classify_clips`` (``e2v_video_classify``: the VideoMAE classifier of all clips in one call), and its
+CLIP score, ``clip_score`` / ``clip_score_only`` / ``n_way_scores`` (``:20-55,145-188``), over ``Engine.clip_embed`` and
+``Engine.clip_similarity`` (``e2v_clip_embed``: the CLIP vision tower of every frame of a side in one call; ``e2v_clip_similarity``:
+the cosine of every pair in one more -- instead of two fp16 forwards per comparison).
 
 The frame metrics take an ``engine=`` keyword; by default one ``Engine()`` without weights is made on first use and kept.
-``img_classify_metric`` and ``video_classify_metric`` take a built classifier (``model=``) or a LOCAL checkpoint directory
-(``cache_dir=``).
+``img_classify_metric``, ``video_classify_metric`` and the CLIP scores take a built model (``model=``) or a LOCAL checkpoint
+directory (``cache_dir=``).
 """
 from __future__ import annotations
 
@@ -188,3 +190,89 @@ def video_classify_metric(pred_videos, gt_videos, n_way: int = 50, num_trials: i
     if return_std:
         return acc_list, std_list
     return acc_list
+
+
+_clip_models = {}
+
+
+def _clip_model(cache_dir: str, device):
+    key = os.path.abspath(cache_dir)
+    if key not in _clip_models:
+        from .clip_vision import CLIPVisionModelWithProjection
+        index = torch.device(device).index if device is not None else None
+        _clip_models[key] = CLIPVisionModelWithProjection.from_pretrained(cache_dir, device=index or 0)
+    return _clip_models[key]
+
+
+class clip_score:
+    """``40_class_run_metrics.py:20-55``: ``clip_score(device, cache_dir)(img1, img2)`` -> the cosine similarity of the CLIP image
+    embeddings of two ``[h,w,3]`` images of pixel values 0..255, a float.  ``model``: a built
+    ``eeg2video_amd.clip_vision.CLIPVisionModelWithProjection``; else ``cache_dir`` must be a LOCAL checkpoint directory of one (the
+    reference names the hub model there; nothing is fetched here), loaded once per directory.  fp32 where the reference runs fp16."""
+
+    def __init__(self, device: Optional[str] = "cuda", cache_dir: str = ".cache", model=None):
+        self.device = device
+        self.clip_model = model if model is not None else _clip_model(cache_dir, device)
+
+    def embed(self, images) -> torch.Tensor:
+        """``[f,h,w,3]`` images (or one) -> ``image_embeds`` ``[f, D]`` on the device, one call"""
+        return self.clip_model.embed(_frames(images), channels_last=True)
+
+    def similarity(self, a: torch.Tensor, b: torch.Tensor, matrix: bool = False) -> torch.Tensor:
+        return self.clip_model.engine.clip_similarity(a, b, matrix=matrix)
+
+    @torch.no_grad()
+    def __call__(self, img1, img2) -> float:
+        return self.similarity(self.embed(img1), self.embed(img2)).item()
+
+
+def clip_score_only(pred_videos, gt_videos, cache_dir: str = ".cache", device: Optional[str] = "cuda", model=None):
+    """``40_class_run_metrics.py:176-188``: the mean over the frames of the CLIP score of a generated frame and its ground truth.
+    ``pred_videos`` / ``gt_videos``: ``[f,h,w,3]`` pixel values 0..255.  Each side is embedded in ONE call, the ``f`` pair scores come
+    from one more."""
+    calc = clip_score(device, cache_dir, model)
+    a, b = calc.embed(pred_videos), calc.embed(gt_videos)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"{a.shape[0]} generated frames against {b.shape[0]} ground-truth frames")
+    scores = [float(v) for v in calc.similarity(a, b).cpu().numpy()]
+    return np.mean(scores)
+
+
+def n_way_from_matrix(scores, n_way: int, top_k: int, num_trials: int) -> List[float]:
+    """The trial loop of ``n_way_scores`` (``40_class_run_metrics.py:158-174``) over a matrix that already holds every score the
+    loop could ask for: ``scores[i][j]`` is the score of generated image ``i`` against ground-truth image ``j`` (square).  Host
+    arithmetic only.  The ``np.random.choice(len(rest), n_way - 1, replace=False)`` calls are the reference's, in its order, and index
+    its ``rest`` (the ground truths without ``idx``: entry ``r`` is ground truth ``r`` below ``idx`` and ``r + 1`` from there on);
+    ``0 in np.argsort(score_list)[-top_k:]`` is evaluated on the looked-up scores as Python floats, as ``.item()`` hands them to the
+    reference -> ``correct / num_trials`` per generated image."""
+    m = np.asarray(scores.detach().cpu() if isinstance(scores, torch.Tensor) else scores)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError(f"expected a square score matrix, got shape {m.shape}")
+    n = m.shape[0]
+    corrects = []
+    for idx in range(n):
+        row = [float(v) for v in m[idx]]
+        gt_score = row[idx]
+        correct_count = 0
+        for _ in range(num_trials):
+            n_imgs_idx = np.random.choice(n - 1, n_way - 1, replace=False)
+            score_list = [gt_score] + [row[int(r) if r < idx else int(r) + 1] for r in n_imgs_idx]
+            correct_count += 1 if 0 in np.argsort(score_list)[-top_k:] else 0
+        corrects.append(correct_count / num_trials)
+    return corrects
+
+
+def n_way_scores(pred_videos, gt_videos, n_way: int = 50, top_k: int = 1, num_trials: int = 10, cache_dir: str = ".cache",
+                 device: Optional[str] = "cuda", model=None) -> List[float]:
+    """``40_class_run_metrics.py:145-174``: per generated image, the fraction of ``num_trials`` trials in which its CLIP score against
+    its own ground truth is among the ``top_k`` of that score and the scores against ``n_way - 1`` other ground truths drawn at random.
+    ``pred_videos`` / ``gt_videos``: ``[n,h,w,3]`` pixel values 0..255, ``n >= n_way``.  The reference runs the processor and the model
+    again for both images of each of its ``n * (num_trials * (n_way - 1) + 1)`` comparisons; here each side is embedded ONCE, one
+    matrix call gives every score, and ``n_way_from_matrix`` replays the reference's draws on it: under the same numpy seed the
+    result is the reference's loop over the same scores."""
+    assert n_way > top_k
+    calc = clip_score(device, cache_dir, model)
+    a, b = calc.embed(pred_videos), calc.embed(gt_videos)
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f"{a.shape[0]} generated images against {b.shape[0]} ground-truth images")
+    return n_way_from_matrix(calc.similarity(a, b, matrix=True), n_way, top_k, num_trials)

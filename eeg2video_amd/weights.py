@@ -223,6 +223,60 @@ def image_param_spec(cfg: ImageConfig) -> "OrderedDict[str, Tuple[int, ...]]":
     return spec
 
 
+@dataclass(frozen=True)
+class ClipVisionConfig:
+    """``CLIPVisionModelWithProjection`` (``transformers`` ``CLIPVisionConfig``: ``hidden_size``, ``num_attention_heads``,
+    ``num_hidden_layers``, ``intermediate_size``, ``image_size``, ``patch_size``, ``projection_dim``, ``hidden_act``,
+    ``layer_norm_eps``) with its ``CLIPImageProcessor`` (``preprocessor_config.json``: ``size.shortest_edge`` = ``resize_edge``,
+    ``resample`` in Pillow's codes, a centre crop of ``image_size``, ``rescale_factor``, ``image_mean``, ``image_std``); defaults are
+    ``openai/clip-vit-base-patch32``, the model of the reference's ``clip_score``.  The head dim is 64 (``hidden == 64 * heads``)."""
+    hidden: int = 768
+    heads: int = 12
+    layers: int = 12
+    intermediate: int = 3072
+    image_size: int = 224
+    patch_size: int = 32
+    projection_dim: int = 512
+    hidden_act: str = "quick_gelu"
+    layer_norm_eps: float = 1e-5
+    resize_edge: int = 224
+    resample: int = 3
+    rescale_factor: float = 1 / 255
+    image_mean: Tuple[float, float, float] = (0.48145466, 0.4578275, 0.40821073)
+    image_std: Tuple[float, float, float] = (0.26862954, 0.26130258, 0.27577711)
+
+    @property
+    def tokens(self) -> int:
+        return (self.image_size // self.patch_size) ** 2 + 1
+
+
+#: 50 tokens -- B/32's count -- for a few hundred thousand parameters (tests/golden/clip_vision_tiny.npz)
+TINY_CLIP_VISION = ClipVisionConfig(hidden=128, heads=2, layers=2, intermediate=256, image_size=112, patch_size=16, projection_dim=64,
+                                    resize_edge=112)
+
+
+def clip_vision_param_spec(cfg: ClipVisionConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of the ``CLIPVisionModelWithProjection`` state dict as the ``openai/clip-vit-base-patch32`` checkpoint keys it
+    (``pre_layrnorm`` is the checkpoint's spelling; no ``position_ids`` buffer); the engine holds them under ``clipv.``."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c = cfg.hidden
+    spec["vision_model.embeddings.class_embedding"] = (c,)
+    spec["vision_model.embeddings.patch_embedding.weight"] = (c, 3, cfg.patch_size, cfg.patch_size)
+    spec["vision_model.embeddings.position_embedding.weight"] = (cfg.tokens, c)
+    _norm(spec, "vision_model.pre_layrnorm", c)
+    for i in range(cfg.layers):
+        p = f"vision_model.encoder.layers.{i}"
+        for n in ("q_proj", "k_proj", "v_proj", "out_proj"):
+            _lin(spec, f"{p}.self_attn.{n}", c, c)
+        _norm(spec, f"{p}.layer_norm1", c)
+        _norm(spec, f"{p}.layer_norm2", c)
+        _lin(spec, f"{p}.mlp.fc1", cfg.intermediate, c)
+        _lin(spec, f"{p}.mlp.fc2", c, cfg.intermediate)
+    _norm(spec, "vision_model.post_layernorm", c)
+    spec["visual_projection.weight"] = (cfg.projection_dim, c)
+    return spec
+
+
 #: how ``transformers`` 5 spells the per-layer tensors of the same model (``vit.layers.{i}.`` instead of ``vit.encoder.layer.{i}.``)
 _VIT_V5_NAMES = (("attention.q_proj.", "attention.attention.query."), ("attention.k_proj.", "attention.attention.key."),
                  ("attention.v_proj.", "attention.attention.value."), ("attention.o_proj.", "attention.output.dense."),

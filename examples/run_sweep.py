@@ -18,6 +18,11 @@ the ViT classifier of every generated and ground-truth frame runs in the score s
 ``--video-classifier DIR`` (with ``--score-against``; a LOCAL ``MCG-NJU/videomae-base-finetuned-kinetics`` checkpoint directory) adds
 its video accuracy (``:332-374``: ``video_classify_metric`` at 2 and 40 ways) as ``video_2way_acc`` / ``video_40way_acc``: the VideoMAE
 classifier of every generated and ground-truth clip, built for the sweep's frame count, runs next to it (``e2v_video_classify``).
+``--clip-model DIR`` (with ``--score-against``; a LOCAL ``openai/clip-vit-base-patch32`` checkpoint directory) adds its CLIP score
+(``:20-55,145-188``): ``clip_score_mean`` over the frames (``clip_score_only``) and the frame-level N-way CLIP accuracy
+``clip_2way_acc`` / ``clip_40way_acc`` (``n_way_scores``: 10 trials, top 1, seeded here; a sweep of fewer frames than ways leaves that
+key out).  Both sides' frames are embedded in the score stage (``e2v_clip_embed``); one ``e2v_clip_similarity`` matrix at the end holds
+every score the trials ask for.
 
     python examples/run_sweep.py --dtype bf16 --batch 32            # 200 clips on one GPU
     python -m torch.distributed.run --nproc-per-node 8 examples/run_sweep.py   # concepts sharded over ranks, frames gathered
@@ -59,7 +64,11 @@ def main(argv=None, engine=None):
                     help="with --score-against: local ViTForImageClassification checkpoint directory -> image_{2,40}way_acc")
     ap.add_argument("--video-classifier", default="", metavar="DIR",
                     help="with --score-against: local VideoMAEForVideoClassification checkpoint directory -> video_{2,40}way_acc")
+    ap.add_argument("--clip-model", default="", metavar="DIR",
+                    help="with --score-against: local CLIPVisionModelWithProjection checkpoint directory -> clip_score_mean, clip_{2,40}way_acc")
     args = ap.parse_args(argv)
+    if args.clip_model and not args.score_against:
+        ap.error("--clip-model scores against ground truth: give --score-against DIR too")
     if args.classifier and not args.score_against:
         ap.error("--classifier scores against ground truth: give --score-against DIR too")
     if args.video_classifier and not args.score_against:
@@ -106,7 +115,7 @@ def main(argv=None, engine=None):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a))
     neg = t(counter_normal(2, "neg", (1, scfg.tokens, ucfg.cross_attention_dim))).to(dev)
     stage = {"glmnet": 0.0, "seq2seq": 0.0, "semantic": 0.0, "dana": 0.0, "generate": 0.0, "uint8_d2h": 0.0, "write": 0.0}
-    mine, scores, classes, video_classes = [], [], [], []
+    mine, scores, classes, video_classes, clip_embeds = [], [], [], [], []
     if args.score_against:
         stage["score"] = 0.0
     vit = None
@@ -117,6 +126,10 @@ def main(argv=None, engine=None):
     if args.video_classifier:                                       # built for the sweep's frame count, as the reference passes num_frames
         from eeg2video_amd.video_classifier import VideoMAEForVideoClassification
         vmae = VideoMAEForVideoClassification.from_pretrained(args.video_classifier, num_frames=F, device=local)
+    clipm = None
+    if args.clip_model:
+        from eeg2video_amd.clip_vision import CLIPVisionModelWithProjection
+        clipm = CLIPVisionModelWithProjection.from_pretrained(args.clip_model, device=local)
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0)) - 2)))
     pending = []
@@ -169,6 +182,8 @@ def main(argv=None, engine=None):
                 classes.append((vit.classify(frames, channels_last=False)[1], vit.classify(gt, channels_last=True)[2]))
             if vmae is not None:                                    # the same per clip
                 video_classes.append((vmae.classify(frames, channels_last=False)[1], vmae.classify(gt, channels_last=True)[2]))
+            if clipm is not None:                                   # embeddings of both sides, per frame
+                clip_embeds.append((clipm.embed(frames, channels_last=False), clipm.embed(gt, channels_last=True)))
             tick("score", t0)
         t0 = time.perf_counter()
         u8 = eng.frames_to_uint8(frames).cpu()
@@ -212,6 +227,24 @@ def main(argv=None, engine=None):
                 np.random.seed(n_way)
                 acc = [n_way_top_k_acc(p, [int(i) for i in g], n_way, 100, 1)[0] for p, g in zip(probs.numpy(), top3.numpy())]
                 score_keys[f"{what}_{n_way}way_acc"] = float(np.mean(acc)) if acc else float("nan")
+        if clipm is not None:
+            from eeg2video_amd.metrics import n_way_from_matrix
+            D = clipm.config.projection_dim
+            pe = torch.cat([p for p, _ in clip_embeds]).cpu() if clip_embeds else torch.zeros((0, D))
+            ge = torch.cat([g for _, g in clip_embeds]).cpu() if clip_embeds else torch.zeros((0, D))
+            if world > 1:
+                parts = [None] * world
+                dist.all_gather_object(parts, (pe, ge))
+                pe, ge = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+            if len(pe):
+                t0 = time.perf_counter()
+                matrix = clipm.engine.clip_similarity(pe, ge, matrix=True).cpu().numpy()       # the pair scores are its diagonal, bit for bit
+                stage["score"] += time.perf_counter() - t0
+                score_keys["clip_score_mean"] = float(np.mean([float(v) for v in np.diagonal(matrix)]))
+                for n_way in (2, 40):
+                    if n_way <= len(pe):
+                        np.random.seed(n_way)
+                        score_keys[f"clip_{n_way}way_acc"] = float(np.mean(n_way_from_matrix(matrix, n_way, 1, 10)))
     if world > 1:
         u8_all = all_gather_frames(u8_all.to(dev).float() / 255.0, as_uint8=True).cpu()
         tt = torch.tensor([elapsed], device=dev, dtype=torch.float64)

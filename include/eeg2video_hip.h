@@ -129,6 +129,30 @@ const char* e2v_version(void);
 /* device = -1 creates a HOST-ONLY context: it serves the key scheme and the DDIM schedule (no HIP call is
  * made, so it works on a machine without a GPU); every device entry point then returns E2V_ESTATE. */
 e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out);
+
+/* CLIP vision tower (transformers CLIPVisionModelWithProjection, vision_config of openai/clip-vit-base-patch32: hidden_size,
+ * num_attention_heads, num_hidden_layers, intermediate_size, image_size, patch_size, projection_dim, hidden_act, layer_norm_eps:
+ * 768, 12, 12, 3072, 224, 32, 512, quick_gelu, 1e-5) and its CLIPImageProcessor (preprocessor_config.json: size.shortest_edge
+ * 224 = clipv_resize_edge, resample 3 = BICUBIC, a centre crop of image_size x image_size, rescale_factor 1 / 255, CLIP's mean
+ * and std).  A struct of its own, handed to e2v_create_clip_vision beside the e2v_config: e2v_config keeps its layout, and a binding
+ * made for an earlier library keeps working.  clipv_hidden must be 64 * clipv_heads, a multiple of 4 and at most 1280 (the LayerNorm
+ * kernel), clipv_intermediate and clipv_projection_dim multiples of 4, clipv_image_size a multiple of clipv_patch_size,
+ * 3 * clipv_patch_size^2 a multiple of 4, (image_size / patch_size)^2 + 1 tokens at most 288 (B/32: 50, B/16: 197, L/14: 257),
+ * clipv_resize_edge >= clipv_image_size, clipv_resample 2 or 3, every clipv_std non-zero. */
+typedef struct {
+    int clipv_hidden, clipv_heads, clipv_layers, clipv_intermediate, clipv_image_size, clipv_patch_size, clipv_projection_dim;
+    int clipv_act;                          /* 0 = quick_gelu, 1 = gelu (erf) */
+    float clipv_norm_eps;
+    int clipv_resize_edge;                  /* the processor's shortest_edge */
+    int clipv_resample;                     /* Pillow's filter code: 2 = BILINEAR, 3 = BICUBIC */
+    double clipv_rescale;                   /* pixel value of a byte b: ((float)(b * clipv_rescale) - clipv_mean[c]) / clipv_std[c], in fp32 */
+    float clipv_mean[3], clipv_std[3];
+} e2v_clipv_config;
+/* sizeof(e2v_clipv_config) as this build sees it: a binding asserts its own against it, as with e2v_config_size */
+int64_t e2v_clipv_config_size(void);
+/* e2v_create with a CLIP vision tower: the context also expects the "clipv." keys (part 64 of e2v_finalize_weights) and serves
+ * e2v_clip_embed.  clipv NULL or all zero: exactly e2v_create (no tower).  A bad tower config: E2V_EINVAL. */
+e2v_status e2v_create_clip_vision(const e2v_config* cfg, const e2v_clipv_config* clipv, int device, e2v_ctx** out);
 void e2v_destroy(e2v_ctx* ctx);
 const char* e2v_last_error(const e2v_ctx* ctx);      /* ctx may be NULL: last error of a failed e2v_create */
 
@@ -162,6 +186,12 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * "layernorm_{before,after}.*", "intermediate.dense.*", "output.dense.*", then "video.fc_norm.*", "video.classifier.*", and one key
  * that is not in a checkpoint: "video.videomae.embeddings.position_embeddings" [T][C], the fixed sinusoid transformers computes at
  * construction for the model's num_frames, supplied by the caller).  fp32 matrices only.
+ * bit 6 (64) = CLIP vision tower (a context made by e2v_create_clip_vision; the names of transformers' CLIPVisionModelWithProjection state dict
+ * under the prefix "clipv.": "clipv.vision_model.embeddings.class_embedding" [C], "...patch_embedding.weight" [C][3][P][P] (no
+ * bias), "...position_embedding.weight" [T][C], "clipv.vision_model.pre_layrnorm.*" (the checkpoint's spelling), per layer
+ * "clipv.vision_model.encoder.layers.{i}." "self_attn.{q,k,v,out}_proj.*", "layer_norm{1,2}.*", "mlp.fc{1,2}.*", then
+ * "clipv.vision_model.post_layernorm.*" and "clipv.visual_projection.weight" [projection_dim][C] (no bias); the position_ids
+ * buffer of older checkpoints is not a weight and not expected).  fp32 matrices only.
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -180,7 +210,8 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * A "text." key: E2V_EINVAL -- the text encoder is frozen on this path (train_finetune_videodiffusion.py:115
  * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8).
  * An "image." key: E2V_EINVAL as well -- the classifier is a frozen yardstick (40_class_run_metrics.py:70-72 loads it and only
- * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32). */
+ * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32).
+ * A "clipv." key (part 64) is updated like a UNet key: the tower keeps fp32 forms only. */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
@@ -206,7 +237,7 @@ enum {
  * finalize makes: a 3x3 conv [Cout,Cin,3,3] from the torch-layout weight the context keeps, a row range of a fused QKV / KV matrix
  * (and of its fused bias), the GEGLU row interleave of ff.net.0.proj undone, the K-padded first layer of the Semantic Predictor
  * without its padding columns, plain linears, 1x1 convs, norm affines and embeddings as they are.
- * `key`: any expected key (UNet, "vae.", "semantic.", "text.", "image.", "video.": reading a text or classifier tensor is allowed, only updating one is refused).
+ * `key`: any expected key (UNet, "vae.", "semantic.", "text.", "image.", "video.", "clipv.": reading a text or classifier tensor is allowed, only updating one is refused).
  * `form`: which stored form is read -- 0 or E2V_FORM_F32: the fp32 values (every tensor has them).  For the weight of a linear
  * (or 1x1 conv) also E2V_FORM_BF16 / E2V_FORM_F16: that stored 16-bit copy, widened exactly, and E2V_FORM_X3: (p0 + p1) + p2 of the
  * three planes in fp32, which is the fp32 weight exactly.  A form e2v_op_weight_forms does not report for the key: E2V_ESTATE ("form
@@ -456,6 +487,36 @@ e2v_status e2v_image_classify(e2v_ctx* ctx, const void* frames, int kind, int n,
  * no video classifier in the config, the part not finalized, or a host-only context: E2V_ESTATE. */
 e2v_status e2v_video_classify(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W,
                               float* logits, float* probs, int32_t* top3, e2v_stream stream);
+
+/* rank 8 -- replaces the model half of the CLIP score (EEG2Video/40_class_run_metrics.py:20-55: the clip_score class, called per
+ * frame pair by clip_score_only :176-188 and per comparison by n_way_scores :145-174): CLIPImageProcessor(image) and
+ * CLIPVisionModelWithProjection(...).image_embeds of every frame, on the device -- one call for a batch of frames instead of one
+ * fp16 forward per image of every comparison.
+ * frames, kind: as e2v_image_classify.  embeds [n*F][clipv_projection_dim] fp32 on the device, 4-byte aligned: the model's
+ * image_embeds, NOT normalised (e2v_clip_similarity divides by the norms).
+ * Preprocess: Pillow's Image.resize((nw, nh), clipv_resample) with the SHORTEST edge at clipv_resize_edge = E and the aspect ratio
+ * kept -- (nh, nw) = (E, int(E * W / H)) for H <= W, else (int(E * H / W), E) --, of which only the centre crop of S x S
+ * (S = clipv_image_size) is computed, then the pixel value of the config; bit-identical to CLIPImageProcessor on Pillow 12.
+ * Model: the patch embedding (no bias), the class embedding, position embeddings, pre_layrnorm over every token row,
+ * clipv_layers pre-LN encoder layers (non-causal attention, head dim 64, clipv_act), post_layernorm on the class row,
+ * visual_projection (no bias).  FP32 IN EVERY COMPUTE MODE.
+ * Images are walked in chunks; an image's embedding does not depend on the chunking, on n * F, on its position, on the compute mode
+ * or on the run.  Stream-ordered, does not synchronise, allocates nothing outside the workspace pool.
+ * Errors, in this order: null ctx / frames / embeds, misaligned, unknown bits in kind, n < 1: E2V_EINVAL; F, H or W < 1, or a
+ * downscale whose band does not fit the preprocess kernel's LDS: E2V_ESHAPE; no vision tower in the context (e2v_create_clip_vision), the part not finalized,
+ * or a host-only context: E2V_ESTATE. */
+e2v_status e2v_clip_embed(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W, float* embeds, e2v_stream stream);
+
+/* The score half: torch.nn.functional.cosine_similarity(a, b, dim=-1) with its eps = 1e-8,
+ * dot(a, b) / (max(|a|, eps) * max(|b|, eps)), of fp32 rows on the device.  a [na][D], b [nb][D], contiguous and 16-byte aligned,
+ * D a positive multiple of 4 (any D: the rows need not come from e2v_clip_embed and the context needs no vision tower).
+ * matrix = 0: na == nb, out[na], out[i] = cos(a[i], b[i]); matrix = 1: out[na][nb], out[i][j] = cos(a[i], b[j]).
+ * fp32 products summed in a fixed order that depends on D alone, no atomics: out[i][j] of the matrix form carries the bits of the
+ * pair form on (a[i], b[j]); a zero row gives 0, not NaN.  Stream-ordered, allocates nothing.
+ * Errors: a null or misaligned pointer, matrix not 0 or 1: E2V_EINVAL; na or nb < 1, D < 4 or not a multiple of 4, na != nb in the
+ * pair form, more than 65535 * 16 rows of a in the matrix form: E2V_ESHAPE; a host-only context: E2V_ESTATE. */
+e2v_status e2v_clip_similarity(e2v_ctx* ctx, const float* a, int na, const float* b, int nb, int D, int matrix, float* out,
+                               e2v_stream stream);
 
 /* ---- multi-GPU: the one exchange of the path ------------------------------------------------------------------
  * replaces: nothing in the reference (it generates its 200 clips serially on one GPU, inference_eeg2video.py:90); clips shard

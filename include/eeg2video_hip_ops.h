@@ -93,6 +93,10 @@ e2v_status e2v_op_causal_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, fl
  * HOST-ONLY: plain arithmetic, no context, no GPU.  first, count: out_size ints each; coeff: out_size * ksize entries; all three may be
  * NULL to ask for *ksize = 2 * ceil(max(in_size / out_size, 1)) + 1 alone.  E2V_EINVAL for a null ksize or a size below 1. */
 e2v_status e2v_image_resize_table(int in_size, int out_size, int* first, int* count, int32_t* coeff, int* ksize);
+/* The same with the filter named in Pillow's codes: 2 = BILINEAR (the table above, bit for bit), 3 = BICUBIC (Resample.c's
+ * bicubic_filter, a = -0.5, support 2: *ksize = 2 * ceil(2 * max(in_size / out_size, 1)) + 1, coefficients negative in places; an
+ * output's sum may leave [0, 255] and is clipped to a byte after the arithmetic >> 22, as Pillow does).  Any other filter: E2V_EINVAL. */
+e2v_status e2v_image_resize_table_filter(int in_size, int out_size, int filter, int* first, int* count, int32_t* coeff, int* ksize);
 
 /* The preprocess of e2v_image_classify on its own: n * F images of H x W (frames / kind as there) -> Pillow's bytes at S x S -> the
  * patch-row matrix rows [n*F*(S/P)^2][3*P*P] fp32 (device, 4-byte aligned), patch (py, px) of image i at row (i*(S/P) + py)*(S/P) + px,
@@ -116,6 +120,12 @@ e2v_status e2v_op_image_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, flo
  * has none).  S a multiple of P, edge >= S.  Needs no weights. */
 e2v_status e2v_op_video_preprocess(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W, int S, int P, int ts,
                                    int edge, const float* host_lut, float* rows, e2v_stream stream);
+
+/* The preprocess of e2v_clip_embed on its own: e2v_op_video_preprocess at ts = 1 (every frame an image of its own: row
+ * ((i*F + f)*(S/P) + py)*(S/P) + px, column (c*P + y)*P + x) with the resize filter named (2 = BILINEAR, 3 = BICUBIC; another:
+ * E2V_EINVAL).  host_lut NULL: the table of the context's vision-tower config (E2V_ESTATE if it has none). */
+e2v_status e2v_op_clip_preprocess(e2v_ctx* ctx, const void* frames, int kind, int n, int F, int H, int W, int S, int P, int edge,
+                                  int filter, const float* host_lut, float* rows, e2v_stream stream);
 
 /* Non-causal self-attention over each of B sequences of T tokens, ANY T >= 1, head dim 64, scale 64^-0.5, fp32 (exact fp32 matrix
  * instructions, online softmax over key tiles; K and V are read per tile and never resident).  qkv [B*T][ldqkv]: q | k | v, heads * 64
