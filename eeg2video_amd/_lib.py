@@ -119,6 +119,8 @@ SIGNATURES = {
     "e2v_ddim_next_step": (_i, [_ctx, _p, _p, _p, _i64, _i64, _i, _stream]),
     "e2v_ddim_invert": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
     "e2v_set_compute_dtype": (_i, [_ctx, _i]),
+    "e2v_set_tower_dtype": (_i, [_ctx, _i, _i]),
+    "e2v_tower_dtype": (_i, [_ctx, _i]),
     "e2v_set_conv_algo": (_i, [_ctx, _i]),
     "e2v_device_bytes": (_i64, [_ctx]),
     "e2v_comm_unique_id": (_i, [_p]),
@@ -146,6 +148,12 @@ SIGNATURES = {
     "e2v_op_image_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_video_preprocess": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
     "e2v_op_token_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
+    "e2v_op_tower_preprocess": (_i, [_ctx, _i, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_float), _p, _stream]),
+    "e2v_op_tower_attention": (_i, [_ctx, _i, _p, _i, _p, _i, _i, _i, _i, _stream]),
+    "e2v_op_tower_token_mean": (_i, [_ctx, _i, _p, _i, _i, _i, _p, _stream]),
+    "e2v_op_tower_layernorm": (_i, [_ctx, _i, _p, _i64, _i, _i, _p, _p, _f, _p, _stream]),
+    "e2v_op_tower_activation": (_i, [_ctx, _i, _p, _i64, _i, _p, _stream]),
+    "e2v_op_tower_embed": (_i, [_ctx, _i, _p, _p, _p, _i, _i, _i, _p, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
     "e2v_op_set_knob": (_i, [C.c_char_p, _i]),

@@ -83,6 +83,12 @@ struct OpRecord {
     }
     ~OpRecord() { op_recording() = false; }
 };
+// An entry point that may refuse a call BEFORE its OpRecord exists (argument checks, a host-only context) starts the record afresh
+// here: e2v_op_last_dispatch then says "" for the refused call, never the launches of an earlier one.
+void op_record_reset() {
+    static const int* const on = knob("E2V_OP_RECORD", 0);
+    if (*on) op_dispatch().clear();
+}
 
 // Test aid (E2V_OP_IO16): e2v_op_linear / e2v_op_conv3x3 of a 16-bit context build the launch of Runner::linear / Runner::conv3
 // (model.cpp) -- a 16-bit pool tensor of exactly M x N for the output, the residual converted to the type, out_f32 = 0, resid_bf16 = 1
@@ -834,6 +840,194 @@ e2v_status e2v_op_token_attention(e2v_ctx* c, const float* qkv, int ldqkv, float
     });
 }
 
+// ---- the metric towers in a 16-bit mode (e2v_set_tower_dtype) and the pieces of that path on their own ----------------------------
+namespace {
+int tower_mode_of(int dtype) { return dtype == E2V_BF16 ? H16_BF16 : dtype == E2V_F16 ? H16_FP16 : dtype == E2V_F32 ? H16_NONE : -1; }
+bool tower_exists(const e2v_ctx* c, int part) {
+    return part == 16 ? c->cfg.vit_layers > 0 : part == 32 ? c->cfg.vmae_layers > 0 : part == 64 ? c->vcfg.clipv_layers > 0 : false;
+}
+void require_h16(const char* who, int dtype) {
+    E2V_REQUIRE(dtype == E2V_BF16 || dtype == E2V_F16, E2V_EINVAL, std::string(who) + ": dtype is E2V_BF16 or E2V_F16");
+}
+}  // namespace
+
+e2v_status e2v_set_tower_dtype(e2v_ctx* c, int part, int dtype) {
+    if (!c) return E2V_EINVAL;
+    const int slot = e2v_ctx::tower_slot(part), mode = tower_mode_of(dtype);
+    if (slot < 0 || mode < 0) {
+        c->err = "e2v_set_tower_dtype: part is 16 (image classifier), 32 (video classifier) or 64 (CLIP vision tower); dtype is E2V_F32, E2V_BF16 or E2V_F16";
+        return E2V_EINVAL;
+    }
+    if (!tower_exists(c, part)) {
+        c->err = "e2v_set_tower_dtype: the context has no such tower (part " + std::to_string(part) + ")";
+        return E2V_ESTATE;
+    }
+    c->tower_h16[slot] = mode;
+    return E2V_OK;
+}
+
+int e2v_tower_dtype(const e2v_ctx* c, int part) {
+    const int slot = e2v_ctx::tower_slot(part);
+    if (!c || slot < 0) return -1;
+    const int m = c->tower_h16[slot];
+    return m == H16_BF16 ? E2V_BF16 : m == H16_FP16 ? E2V_F16 : E2V_F32;
+}
+
+// The three preprocess kernels storing 16-bit patch rows (what a tower in that mode feeds its patch linear), widened exactly into
+// the caller's fp32 `rows`: tower = 16 (image_preprocess), 32 (video_preprocess: ts, edge) or 64 (frame_preprocess: edge, filter).
+e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void* frames, int kind, int n, int F, int H, int W, int size,
+                                   int patch, int ts, int edge, int filter, const float* host_lut, float* rows, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    ImagePrepPlan iplan;
+    VideoPrepPlan vplan;
+    try {
+        check_frames("e2v_op_tower_preprocess", frames, kind, n, F, H, W);
+        require_h16("e2v_op_tower_preprocess", dtype);
+        E2V_REQUIRE(tower == 16 || tower == 32 || tower == 64, E2V_EINVAL, "e2v_op_tower_preprocess: tower is 16, 32 or 64");
+        E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0 && host_lut, E2V_EINVAL, "e2v_op_tower_preprocess: null or misaligned rows, or no pixel table");
+        E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0, E2V_ESHAPE, "e2v_op_tower_preprocess: 1 <= S <= 4096, a multiple of P >= 1");
+        if (tower == 32) E2V_REQUIRE(ts >= 1 && F % ts == 0 && F <= 4096, E2V_ESHAPE, "e2v_op_tower_preprocess: F must be a multiple of ts >= 1, at most 4096");
+        if (tower != 16) E2V_REQUIRE(edge >= size && edge <= 4096, E2V_ESHAPE, "e2v_op_tower_preprocess: S <= edge <= 4096");
+        if (tower == 64) E2V_REQUIRE(filter == kResizeBilinear || filter == kResizeBicubic, E2V_EINVAL, "e2v_op_tower_preprocess: filter 2 (BILINEAR) or 3 (BICUBIC)");
+        if (tower == 16) iplan = image_prep_plan(H, W, size, patch, host_lut);
+        else vplan = video_prep_plan(H, W, edge, size, patch, host_lut, tower == 64 ? filter : kResizeBilinear);
+        E2V_REQUIRE((tower == 16 ? iplan.band : vplan.band) >= 1, E2V_ESHAPE, "e2v_op_tower_preprocess: the source rows of one output row do not fit the kernel's LDS band");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype);
+        const std::vector<int>& words = tower == 16 ? iplan.words : vplan.words;
+        Act tables(c->pool, (int64_t)words.size(), 1);
+        E2V_HIP(hipMemcpyAsync(tables.p, words.data(), words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        E2V_HIP(hipStreamSynchronize(s));                    // (the plans are locals: a test aid may wait)
+        const int* tab = reinterpret_cast<const int*>(tables.p);
+        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const int tsz = tower == 32 ? ts : 1;
+        const long long np2 = (long long)(size / patch) * (size / patch);
+        const int K = 3 * tsz * patch * patch;
+        const long long per_img = np2 * 3 * patch * patch;      // row elements one frame contributes
+        const long long total = (long long)n * F;
+        const long long step = tower == 32 ? (long long)std::max(1, 4096 / F) * F : 4096;     // frames per launch (whole clips for the tubelets)
+        for (long long i0 = 0; i0 < total; i0 += step) {
+            const int ni = (int)std::min<long long>(step, total - i0);
+            const long long nrows = (long long)ni * per_img / K;
+            Act r16(c->pool, nrows, K, true);
+            if (tower == 16) image_preprocess(src, n, F, i0, ni, iplan, tab, patch, r16.p, s, mode);
+            else if (tower == 32) video_preprocess(src, n, F, ts, i0 / F, ni / F, vplan, tab, patch, r16.p, s, mode);
+            else frame_preprocess(src, n, F, i0, ni, vplan, tab, patch, r16.p, s, mode);
+            cvt_rows(r16.p, K, mode, rows + i0 * per_img, K, 0, nrows, K, K, s);
+        }
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// Attention as a tower in 16-bit mode runs it: qkv [B*T][ldqkv] (q | k | v of heads * 64 columns) rounded once to `dtype`, then
+// flash_attention on the 16-bit rows (mode 1, F = 1, Nq = Nk = T, head dim 64, scale 1/8), the 16-bit output widened exactly.
+e2v_status e2v_op_tower_attention(e2v_ctx* c, int dtype, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
+                                  e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        require_h16("e2v_op_tower_attention", dtype);
+        E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
+        E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && (double)B * T < 2147483648.0, E2V_ESHAPE, "tower attention: B, heads, T >= 1");
+        E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldo >= heads * 64, E2V_EINVAL, "tower attention: qkv rows of q | k | v, out rows of heads * 64 columns");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype), C = heads * 64;
+        const int64_t M = (int64_t)B * T;
+        OpRecord rec;
+        Act b(c->pool, M, 3 * C, true), o(c->pool, M, C, true);
+        cvt_rows(qkv, ldqkv, 0, b.p, 3 * C, mode, M, 3 * C, 3 * C, s);
+        AttnArgs a;
+        a.q = b.at(0); a.ldq = 3 * C; a.k = b.at(C); a.v = b.at(2 * C); a.ldkv = 3 * C; a.o = o.p; a.ldo = C;
+        a.n = B; a.F = 1; a.heads = heads; a.D = 64; a.Nq = T; a.Nk = T; a.mode = 1; a.scale = 0.125f; a.io_bf16 = mode;
+        flash_attention(a, s);
+        cvt_rows(o.p, C, mode, out, ldo, 0, M, C, C, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// token_mean over 16-bit rows: x [B*T][C] fp32 rounded once to `dtype`, out [B][C] fp32 (the sum in index order, fp32)
+e2v_status e2v_op_tower_token_mean(e2v_ctx* c, int dtype, const float* x, int B, int T, int C, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        require_h16("e2v_op_tower_token_mean", dtype);
+        E2V_REQUIRE(x && out && B >= 1 && B <= 65535 && T >= 1 && C >= 1, E2V_EINVAL, "tower token mean: null argument or bad sizes");
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype);
+        Act b(c->pool, (int64_t)B * T, C, true);
+        cvt_rows(x, C, 0, b.p, C, mode, (int64_t)B * T, C, C, s);
+        token_mean(b.p, out, B, T, C, s, mode);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// The LayerNorm in front of a tower's head in 16-bit mode: x [total_rows][C] fp32 rounded once to `dtype`; rows 0, stride, 2 stride, ...
+// (`rows` of them, stride in ROWS: a tower's class rows are T apart) are normalised into out [rows][C] fp32, not rounded.
+e2v_status e2v_op_tower_layernorm(e2v_ctx* c, int dtype, const float* x, int64_t rows, int stride, int C, const float* gamma,
+                                  const float* beta, float eps, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        require_h16("e2v_op_tower_layernorm", dtype);
+        E2V_REQUIRE(x && gamma && beta && out && rows >= 1 && stride >= 1 && C % 4 == 0 && C >= 4 && C <= 1280 && (double)stride * C < 2147483648.0 &&
+                        (double)rows * stride < 2147483648.0,
+                    E2V_EINVAL, "tower layernorm: null argument or bad sizes (C a multiple of 4 up to 1280)");
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype);
+        const int64_t total = (rows - 1) * stride + 1;
+        OpRecord rec;
+        Act b(c->pool, total, C, true);
+        cvt_rows(x, C, 0, b.p, C, mode, total, C, C, s);
+        layernorm_f32_out(b.p, stride * C, gamma, beta, out, C, (int)rows, C, eps, s, mode);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// The MLP activation on 16-bit storage: x [count] fp32 rounded once to `dtype`, act (0 quick-GELU, 1 erf GELU) in fp32, rounded
+// once more at the store; out [count] fp32 = the stored values widened.  count a multiple of 8.
+e2v_status e2v_op_tower_activation(e2v_ctx* c, int dtype, const float* x, int64_t count, int act, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        require_h16("e2v_op_tower_activation", dtype);
+        E2V_REQUIRE(x && out && count >= 8 && count % 8 == 0 && (act == 0 || act == 1), E2V_EINVAL, "tower activation: count a positive multiple of 8, act 0 or 1");
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype);
+        Act b(c->pool, count / 8, 8, true);
+        cvt_rows(x, 8, 0, b.p, 8, mode, count / 8, 8, 8, s);
+        text_activation(b.p, count, act, s, mode);
+        cvt_rows(b.p, 8, mode, out, 8, 0, count / 8, 8, 8, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// The token rows of a tower in 16-bit mode: patches [nimg*(T-1)][C] (cls != NULL: a class row in front, image_embed) or [nimg*T][C]
+// (cls == NULL: video_embed) fp32 rounded once to `dtype`; cls [C] and pos [T][C] stay fp32; out [nimg*T][C] fp32 = the stored rows widened.
+e2v_status e2v_op_tower_embed(e2v_ctx* c, int dtype, const float* patches, const float* cls, const float* pos, int nimg, int T, int C,
+                              float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        require_h16("e2v_op_tower_embed", dtype);
+        E2V_REQUIRE(patches && pos && out && nimg >= 1 && T >= (cls ? 2 : 1) && C >= 4 && C % 4 == 0 && (double)nimg * T < 2147483648.0, E2V_EINVAL,
+                    "tower embed: null argument or bad sizes (C a multiple of 4)");
+        hipStream_t s = S(c, stream);
+        const int mode = tower_mode_of(dtype);
+        const int64_t prow = (int64_t)nimg * (cls ? T - 1 : T), M = (int64_t)nimg * T;
+        Act p16(c->pool, prow, C, true), x16(c->pool, M, C, true);
+        cvt_rows(patches, C, 0, p16.p, C, mode, prow, C, C, s);
+        if (cls) image_embed(p16.p, cls, pos, x16.p, nimg, T, C, s, mode);
+        else video_embed(p16.p, pos, x16.p, nimg, T, C, s, mode);
+        cvt_rows(x16.p, C, mode, out, C, 0, M, C, C, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
 e2v_status e2v_profile_begin(e2v_ctx* c) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] { E2V_HIP(hipDeviceSynchronize()); profiler().begin(); });
@@ -1503,6 +1697,7 @@ e2v_status e2v_op_linear(e2v_ctx* c, const float* x, int ldx, int64_t M, int K, 
 e2v_status e2v_op_linear_cat(e2v_ctx* c, const float* x0, int c0, int ld0, const float* x1, int c1, int ld1, int64_t M, const float* w,
                              const float* bias, int N, const float* resid, int geglu, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
+    op_record_reset();
     // the argument checks make no HIP call, so they come before guarded(): a host-only context answers them too
     // one source: fp32 arithmetic reads 16-byte row pieces of the caller's tensor; the bf16-activation mode re-lays its operands out (K padded to 8)
     if (!(x0 && w && out && c0 > 0 && c1 >= 0 && (c1 == 0 || x1) && M >= 0 && N > 0 && (c->bf16_compute || (c0 % 4 == 0 && ld0 % 4 == 0)))) {

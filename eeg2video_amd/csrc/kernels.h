@@ -190,6 +190,10 @@ void groupnorm(const GroupNormArgs& a, hipStream_t s);
 void groupnorm_stats(const GroupNormArgs& a, hipStream_t s);
 void layernorm(const float* x, int ldx, const float* gamma, const float* beta, float* out, int ldo,
                int rows, int C, float eps, hipStream_t s, int bf16 = 0);      // bf16: x / out are bf16 rows
+// x16: bf16 / fp16 rows (h16: 1 / 2), out: fp32 rows -- the LayerNorm in front of a metric tower's head in 16-bit mode (the strided
+// class rows, or the pooled rows).  fp32 statistics, the result is not rounded.  C a multiple of 4 up to 1280.
+void layernorm_f32_out(const void* x16, int ldx, const float* gamma, const float* beta, float* out, int ldo, int rows, int C, float eps,
+                       hipStream_t s, int h16);
 
 // ---------------------------------------------------------------------------------------
 // attention (attn.hip)
@@ -229,10 +233,11 @@ void text_embed(const int* ids, const float* tok, const float* pos, float* out, 
 constexpr int kTextAttnMaxT = 128;      // 2 x 128 rows x 272 bytes = 68 KiB of the CU's 160; two keys per lane
 void text_causal_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
 // in place: act 0 = quick-GELU x sigmoid(1.702 x), 1 = erf GELU; count a multiple of 4
-void text_activation(float* x, long long count, int act, hipStream_t s);
+// h16 = 1 / 2: x is bf16 / fp16 storage (count a multiple of 8): widened, the activation in fp32, rounded once at the store
+void text_activation(float* x, long long count, int act, hipStream_t s, int h16 = 0);
 
 // ---------------------------------------------------------------------------------------
-// ViT image classifier (vit.hip; e2v_image_classify): fp32 in every compute mode.  LayerNorm, the linears and the GELU are
+// ViT image classifier (vit.hip; e2v_image_classify): fp32 whatever the context's mode; `h16` selects the tower's 16-bit rows.  LayerNorm, the linears and the GELU are
 // norm.hip's, igemm.hip's and text.hip's.
 // ---------------------------------------------------------------------------------------
 struct FrameSrc;                            // (below: the input description e2v_frame_metrics shares)
@@ -257,10 +262,13 @@ constexpr int kImagePrepLdsBytes = 48 * 1024;     // the band of horizontally re
 ImagePrepPlan image_prep_plan(int H, int W, int S, int P, const float* lut768);
 // frames (FrameSrc: fp32 quantised at load or bytes, planar [n,3,F,H,W] or channels-last [n,F,H,W,3]) -> rows [n*F*(S/P)^2][3*P*P];
 // `plan_dev`: plan.words on the device
+// h16 = 1 / 2: `rows` is bf16 / fp16 storage -- the pixel table's fp32 value rounded once at the store (the integer arithmetic in
+// front of the table is the same)
 void image_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const ImagePrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s);
+                      float* rows, hipStream_t s, int h16 = 0);
 // x[i][0][:] = cls + pos[0], x[i][1 + p][:] = patches[i * (T - 1) + p][:] + pos[1 + p]   (C a multiple of 4)
-void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s);
+// h16 = 1 / 2: patches and x are bf16 / fp16 rows (cls and pos stay fp32; fp32 sum, one rounding at the store)
+void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s, int h16 = 0);
 // non-causal self-attention over each of B images of T tokens, head dim 64, scale 64^-0.5; layouts as text_causal_attention.
 // K and V of an (image, head) live in LDS at the 68-float stride, which bounds T:
 constexpr int kImageAttnMaxT = 288;     // 2 x 288 rows x 272 bytes = 153 KiB of the CU's 160; up to five keys per lane
@@ -270,7 +278,7 @@ void image_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, in
 void image_head(const float* logits, int ld, int L, int nimg, float* logits_out, float* probs, int* top3, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
-// VideoMAE video classifier (video.hip; e2v_video_classify): fp32 in every compute mode.  The encoder layers are the image
+// VideoMAE video classifier (video.hip; e2v_video_classify): fp32 whatever the context's mode; `h16` as above.  The encoder layers are the image
 // classifier's; the head's softmax / top 3 is image_head.
 // ---------------------------------------------------------------------------------------
 // VideoMAEImageProcessor's geometry: the shortest edge resized to `edge` with the aspect ratio kept, then the centre crop of S x S
@@ -287,21 +295,22 @@ VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float*
 // clips clip0 .. clip0 + nclips - 1 of `src` ([n][F] frames of plan.H x plan.W) -> rows [nclips*(F/ts)*(S/P)^2][3*ts*P*P]: frame
 // ts*t + dt of a clip writes columns ((c*ts + dt)*P + y)*P + x of the clip's token rows (t, py, px)
 void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
-                      int P, float* rows, hipStream_t s);
+                      int P, float* rows, hipStream_t s, int h16 = 0);     // h16: as image_preprocess
 // the same at ts = 1 for frames img0 .. img0 + nimg - 1 of the [n][F] source, every frame an image of its own (a range may start
 // and end inside a clip) -> rows [nimg*(S/P)^2][3*P*P]: the patch layout of image_preprocess
 void frame_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s);
+                      float* rows, hipStream_t s, int h16 = 0);
 // x[b*T + t][:] = patches[b*T + t][:] + pos[t][:]   (C a multiple of 4; no class row)
-void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s);
+void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s, int h16 = 0);     // h16: as image_embed
 // non-causal self-attention over each of B sequences of T tokens (any T >= 1), head dim 64, scale 64^-0.5; q | k | v in one row matrix
 // as image_attention takes them (16-byte aligned rows, strides multiples of 4).  K and V are read per key tile, never resident.
 void token_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
 // out[b][:] = (sum over t of x[b*T + t][:], t ascending) / T   (x rows of C columns, contiguous)
-void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s);
+// h16 = 1 / 2: x is bf16 / fp16 rows, widened exactly; the sum, its order and the fp32 output are the same
+void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s, int h16 = 0);
 
 // ---------------------------------------------------------------------------------------
-// CLIP vision tower and CLIP score (clip.hip; e2v_clip_embed, e2v_clip_similarity): fp32 in every compute mode.  The processor is
+// CLIP vision tower and CLIP score (clip.hip; e2v_clip_embed, e2v_clip_similarity): the similarity is fp32 always, the tower as the classifiers.  The processor is
 // video_preprocess at ts = 1 over a bicubic plan (every frame its own image: rows [images * patches][3 P P]); the token rows, the
 // attention and the layers are the image classifier's.
 // ---------------------------------------------------------------------------------------

@@ -351,20 +351,31 @@ void e2v_ctx::conv_fill(const ConvW& w, ConvForm f, hipStream_t s) {
 
 // fp16 mode: the IEEE-half copy of a linear's weight, derived on first use from the fp32 matrix finalize() kept (same layout as the
 // bf16 copy: rows zero-padded to in16), filed under the finalize() group that owns the layer.
-const void* e2v_ctx::lin_f16(const LinW& w, hipStream_t s) {
-    if (w.w16h) return w.w16h;
-    AllocPart guard(this, w.part);
+static const void* lin_h16_form(e2v_ctx* c, const LinW& w, int mode, hipStream_t s) {
+    e2v_ctx::AllocPart guard(c, w.part);
     const size_t n = (size_t)w.out * w.in16;
-    float* d16 = dev_alloc((n + 1) / 2);
+    float* d16 = c->dev_alloc((n + 1) / 2);
     if (w.in16 == w.in) {
-        to_h16(w.w, d16, n, H16_FP16, s);
+        to_h16(w.w, d16, n, mode, s);
     } else {
-        Act tmp(pool, (int64_t)((n + 1023) / 1024), 1024);
+        Act tmp(c->pool, (int64_t)((n + 1023) / 1024), 1024);
         pad_cols(w.w, w.in, tmp.p, w.in16, w.out, s);
-        to_h16(tmp.p, d16, n, H16_FP16, s);
+        to_h16(tmp.p, d16, n, mode, s);
     }
-    w.w16h = d16;
     return d16;
+}
+
+const void* e2v_ctx::lin_f16(const LinW& w, hipStream_t s) {
+    if (!w.w16h) w.w16h = lin_h16_form(this, w, H16_FP16, s);
+    return w.w16h;
+}
+
+// The bf16 copy of a linear that finalize() left fp32 only (the metric towers; a tower in bf16 mode): the same derivation, on first
+// use.  Both 16-bit copies of a tower stay until the part is finalized again -- switching a tower's mode back and forth costs nothing
+// after the first call in each mode, and e2v_update_tensor keeps every copy that exists in step.
+const void* e2v_ctx::lin_b16(const LinW& w, hipStream_t s) {
+    if (!w.w16) w.w16 = lin_h16_form(this, w, H16_BF16, s);
+    return w.w16;
 }
 
 void e2v_ctx::enter_stream(hipStream_t s) {
@@ -407,6 +418,13 @@ struct Packer {
         WBind b;
         b.kind = WBind::LIN; b.anchor = anchor; b.rows = (int)w.shape[0]; b.in = (int)w.shape[1]; b.row_off = row_off;
         b.half = half; b.blk = 32;
+        c->bind[k] = b;
+    }
+    // a conv weight that IS a linear as it stands ([rows][in] over its trailing dims: the towers' patch convolutions): bound as one, so
+    // that the 16-bit copies a tower builds on first use follow e2v_update_tensor and can be read back
+    void bind_matrix(const std::string& k, const float* anchor, int rows, int in) {
+        WBind b;
+        b.kind = WBind::LIN; b.anchor = anchor; b.rows = rows; b.in = in; b.blk = 32;
         c->bind[k] = b;
     }
     const void* half(const float* w, size_t n) {             // bf16 copy of a (packed) weight for the bf16-MFMA mode
@@ -698,7 +716,7 @@ void e2v_ctx::finalize(int which) {
         {   // the patch convolution [C][3][P][P] is the linear [C][3 P P] over the patch rows as it stands
             const std::string n = m + "embeddings.patch_embeddings.projection";
             const WTensor& w = P.t(n + ".weight");
-            P.bind_raw(n + ".weight", w.d(), C, K);
+            P.bind_matrix(n + ".weight", w.d(), C, K);
             P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
             v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
         }
@@ -724,7 +742,7 @@ void e2v_ctx::finalize(int which) {
         {   // the tubelet convolution [C][3][ts][P][P] is the linear [C][3 ts P P] over the patch rows as it stands
             const std::string n = m + "embeddings.patch_embeddings.projection";
             const WTensor& w = P.t(n + ".weight");
-            P.bind_raw(n + ".weight", w.d(), C, K);
+            P.bind_matrix(n + ".weight", w.d(), C, K);
             P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
             v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
         }
@@ -750,7 +768,7 @@ void e2v_ctx::finalize(int which) {
         P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), T, C);
         {   // the patch convolution [C][3][P][P] (no bias) is the linear [C][3 P P] over the patch rows as it stands
             const WTensor& w = P.t(m + "embeddings.patch_embedding.weight");
-            P.bind_raw(m + "embeddings.patch_embedding.weight", w.d(), C, K);
+            P.bind_matrix(m + "embeddings.patch_embedding.weight", w.d(), C, K);
             v.patch = P.mk_lin(w.d(), nullptr, K, C);
         }
         v.pre_ln = P.norm(m + "pre_layrnorm");
@@ -1027,13 +1045,14 @@ struct Runner {
     hipStream_t s;
     const bool small_family;          // the dispatch family of the API call this runner serves (model.h), fixed for its lifetime
     int res_idx = 0, tr_idx = 0;      // position in the per-generate caches (resnets with a time embedding / transformers)
+    int tower = -1;                   // >= 0: the runner serves a metric tower and this is ITS mode (e2v_set_tower_dtype), not the context's
     Pool& pool() { return c->pool; }
     // bf16-activation mode (e2v_set_compute_dtype(E2V_BF16)): every activation the graph stores in HBM is bf16; accumulation,
     // GroupNorm / LayerNorm statistics, softmax and the time-embedding rows stay fp32
-    bool bf() const { return c->bf16_compute; }
-    int h16() const { return c->bf16_compute ? c->h16_mode : 0; }      // the mode flag of every 16-bit launch: 1 bf16, 2 fp16 (h16.h)
+    int h16() const { return tower >= 0 ? tower : c->bf16_compute ? c->h16_mode : 0; }      // the mode flag of every 16-bit launch: 1 bf16, 2 fp16 (h16.h)
+    bool bf() const { return h16() != 0; }
     bool fp16() const { return h16() == H16_FP16; }
-    const void* w16_of(const LinW& w) { return fp16() ? c->lin_f16(w, s) : w.w16; }
+    const void* w16_of(const LinW& w) { return fp16() ? c->lin_f16(w, s) : c->lin_b16(w, s); }
     Act new_act(int64_t rows, int C) { return Act(pool(), rows, C, bf()); }
     // fp32 rows -> bf16 rows padded to `cpad` channels (boundary tensors: latents, z, images, conditioning)
     Act to_act16(const float* x, int cols, int cpad, int64_t rows) {
@@ -1639,6 +1658,59 @@ void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, flo
 }
 
 // -----------------------------------------------------------------------------------------------------
+// The encoder layers of a metric tower (parts 16 / 32 / 64: pre-LN, no mask, head dim 64) over n sequences of T token rows, in the
+// mode of the tower the runner serves (Runner::tower, e2v_set_tower_dtype) -- ONE body for the three modes:
+//   fp32 (0)    fp32 rows, the linears as the time-embedding MLP takes them (f32_rows), attention by `attn32` (the tower's fp32 kernel);
+//   bf16 / fp16 the token rows live in HBM as 16-bit; LayerNorm is the 16-bit kernel (fp32 statistics, the tower's eps); the linears
+//               are 16-bit MFMA with fp32 accumulation, fp32 bias and residual added before the one store rounding; the activation is
+//               computed in fp32 on 16-bit storage, in place; attention is flash_attention on the 16-bit rows (mode 1, F = 1,
+//               Nq = Nk = T: fp32 scores and softmax, 16-bit P and output).
+// Every kernel computes a row from its own sequence in an order fixed by (T, C, I), and the runner is of the large dispatch family (no
+// split-K), so a sequence's bits do not depend on n.
+// -----------------------------------------------------------------------------------------------------
+namespace {
+
+LinOpt tower_rows(const Runner& R) { LinOpt o; o.f32_io = !R.bf(); return o; }      // fp32 mode: fp32 rows whatever the context's mode
+
+template <class Attn32>
+Act tower_layers(Runner& R, const std::vector<TextLayerW>& layers, Act x, int n, int T, int heads, int I, float eps, int act, Attn32 attn32) {
+    const int C = heads * 64, h16 = R.h16();
+    const int64_t M = (int64_t)n * T;
+    hipStream_t s = R.s;
+    E2V_REQUIRE(!h16 || I % 8 == 0, E2V_ESHAPE, "a tower in 16-bit mode needs an intermediate width that is a multiple of 8");
+    auto ln = [&](const NormW& w, const Act& in, Act& out) { layernorm(in.p, C, w.g, w.b, out.p, C, (int)M, C, eps, s, h16); };
+    auto plus = [&](const Act& r) { LinOpt o = tower_rows(R); o.resid = r.p; o.ldr = C; return o; };
+    for (const TextLayerW& l : layers) {
+        Act h(R.pool(), M, C, R.bf());
+        ln(l.ln1, x, h);
+        Act qkv = R.linear(l.qkv, h.p, C, M, tower_rows(R));
+        Act a(R.pool(), M, C, R.bf());
+        if (!h16) {
+            attn32(qkv.p, a.p);
+        } else {
+            AttnArgs g;
+            g.q = qkv.at(0); g.ldq = 3 * C; g.k = qkv.at(C); g.v = qkv.at(2 * C); g.ldkv = 3 * C; g.o = a.p; g.ldo = C;
+            g.n = n; g.F = 1; g.heads = heads; g.D = 64; g.Nq = T; g.Nk = T; g.mode = 1; g.scale = 0.125f; g.io_bf16 = h16;
+            flash_attention(g, s);
+        }
+        x = R.linear(l.out, a.p, C, M, plus(x));
+        ln(l.ln2, x, h);
+        Act f = R.linear(l.fc1, h.p, C, M, tower_rows(R));
+        text_activation(f.p, M * I, act, s, h16);
+        x = R.linear(l.fc2, f.p, I, M, plus(x));
+    }
+    return x;
+}
+
+// the LayerNorm in front of a tower's head: `rows` rows of x at stride ldx (the class rows, or pooled fp32 rows) -> fp32 rows
+void tower_head_ln(const Runner& R, const NormW& w, const float* x, int ldx, bool x_is_f32, float* out, int rows, int C, float eps) {
+    if (R.h16() && !x_is_f32) layernorm_f32_out(x, ldx, w.g, w.b, out, C, rows, C, eps, R.s, R.h16());
+    else layernorm(x, ldx, w.g, w.b, out, C, rows, C, eps, R.s);
+}
+
+}  // namespace
+
+// -----------------------------------------------------------------------------------------------------
 // CLIPTextModel.forward(input_ids)[0] (transformers: CLIPTextTransformer -- embeddings, pre-LN encoder layers under the causal
 // mask, final_layer_norm).  fp32 rows and fp32 arithmetic whatever the context's compute mode (the linears go the way of the
 // time-embedding MLP), so the same ids give the same bits in every mode.
@@ -1672,8 +1744,9 @@ void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t 
 // -----------------------------------------------------------------------------------------------------
 // ViTImageProcessor + ViTForImageClassification.forward(pixel_values).logits (transformers: ViTEmbeddings -- patch convolution,
 // class token, position embeddings --, pre-LN encoder layers without a mask, the final LayerNorm, the classifier on the class row),
-// then the softmax and the top-3 indices img_classify_metric takes from it (40_class_run_metrics.py:95-98).  fp32 rows and fp32
-// arithmetic whatever the context's compute mode, as text_encode.  Images are walked in chunks of E2V_VIT_CHUNK (64): every kernel
+// then the softmax and the top-3 indices img_classify_metric takes from it (40_class_run_metrics.py:95-98).  The arithmetic is the
+// TOWER's mode (e2v_set_tower_dtype; tower_layers above), fp32 by default, whatever the context's compute mode; the head is fp32
+// always.  Images are walked in chunks of E2V_VIT_CHUNK (64): every kernel
 // here computes a row from that row's image alone and in an order that does not depend on the row count, so the chunking does not
 // show in the result.
 // -----------------------------------------------------------------------------------------------------
@@ -1690,9 +1763,12 @@ const ImagePrepPlan& e2v_ctx::prep_plan(int H, int W) {
 void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, float* logits, float* probs, int* top3, hipStream_t s) {
     E2V_REQUIRE(image_ready, E2V_ESTATE, "image classifier weights are not finalized");
     Runner R{this, s, false};
+    R.tower = tower_h16[tower_slot(16)];
+    const int h16 = R.h16();
     const int C = cfg.vit_hidden, I = cfg.vit_intermediate, P = cfg.vit_patch_size, L = cfg.vit_num_labels;
     const int T = image_tokens(), K = 3 * P * P;
     const float eps = cfg.vit_norm_eps;
+    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_image_classify: a 16-bit tower needs 3 * patch_size^2 to be a multiple of 8");
     const ImagePrepPlan& plan = prep_plan(H, W);
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
     Act tables(pool, (int64_t)plan.words.size(), 1);
@@ -1703,29 +1779,17 @@ void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, fl
     for (long long i0 = 0; i0 < total; i0 += chunk) {
         const int ni = (int)std::min<long long>(chunk, total - i0);
         const int64_t M = (int64_t)ni * T;
-        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
-        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
-        Act x(pool, M, C);
+        Act x(pool, M, C, R.bf());
         {
-            Act rows(pool, (int64_t)ni * (T - 1), K);
-            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
-            Act patches = R.linear(image.patch, rows.p, K, (int64_t)ni * (T - 1), R.f32_rows());
-            image_embed(patches.p, image.cls, image.pos, x.p, ni, T, C, s);
+            Act rows(pool, (int64_t)ni * (T - 1), K, R.bf());
+            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
+            Act patches = R.linear(image.patch, rows.p, K, (int64_t)ni * (T - 1), tower_rows(R));
+            image_embed(patches.p, image.cls, image.pos, x.p, ni, T, C, s, h16);
         }
-        for (const TextLayerW& l : image.layers) {
-            Act h(pool, M, C);
-            ln(l.ln1, x.p, h.p);
-            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
-            Act a(pool, M, C);
-            image_attention(qkv.p, 3 * C, a.p, C, ni, T, cfg.vit_heads, s);
-            x = R.linear(l.out, a.p, C, M, plus(x));
-            ln(l.ln2, x.p, h.p);
-            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
-            text_activation(f.p, M * I, 1, s);
-            x = R.linear(l.fc2, f.p, I, M, plus(x));
-        }
-        Act cls(pool, ni, C);                                   // the final LayerNorm on the class rows only (row stride T * C)
-        layernorm(x.p, T * C, image.ln_f.g, image.ln_f.b, cls.p, C, ni, C, eps, s);
+        x = tower_layers(R, image.layers, std::move(x), ni, T, cfg.vit_heads, I, eps, 1,
+                         [&](const float* qkv, float* a) { image_attention(qkv, 3 * C, a, C, ni, T, cfg.vit_heads, s); });
+        Act cls(pool, ni, C);                                   // the final LayerNorm on the class rows only (row stride T * C): fp32 from here on
+        tower_head_ln(R, image.ln_f, x.p, T * C, false, cls.p, ni, C, eps);
         Act lg = R.linear(image.head, cls.p, C, ni, R.f32_rows());
         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
                    top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
@@ -1737,7 +1801,7 @@ void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, fl
 // VideoMAEImageProcessor + VideoMAEForVideoClassification.forward(pixel_values).logits (transformers: VideoMAEEmbeddings -- the
 // tubelet convolution and the fixed sinusoid table --, pre-LN encoder layers without a mask, no final LayerNorm under
 // use_mean_pooling, the mean over the tokens, fc_norm at nn.LayerNorm's default eps, the classifier), then the softmax and the top-3
-// indices video_classify_metric takes from it (40_class_run_metrics.py:128-139).  fp32 rows and arithmetic whatever the compute mode.
+// indices video_classify_metric takes from it (40_class_run_metrics.py:128-139).  The tower's own mode, as image_classify.
 // Clips are walked in chunks of E2V_VMAE_CHUNK (16): every kernel here computes a row from that row's clip alone and in an order
 // that does not depend on the row count, so the chunking does not show in the result.
 // -----------------------------------------------------------------------------------------------------
@@ -1755,9 +1819,12 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
     E2V_REQUIRE(video_ready, E2V_ESTATE, "video classifier weights are not finalized");
     E2V_REQUIRE(F == cfg.vmae_num_frames, E2V_ESHAPE, "e2v_video_classify: F must be vmae_num_frames");
     Runner R{this, s, false};
+    R.tower = tower_h16[tower_slot(32)];
+    const int h16 = R.h16();
     const int C = cfg.vmae_hidden, I = cfg.vmae_intermediate, P = cfg.vmae_patch_size, ts = cfg.vmae_tubelet_size, L = cfg.vmae_num_labels;
     const int T = video_tokens(), K = 3 * ts * P * P;
     const float eps = cfg.vmae_norm_eps;
+    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_video_classify: a 16-bit tower needs 3 * tubelet_size * patch_size^2 to be a multiple of 8");
     const VideoPrepPlan& plan = video_prep_plan(H, W);
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
     Act tables(pool, (int64_t)plan.words.size(), 1);
@@ -1767,30 +1834,18 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int ni = std::min(chunk, n - i0);
         const int64_t M = (int64_t)ni * T;
-        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
-        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
-        Act x(pool, M, C);
+        Act x(pool, M, C, R.bf());
         {
-            Act rows(pool, M, K);
-            video_preprocess(src, n, F, ts, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
-            Act patches = R.linear(video.patch, rows.p, K, M, R.f32_rows());
-            video_embed(patches.p, video.pos, x.p, ni, T, C, s);
+            Act rows(pool, M, K, R.bf());
+            video_preprocess(src, n, F, ts, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
+            Act patches = R.linear(video.patch, rows.p, K, M, tower_rows(R));
+            video_embed(patches.p, video.pos, x.p, ni, T, C, s, h16);
         }
-        for (const TextLayerW& l : video.layers) {
-            Act h(pool, M, C);
-            ln(l.ln1, x.p, h.p);
-            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
-            Act a(pool, M, C);
-            token_attention(qkv.p, 3 * C, a.p, C, ni, T, cfg.vmae_heads, s);
-            x = R.linear(l.out, a.p, C, M, plus(x));
-            ln(l.ln2, x.p, h.p);
-            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
-            text_activation(f.p, M * I, 1, s);
-            x = R.linear(l.fc2, f.p, I, M, plus(x));
-        }
-        Act mean(pool, ni, C), pooled(pool, ni, C);
-        token_mean(x.p, mean.p, ni, T, C, s);
-        layernorm(mean.p, C, video.fc_norm.g, video.fc_norm.b, pooled.p, C, ni, C, 1e-5f, s);       // fc_norm = nn.LayerNorm(hidden): the default eps
+        x = tower_layers(R, video.layers, std::move(x), ni, T, cfg.vmae_heads, I, eps, 1,
+                         [&](const float* qkv, float* a) { token_attention(qkv, 3 * C, a, C, ni, T, cfg.vmae_heads, s); });
+        Act mean(pool, ni, C), pooled(pool, ni, C);             // fp32 from here on: the mean reads the 16-bit rows of a 16-bit tower
+        token_mean(x.p, mean.p, ni, T, C, s, h16);
+        tower_head_ln(R, video.fc_norm, mean.p, C, true, pooled.p, ni, C, 1e-5f);                   // fc_norm = nn.LayerNorm(hidden): the default eps
         Act lg = R.linear(video.head, pooled.p, C, ni, R.f32_rows());
         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
                    top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
@@ -1803,8 +1858,8 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
 // patch convolution without bias, the class embedding, position embeddings --, pre_layrnorm over every token row, pre-LN encoder
 // layers without a mask, post_layernorm on the class row, visual_projection without bias): what the reference's clip_score
 // (40_class_run_metrics.py:20-55) normalises and multiplies.  The processor is the video classifier's crop-window preprocess with
-// bicubic tables and one frame per image; the rest is image_classify with a LayerNorm in front of the layers and clipv_act.  fp32 rows
-// and arithmetic whatever the compute mode.  Images are walked in chunks of E2V_CLIPV_CHUNK (256: at B/32's 50 tokens an image a
+// bicubic tables and one frame per image; the rest is image_classify with a LayerNorm in front of the layers and clipv_act.  The
+// tower's own mode, as image_classify.  Images are walked in chunks of E2V_CLIPV_CHUNK (256: at B/32's 50 tokens an image a
 // GEMM then sees 12800 rows, about the 64 x 197 = 12608 of the image classifier's chunk); every kernel here computes a row from
 // that row's image alone and in an order that does not depend on the row count, so the chunking does not show in the result.
 // -----------------------------------------------------------------------------------------------------
@@ -1822,9 +1877,12 @@ const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
 void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float* embeds, hipStream_t s) {
     E2V_REQUIRE(clipv_ready, E2V_ESTATE, "CLIP vision tower weights are not finalized");
     Runner R{this, s, false};
+    R.tower = tower_h16[tower_slot(64)];
+    const int h16 = R.h16();
     const int C = vcfg.clipv_hidden, I = vcfg.clipv_intermediate, P = vcfg.clipv_patch_size, E = vcfg.clipv_projection_dim;
     const int T = clipv_tokens(), K = 3 * P * P;
     const float eps = vcfg.clipv_norm_eps;
+    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_clip_embed: a 16-bit tower needs 3 * patch_size^2 to be a multiple of 8");
     const VideoPrepPlan& plan = clipv_prep_plan(H, W);
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band");
     Act tables(pool, (int64_t)plan.words.size(), 1);
@@ -1835,31 +1893,19 @@ void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float*
     for (long long i0 = 0; i0 < total; i0 += chunk) {
         const int ni = (int)std::min<long long>(chunk, total - i0);
         const int64_t M = (int64_t)ni * T;
-        auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
-        auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
-        Act x(pool, M, C);
+        Act x(pool, M, C, R.bf());
         {
-            Act rows(pool, (int64_t)ni * (T - 1), K);
-            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s);
-            Act patches = R.linear(clipv.patch, rows.p, K, (int64_t)ni * (T - 1), R.f32_rows());
-            Act tok(pool, M, C);
-            image_embed(patches.p, clipv.cls, clipv.pos, tok.p, ni, T, C, s);
-            ln(clipv.pre_ln, tok.p, x.p);
+            Act rows(pool, (int64_t)ni * (T - 1), K, R.bf());
+            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
+            Act patches = R.linear(clipv.patch, rows.p, K, (int64_t)ni * (T - 1), tower_rows(R));
+            Act tok(pool, M, C, R.bf());
+            image_embed(patches.p, clipv.cls, clipv.pos, tok.p, ni, T, C, s, h16);
+            layernorm(tok.p, C, clipv.pre_ln.g, clipv.pre_ln.b, x.p, C, (int)M, C, eps, s, h16);
         }
-        for (const TextLayerW& l : clipv.layers) {
-            Act h(pool, M, C);
-            ln(l.ln1, x.p, h.p);
-            Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
-            Act a(pool, M, C);
-            image_attention(qkv.p, 3 * C, a.p, C, ni, T, vcfg.clipv_heads, s);
-            x = R.linear(l.out, a.p, C, M, plus(x));
-            ln(l.ln2, x.p, h.p);
-            Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
-            text_activation(f.p, M * I, vcfg.clipv_act, s);
-            x = R.linear(l.fc2, f.p, I, M, plus(x));
-        }
-        Act cls(pool, ni, C);                                   // post_layernorm on the class rows only (row stride T * C)
-        layernorm(x.p, T * C, clipv.post_ln.g, clipv.post_ln.b, cls.p, C, ni, C, eps, s);
+        x = tower_layers(R, clipv.layers, std::move(x), ni, T, vcfg.clipv_heads, I, eps, vcfg.clipv_act,
+                         [&](const float* qkv, float* a) { image_attention(qkv, 3 * C, a, C, ni, T, vcfg.clipv_heads, s); });
+        Act cls(pool, ni, C);                                   // post_layernorm on the class rows only (row stride T * C): fp32 from here on
+        tower_head_ln(R, clipv.post_ln, x.p, T * C, false, cls.p, ni, C, eps);
         Act emb = R.linear(clipv.proj, cls.p, C, ni, R.f32_rows());
         copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s);
     }

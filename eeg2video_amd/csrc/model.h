@@ -15,7 +15,8 @@
 namespace e2v {
 
 struct NormW { const float* g = nullptr; const float* b = nullptr; int c = 0; };
-struct LinW { const float* w = nullptr; const float* b = nullptr; int in = 0, out = 0; const void* w16 = nullptr;
+struct LinW { const float* w = nullptr; const float* b = nullptr; int in = 0, out = 0;
+              mutable const void* w16 = nullptr;   // the bf16 copy: made by finalize(), or -- the metric towers, whose finalize() keeps fp32 only -- on first use (e2v_ctx::lin_b16)
               const void* w3 = nullptr;         // three bf16 planes of w (out*in elements apart) for the f32x3 mode
               int in16 = 0;                     // row length of w16: `in` rounded up to 8 (zero columns; 16-byte DMA pieces)
               int part = 0;                     // which finalize() group owns the lazily built fp16 form
@@ -92,7 +93,9 @@ struct VAEW {
     NormW enc_norm_out;
 };
 
-// CLIPTextModel (transformers: the text tower of SD-v1-4, keys "text.text_model...."): fp32 matrices only, in every compute mode
+// CLIPTextModel (transformers: the text tower of SD-v1-4, keys "text.text_model...."): fp32 matrices only, in every compute mode.
+// The metric towers (parts 16 / 32 / 64) share the packing; finalize() gives them fp32 matrices too, and a tower switched to a 16-bit
+// mode (e2v_set_tower_dtype) derives the bf16 / fp16 copy of each matrix on first use (LinW::w16 / w16h).
 struct TextLayerW { NormW ln1, ln2; LinW qkv, out, fc1, fc2; };      // qkv: q_proj | k_proj | v_proj fused [3C][C] with its [3C] bias
 struct TextW {
     const float* tok = nullptr; const float* pos = nullptr;          // [vocab][C], [max_positions][C]
@@ -223,6 +226,10 @@ struct e2v_ctx {
     bool bf16_compute = false;                                   // e2v_set_compute_dtype: a 16-bit activation mode (16-bit MFMA, 16-bit rows in HBM) ...
     int h16_mode = 0;                                            // ... and which: 0 none, 1 bf16 (E2V_BF16), 2 fp16 (E2V_F16) -- the flag every 16-bit launch carries (h16.h)
     void set_h16_mode(int m) { h16_mode = m; bf16_compute = m != 0; }
+    // e2v_set_tower_dtype: the arithmetic of the three metric towers, each on its own and whatever the mode above -- 0 fp32 (the
+    // default), 1 bf16, 2 fp16 (h16.h), indexed by tower_slot(part)
+    int tower_h16[3] = {0, 0, 0};
+    static int tower_slot(int part) { return part == 16 ? 0 : part == 32 ? 1 : part == 64 ? 2 : -1; }
     std::vector<e2v::LinW> sem;                                  // semantic predictor layers (first one K-padded to 4)
     int sem_in_pad = 0;
     std::vector<float> alphas;                                   // host alpha-bar table
@@ -270,6 +277,7 @@ struct e2v_ctx {
     float* dev_alloc(size_t floats);
     enum ConvForm { FORM_DIRECT32, FORM_BF16, FORM_WINO2, FORM_WINO4, FORM_BF16_UP2, FORM_F16, FORM_F16_UP2 };
     const void* lin_f16(const e2v::LinW& w, hipStream_t s);              // the fp16 copy of a linear's weight (built on first use)
+    const void* lin_b16(const e2v::LinW& w, hipStream_t s);              // the bf16 copy: finalize()'s, or built on first use (metric towers)
     void conv_form(const e2v::ConvW& w, ConvForm f, hipStream_t s);     // build the layout if this is its first use
     void conv_fill(const e2v::ConvW& w, ConvForm f, hipStream_t s);     // derive the (allocated) layout from w.raw: first use and weight updates
     // THE Winograd policy: the output tile a 3x3 conv of this shape runs with -- 0 direct, 2 F(2x2,3x3), 4 F(4x4,3x3)

@@ -746,9 +746,10 @@ void groupnorm(const GroupNormArgs& a, hipStream_t s) {
 // One wave per R rows, a row held in registers (C <= 64 VE NV), all loads of the R rows issued before the first reduction (a wave
 // that owns one 640-byte row spends its life on launch, two shuffle chains and a store: 2.9 TB/s effective).  fp32 rows and 16-bit
 // rows that are no multiple of 8 wide: VE = 4, R = 1; 16-bit rows of 8-channel pieces: VE = 8, R = 4.
-template <typename T, int VE, int NV, int R>
+// TO: the output rows' type -- T, or float behind 16-bit input rows (the head of a metric tower in 16-bit mode: layernorm_f32_out).
+template <typename T, int VE, int NV, int R, typename TO = T>
 __global__ __launch_bounds__(256) void layernorm_wave_kernel(const T* __restrict__ x, int ldx, const float* __restrict__ gamma,
-                                                             const float* __restrict__ beta, T* __restrict__ out, int ldo,
+                                                             const float* __restrict__ beta, TO* __restrict__ out, int ldo,
                                                              int rows, int C, float eps) {
     using V = RowVec<T, VE>;
     const int lane = threadIdx.x & 63;
@@ -799,8 +800,17 @@ __global__ __launch_bounds__(256) void layernorm_wave_kernel(const T* __restrict
             const V g = V::load_f32(gamma + q * VE), b = V::load_f32(beta + q * VE);
 #pragma unroll
             for (int r = 0; r < R; ++r)
-                if (row0 + r < rows)
-                    v[r][k].ln_affine(s[r], rsqrtf(ss[r] / (float)C + eps), g, b).store(out + (size_t)(row0 + r) * ldo + q * VE);
+                if (row0 + r < rows) {
+                    const V y = v[r][k].ln_affine(s[r], rsqrtf(ss[r] / (float)C + eps), g, b);
+                    TO* o = out + (size_t)(row0 + r) * ldo + q * VE;
+                    if constexpr (std::is_same<TO, T>::value) {
+                        y.store(o);
+                    } else {
+                        RowVec<TO, VE> w;
+                        w.q[0] = y.q[0];
+                        w.store(o);
+                    }
+                }
         }
     }
 }
@@ -993,6 +1003,26 @@ void layernorm(const float* x, int ldx, const float* gamma, const float* beta, f
         H* xo = reinterpret_cast<H*>(out);
         if (k.ve == 8) layernorm_launch<H, 8>(k, xi, ldx, gamma, beta, xo, ldo, rows, C, eps, s);
         else layernorm_launch<H, 4>(k, xi, ldx, gamma, beta, xo, ldo, rows, C, eps, s);
+    });
+}
+
+// 16-bit rows in, fp32 rows out: the wave-per-row kernel over four-channel pieces (the statistics and the affine are the 16-bit
+// LayerNorm's, the result is not rounded).  A handful of rows per call: the class rows / pooled rows in front of a tower's head.
+void layernorm_f32_out(const void* x16, int ldx, const float* gamma, const float* beta, float* out, int ldo, int rows, int C, float eps,
+                       hipStream_t s, int h16) {
+    E2V_REQUIRE(h16 == H16_BF16 || h16 == H16_FP16, E2V_EINVAL, "layernorm_f32_out: 16-bit input rows (bf16 or fp16)");
+    E2V_REQUIRE(C % 4 == 0 && C >= 4 && C <= 1280 && ldx % 4 == 0 && ldo % 4 == 0, E2V_ESHAPE, "layernorm_f32_out: C a multiple of 4 up to 1280, strides multiples of 4");
+    if (rows <= 0) return;
+    ProfScope ps("layernorm_f32_out", 8.0 * rows * C, 6.0 * rows * C, s);
+    if (dry_run() || op_recording()) dry_tag(" -> layernorm_kernel f32out");
+    const int blocks = (rows + 3) / 4;
+    h16_dispatch(h16, [&](auto h16_tag) {
+        using H = decltype(h16_tag);
+        const H* xi = reinterpret_cast<const H*>(x16);
+        auto go = [&](auto kern) { E2V_KLAUNCH(kern, dim3(blocks), dim3(256), 0, s, xi, ldx, gamma, beta, out, ldo, rows, C, eps); };
+        if (C <= 256) go(layernorm_wave_kernel<H, 4, 1, 1, float>);
+        else if (C <= 768) go(layernorm_wave_kernel<H, 4, 3, 1, float>);
+        else go(layernorm_wave_kernel<H, 4, 5, 1, float>);
     });
 }
 

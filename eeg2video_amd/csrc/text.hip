@@ -1,8 +1,11 @@
 // Kernels of the CLIP text encoder (transformers CLIPTextModel: the pre-LN text transformer behind e2v_text_encode) that the
 // rest of the library has no counterpart for: the embedding gather, causal self-attention over one prompt and the MLP's
-// activation.  LayerNorm and the linears are norm.hip's and igemm.hip's.  Everything here is fp32 in every compute mode.
+// activation.  LayerNorm and the linears are norm.hip's and igemm.hip's.  fp32 in every compute mode; the activation pass also comes
+// on 16-bit storage, for the metric towers in 16-bit mode (e2v_set_tower_dtype).
 #include <cmath>
 
+#include "act_io.h"
+#include "h16.h"
 #include "kernels.h"
 #include "prof.h"
 #include "runtime.h"
@@ -133,15 +136,37 @@ __global__ __launch_bounds__(256) void text_activation_kernel(float* __restrict_
     }
 }
 
-void text_activation(float* x, long long count, int act, hipStream_t s) {
-    E2V_REQUIRE(count % 4 == 0 && (act == 0 || act == 1), E2V_EINVAL, "text activation: whole quads, quick_gelu (0) or gelu (1)");
+// the same on 16-bit storage (a tower in 16-bit mode): eight elements per 16-byte access, widened exactly, the activation in fp32,
+// rounded once at the store
+template <int ACT, typename H>
+__global__ __launch_bounds__(256) void text_activation_h16_kernel(H* __restrict__ x, size_t octets) {
+    using V = RowVec<H, 8>;
+    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < octets; i += (size_t)gridDim.x * blockDim.x) {
+        V v = V::load(x + 8 * i);
+        v.apply([](float h) { return text_act<ACT>(h); });
+        v.store(x + 8 * i);
+    }
+}
+
+void text_activation(float* x, long long count, int act, hipStream_t s, int h16) {
+    const int per = h16 ? 8 : 4;                // elements per 16-byte access
+    E2V_REQUIRE(count % per == 0 && (act == 0 || act == 1), E2V_EINVAL, "text activation: whole 16-byte pieces, quick_gelu (0) or gelu (1)");
     if (count <= 0) return;
-    const size_t quads = (size_t)count / 4;
-    const size_t blocks = (quads + 255) / 256;
+    const size_t pieces = (size_t)count / per;
+    const size_t blocks = (pieces + 255) / 256;
     const int grid = (int)(blocks < 8192 ? blocks : 8192);
-    ProfScope ps(act == 0 ? "text_quick_gelu" : "text_gelu", 8.0 * count, 8.0 * count, s);
-    if (act == 0) E2V_KLAUNCH(text_activation_kernel<0>, dim3(grid), dim3(256), 0, s, x, quads);
-    else E2V_KLAUNCH(text_activation_kernel<1>, dim3(grid), dim3(256), 0, s, x, quads);
+    ProfScope ps(act == 0 ? "text_quick_gelu" : "text_gelu", 8.0 * count, (h16 ? 4.0 : 8.0) * count, s);
+    if (!h16) {
+        if (act == 0) E2V_KLAUNCH(text_activation_kernel<0>, dim3(grid), dim3(256), 0, s, x, pieces);
+        else E2V_KLAUNCH(text_activation_kernel<1>, dim3(grid), dim3(256), 0, s, x, pieces);
+        return;
+    }
+    h16_dispatch(h16, [&](auto tag) {
+        using H = decltype(tag);
+        H* xh = reinterpret_cast<H*>(x);
+        if (act == 0) E2V_KLAUNCH((text_activation_h16_kernel<0, H>), dim3(grid), dim3(256), 0, s, xh, pieces);
+        else E2V_KLAUNCH((text_activation_h16_kernel<1, H>), dim3(grid), dim3(256), 0, s, xh, pieces);
+    });
 }
 
 }  // namespace e2v

@@ -2,9 +2,13 @@
 // half of video_classify_metric, EEG2Video/40_class_run_metrics.py:108-142) that the image classifier (vit.hip) does not already
 // have: the video processor (Pillow's antialiased resize of the SHORTEST edge, of which only the centre crop is computed, fused with
 // the pixel table and the tubelet patch layout), the token rows (no class token), attention over any number of tokens, and the mean
-// over a clip's tokens.  Everything here is fp32 in every compute mode.
+// over a clip's tokens.  fp32 by default whatever the context's compute mode; the preprocess, the token rows and
+// the mean also come over 16-bit rows for a tower in 16-bit mode (e2v_set_tower_dtype).
 #include <algorithm>
+#include <type_traits>
 
+#include "act_io.h"
+#include "h16.h"
 #include "image_prep.h"
 #include "kernels.h"
 #include "prof.h"
@@ -82,9 +86,10 @@ namespace {
 // rows of the band over the source columns [c0, c0 + cw) the window reads ([band][cw]).  Frame f = ts t + dt of a clip writes column
 // ((c ts + dt) P + y) P + x of token row (t, py, px).  The launch covers frames img0 .. of the [n][F] source; a launch of whole clips
 // starts at a multiple of F, one at ts = 1 (the CLIP processor: every frame an image of its own) anywhere.
-template <bool F32, bool VFIRST>
+// O: the patch rows' storage type, as image_prep_kernel's.
+template <bool F32, bool VFIRST, typename O>
 __global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int ts, long long img0, int S, int P, int kh, int kv, int band,
-                                                         int c0, int cw, const int* __restrict__ plan, float* __restrict__ rows) {
+                                                         int c0, int cw, const int* __restrict__ plan, O* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char vprep_tmp[];
     const int* hfirst = plan;
     const int* hcount = plan + S;
@@ -105,7 +110,7 @@ __global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int 
     const size_t col0 = (size_t)(c * ts + dt) * P * P;
     auto put = [&](int yy, int xx, int byte) {
         const int py = yy / P, px = xx / P;
-        rows[(row0 + (size_t)py * np + px) * K + col0 + (yy - py * P) * P + (xx - px * P)] = lut[c * 256 + byte];
+        rows[(row0 + (size_t)py * np + px) * K + col0 + (yy - py * P) * P + (xx - px * P)] = (O)lut[c * 256 + byte];
     };
     if (VFIRST) {
         for (int i = threadIdx.x; i < (y1 - y0) * cw; i += 256) {
@@ -150,7 +155,7 @@ __global__ __launch_bounds__(256) void video_prep_kernel(PrepView v, int F, int 
 namespace {
 
 void prep_launch(const FrameSrc& src, int F, int ts, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
-                 float* rows, hipStream_t s) {
+                 float* rows, hipStream_t s, int h16) {
     const int S = plan.S;
     const long long HW = (long long)plan.H * plan.W;
     PrepView v;
@@ -160,29 +165,34 @@ void prep_launch(const FrameSrc& src, int F, int ts, long long img0, int nimg, c
     const size_t smem = (size_t)plan.band_rows * (plan.vfirst ? plan.cw : S);
     const dim3 grid((S + plan.band - 1) / plan.band, 3, nimg);
     ProfScope ps("video_preprocess", 2.0 * nimg * 3 * S * ((double)plan.band_rows * (S / plan.band + 1) * plan.kh + (double)S * plan.kv),
-                 (double)nimg * 3 * ((double)S * plan.W * (src.f32 ? 4.0 : 1.0) + 4.0 * S * S), s);
-    auto launch = [&](auto kernel) {
-        E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, ts, img0, S, P, plan.kh, plan.kv, plan.band, plan.c0, plan.cw, plan_dev, rows);
+                 (double)nimg * 3 * ((double)S * plan.W * (src.f32 ? 4.0 : 1.0) + (h16 ? 2.0 : 4.0) * S * S), s);
+    auto launch_as = [&](auto* out) {
+        using O = std::remove_pointer_t<decltype(out)>;
+        auto launch = [&](auto kernel) {
+            E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, ts, img0, S, P, plan.kh, plan.kv, plan.band, plan.c0, plan.cw, plan_dev, out);
+        };
+        if (plan.vfirst) { if (src.f32) launch(video_prep_kernel<true, true, O>); else launch(video_prep_kernel<false, true, O>); }
+        else { if (src.f32) launch(video_prep_kernel<true, false, O>); else launch(video_prep_kernel<false, false, O>); }
     };
-    if (plan.vfirst) { if (src.f32) launch(video_prep_kernel<true, true>); else launch(video_prep_kernel<false, true>); }
-    else { if (src.f32) launch(video_prep_kernel<true, false>); else launch(video_prep_kernel<false, false>); }
+    if (!h16) return launch_as(rows);
+    h16_dispatch(h16, [&](auto tag) { launch_as(reinterpret_cast<decltype(tag)*>(rows)); });
 }
 
 }  // namespace
 
 void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
-                      int P, float* rows, hipStream_t s) {
+                      int P, float* rows, hipStream_t s, int h16) {
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "video preprocess: the source rows of one output row do not fit the kernel's LDS band");
     E2V_REQUIRE(ts >= 1 && F % ts == 0 && nclips >= 1 && (long long)nclips * F <= 65535 && clip0 >= 0 && clip0 + nclips <= n, E2V_EINVAL,
                 "video preprocess: bad clip range");
-    prep_launch(src, F, ts, clip0 * F, nclips * F, plan, plan_dev, P, rows, s);
+    prep_launch(src, F, ts, clip0 * F, nclips * F, plan, plan_dev, P, rows, s, h16);
 }
 
 void frame_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s) {
+                      float* rows, hipStream_t s, int h16) {
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "frame preprocess: the source rows of one output row do not fit the kernel's LDS band");
     E2V_REQUIRE(nimg >= 1 && nimg <= 65535 && img0 >= 0 && img0 + nimg <= (long long)n * F, E2V_EINVAL, "frame preprocess: bad image range");
-    prep_launch(src, F, 1, img0, nimg, plan, plan_dev, P, rows, s);
+    prep_launch(src, F, 1, img0, nimg, plan, plan_dev, P, rows, s, h16);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -200,10 +210,29 @@ __global__ __launch_bounds__(256) void video_embed_kernel(const float* __restric
     for (int c = lane; c < C / 4; c += 64) o[c] = a[c] + p[c];
 }
 
-void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s) {
+// the same over 16-bit patch and token rows (a tower in 16-bit mode): fp32 positions, fp32 sum, one rounding at the store
+template <typename H>
+__global__ __launch_bounds__(256) void video_embed_h16_kernel(const H* __restrict__ patches, const float* __restrict__ pos,
+                                                              H* __restrict__ out, long long rows, int T, int C) {
+    const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int t = (int)(row % T);
+    const H* a = patches + (size_t)row * C;
+    const float* p = pos + (size_t)t * C;
+    H* o = out + (size_t)row * C;
+    for (int c = 4 * lane; c < C; c += 256) st4(o + c, ld4(a + c) + ld4(p + c));
+}
+
+void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s, int h16) {
     const long long rows = (long long)B * T;
-    ProfScope ps("video_embed", (double)rows * C, 12.0 * rows * C, s);
-    E2V_KLAUNCH(video_embed_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, patches, pos, x, rows, T, C);
+    ProfScope ps("video_embed", (double)rows * C, (h16 ? 8.0 : 12.0) * rows * C, s);
+    const dim3 grid((unsigned)((rows + 3) / 4));
+    if (!h16) { E2V_KLAUNCH(video_embed_kernel, grid, dim3(256), 0, s, patches, pos, x, rows, T, C); return; }
+    h16_dispatch(h16, [&](auto tag) {
+        using H = decltype(tag);
+        E2V_KLAUNCH(video_embed_h16_kernel<H>, grid, dim3(256), 0, s, reinterpret_cast<const H*>(patches), pos, reinterpret_cast<H*>(x), rows, T, C);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -228,27 +257,34 @@ void token_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, in
 // mean over the T token rows of a clip: one thread per (clip, column), the rows added in index order (a fixed order, no atomics),
 // eight loads in flight per thread; then one division by T (torch's mean: sum / count)
 // ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void token_mean_kernel(const float* __restrict__ x, float* __restrict__ out, int T, int C) {
+// X: fp32 rows, or the 16-bit rows of a tower in 16-bit mode (widened exactly; the sum and the output stay fp32).
+template <typename X>
+__global__ __launch_bounds__(256) void token_mean_kernel(const X* __restrict__ x, float* __restrict__ out, int T, int C) {
     const int col = blockIdx.x * 256 + threadIdx.x;
     if (col >= C) return;
-    const float* p = x + (size_t)blockIdx.y * T * C + col;
+    const X* p = x + (size_t)blockIdx.y * T * C + col;
     float acc = 0.f;
     int t = 0;
     for (; t + 8 <= T; t += 8) {
         float v[8];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = p[(size_t)(t + e) * C];
+        for (int e = 0; e < 8; ++e) v[e] = (float)p[(size_t)(t + e) * C];
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc += v[e];
     }
-    for (; t < T; ++t) acc += p[(size_t)t * C];
+    for (; t < T; ++t) acc += (float)p[(size_t)t * C];
     out[(size_t)blockIdx.y * C + col] = acc / (float)T;
 }
 
-void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s) {
+void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s, int h16) {
     E2V_REQUIRE(B >= 1 && B <= 65535, E2V_ESHAPE, "token mean: 1 <= B <= 65535");
-    ProfScope ps("token_mean", (double)B * T * C, 4.0 * B * (T + 1.0) * C, s);
-    E2V_KLAUNCH(token_mean_kernel, dim3((C + 255) / 256, B), dim3(256), 0, s, x, out, T, C);
+    ProfScope ps("token_mean", (double)B * T * C, (h16 ? 2.0 : 4.0) * B * T * C + 4.0 * B * C, s);
+    const dim3 grid((C + 255) / 256, B);
+    if (!h16) { E2V_KLAUNCH(token_mean_kernel<float>, grid, dim3(256), 0, s, x, out, T, C); return; }
+    h16_dispatch(h16, [&](auto tag) {
+        using H = decltype(tag);
+        E2V_KLAUNCH(token_mean_kernel<H>, grid, dim3(256), 0, s, reinterpret_cast<const H*>(x), out, T, C);
+    });
 }
 
 }  // namespace e2v

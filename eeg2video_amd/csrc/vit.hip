@@ -2,10 +2,14 @@
 // img_classify_metric, EEG2Video/40_class_run_metrics.py:86-98) that the rest of the library has no counterpart for: the image
 // processor (Pillow's antialiased resize fused with the pixel table and the patch layout), the assembly of the token rows,
 // non-causal self-attention over the tokens of one image, and the softmax / top-3 head.  LayerNorm, the linears and the erf GELU
-// are norm.hip's, igemm.hip's and text.hip's.  Everything here is fp32 in every compute mode.
+// are norm.hip's, igemm.hip's and text.hip's.  fp32 by default whatever the context's compute mode; the preprocess and the
+// token rows also come over 16-bit rows for a tower in 16-bit mode (e2v_set_tower_dtype).
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
+#include "act_io.h"
+#include "h16.h"
 #include "image_prep.h"
 #include "kernels.h"
 #include "prof.h"
@@ -129,9 +133,10 @@ namespace {
 // Integer arithmetic as Pillow's: 32-bit accumulators starting at 2^21, >> 22, clipped to a byte.
 // VFIRST (Pillow's order for very tall images): 1. vertical pass of the band's rows at the source width W -> bytes in LDS ([band][W]);
 // 2. horizontal pass over them.
-template <bool F32, bool VFIRST>
+// O: the patch rows' storage type -- fp32, or bf16 / fp16 (a tower in 16-bit mode): the table's fp32 value rounded once, at the store.
+template <bool F32, bool VFIRST, typename O>
 __global__ __launch_bounds__(256) void image_prep_kernel(PrepView v, int F, long long img0, int W, int S, int P, int kh, int kv, int band,
-                                                         const int* __restrict__ plan, float* __restrict__ rows) {
+                                                         const int* __restrict__ plan, O* __restrict__ rows) {
     extern __shared__ __attribute__((aligned(16))) unsigned char prep_tmp[];
     const int* hfirst = plan;
     const int* hcount = plan + S;
@@ -164,7 +169,7 @@ __global__ __launch_bounds__(256) void image_prep_kernel(PrepView v, int F, long
             const int byte = clip8(acc >> 22);
             const int py = yy / P, px = xx / P;
             const size_t row = ((size_t)blockIdx.z * np + py) * np + px;
-            rows[row * K + (size_t)c * P * P + (yy - py * P) * P + (xx - px * P)] = lut[c * 256 + byte];
+            rows[row * K + (size_t)c * P * P + (yy - py * P) * P + (xx - px * P)] = (O)lut[c * 256 + byte];
         }
         return;
     }
@@ -186,14 +191,14 @@ __global__ __launch_bounds__(256) void image_prep_kernel(PrepView v, int F, long
         const int byte = clip8(acc >> 22);
         const int py = yy / P, px = xx / P;
         const size_t row = ((size_t)blockIdx.z * np + py) * np + px;
-        rows[row * K + (size_t)c * P * P + (yy - py * P) * P + (xx - px * P)] = lut[c * 256 + byte];
+        rows[row * K + (size_t)c * P * P + (yy - py * P) * P + (xx - px * P)] = (O)lut[c * 256 + byte];
     }
 }
 
 }  // namespace
 
 void image_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const ImagePrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s) {
+                      float* rows, hipStream_t s, int h16) {
     const int S = plan.S;
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "image preprocess: the source rows of one output row do not fit the kernel's LDS band");
     E2V_REQUIRE(nimg >= 1 && nimg <= 65535 && img0 >= 0 && img0 + nimg <= (long long)n * F, E2V_EINVAL, "image preprocess: bad image range");
@@ -205,12 +210,17 @@ void image_preprocess(const FrameSrc& src, int n, int F, long long img0, int nim
     const size_t smem = (size_t)plan.band_rows * (plan.vfirst ? plan.W : S);
     const dim3 grid((S + plan.band - 1) / plan.band, 3, nimg);
     ProfScope ps("image_preprocess", 2.0 * nimg * 3 * S * ((double)plan.H * plan.kh + (double)S * plan.kv),
-                 (double)nimg * 3 * (HW * (src.f32 ? 4.0 : 1.0) + 4.0 * S * S), s);
-    auto launch = [&](auto kernel) {
-        E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, img0, plan.W, S, P, plan.kh, plan.kv, plan.band, plan_dev, rows);
+                 (double)nimg * 3 * (HW * (src.f32 ? 4.0 : 1.0) + (h16 ? 2.0 : 4.0) * S * S), s);
+    auto launch_as = [&](auto* out) {
+        using O = std::remove_pointer_t<decltype(out)>;
+        auto launch = [&](auto kernel) {
+            E2V_KLAUNCH(kernel, grid, dim3(256), smem, s, v, F, img0, plan.W, S, P, plan.kh, plan.kv, plan.band, plan_dev, out);
+        };
+        if (plan.vfirst) { if (src.f32) launch(image_prep_kernel<true, true, O>); else launch(image_prep_kernel<false, true, O>); }
+        else { if (src.f32) launch(image_prep_kernel<true, false, O>); else launch(image_prep_kernel<false, false, O>); }
     };
-    if (plan.vfirst) { if (src.f32) launch(image_prep_kernel<true, true>); else launch(image_prep_kernel<false, true>); }
-    else { if (src.f32) launch(image_prep_kernel<true, false>); else launch(image_prep_kernel<false, false>); }
+    if (!h16) return launch_as(rows);
+    h16_dispatch(h16, [&](auto tag) { launch_as(reinterpret_cast<decltype(tag)*>(rows)); });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -228,10 +238,30 @@ __global__ __launch_bounds__(256) void image_embed_kernel(const float* __restric
     for (int c = lane; c < C / 4; c += 64) o[c] = a[c] + p[c];
 }
 
-void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s) {
+// the same over 16-bit patch and token rows (a tower in 16-bit mode): the class row and the positions stay fp32, the sum is fp32 and
+// is rounded once at the store
+template <typename H>
+__global__ __launch_bounds__(256) void image_embed_h16_kernel(const H* __restrict__ patches, const float* __restrict__ cls,
+                                                              const float* __restrict__ pos, H* __restrict__ out, int rows, int T, int C) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int lane = threadIdx.x & 63;
+    const int img = row / T, t = row - img * T;
+    const H* a = patches + ((size_t)img * (T - 1) + (t - 1)) * C;          // (t == 0: not read)
+    const float* p = pos + (size_t)t * C;
+    H* o = out + (size_t)row * C;
+    for (int c = 4 * lane; c < C; c += 256) st4(o + c, (t == 0 ? ld4(cls + c) : ld4(a + c)) + ld4(p + c));
+}
+
+void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s, int h16) {
     const int rows = nimg * T;
-    ProfScope ps("image_embed", (double)rows * C, 12.0 * rows * C, s);
-    E2V_KLAUNCH(image_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, patches, cls, pos, x, rows, T, C);
+    ProfScope ps("image_embed", (double)rows * C, (h16 ? 8.0 : 12.0) * rows * C, s);
+    if (!h16) { E2V_KLAUNCH(image_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, patches, cls, pos, x, rows, T, C); return; }
+    h16_dispatch(h16, [&](auto tag) {
+        using H = decltype(tag);
+        E2V_KLAUNCH(image_embed_h16_kernel<H>, dim3((rows + 3) / 4), dim3(256), 0, s, reinterpret_cast<const H*>(patches), cls, pos,
+                    reinterpret_cast<H*>(x), rows, T, C);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

@@ -252,6 +252,22 @@ class Engine:
         self._check(self.lib.e2v_set_compute_dtype(self.ctx, code))
         self.compute_dtype = {_lib.E2V_F32: "fp32", _lib.E2V_F16: "fp16", _lib.E2V_BF16: "bf16", _lib.E2V_F32X3: "f32x3"}[code]
 
+    _DTYPE_NAMES = {_lib.E2V_F32: "fp32", _lib.E2V_F16: "fp16", _lib.E2V_BF16: "bf16", _lib.E2V_F32X3: "f32x3"}
+
+    def set_tower_dtype(self, part: int, dtype) -> None:
+        """The arithmetic of ONE metric tower (``e2v_set_tower_dtype``): ``part`` is ``Engine.IMAGE``, ``VIDEO`` or ``CLIP_VISION``,
+        ``dtype`` ``'fp32'`` (the default, bit for bit the fp32 path), ``'bf16'`` or ``'fp16'`` (the reference's own dtype for these
+        models, ``40_class_run_metrics.py:41,89,125``) or the ``torch.dtype``.  Independent of ``set_compute_dtype``; the outputs stay
+        fp32.  May be called at any time; the 16-bit copies of the tower's matrices are built on the first call in that mode."""
+        self._check(self.lib.e2v_set_tower_dtype(self.ctx, int(part), compute_dtype_code(dtype)))
+
+    def tower_dtype(self, part: int) -> str:
+        """``'fp32'``, ``'bf16'`` or ``'fp16'``: what ``set_tower_dtype`` left ``part`` at (``e2v_tower_dtype``)."""
+        code = self.lib.e2v_tower_dtype(self.ctx, int(part))
+        if code not in self._DTYPE_NAMES:
+            raise ValueError(f"tower_dtype(part={part!r}): Engine.IMAGE, Engine.VIDEO or Engine.CLIP_VISION")
+        return self._DTYPE_NAMES[code]
+
     def set_conv_algo(self, algo: str) -> None:
         """'auto' (default: Winograd F(2x2,3x3) for the wide stride-1 3x3 convs, direct implicit GEMM elsewhere),
         'direct' or 'winograd'.  For the graph entry points call it before the weights are finalized."""
@@ -625,7 +641,7 @@ class Engine:
         twice and int32 ``[n*F, 3]``, the indices of the three largest logits in ascending order (``argsort(-1)[-3:]``), on the engine's
         device, frame ``f`` of clip ``i`` at row ``i*F + f``.  ``frames``: uint8, or float32 in ``[0,1]`` (quantised as
         ``frames_to_uint8`` does), planar ``[n,3,F,H,W]`` (``[3,F,H,W]``: one clip) or, with ``channels_last``, ``[n,F,H,W,3]``; host
-        tensors are copied over.  fp32 arithmetic whatever the engine's compute dtype."""
+        tensors are copied over.  The tower's own arithmetic (``set_tower_dtype``; fp32 by default) whatever the engine's compute dtype."""
         if self.image_cfg is None:
             raise RuntimeError("this engine was built without an image classifier (Engine(..., image_cfg=ImageConfig()))")
         t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
@@ -658,7 +674,7 @@ class Engine:
         """``CLIPImageProcessor`` + ``CLIPVisionModelWithProjection`` over every frame (``e2v_clip_embed``; the model half of the
         reference's ``clip_score``, ``40_class_run_metrics.py:20-55``) -> ``image_embeds`` fp32 ``[n*F, projection_dim]`` on the
         engine's device, NOT normalised, frame ``f`` of clip ``i`` at row ``i*F + f``.  ``frames``: as ``classify_frames`` takes them.
-        fp32 arithmetic whatever the engine's compute dtype."""
+        The tower's own arithmetic (``set_tower_dtype``; fp32 by default) whatever the engine's compute dtype."""
         if self.clip_vision_cfg is None:
             raise RuntimeError("this engine was built without a CLIP vision tower (Engine(..., clip_vision_cfg=ClipVisionConfig()))")
         t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
@@ -895,6 +911,70 @@ class Engine:
         out = self._op_out(out, (B * T, 64 * heads), strided=True)
         self._check(self.lib.e2v_op_token_attention(self.ctx, qkv.data_ptr(), qkv.stride(0), out.data_ptr(), out.stride(0), B, T, heads,
                                                     _stream()))
+        return out
+
+    # ---- the pieces of a metric tower in a 16-bit mode (fp32 at the boundary: inputs rounded once, 16-bit results widened exactly)
+    def op_tower_preprocess(self, frames, *, tower, dtype, size, patch, lut, tubelet=1, edge=0, filter=3, channels_last=False, out=None):
+        """``e2v_op_tower_preprocess``: the preprocess of tower ``Engine.IMAGE`` / ``VIDEO`` / ``CLIP_VISION`` storing ``dtype`` patch
+        rows (returned widened): ``op_image_preprocess`` / ``op_video_preprocess`` / ``op_clip_preprocess`` rounded once."""
+        t, kind, (n, f, h, w) = self._frames_arg(frames, channels_last)
+        lut = np.ascontiguousarray(np.asarray(lut, dtype=np.float32).reshape(3, 256))
+        ts = tubelet if tower == self.VIDEO else 1
+        out = self._op_out(out, (n * (f // max(ts, 1)) * (size // patch) ** 2, 3 * ts * patch * patch))
+        self._check(self.lib.e2v_op_tower_preprocess(self.ctx, int(tower), compute_dtype_code(dtype), t.data_ptr(), kind, n, f, h, w, size,
+                                                     patch, tubelet, edge, filter, lut.ctypes.data_as(C.POINTER(C.c_float)), out.data_ptr(),
+                                                     _stream()))
+        return out
+
+    def op_tower_attention(self, qkv, *, dtype, B, T, heads, out=None):
+        """``e2v_op_tower_attention``: ``qkv`` ``[B*T, 3*64*heads]`` rounded to ``dtype`` -> ``[B*T, 64*heads]``, the attention of a
+        16-bit tower (non-causal, any ``T``; fp32 scores and softmax, 16-bit probabilities and output, widened)."""
+        if not (isinstance(qkv, torch.Tensor) and qkv.device == self.device and qkv.dtype == torch.float32 and qkv.dim() == 2
+                and qkv.stride(1) == 1):
+            qkv = self._dev(qkv, "qkv")
+        if qkv.dim() != 2 or qkv.shape[0] != B * T or qkv.shape[1] != 3 * 64 * heads:
+            raise ValueError(f"expected qkv [B*T, 3*64*heads] = [{B * T}, {3 * 64 * heads}], got {tuple(qkv.shape)}")
+        out = self._op_out(out, (B * T, 64 * heads), strided=True)
+        self._check(self.lib.e2v_op_tower_attention(self.ctx, compute_dtype_code(dtype), qkv.data_ptr(), qkv.stride(0), out.data_ptr(),
+                                                    out.stride(0), B, T, heads, _stream()))
+        return out
+
+    def op_tower_token_mean(self, x, *, dtype, B, T, out=None):
+        """``e2v_op_tower_token_mean``: ``x`` ``[B*T, C]`` rounded to ``dtype`` -> the fp32 mean over each clip's ``T`` rows ``[B, C]``."""
+        x = self._dev(x, "x")
+        out = self._op_out(out, (B, x.shape[1]))
+        self._check(self.lib.e2v_op_tower_token_mean(self.ctx, compute_dtype_code(dtype), x.data_ptr(), B, T, x.shape[1], out.data_ptr(), _stream()))
+        return out
+
+    def op_tower_layernorm(self, x, gamma, beta, *, dtype, rows, stride=1, eps=1e-5, out=None):
+        """``e2v_op_tower_layernorm``: rows ``0, stride, 2 stride, ...`` (``rows`` of them) of ``x`` ``[>= (rows-1)*stride+1, C]`` rounded
+        to ``dtype``, normalised into fp32 ``[rows, C]`` (not rounded): the LayerNorm in front of a 16-bit tower's head."""
+        x, gamma, beta = self._dev(x, "x"), self._dev(gamma, "gamma"), self._dev(beta, "beta")
+        if x.dim() != 2 or x.shape[0] < (rows - 1) * stride + 1:
+            raise ValueError(f"`x` has shape {tuple(x.shape)}: at least {(rows - 1) * stride + 1} rows are read")
+        out = self._op_out(out, (rows, x.shape[1]))
+        self._check(self.lib.e2v_op_tower_layernorm(self.ctx, compute_dtype_code(dtype), x.data_ptr(), rows, stride, x.shape[1],
+                                                    gamma.data_ptr(), beta.data_ptr(), float(eps), out.data_ptr(), _stream()))
+        return out
+
+    def op_tower_activation(self, x, *, dtype, act, out=None):
+        """``e2v_op_tower_activation``: ``act`` 0 quick-GELU / 1 erf GELU in fp32 on ``x`` rounded to ``dtype``, the result rounded once
+        (returned widened).  ``x.numel()`` a multiple of 8."""
+        x = self._dev(x, "x")
+        out = self._op_out(out, tuple(x.shape))
+        self._check(self.lib.e2v_op_tower_activation(self.ctx, compute_dtype_code(dtype), x.data_ptr(), x.numel(), int(act), out.data_ptr(), _stream()))
+        return out
+
+    def op_tower_embed(self, patches, pos, *, dtype, nimg, cls=None, out=None):
+        """``e2v_op_tower_embed``: the token rows of a 16-bit tower from ``patches`` rounded to ``dtype`` -- with a class row ``cls``
+        ``[C]`` in front (ViT, CLIP: ``patches`` ``[nimg*(T-1), C]``) or without (VideoMAE: ``[nimg*T, C]``) -- plus ``pos`` ``[T, C]``
+        in fp32, rounded once (returned widened)."""
+        patches, pos = self._dev(patches, "patches"), self._dev(pos, "pos")
+        cls = self._dev(cls, "cls") if cls is not None else None
+        T, Cw = pos.shape
+        out = self._op_out(out, (nimg * T, Cw))
+        self._check(self.lib.e2v_op_tower_embed(self.ctx, compute_dtype_code(dtype), patches.data_ptr(), cls.data_ptr() if cls is not None else None,
+                                                pos.data_ptr(), nimg, T, Cw, out.data_ptr(), _stream()))
         return out
 
     def op_to_channels_last(self, x, *, Cpad=None, out=None):

@@ -5,7 +5,8 @@ Mirror of the pair ``EEG2Video/40_class_run_metrics.py:86-98`` builds for ``img_
 object: ``from_pretrained(local_dir)`` reads the model AND the processor config, ``model(frames)`` takes the frames themselves -- uint8
 (or float ``[0,1]``) clips, on the device or not -- and returns the logits; ``classify(frames)`` also returns the softmax and the
 indices of the three largest logits, which is what the metric uses.  The model lives on an ``Engine`` created with an ``ImageConfig``
-and runs in fp32 whatever the engine's compute dtype (``e2v_image_classify``).  The weights are frozen once loaded.
+and runs in its OWN arithmetic (``set_compute_dtype``: fp32 by default, opt-in bf16 / fp16) whatever the engine's compute dtype
+(``e2v_image_classify``).  The weights are frozen once loaded.
 
 Nothing here reads the network: a checkpoint is a LOCAL directory (``config.json``, ``preprocessor_config.json``,
 ``model.safetensors`` or ``pytorch_model.bin``), e.g. a ``snapshot_download`` of the hub model made elsewhere.
@@ -69,7 +70,19 @@ class ViTForImageClassification:
     def device(self) -> torch.device:
         return self.engine.device
 
-    def to(self, *a, **k):          # the weights live on the engine's GPU and the arithmetic is fp32 in every mode
+    def to(self, *a, **k):          # the weights live on the engine's GPU; the arithmetic is chosen by set_compute_dtype alone
+        return self
+
+    @property
+    def compute_dtype(self) -> str:
+        """``'fp32'`` (the default), ``'bf16'`` or ``'fp16'``: the arithmetic of this model on its engine (``Engine.tower_dtype``)."""
+        return self.engine.tower_dtype(Engine.IMAGE)
+
+    def set_compute_dtype(self, dtype):
+        """Opt into 16-bit arithmetic for this model alone: ``'fp16'`` (what the reference runs it in,
+        ``40_class_run_metrics.py``: ``.to(device, torch.float16)``), ``'bf16'``, or back to ``'fp32'`` -- a name or a ``torch.dtype``
+        (``Engine.set_tower_dtype``).  The outputs stay fp32; ``torch_dtype=`` and ``.to()`` do not select it."""
+        self.engine.set_tower_dtype(Engine.IMAGE, dtype)
         return self
 
     def eval(self):
@@ -163,9 +176,10 @@ class ViTForImageClassification:
                            image_mean=tuple(pj.get("image_mean", d.image_mean)), image_std=tuple(pj.get("image_std", d.image_std)))
 
     @classmethod
-    def from_pretrained(cls, pretrained_model_path: str, torch_dtype=None, *, engine: Optional[Engine] = None, device: int = 0, **kwargs):
+    def from_pretrained(cls, pretrained_model_path: str, torch_dtype=None, *, engine: Optional[Engine] = None, device: int = 0,
+                        compute_dtype=None, **kwargs):
         """LOCAL directory only.  ``torch_dtype`` and ``cache_dir`` are accepted for drop-in use: checkpoints of any float type are
-        widened to fp32, and nothing is ever fetched."""
+        widened to fp32, and nothing is ever fetched.  ``compute_dtype``: ``set_compute_dtype`` on the built model (``None``: fp32)."""
         path = str(pretrained_model_path)
         if not os.path.isdir(path):
             raise RuntimeError(f"{path!r} is not a directory: this classifier loads from a local checkpoint directory only and never "
@@ -173,6 +187,8 @@ class ViTForImageClassification:
         model = cls(cls.config_from_dir(path), engine=engine, device=device)
         if not os.path.isfile(os.path.join(path, WEIGHTS_NAME)) and not os.path.isfile(os.path.join(path, SAFETENSORS_NAME)):
             raise RuntimeError(f"{os.path.join(path, SAFETENSORS_NAME)} does not exist")
+        if compute_dtype is not None:
+            model.set_compute_dtype(compute_dtype)
         return model.load_state_dict(_load_checkpoint(path, SAFETENSORS_NAME, WEIGHTS_NAME), strict=False)
 
     # -- forward -----------------------------------------------------------------------------

@@ -6,7 +6,7 @@ Mirror of the pair ``EEG2Video/40_class_run_metrics.py:113-118`` builds for ``vi
 ``image_classifier.ViTForImageClassification``: ``from_pretrained(local_dir, num_frames=...)`` reads the model AND the processor
 config, ``model(frames)`` takes the clips themselves -- uint8 (or float ``[0,1]``), on the device or not -- and returns the logits per
 clip; ``classify(frames)`` also returns the softmax and the indices of the three largest logits, which is what the metric uses.  The
-model lives on an ``Engine`` created with a ``VideoConfig`` and runs in fp32 whatever the engine's compute dtype
+model lives on an ``Engine`` created with a ``VideoConfig`` and runs in its OWN arithmetic (``set_compute_dtype``: fp32 by default, opt-in bf16 / fp16) whatever the engine's compute dtype
 (``e2v_video_classify``).  The weights are frozen once loaded.
 
 The position table is no checkpoint tensor: ``transformers`` computes the fixed sinusoid at construction, sized by ``num_frames``.
@@ -59,7 +59,19 @@ class VideoMAEForVideoClassification:
     def device(self) -> torch.device:
         return self.engine.device
 
-    def to(self, *a, **k):          # the weights live on the engine's GPU and the arithmetic is fp32 in every mode
+    def to(self, *a, **k):          # the weights live on the engine's GPU; the arithmetic is chosen by set_compute_dtype alone
+        return self
+
+    @property
+    def compute_dtype(self) -> str:
+        """``'fp32'`` (the default), ``'bf16'`` or ``'fp16'``: the arithmetic of this model on its engine (``Engine.tower_dtype``)."""
+        return self.engine.tower_dtype(Engine.VIDEO)
+
+    def set_compute_dtype(self, dtype):
+        """Opt into 16-bit arithmetic for this model alone: ``'fp16'`` (what the reference runs it in,
+        ``40_class_run_metrics.py``: ``.to(device, torch.float16)``), ``'bf16'``, or back to ``'fp32'`` -- a name or a ``torch.dtype``
+        (``Engine.set_tower_dtype``).  The outputs stay fp32; ``torch_dtype=`` and ``.to()`` do not select it."""
+        self.engine.set_tower_dtype(Engine.VIDEO, dtype)
         return self
 
     def eval(self):
@@ -177,10 +189,10 @@ class VideoMAEForVideoClassification:
 
     @classmethod
     def from_pretrained(cls, pretrained_model_path: str, torch_dtype=None, *, num_frames: Optional[int] = None,
-                        engine: Optional[Engine] = None, device: int = 0, **kwargs):
+                        engine: Optional[Engine] = None, device: int = 0, compute_dtype=None, **kwargs):
         """LOCAL directory only.  ``num_frames`` overrides the checkpoint's (the reference passes 6 where the checkpoint says 16): the
         token count and the position table follow it; the weights do not depend on it.  ``torch_dtype`` and ``cache_dir`` are accepted
-        for drop-in use: checkpoints of any float type are widened to fp32, and nothing is ever fetched."""
+        for drop-in use: checkpoints of any float type are widened to fp32, and nothing is ever fetched.  ``compute_dtype``: ``set_compute_dtype`` on the built model (``None``: fp32)."""
         path = str(pretrained_model_path)
         if not os.path.isdir(path):
             raise RuntimeError(f"{path!r} is not a directory: this classifier loads from a local checkpoint directory only and never "
@@ -191,6 +203,8 @@ class VideoMAEForVideoClassification:
         model = cls(config, engine=engine, device=device)
         if not os.path.isfile(os.path.join(path, WEIGHTS_NAME)) and not os.path.isfile(os.path.join(path, SAFETENSORS_NAME)):
             raise RuntimeError(f"{os.path.join(path, SAFETENSORS_NAME)} does not exist")
+        if compute_dtype is not None:
+            model.set_compute_dtype(compute_dtype)
         return model.load_state_dict(_load_checkpoint(path, SAFETENSORS_NAME, WEIGHTS_NAME), strict=False)
 
     # -- forward -----------------------------------------------------------------------------

@@ -66,6 +66,8 @@ def main(argv=None, engine=None):
                     help="with --score-against: local VideoMAEForVideoClassification checkpoint directory -> video_{2,40}way_acc")
     ap.add_argument("--clip-model", default="", metavar="DIR",
                     help="with --score-against: local CLIPVisionModelWithProjection checkpoint directory -> clip_score_mean, clip_{2,40}way_acc")
+    ap.add_argument("--metric-dtype", default="fp32", choices=["fp32", "bf16", "fp16"],
+                    help="arithmetic of the metric models given above (fp16: what the reference runs them in; fp32: the default)")
     args = ap.parse_args(argv)
     if args.clip_model and not args.score_against:
         ap.error("--clip-model scores against ground truth: give --score-against DIR too")
@@ -121,15 +123,16 @@ def main(argv=None, engine=None):
     vit = None
     if args.classifier:
         from eeg2video_amd.image_classifier import ViTForImageClassification
-        vit = ViTForImageClassification.from_pretrained(args.classifier, device=local)      # its own context, fp32 in every mode
+        vit = ViTForImageClassification.from_pretrained(args.classifier, device=local,       # its own context; --dtype does not reach it
+                                                        compute_dtype=args.metric_dtype)
     vmae = None
     if args.video_classifier:                                       # built for the sweep's frame count, as the reference passes num_frames
         from eeg2video_amd.video_classifier import VideoMAEForVideoClassification
-        vmae = VideoMAEForVideoClassification.from_pretrained(args.video_classifier, num_frames=F, device=local)
+        vmae = VideoMAEForVideoClassification.from_pretrained(args.video_classifier, num_frames=F, device=local, compute_dtype=args.metric_dtype)
     clipm = None
     if args.clip_model:
         from eeg2video_amd.clip_vision import CLIPVisionModelWithProjection
-        clipm = CLIPVisionModelWithProjection.from_pretrained(args.clip_model, device=local)
+        clipm = CLIPVisionModelWithProjection.from_pretrained(args.clip_model, device=local, compute_dtype=args.metric_dtype)
     from concurrent.futures import ThreadPoolExecutor
     pool = ThreadPoolExecutor(max_workers=max(1, min(8, len(os.sched_getaffinity(0)) - 2)))
     pending = []

@@ -211,7 +211,8 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8).
  * An "image." key: E2V_EINVAL as well -- the classifier is a frozen yardstick (40_class_run_metrics.py:70-72 loads it and only
  * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32).
- * A "clipv." key (part 64) is updated like a UNet key: the tower keeps fp32 forms only. */
+ * A "clipv." key (part 64) is updated like a UNet key: the fp32 form, and the bf16 / fp16 copy of a matrix (the layers' linears, the
+ * patch embedding) once the tower has built it in a 16-bit mode (e2v_set_tower_dtype) -- every copy that exists is refreshed. */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
                              const int64_t* shape, int ndim, e2v_stream stream);
 
@@ -553,8 +554,33 @@ int64_t e2v_profile_end(e2v_ctx* ctx, char* json, int64_t cap);
  * E2V_F32X3 (opt-in, experimental): fp32 results from the bf16 matrix pipe -- every operand of a linear / Winograd-domain
  * GEMM is split exactly into three bf16 pieces and the six significant piece products are accumulated in fp32 (error at
  * the level of the fp32 FMA chain); must be selected BEFORE e2v_finalize_weights (the weights are split there), else
- * E2V_ESTATE.  Also selectable with E2V_F32X3=1 in the environment at e2v_create. */
+ * E2V_ESTATE.  Also selectable with E2V_F32X3=1 in the environment at e2v_create.
+ * The metric towers (e2v_image_classify, e2v_video_classify, e2v_clip_embed) and the text encoder do NOT follow this switch: the
+ * towers have their own (e2v_set_tower_dtype, fp32 by default), the text encoder is fp32 always. */
 e2v_status e2v_set_compute_dtype(e2v_ctx* ctx, int dtype);
+
+/* Arithmetic of ONE metric tower -- part 16 (e2v_image_classify), 32 (e2v_video_classify) or 64 (e2v_clip_embed) -- whatever
+ * e2v_set_compute_dtype says.  E2V_F32 (default): the fp32 path, bit for bit what it was before any switch.  E2V_BF16 / E2V_F16: the
+ * reference's own arithmetic for these models (EEG2Video/40_class_run_metrics.py:41,50-51 / :89,97-98 / :125,134-135:
+ * `.to(device, torch.float16)`).  One rounding rule for the three towers:
+ *   - the preprocess keeps Pillow's integer arithmetic and the fp32 pixel table and rounds each value once, storing the patch rows;
+ *   - the token rows live in HBM as 16-bit: patch / tubelet linear and the encoder linears are 16-bit MFMA with fp32 accumulation,
+ *     fp32 bias and residual added before the single store rounding; the class row and positions are added in fp32; LayerNorm has
+ *     fp32 statistics (the tower's eps); GELU / quick-GELU is computed in fp32 on 16-bit storage; attention keeps scores and softmax
+ *     fp32, the probabilities and the output are 16-bit;
+ *   - the head is fp32: the final / post / fc_norm LayerNorm reads 16-bit rows (VideoMAE: the fp32 mean over the 16-bit token rows,
+ *     summed in index order) and writes fp32, the classifier / projection, softmax, top 3 and e2v_clip_similarity are unchanged.
+ * The outputs keep their fp32 types and shapes.  An image's or clip's bits depend on neither the batch, its position, the chunking,
+ * the context's compute dtype nor the run, as in fp32.  The 16-bit copies of the tower's matrices are derived from the fp32 ones on
+ * the first call in that mode and KEPT when the mode changes (freed when the part is finalized again); e2v_update_tensor refreshes
+ * every copy that exists, e2v_op_weight_forms reports them, e2v_read_tensor reads them (E2V_FORM_BF16 / E2V_FORM_F16).
+ * May be called before or after e2v_finalize_weights, and repeatedly; takes effect for the following calls.  In a 16-bit mode the
+ * patch row length (3 P^2, VideoMAE 3 ts P^2) and the intermediate width must be multiples of 8, else the call answers E2V_ESHAPE.
+ * E2V_EINVAL: a null ctx, any other part (8, the text encoder, included), E2V_F32X3 or an unknown dtype.  E2V_ESTATE: the context
+ * has no such tower.  No HIP call: a host-only context answers too. */
+e2v_status e2v_set_tower_dtype(e2v_ctx* ctx, int part, int dtype);
+/* the dtype a tower is set to (E2V_F32 / E2V_BF16 / E2V_F16); -1 for a null ctx or a part that is not 16, 32 or 64 */
+int e2v_tower_dtype(const e2v_ctx* ctx, int part);
 
 /* Algorithm of the stride-1 3x3 convolutions in fp32 arithmetic.  E2V_CONV_AUTO (default): Winograd F(4x4,3x3) -- 4x
  * fewer matrix-core flops than the direct implicit GEMM -- where min(Cin, Cout) >= 128 and the map padded to multiples of

@@ -134,6 +134,40 @@ e2v_status e2v_op_clip_preprocess(e2v_ctx* ctx, const void* frames, int kind, in
 e2v_status e2v_op_token_attention(e2v_ctx* ctx, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
                                   e2v_stream stream);
 
+/* ---- the pieces of a metric tower in a 16-bit mode (e2v_set_tower_dtype), on their own.  dtype: E2V_BF16 or E2V_F16 (another:
+ * E2V_EINVAL).  The boundary stays fp32: an fp32 input is rounded once to `dtype` (round to nearest even) where the tower would hold
+ * 16-bit rows, and a 16-bit result is widened exactly.  They need no weights. ---- */
+
+/* The preprocess storing 16-bit patch rows: tower = 16: e2v_op_image_preprocess (ts / edge / filter ignored), 32:
+ * e2v_op_video_preprocess (filter ignored), 64: e2v_op_clip_preprocess (ts ignored); host_lut is required.  rows as there, each value
+ * the pixel table's fp32 value rounded once to `dtype`: the fp32 preprocess rounded, bit for bit. */
+e2v_status e2v_op_tower_preprocess(e2v_ctx* ctx, int tower, int dtype, const void* frames, int kind, int n, int F, int H, int W, int S,
+                                   int P, int ts, int edge, int filter, const float* host_lut, float* rows, e2v_stream stream);
+
+/* Non-causal self-attention over each of B sequences of T tokens (any T >= 1), head dim 64, scale 64^-0.5, as a 16-bit tower runs it:
+ * qkv [B*T][ldqkv] (q | k | v, heads * 64 columns each, any alignment) rounded to `dtype`, the 16-bit MFMA attention of the UNet
+ * (cross form: one "frame" per sequence, Nq = Nk = T; fp32 scores and softmax, 16-bit probabilities and output), out [B*T][ldo]. */
+e2v_status e2v_op_tower_attention(e2v_ctx* ctx, int dtype, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
+                                  e2v_stream stream);
+
+/* out[b][:] = (sum over t ascending of round(x[b*T + t][:])) / T in fp32: the mean over the 16-bit token rows of a clip.  B <= 65535. */
+e2v_status e2v_op_tower_token_mean(e2v_ctx* ctx, int dtype, const float* x, int B, int T, int C, float* out, e2v_stream stream);
+
+/* LayerNorm of 16-bit rows into fp32 rows: x [(rows - 1) * stride + 1][C] rounded to `dtype`; rows 0, stride, 2 stride, ... (a tower's
+ * class rows: stride = T) are normalised with fp32 statistics into out [rows][C], which is NOT rounded.  C a multiple of 4 up to 1280. */
+e2v_status e2v_op_tower_layernorm(e2v_ctx* ctx, int dtype, const float* x, int64_t rows, int stride, int C, const float* gamma,
+                                  const float* beta, float eps, float* out, e2v_stream stream);
+
+/* The MLP activation on 16-bit storage: out = round(act(round(x))) widened, act 0 = quick-GELU, 1 = erf GELU, evaluated in fp32.
+ * count a positive multiple of 8. */
+e2v_status e2v_op_tower_activation(e2v_ctx* ctx, int dtype, const float* x, int64_t count, int act, float* out, e2v_stream stream);
+
+/* The token rows of a 16-bit tower: cls != NULL: out[i][0] = cls + pos[0], out[i][1 + p] = round(patches[i*(T-1) + p]) + pos[1 + p]
+ * (ViT, CLIP); cls == NULL: out[i*T + t] = round(patches[i*T + t]) + pos[t] (VideoMAE).  fp32 sums, rounded once; cls [C] and
+ * pos [T][C] are fp32 (16-byte aligned).  C a multiple of 4. */
+e2v_status e2v_op_tower_embed(e2v_ctx* ctx, int dtype, const float* patches, const float* cls, const float* pos, int nimg, int T, int C,
+                              float* out, e2v_stream stream);
+
 /* layout conversion at the boundary: [n][C][FHW] <-> [n][FHW][Cpad] */
 e2v_status e2v_op_to_channels_last(e2v_ctx* ctx, const float* in, float* out, int n, int C, int Cpad, int FHW,
                                    e2v_stream stream);
@@ -179,7 +213,9 @@ e2v_status e2v_op_last_dispatch(char* buf, int64_t cap);
  * now -- one bit each in *mask.  A linear (or 1x1 conv) weight: its fp32 matrix, the bf16 copy finalize makes, the fp16 copy the fp16
  * mode builds on first use, the three bf16 planes of the f32x3 mode.  A 3x3 conv weight: F32 = the torch-layout weight, BF16 / F16 = the
  * direct 16-bit layouts, and the remaining bits the layouts built on first use by the kernel that needs them.  Norm affines and biases
- * have the F32 bit only, and so does every tensor of the text encoder ("text." keys: fp32 in every compute mode).  The update tests use it to prove that an update ran against each form.  E2V_ENOWEIGHT for an unknown key,
+ * have the F32 bit only, and so does every tensor of the text encoder ("text." keys: fp32 in every compute mode).  A matrix of a metric
+ * tower ("image." / "video." / "clipv.": the layers' linears and the patch embedding) has F32 after finalize and gains BF16 / F16 on the
+ * tower's first call in that mode (e2v_set_tower_dtype); the classifier / projection of the fp32 head stays F32.  The update tests use it to prove that an update ran against each form.  E2V_ENOWEIGHT for an unknown key,
  * E2V_ESTATE when the key's part is not finalized (and on a host-only context).  The bits are the E2V_FORM_* values of
  * eeg2video_hip.h (e2v_read_tensor names one of them as its source).  No reference counterpart. */
 e2v_status e2v_op_weight_forms(e2v_ctx* ctx, const char* key, int* mask);

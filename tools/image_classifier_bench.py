@@ -106,6 +106,9 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--clips", type=int, default=32)
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--metric-dtype", default=None, choices=["fp32", "bf16", "fp16", "all"],
+                    help="measure ONLY the arms of the call -- the tower in fp32 and in this 16-bit mode ('all': bf16 and fp16) -- in one "
+                         "session, alternating (tools/metric_dtype_arms.py), and merge them into --out under 'metric_dtype_arms'")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("tools/image_classifier_bench.py measures on the GPU: none found")
@@ -118,6 +121,13 @@ def main():
     n, F, H, W = 2 * a.clips, 6, 288, 512
     frames = torch.from_numpy(np.random.default_rng(0).integers(0, 256, (n, F, H, W, 3), dtype=np.uint8))
     d_frames = frames.cuda()
+    if a.metric_dtype:
+        from metric_dtype_arms import measure_arms, merge_into
+        arms = measure_arms(clf, lambda: eng.classify_frames(d_frames, channels_last=True), a.metric_dtype, a.repeats)
+        arms["device"], arms["input"] = torch.cuda.get_device_name(0), f"{n * F} images of {H} x {W} uint8, channels-last, one call"
+        merge_into(a.out, "metric_dtype_arms", arms)
+        print(json.dumps({"tool": os.path.basename(__file__), "metric_dtype_arms": {k: v for k, v in arms.items() if k != "kernel_classes"}}))
+        return
     wall = timed(lambda: eng.classify_frames(d_frames, channels_last=True), a.repeats)
     logits = eng.classify_frames(d_frames, channels_last=True)[0]
     torch.cuda.synchronize()
