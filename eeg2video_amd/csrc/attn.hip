@@ -77,12 +77,22 @@ std::string attn_shape_tag(const AttnArgs& a) {
            " h" + std::to_string(a.heads);
 }
 
+// Both half-waves' values of x: lo = lane (l & 31)'s, hi = lane (l & 31) + 32's, in every lane.  v_permlane32_swap a, b exchanges lanes
+// 32-63 of a with lanes 0-31 of b; from two copies of x that leaves a = the lower half's value and b = the upper half's (one
+// instruction; __shfl_xor(x, 32) is a ds_bpermute and its index arithmetic).  Inline asm: given through the builtin, hipcc of ROCm 7.2
+// drops the second result.  The two wait states a VALU-written operand needs in front of a permlane are inside the string.
+__device__ __forceinline__ void half_pair(const float x, float& lo, float& hi) {
+    lo = x; hi = x;
+    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo), "+v"(hi));
+}
+
 template <int D>
 __global__ __launch_bounds__(256) void flash_attn_kernel(const AttnArgs p) {
     constexpr int LD = D + 4;               // padded LDS row: conflict-free ds_read_b128 of 16 rows
     // O^T is built from 32-row MFMA tiles over the value columns.  When 8 columns are left over (d = 40: 32 + 8)
-    // they are accumulated on the VALU from the same P registers (128 FMAs per key tile, on the vector pipe while the
-    // matrix pipe runs the next MFMAs) instead of a second MFMA tile with 24 dead rows (16 of 52 MFMAs per tile).
+    // they are accumulated from the same P registers by 32 v_mfma_f32_4x4x1_16b_f32 per key tile (256 matrix-pipe cycles; as 64
+    // packed FMAs fed by 32 broadcast ds_read_b128 they cost twice that in vector issue, which the fp32 MFMA does not hide)
+    // instead of a second MFMA tile with 24 dead rows (16 of 52 MFMAs per tile).
     constexpr int TF = D / 32;
     constexpr bool VREM = (D - 32 * TF) == 8;
     constexpr int T = VREM ? TF : (D + 31) / 32;
@@ -153,9 +163,7 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const AttnArgs p) {
         ld_off[e] = idx < NF4 ? (unsigned)(row * p.ldkv + c4 * 4) * 4u : OOB;
     }
     f32x4 kreg[LPT], vreg[LPT];
-    auto load_tile = [&](int tt) {
-        const int seg = tt / tps;
-        const int key0 = (tt - seg * tps) * KT;
+    auto load_tile = [&](const int seg, const int key0) {        // position of the tile, kept incrementally by the caller
         const size_t first = (kvbase[seg] + key0) * p.ldkv + head * D;
         const __amdgpu_buffer_rsrc_t rk = rsrc_of(p.k + first), rv = rsrc_of(p.v + first);
         const int left = p.Nk - key0;                           // keys this tile really has (uniform)
@@ -189,110 +197,136 @@ __global__ __launch_bounds__(256) void flash_attn_kernel(const AttnArgs p) {
     f32x4 rem0 = {0.f, 0.f, 0.f, 0.f}, rem1 = {0.f, 0.f, 0.f, 0.f};     // value columns 32*TF+0..3 / +4..7
     float m_i = -INFINITY, l_i = 0.f;
 
-    load_tile(0);
+    // one 32-key tile out of LDS buffer `buf`; `ragged` adds the key mask of a segment's last, partial tile
+    auto tile_body = [&](const int buf, const int key0, const bool ragged) {
+        const float* Ks = smem + buf * (2 * KT * LD);
+        const float* Vs = Ks + KT * LD;
+        // S^T[key][query] = sum_d K[key][d] Q[query][d]
+        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f32x16 st;
+        const float* kp = Ks + j * LD + h * 4;
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + g * 8);
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+                st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[g][s], (g == 0 && s == 0) ? zero16 : st, 0, 0, 0);
+        }
+        // online softmax; register r of lane half h holds key  key0 + (r&3) + 8(r>>2) + 4h.
+        // On gfx950 the fp32 MFMA runs at the vector rate and VALU instructions are NOT hidden behind it
+        // (measured: kernel cycles = MFMA busy + VALU active), so the softmax is kept lean: key masking only on
+        // the ragged last tile, raw v_exp_f32, and the accumulator rescale only when some row's max moved.
+        if (ragged) {
+            asm volatile("" ::: "memory");                      // (rare path: a branch, not 16 selects on every tile)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                if (key >= p.Nk) st[r] = -INFINITY;
+            }
+        }
+        float mt = st[0];
+#pragma unroll
+        for (int r = 1; r < 16; ++r) mt = __builtin_fmaxf(mt, st[r]);
+        {
+            float lo, hi;
+            half_pair(mt, lo, hi);
+            mt = __builtin_fmaxf(lo, hi);
+        }
+        const float m_new = __builtin_fmaxf(m_i, mt);
+        const bool moved = __any(m_new > m_i);                  // wave-uniform
+        float ps = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            st[r] = __builtin_amdgcn_exp2f(st[r] - m_new);
+            ps += st[r];
+        }
+        if (moved) {                                            // rescale in place, under a branch
+            asm volatile("" ::: "memory");
+            const float alpha = __builtin_amdgcn_exp2f(m_i - m_new);
+            l_i *= alpha;
+#pragma unroll
+            for (int t = 0; t < T; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[t][r] *= alpha;
+            if constexpr (VREM) {
+                rem0 *= alpha;
+                rem1 *= alpha;
+            }
+        }
+        l_i += ps;
+        m_i = m_new;
+        // O^T[dv][query] += sum_key V[key][dv] P[query][key]
+#pragma unroll
+        for (int t = 0; t < T; ++t) {
+            const int dv = min(t * 32 + j, D - 1);
+            const float* vp = Vs + (4 * h) * LD + dv;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float vv = vp[((r & 3) + 8 * (r >> 2)) * LD];
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, st[r], acc[t], 0, 0, 0);
+            }
+        }
+        if constexpr (VREM) {
+            // value columns 32*TF .. 32*TF+7 over this lane's 16 keys, on v_mfma_f32_4x4x1_16b_f32: 16 independent 4x4 outer products,
+            // one per group of four lanes.  Lane 4b+i supplies A[i] = V[key][32*TF + 4g + i] (the four lanes of a group lie in one
+            // half-wave: the same key), lane 4b+j supplies B[j] = its own P[query][key] and receives D[0..3][j] = rem_g[0..3] of its
+            // query: the fused multiply-add per key and column of the VALU form it replaces, in the same registers and key order.
+            const float* vr = Vs + (4 * h) * LD + 32 * TF + (lane & 3);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const float* row = vr + ((r & 3) + 8 * (r >> 2)) * LD;
+                rem0 = __builtin_amdgcn_mfma_f32_4x4x1f32(row[0], st[r], rem0, 0, 0, 0);
+                rem1 = __builtin_amdgcn_mfma_f32_4x4x1f32(row[4], st[r], rem1, 0, 0, 0);
+            }
+        }
+    };
+
+    load_tile(0, 0);
     store_tile(0);
     __syncthreads();
 
-    for (int tt = 0; tt < ntiles; ++tt) {
-        const int buf = tt & 1;
-        if (tt + 1 < ntiles) load_tile(tt + 1);
-        const int seg_c = tt / tps;
-        const int kbase = (tt - seg_c * tps) * KT;
-        // one 32-key tile; `ragged` (compile-time) adds the key mask of a segment's last, partial tile
-        auto tile_body = [&](const int key0, const int sub, auto ragged) {
-            const float* Ks = smem + buf * (2 * KT * LD) + sub * 32 * LD;
-            const float* Vs = smem + buf * (2 * KT * LD) + KT * LD + sub * 32 * LD;
-            // S^T[key][query] = sum_d K[key][d] Q[query][d]
-            const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            f32x16 st;
-            const float* kp = Ks + j * LD + h * 4;
-#pragma unroll
-            for (int g = 0; g < G; ++g) {
-                const f32x4 kf = *reinterpret_cast<const f32x4*>(kp + g * 8);
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-                    st = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[g][s], (g == 0 && s == 0) ? zero16 : st, 0, 0, 0);
-            }
-            // online softmax; register r of lane half h holds key  key0 + (r&3) + 8(r>>2) + 4h.
-            // On gfx950 the fp32 MFMA runs at the vector rate and VALU instructions are NOT hidden behind it
-            // (measured: kernel cycles = MFMA busy + VALU active), so the softmax is kept lean: key masking only on
-            // the ragged last tile, raw v_exp_f32, and the accumulator rescale only when some row's max moved.
-            if constexpr (decltype(ragged)::value) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int key = key0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                    if (key >= p.Nk) st[r] = -INFINITY;
-                }
-            }
-            float mt = st[0];
-#pragma unroll
-            for (int r = 1; r < 16; ++r) mt = __builtin_fmaxf(mt, st[r]);
-            mt = __builtin_fmaxf(mt, __shfl_xor(mt, 32));
-            const float m_new = __builtin_fmaxf(m_i, mt);
-            const bool moved = __any(m_new > m_i);                  // wave-uniform
-            float ps = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                st[r] = __builtin_amdgcn_exp2f(st[r] - m_new);
-                ps += st[r];
-            }
-            float alpha = 1.0f;
-            if (moved) {
-                alpha = __builtin_amdgcn_exp2f(m_i - m_new);
-                l_i *= alpha;
-            }
-            l_i += ps;
-            m_i = m_new;
-            // O^T[dv][query] += sum_key V[key][dv] P[query][key]
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                if (moved) {
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) acc[t][r] *= alpha;
-                }
-                const int dv = min(t * 32 + j, D - 1);
-                const float* vp = Vs + (4 * h) * LD + dv;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float vv = vp[((r & 3) + 8 * (r >> 2)) * LD];
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(vv, st[r], acc[t], 0, 0, 0);
-                }
-            }
-            if constexpr (VREM) {      // value columns 32*TF .. 32*TF+7 for this lane's 16 keys
-                if (moved) {
-                    rem0 *= alpha;
-                    rem1 *= alpha;
-                }
-                const float* vr = Vs + (4 * h) * LD + 32 * TF;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const float* row = vr + ((r & 3) + 8 * (r >> 2)) * LD;
-                    const f32x4 v0 = *reinterpret_cast<const f32x4*>(row);
-                    const f32x4 v1 = *reinterpret_cast<const f32x4*>(row + 4);
-                    rem0 += v0 * st[r];
-                    rem1 += v1 * st[r];
-                }
-            }
-        };
-#pragma unroll
-        for (int sub = 0; sub < KT / 32; ++sub) {
-            const int key0 = kbase + 32 * sub;
-            if (active && key0 < p.Nk) {
-                if (key0 + 32 <= p.Nk) tile_body(key0, sub, std::false_type{});
-                else tile_body(key0, sub, std::true_type{});
-            }
-        }
-        if (tt + 1 < ntiles) store_tile(buf ^ 1);
+    // tile tt = (segment seg, local tile lt): fetch tile tt + 1, compute tile tt, stage tile tt + 1 into the other buffer
+    const int nfull = p.Nk / KT;                                  // whole tiles of a segment; tps - nfull is 0 or 1
+    int seg = 0, lt = 0;
+    auto step = [&](const int buf, const bool last, const bool ragged) {
+        const int key0 = lt * KT;
+        if (++lt == tps) { lt = 0; ++seg; }
+        if (!last) load_tile(seg, lt * KT);
+        if (active) tile_body(buf, key0, ragged);
+        if (!last) store_tile(buf ^ 1);
         __syncthreads();
+    };
+    // Whole tiles go in pairs, so that the LDS buffer of a tile body is a compile-time constant (every LDS address of the loop is a
+    // loop-invariant base plus an immediate) and the loop holds one kind of body; a leading odd tile, a trailing whole tile and each
+    // segment's ragged last tile take the general body outside that loop.
+    int tt = 0;
+    while (tt < ntiles) {
+        if (!(tt & 1))
+            for (; tt < ntiles && lt + 2 <= nfull; tt += 2) {
+                step(0, false, false);
+                step(1, tt + 2 == ntiles, false);
+            }
+        if (tt < ntiles) {
+            step(tt & 1, tt + 1 == ntiles, lt >= nfull);
+            ++tt;
+        }
     }
 
     // lanes l and l+32 hold the two key halves of the same query: fold the partial row sums
-    const float l_tot = l_i + __shfl_xor(l_i, 32);
+    float l_tot;
+    {
+        float lo, hi;
+        half_pair(l_i, lo, hi);
+        l_tot = lo + hi;
+    }
     if constexpr (VREM) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            rem0[e] += __shfl_xor(rem0[e], 32);
-            rem1[e] += __shfl_xor(rem1[e], 32);
+            float lo, hi;
+            half_pair(rem0[e], lo, hi);
+            rem0[e] = lo + hi;
+            half_pair(rem1[e], lo, hi);
+            rem1[e] = lo + hi;
         }
     }
     if (active && q0 + j < p.Nq) {
