@@ -13,16 +13,18 @@ Layout (only what the path needs):
   accuracy (``img_classify_metric``) over ``image_classifier``, ``transformers``' ``ViTForImageClassification`` on the library, and
   the video N-way accuracy (``video_classify_metric``) over ``video_classifier``, its ``VideoMAEForVideoClassification``, and the
   CLIP score (``clip_score``, ``clip_score_only``, ``n_way_scores``) over ``clip_vision``, its ``CLIPVisionModelWithProjection``
+* ``seq2seq``   the reference's Seq2Seq latent model ``myTransformer`` on the library: EEG windows in, UNet latents out
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
 * ``dist``       sharding of clips over ranks and the all-gather of decoded frames
 
 The compute path has no CPU fallback: without the built library or without a GPU it raises.
 """
-from .weights import (TINY_CLIP_VISION, TINY_IMAGE, TINY_SEMANTIC, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO, ClipVisionConfig,  # noqa: F401
-                      ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig)
+from .weights import (TINY_CLIP_VISION, TINY_IMAGE, TINY_SEMANTIC, TINY_SEQ2SEQ, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO,  # noqa: F401
+                      ClipVisionConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig)
 
 __all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig", "ViTForImageClassification", "ImageConfig", "VideoMAEForVideoClassification", "VideoConfig", "CLIPVisionModelWithProjection", "ClipVisionConfig",
+           "myTransformer", "Seq2Seq", "Seq2SeqConfig",
            "DDIMScheduler", "PNDMScheduler", "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler",
            "DPMSolverMultistepScheduler", "TuneAVideoPipeline", "build_pipeline", "save_videos_grid"]
 
@@ -46,6 +48,9 @@ def __getattr__(name):          # lazy: importing the package must not need torc
     if name == "CLIPVisionModelWithProjection":
         from .clip_vision import CLIPVisionModelWithProjection
         return CLIPVisionModelWithProjection
+    if name in ("myTransformer", "Seq2Seq"):
+        from .seq2seq import myTransformer
+        return myTransformer
     if name == "AutoencoderKL":
         from .vae import AutoencoderKL
         return AutoencoderKL

@@ -53,6 +53,19 @@ class E2VClipVConfig(C.Structure):
     ]
 
 
+class E2VS2sConfig(C.Structure):
+    """``e2v_s2s_config`` of include/eeg2video_hip.h (field order is the ABI): the Seq2Seq latent model, handed to ``e2v_create_ex``
+    beside the ``e2v_config``."""
+    _fields_ = [
+        ("s2s_electrodes", C.c_int), ("s2s_samples", C.c_int), ("s2s_windows", C.c_int),
+        ("s2s_f1", C.c_int), ("s2s_d", C.c_int), ("s2s_f2", C.c_int),
+        ("s2s_d_model", C.c_int), ("s2s_heads", C.c_int), ("s2s_ffn", C.c_int), ("s2s_encoder_layers", C.c_int),
+        ("s2s_decoder_layers", C.c_int), ("s2s_steps", C.c_int),
+        ("s2s_latent_channels", C.c_int), ("s2s_latent_h", C.c_int), ("s2s_latent_w", C.c_int), ("s2s_txt_classes", C.c_int),
+        ("s2s_norm_eps", C.c_float), ("s2s_bn_eps", C.c_float),
+    ]
+
+
 class E2VPlanOp(C.Structure):
     """``e2v_plan_op`` of include/eeg2video_hip.h (field order is the ABI)."""
     _fields_ = [
@@ -85,6 +98,9 @@ SIGNATURES = {
     "e2v_create": (_i, [C.POINTER(E2VConfig), _i, C.POINTER(_ctx)]),
     "e2v_clipv_config_size": (_i64, []),
     "e2v_create_clip_vision": (_i, [C.POINTER(E2VConfig), C.POINTER(E2VClipVConfig), _i, C.POINTER(_ctx)]),
+    "e2v_default_s2s_config": (None, [C.POINTER(E2VS2sConfig)]),
+    "e2v_s2s_config_size": (_i64, []),
+    "e2v_create_ex": (_i, [C.POINTER(E2VConfig), C.POINTER(E2VClipVConfig), C.POINTER(E2VS2sConfig), _i, C.POINTER(_ctx)]),
     "e2v_destroy": (None, [_ctx]),
     "e2v_last_error": (C.c_char_p, [_ctx]),
     "e2v_load_tensor": (_i, [_ctx, C.c_char_p, _p, _i, c_int64_p, _i]),
@@ -107,6 +123,7 @@ SIGNATURES = {
     "e2v_generate_plan": (_i, [_ctx, _p, _p, _p, _i, _i, _i, _i, _i, _i, C.POINTER(E2VPlanOp), _i, _i, _i, _p, _i, _f, _p, _p, _stream]),
     "e2v_semantic_predict": (_i, [_ctx, _p, _i, _p, _stream]),
     "e2v_text_encode": (_i, [_ctx, c_int64_p, _i, _i, _p, _stream]),
+    "e2v_seq2seq_latents": (_i, [_ctx, _p, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _p, _p, _p, _stream]),
     "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
     "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
@@ -154,6 +171,8 @@ SIGNATURES = {
     "e2v_op_tower_layernorm": (_i, [_ctx, _i, _p, _i64, _i, _i, _p, _p, _f, _p, _stream]),
     "e2v_op_tower_activation": (_i, [_ctx, _i, _p, _i64, _i, _p, _stream]),
     "e2v_op_tower_embed": (_i, [_ctx, _i, _p, _p, _p, _i, _i, _i, _p, _stream]),
+    "e2v_op_eegnet_embed": (_i, [_ctx, _p, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _p, _stream]),
+    "e2v_op_seq_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
     "e2v_op_set_knob": (_i, [C.c_char_p, _i]),
@@ -195,6 +214,9 @@ def load() -> C.CDLL:
                           "(include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     if lib.e2v_clipv_config_size() != C.sizeof(E2VClipVConfig):
         raise ImportError(f"{LIB_PATH}: e2v_clipv_config is {lib.e2v_clipv_config_size()} bytes in the library, {C.sizeof(E2VClipVConfig)} in "
+                          "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
+    if lib.e2v_s2s_config_size() != C.sizeof(E2VS2sConfig):
+        raise ImportError(f"{LIB_PATH}: e2v_s2s_config is {lib.e2v_s2s_config_size()} bytes in the library, {C.sizeof(E2VS2sConfig)} in "
                           "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     if lib.e2v_plan_op_size() != C.sizeof(E2VPlanOp):
         raise ImportError(f"{LIB_PATH}: e2v_plan_op is {lib.e2v_plan_op_size()} bytes in the library, {C.sizeof(E2VPlanOp)} in this binding "

@@ -142,6 +142,33 @@ void check_clipv_config(const e2v_clipv_config* v) {
                 "clipv_resample must be 2 (BILINEAR) or 3 (BICUBIC), Pillow's codes");
     for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(v->clipv_std[ch] != 0.f, E2V_EINVAL, "clipv_std must be non-zero");
 }
+// what e2v_create_ex refuses of a Seq2Seq config (s2s_d_model != 0): each message names the limit it enforces
+void check_s2s_config(const e2v_s2s_config* v) {
+    E2V_REQUIRE(v->s2s_electrodes > 0 && v->s2s_samples > 0 && v->s2s_windows > 0 && v->s2s_f1 > 0 && v->s2s_d > 0 && v->s2s_f2 > 0 &&
+                    v->s2s_d_model > 0 && v->s2s_heads > 0 && v->s2s_ffn > 0 && v->s2s_encoder_layers > 0 && v->s2s_decoder_layers > 0 &&
+                    v->s2s_steps > 0 && v->s2s_latent_channels > 0 && v->s2s_latent_h > 0 && v->s2s_latent_w > 0 && v->s2s_txt_classes > 0 &&
+                    v->s2s_norm_eps > 0.f && v->s2s_bn_eps > 0.f,
+                E2V_EINVAL, "bad Seq2Seq config: every size and both eps must be positive");
+    E2V_REQUIRE(v->s2s_d_model % v->s2s_heads == 0, E2V_EINVAL, "s2s_d_model must be a multiple of s2s_heads");
+    const int hd = v->s2s_d_model / v->s2s_heads;
+    E2V_REQUIRE(hd % 4 == 0 && hd <= 128, E2V_EINVAL,
+                "s2s_d_model / s2s_heads must be a multiple of 4, at most 128: the head dims of the sequence attention kernel");
+    E2V_REQUIRE(v->s2s_d_model % 4 == 0 && v->s2s_d_model <= 1280, E2V_EINVAL, "s2s_d_model must be a multiple of 4, at most 1280 (the LayerNorm kernel's limit)");
+    E2V_REQUIRE(v->s2s_windows <= kSeqAttnMaxKeys && v->s2s_steps + 1 <= kSeqAttnMaxKeys, E2V_EINVAL,
+                "s2s_windows and s2s_steps + 1 must be at most " + std::to_string(kSeqAttnMaxKeys) + ": the sequence attention kernel holds one key per lane of half a wave");
+    E2V_REQUIRE(v->s2s_ffn % 4 == 0, E2V_EINVAL, "s2s_ffn must be a multiple of 4 (the linear kernels read and store quads)");
+    E2V_REQUIRE(v->s2s_samples >= 32 && v->s2s_samples <= 65536 && v->s2s_electrodes <= 4096 && v->s2s_f1 <= 1024 && v->s2s_d <= 1024 && v->s2s_f2 <= 1024,
+                E2V_EINVAL, "s2s_samples must be at least 32 (the two pools leave samples / 32 columns); sizes of the EEGNet embedding are bounded");
+    const long long feat = (long long)v->s2s_f2 * ((v->s2s_samples / 4) / 8);
+    E2V_REQUIRE(feat % 4 == 0, E2V_EINVAL, "s2s_f2 * ((s2s_samples / 4) / 8), the width of the EEGNet features, must be a multiple of 4");
+    const EegnetLayout L = eegnet_layout(v->s2s_electrodes, v->s2s_samples, v->s2s_f1, v->s2s_d, v->s2s_f2);
+    E2V_REQUIRE(L.total_floats * sizeof(float) <= (size_t)kEegnetMaxLdsBytes, E2V_EINVAL,
+                "one EEG window with its intermediates must fit the embedding kernel's " + std::to_string(kEegnetMaxLdsBytes) + " bytes of LDS (this config: " +
+                    std::to_string(L.total_floats * sizeof(float)) + ")");
+    const long long lat = (long long)v->s2s_latent_channels * v->s2s_latent_h * v->s2s_latent_w;
+    E2V_REQUIRE(lat % 4 == 0 && (v->s2s_latent_h * (long long)v->s2s_latent_w) % 4 == 0 && lat <= (1 << 24), E2V_EINVAL,
+                "s2s_latent_h * s2s_latent_w must be a multiple of 4 (the linear and layout kernels store quads), a latent at most 2^24 values");
+}
 }  // namespace
 
 extern "C" {
@@ -155,7 +182,28 @@ e2v_status e2v_create(const e2v_config* cfg, int device, e2v_ctx** out) { return
 int64_t e2v_clipv_config_size(void) { return (int64_t)sizeof(e2v_clipv_config); }
 
 e2v_status e2v_create_clip_vision(const e2v_config* cfg, const e2v_clipv_config* clipv, int device, e2v_ctx** out) {
+    return e2v_create_ex(cfg, clipv, nullptr, device, out);
+}
+
+int64_t e2v_s2s_config_size(void) { return (int64_t)sizeof(e2v_s2s_config); }
+
+void e2v_default_s2s_config(e2v_s2s_config* s) {      // myTransformer() as the reference constructs it (my_autoregressive_transformer.py:125-149)
+    std::memset(s, 0, sizeof(*s));
+    s->s2s_electrodes = 62; s->s2s_samples = 100; s->s2s_windows = 7;
+    s->s2s_f1 = 16; s->s2s_d = 4; s->s2s_f2 = 16;
+    s->s2s_d_model = 512; s->s2s_heads = 4; s->s2s_ffn = 2048; s->s2s_encoder_layers = 2; s->s2s_decoder_layers = 4;
+    s->s2s_steps = 6;
+    s->s2s_latent_channels = 4; s->s2s_latent_h = 36; s->s2s_latent_w = 64;
+    s->s2s_txt_classes = 13;
+    s->s2s_norm_eps = 1e-5f; s->s2s_bn_eps = 1e-5f;
+}
+
+e2v_status e2v_create_ex(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, int device, e2v_ctx** out) {
     if (clipv && clipv->clipv_layers == 0) clipv = nullptr;      // (all zero: no tower)
+    if (s2s) {                                                   // (all zero: no Seq2Seq model)
+        static const e2v_s2s_config none = {};
+        if (std::memcmp(s2s, &none, sizeof(none)) == 0) s2s = nullptr;
+    }
     if (!cfg || !out) { g_create_error = "null argument"; return E2V_EINVAL; }
     *out = nullptr;
     e2v_ctx* c = nullptr;
@@ -226,10 +274,12 @@ e2v_status e2v_create_clip_vision(const e2v_config* cfg, const e2v_clipv_config*
             for (int ch = 0; ch < 3; ++ch) E2V_REQUIRE(cfg->vmae_std[ch] != 0.f, E2V_EINVAL, "vmae_std must be non-zero");
         }
         if (clipv) check_clipv_config(clipv);
+        if (s2s) check_s2s_config(s2s);
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
         if (clipv) c->vcfg = *clipv;
+        if (s2s) c->scfg = *s2s;
         for (int ch = 0; ch < 3 && c->vcfg.clipv_layers > 0; ++ch) // CLIPImageProcessor: as the image processor's table
             for (int b = 0; b < 256; ++b) {
                 const float x = (float)((double)b * c->vcfg.clipv_rescale);
@@ -323,7 +373,7 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
     const int part = e2v_ctx::key_part(k);
-    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : part == 64 ? c->clipv_ready : c->unet_ready;
+    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : part == 64 ? c->clipv_ready : part == 128 ? c->s2s_ready : c->unet_ready;
     E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
@@ -346,6 +396,10 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
     }
     if (e2v_ctx::key_part(key) == 32) {
         c->err = "e2v_update_tensor: the video classifier is a frozen yardstick (40_class_run_metrics.py:113-118); load a new one with e2v_load_tensor + e2v_finalize_weights";
+        return E2V_EINVAL;
+    }
+    if (e2v_ctx::key_part(key) == 128) {
+        c->err = "e2v_update_tensor: the Seq2Seq model is only called here and its BatchNorms are folded at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128)";
         return E2V_EINVAL;
     }
     return guarded(c, [&] {
@@ -400,8 +454,10 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(which >= 1 && which <= 127, E2V_EINVAL,
-                    "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier, 64 CLIP vision tower");
+        // (bit 7 belongs to the mask of a context that was made with a Seq2Seq config; on any other it is out of range, as it always was)
+        E2V_REQUIRE(which >= 1 && which <= (c->scfg.s2s_d_model > 0 ? 255 : 127), E2V_EINVAL,
+                    "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier, 64 CLIP vision tower, "
+                    "128 Seq2Seq latent model (a context made by e2v_create_ex with an e2v_s2s_config only)");
         c->finalize(which);
     });
 }
@@ -497,6 +553,43 @@ e2v_status e2v_text_encode(e2v_ctx* c, const int64_t* host_ids, int B, int T, fl
         Act d(c->pool, (int64_t)n, 1);
         E2V_HIP(hipMemcpyAsync(d.p, ids.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
         c->text_encode(reinterpret_cast<const int*>(d.p), B, T, out, s);
+    });
+}
+
+// myTransformer.forward + the [:, :-1] of its inference.  What is wrong with the call itself is answered first and without a HIP call
+// (E2V_EINVAL, a host-only context included); then the state of the context (E2V_ESTATE); nothing is enqueued before both passed.
+e2v_status e2v_seq2seq_latents(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
+                               const float* mean, const float* scale, int B, int first, int count, int layout, float* latents,
+                               float* txt_logits, float* tokens, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    try {
+        auto off = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
+        E2V_REQUIRE(eeg, E2V_EINVAL, "e2v_seq2seq_latents: eeg is NULL");
+        E2V_REQUIRE(latents || txt_logits || tokens, E2V_EINVAL, "e2v_seq2seq_latents: no output asked for (latents, txt_logits and tokens are all NULL)");
+        E2V_REQUIRE((mean == nullptr) == (scale == nullptr), E2V_EINVAL, "e2v_seq2seq_latents: the input scaler is a mean AND a scale, or neither");
+        E2V_REQUIRE(!off(eeg, 3) && !off(mean, 3) && !off(scale, 3) && !off(txt_logits, 3), E2V_EINVAL,
+                    "e2v_seq2seq_latents: eeg, mean, scale and txt_logits must be 4-byte aligned");
+        E2V_REQUIRE(!off(latents, 15) && !off(tokens, 15), E2V_EINVAL, "e2v_seq2seq_latents: latents and tokens must be 16-byte aligned");
+        E2V_REQUIRE(clip_stride >= 0 && window_stride >= 0 && channel_stride >= 0, E2V_EINVAL, "e2v_seq2seq_latents: strides are non-negative element counts");
+        if (latents || tokens) {
+            E2V_REQUIRE(layout == 0 || layout == 1, E2V_EINVAL, "e2v_seq2seq_latents: layout is 0 ([B][count][C][h][w]) or 1 ([B][C][count][h][w])");
+            const int T1 = c->scfg.s2s_d_model > 0 ? c->scfg.s2s_steps + 1 : 0x7FFFFFF;      // (without a config the range has no upper end to miss)
+            E2V_REQUIRE(first >= 0 && count >= 1 && (long long)first + count <= T1, E2V_EINVAL,
+                        "e2v_seq2seq_latents: tokens [first, first + count) must lie in [0, s2s_steps + 1) with count >= 1");
+        }
+        E2V_REQUIRE(B >= 1, E2V_EINVAL, "e2v_seq2seq_latents: B must be at least 1");
+        E2V_REQUIRE(c->scfg.s2s_d_model > 0, E2V_ESTATE, "the context has no Seq2Seq latent model (e2v_create_ex)");
+        E2V_REQUIRE(c->s2s_ready, E2V_ESTATE, "Seq2Seq weights are not finalized");
+        E2V_REQUIRE((long long)B * std::max(c->scfg.s2s_windows, c->scfg.s2s_steps + 1) * std::max(c->scfg.s2s_ffn, 3 * c->scfg.s2s_d_model) <= 0x7FFFFFFFLL &&
+                        (long long)B * (c->scfg.s2s_steps + 1) <= (1 << 20), E2V_ESHAPE, "e2v_seq2seq_latents: B is too large for one call");
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, [&] {
+        EegnetArgs e;
+        e.eeg = eeg; e.clip_stride = clip_stride; e.window_stride = window_stride; e.channel_stride = channel_stride; e.mean = mean; e.scale = scale;
+        c->seq2seq_latents(e, B, first, count, layout, latents, txt_logits, tokens, S(c, stream));
     });
 }
 
@@ -1887,6 +1980,60 @@ e2v_status e2v_op_causal_attention(e2v_ctx* c, const float* qkv, int ldqkv, floa
         E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && T <= kTextAttnMaxT, E2V_ESHAPE, "causal attention: B, heads >= 1 and 1 <= T <= " + std::to_string(kTextAttnMaxT));
         E2V_REQUIRE(ldqkv % 4 == 0 && ldqkv >= 3 * 64 * heads && ldo >= 64 * heads, E2V_EINVAL, "bad strides: ldqkv >= 3 * 64 * heads (a multiple of 4), ldo >= 64 * heads");
         text_causal_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// the EEGNet embedding kernel of e2v_seq2seq_latents from torch-layout device tensors (folded on the host, as finalize does)
+e2v_status e2v_op_eegnet_embed(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
+                               const float* mean, const float* scale, int B, int W, int C, int T, int F1, int D, int F2, const float* w1,
+                               const float* bn1, const float* w2, const float* bn2, const float* w3, const float* w4, const float* bn3,
+                               float bn_eps, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(eeg && out && w1 && bn1 && w2 && bn2 && w3 && w4 && bn3, E2V_EINVAL, "null argument");
+        E2V_REQUIRE((mean == nullptr) == (scale == nullptr), E2V_EINVAL, "the scaler is a mean AND a scale, or neither");
+        E2V_REQUIRE(clip_stride >= 0 && window_stride >= 0 && channel_stride >= 0 && bn_eps > 0.f, E2V_EINVAL, "negative stride or eps");
+        E2V_REQUIRE(B >= 1 && W >= 1 && C >= 1 && C <= 4096 && T >= 32 && T <= 65536 && F1 >= 1 && F1 <= 1024 && D >= 1 && D <= 1024 && F2 >= 1 && F2 <= 1024,
+                    E2V_ESHAPE, "EEGNet embedding: positive, bounded sizes and at least 32 samples a window");
+        hipStream_t s = S(c, stream);
+        const int FD = F1 * D;
+        auto host = [&](const float* d, size_t n) {
+            std::vector<float> h(n);
+            E2V_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost, s));
+            return h;
+        };
+        const std::vector<float> h1 = host(w1, (size_t)F1 * 64), hb1 = host(bn1, 4 * (size_t)F1), h2 = host(w2, (size_t)FD * C), hb2 = host(bn2, 4 * (size_t)FD),
+                                 h3 = host(w3, (size_t)FD * 16), h4 = host(w4, (size_t)F2 * FD), hb3 = host(bn3, 4 * (size_t)F2);
+        E2V_HIP(hipStreamSynchronize(s));
+        const std::vector<float> pk = eegnet_pack(EegnetHostW{h1.data(), hb1.data(), h2.data(), hb2.data(), h3.data(), h4.data(), hb3.data()}, C, F1, D, F2, bn_eps);
+        Act dp(c->pool, (int64_t)pk.size(), 1);
+        E2V_HIP(hipMemcpyAsync(dp.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        EegnetArgs a;
+        a.eeg = eeg; a.clip_stride = clip_stride; a.window_stride = window_stride; a.channel_stride = channel_stride; a.mean = mean; a.scale = scale;
+        a.pack = dp.p; a.out = out; a.B = B; a.W = W; a.C = C; a.T = T; a.F1 = F1; a.D = D; a.F2 = F2;
+        eegnet_embed(a, s);
+        E2V_HIP(hipStreamSynchronize(s));                        // (pk is pageable host memory: the copy has to have left it)
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// the attention kernel of e2v_seq2seq_latents on caller tensors
+e2v_status e2v_op_seq_attention(e2v_ctx* c, const float* q, int ldq, const float* k, const float* v, int ldkv, float* out, int ldo, int B,
+                                int heads, int D, int Nq, int Nk, int q_pos0, int causal, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(q && k && v && out && ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k)) & 15) == 0, E2V_EINVAL,
+                    "null or misaligned argument (q, k: 16 bytes)");
+        E2V_REQUIRE(B >= 1 && heads >= 1 && Nq >= 1 && Nq <= (1 << 16) && Nk >= 1 && Nk <= kSeqAttnMaxKeys && q_pos0 >= 0 && D >= 4 && D % 4 == 0 && D <= 128 && heads <= 4096,
+                    E2V_ESHAPE, "sequence attention: B, heads, Nq >= 1, 1 <= Nk <= " + std::to_string(kSeqAttnMaxKeys) + ", D a multiple of 4 up to 128");
+        E2V_REQUIRE(ldq % 4 == 0 && ldkv % 4 == 0 && ldq >= heads * D && ldkv >= heads * D && ldo >= heads * D, E2V_EINVAL,
+                    "bad strides: ldq, ldkv (multiples of 4) and ldo are at least heads * D");
+        SeqAttnArgs a;
+        a.q = q; a.sq = (long long)Nq * ldq; a.ldq = ldq; a.k = k; a.v = v; a.skv = (long long)Nk * ldkv; a.ldkv = ldkv;
+        a.o = out; a.so = (long long)Nq * ldo; a.ldo = ldo;
+        a.B = B; a.heads = heads; a.D = D; a.Nq = Nq; a.Nk = Nk; a.q_pos0 = q_pos0; a.causal = causal ? 1 : 0; a.scale = 1.0f / std::sqrt((float)D);
+        seq_attention(a, S(c, stream));
         E2V_HIP(hipGetLastError());
     });
 }

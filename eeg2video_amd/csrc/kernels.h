@@ -321,6 +321,74 @@ void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s, 
 void clip_similarity(const float* a, int na, const float* b, int nb, int D, bool matrix, float eps, float* out, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
+// Seq2Seq latent model (seq2seq.hip; e2v_seq2seq_latents): fp32 in every compute mode.  The linears, LayerNorm, the positions, the mean
+// over the window rows and the appended rows are igemm, layernorm, video_embed, token_mean and copy_rows.
+// ---------------------------------------------------------------------------------------
+// Where the EEGNet kernel keeps things, in floats (every offset a multiple of 4): the pack of folded weights -- w1 [F1][64], w2 [FD][C],
+// a2 / c2 [FD], w3 [FD][16], w4 [F2][FD], a3 / c3 [F2], offsets relative to `pack` -- and, behind it in LDS, the window xs [C][T], the
+// spatial mixes zp [FD][T + 63], the pooled block-2 rows pp [FD][T/4 + 15], the depthwise rows dw [FD][T/4], block 3 before its pool
+// qe [F2][T/4]
+struct EegnetLayout {
+    int w1, w2, a2, c2, w3, w4, a3, c3, pack_floats;
+    int pack, xs, zp, pp, dw, qe;
+    size_t total_floats;
+};
+E2V_SCHED_HD inline EegnetLayout eegnet_layout(int C, int T, int F1, int D, int F2) {
+    const int FD = F1 * D, T4 = T / 4;
+    auto up4 = [](long long v) { return (v + 3) / 4 * 4; };
+    EegnetLayout L;
+    long long o = 0;
+    L.w1 = (int)o; o = up4(o + (long long)F1 * 64);
+    L.w2 = (int)o; o = up4(o + (long long)FD * C);
+    L.a2 = (int)o; o = up4(o + FD);
+    L.c2 = (int)o; o = up4(o + FD);
+    L.w3 = (int)o; o = up4(o + (long long)FD * 16);
+    L.w4 = (int)o; o = up4(o + (long long)F2 * FD);
+    L.a3 = (int)o; o = up4(o + F2);
+    L.c3 = (int)o; o = up4(o + F2);
+    L.pack_floats = (int)o;
+    L.pack = 0;
+    L.xs = (int)o; o = up4(o + (long long)C * T);
+    L.zp = (int)o; o = up4(o + (long long)FD * (T + 63));
+    L.pp = (int)o; o = up4(o + (long long)FD * (T4 + 15));
+    L.dw = (int)o; o = up4(o + (long long)FD * T4);
+    L.qe = (int)o; o = up4(o + (long long)F2 * T4);
+    L.total_floats = (size_t)o;
+    return L;
+}
+constexpr int kEegnetMaxLdsBytes = 156 * 1024;      // of the CU's 160 KiB; the reference's window (62 x 100, F1 16, D 4, F2 16) takes 111 KiB
+// the torch-layout tensors of MyEEGNet_embedding on the HOST: block_1.1 [F1][1][1][64], block_2.0 [F1 D][1][C][1], block_3.1 [F1 D][1][1][16],
+// block_3.2 [F2][F1 D][1][1], and each BatchNorm as weight | bias | running_mean | running_var, n values each
+struct EegnetHostW { const float* w1; const float* bn1; const float* w2; const float* bn2; const float* w3; const float* w4; const float* bn3; };
+std::vector<float> eegnet_pack(const EegnetHostW& h, int C, int F1, int D, int F2, float bn_eps);      // eegnet_layout(...).pack_floats floats
+// One workgroup per (clip, window): out[(b W + w)][F2 ((T / 4) / 8)], the flattened block-3 output.  Sample t of channel c of window w
+// of clip b is eeg[b clip_stride + w window_stride + c channel_stride + t] (element strides; 4-byte alignment is all a load assumes);
+// mean / scale [W][C][T]: the optional input scaler (x - mean) / scale, both or neither.
+struct EegnetArgs {
+    const float* eeg = nullptr; long long clip_stride = 0, window_stride = 0, channel_stride = 0;
+    const float* mean = nullptr; const float* scale = nullptr;
+    const float* pack = nullptr;                 // eegnet_pack, on the device
+    float* out = nullptr;
+    int B = 0, W = 0, C = 0, T = 0, F1 = 0, D = 0, F2 = 0;
+};
+void eegnet_embed(const EegnetArgs& a, hipStream_t s);
+// softmax(q k^T scale) v for the few tokens the model holds: Nq queries of every (clip, head) against Nk <= 32 keys.  Row i of clip b
+// of q is q[b sq + i ldq + head D ..] (k, v: skv / ldkv; o: so / ldo; element strides, q and k rows 16-byte aligned with strides
+// multiples of 4), D a multiple of 4 up to 128.  causal: query i sits at absolute position q_pos0 + i and sees keys 0 .. q_pos0 + i.
+// fp32 softmax, sums in key order.
+constexpr int kSeqAttnMaxKeys = 32;
+struct SeqAttnArgs {
+    const float* q = nullptr; long long sq = 0; int ldq = 0;
+    const float* k = nullptr; const float* v = nullptr; long long skv = 0; int ldkv = 0;
+    float* o = nullptr; long long so = 0; int ldo = 0;
+    int B = 0, heads = 0, D = 0, Nq = 0, Nk = 0, q_pos0 = 0, causal = 0;
+    float scale = 1.f;
+};
+void seq_attention(const SeqAttnArgs& a, hipStream_t s);
+// [B][F][C][HW] -> [B][C][F][HW] (HW a multiple of 4, 16-byte aligned)
+void seq_latents_bcfhw(const float* in, float* out, int B, int F, int C, int HW, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)
 // ---------------------------------------------------------------------------------------
 void ncfhw_to_cl(const float* in, float* out, int n, int C, int Cpad, int FHW, float scale, hipStream_t s, int out_bf16 = 0);

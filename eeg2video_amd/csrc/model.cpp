@@ -208,6 +208,41 @@ void e2v_ctx::expected_keys() {
         s.norm(m + "post_layernorm", C);
         s.lin("clipv.visual_projection", vcfg.clipv_projection_dim, C, false);
     }
+
+    // ---- Seq2Seq latent model ("s2s." prefix; the names of the reference's myTransformer state dict in its order, without what
+    // inference never reads -- embedding.weight, img_embedding.*, every num_batches_tracked -- and with the position table as the
+    // [windows][d_model] rows that are read, not the [1][5000][d_model] buffer) ----
+    if (scfg.s2s_d_model > 0) {
+        const int C = scfg.s2s_d_model, I = scfg.s2s_ffn, FD = scfg.s2s_f1 * scfg.s2s_d;
+        const std::string e = "s2s.eeg_embedding.";
+        auto bn = [&](const std::string& n, int ch) {
+            for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) s.add(n + t, {ch});
+        };
+        auto mha = [&](const std::string& n) {
+            s.add(n + ".in_proj_weight", {3 * C, C}); s.add(n + ".in_proj_bias", {3 * C});
+            s.lin(n + ".out_proj", C, C);
+        };
+        s.add(e + "block_1.1.weight", {scfg.s2s_f1, 1, 1, 64}); bn(e + "block_1.2", scfg.s2s_f1);
+        s.add(e + "block_2.0.weight", {FD, 1, scfg.s2s_electrodes, 1}); bn(e + "block_2.1", FD);
+        s.add(e + "block_3.1.weight", {FD, 1, 1, 16});
+        s.add(e + "block_3.2.weight", {scfg.s2s_f2, FD, 1, 1}); bn(e + "block_3.3", scfg.s2s_f2);
+        s.lin(e + "embedding", C, s2s_features());
+        for (int i = 0; i < scfg.s2s_encoder_layers; ++i) {
+            const std::string l = "s2s.transformer_encoder.layers." + std::to_string(i);
+            mha(l + ".self_attn");
+            s.lin(l + ".linear1", I, C); s.lin(l + ".linear2", C, I);
+            s.norm(l + ".norm1", C); s.norm(l + ".norm2", C);
+        }
+        for (int i = 0; i < scfg.s2s_decoder_layers; ++i) {
+            const std::string l = "s2s.transformer_decoder.layers." + std::to_string(i);
+            mha(l + ".self_attn"); mha(l + ".multihead_attn");
+            s.lin(l + ".linear1", I, C); s.lin(l + ".linear2", C, I);
+            s.norm(l + ".norm1", C); s.norm(l + ".norm2", C); s.norm(l + ".norm3", C);
+        }
+        s.add("s2s.positional_encoding.pe", {scfg.s2s_windows, C});
+        s.lin("s2s.txtpredictor", scfg.s2s_txt_classes, C);
+        s.lin("s2s.predictor", s2s_latent(), C);
+    }
 }
 
 // a block of a weight layout, owned by the part its caller selected (AllocPart); guarded, and its payload poisoned before the first
@@ -562,6 +597,7 @@ void e2v_ctx::finalize(int which) {
     E2V_REQUIRE(!(which & 16) || cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
     E2V_REQUIRE(!(which & 32) || cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
     E2V_REQUIRE(!(which & 64) || vcfg.clipv_layers > 0, E2V_ESTATE, "the context has no CLIP vision tower (e2v_create_clip_vision)");
+    E2V_REQUIRE(!(which & 128) || !dry_run(), E2V_ESTATE, "the Seq2Seq latent model has no dry run");
     for (const auto& k : keys)
         if (which & key_part(k)) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
@@ -778,6 +814,97 @@ void e2v_ctx::finalize(int which) {
         P.f32_only = false;
         clipv = std::move(v);
     }
+    if (which & 128) {
+        free_part(7);
+        alloc_part = 7;
+        P.f32_only = true;
+        S2sW v;
+        const int C = scfg.s2s_d_model, F1 = scfg.s2s_f1, D = scfg.s2s_d, F2 = scfg.s2s_f2, E = scfg.s2s_electrodes;
+        // every tensor stays where e2v_load_tensor put it and is read back from there: a matrix is used as it stands, in_proj as views
+        auto keep = [&](const std::string& k) -> const WTensor& {
+            const WTensor& t = P.t(k);
+            const int rows = t.shape.size() > 1 ? (int)t.shape[0] : 1;
+            P.bind_raw(k, t.d(), rows, (int)(t.numel / (size_t)rows));
+            return t;
+        };
+        auto lin = [&](const std::string& n) {
+            const WTensor& w = keep(n + ".weight");
+            return P.mk_lin(w.d(), keep(n + ".bias").d(), (int)w.shape[1], (int)w.shape[0]);
+        };
+        auto norm = [&](const std::string& n) { return NormW{keep(n + ".weight").d(), keep(n + ".bias").d(), C}; };
+        {   // the EEGNet embedding: the four convs and the three BatchNorms (eval mode: running statistics) folded on the host
+            const std::string e = "s2s.eeg_embedding.";
+            auto host = [&](const std::string& k) {
+                const WTensor& t = keep(k);
+                std::vector<float> h(t.numel);
+                E2V_HIP(hipMemcpy(h.data(), t.d(), t.numel * sizeof(float), hipMemcpyDeviceToHost));
+                return h;
+            };
+            auto host_bn = [&](const std::string& n) {
+                std::vector<float> h;
+                for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) {
+                    const std::vector<float> part = host(n + t);
+                    h.insert(h.end(), part.begin(), part.end());
+                }
+                return h;
+            };
+            const std::vector<float> w1 = host(e + "block_1.1.weight"), w2 = host(e + "block_2.0.weight"), w3 = host(e + "block_3.1.weight"),
+                                     w4 = host(e + "block_3.2.weight");
+            const std::vector<float> bn1 = host_bn(e + "block_1.2"), bn2 = host_bn(e + "block_2.1"), bn3 = host_bn(e + "block_3.3");
+            for (int i = 0; i < F1 * D; ++i)
+                E2V_REQUIRE(bn2[3 * F1 * D + i] + scfg.s2s_bn_eps > 0.f, E2V_EINVAL, "s2s.eeg_embedding.block_2.1.running_var + eps must be positive");
+            for (int i = 0; i < F1; ++i)
+                E2V_REQUIRE(bn1[3 * F1 + i] + scfg.s2s_bn_eps > 0.f, E2V_EINVAL, "s2s.eeg_embedding.block_1.2.running_var + eps must be positive");
+            for (int i = 0; i < F2; ++i)
+                E2V_REQUIRE(bn3[3 * F2 + i] + scfg.s2s_bn_eps > 0.f, E2V_EINVAL, "s2s.eeg_embedding.block_3.3.running_var + eps must be positive");
+            const std::vector<float> pk = eegnet_pack(EegnetHostW{w1.data(), bn1.data(), w2.data(), bn2.data(), w3.data(), w4.data(), bn3.data()},
+                                                      E, F1, D, F2, scfg.s2s_bn_eps);
+            float* d = dev_alloc(pk.size());
+            E2V_HIP(hipMemcpy(d, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+            v.eegnet = d;
+            v.embed = lin(e + "embedding");
+        }
+        v.pe = keep("s2s.positional_encoding.pe").d();
+        // nn.MultiheadAttention: in_proj whole (self-attention) or as its q rows and its k | v rows (cross-attention)
+        auto in_proj = [&](const std::string& n, int row0, int rows) {
+            const WTensor& w = keep(n + ".in_proj_weight");
+            const WTensor& b = keep(n + ".in_proj_bias");
+            return P.mk_lin(w.d() + (size_t)row0 * C, b.d() + row0, C, rows);
+        };
+        for (int i = 0; i < scfg.s2s_encoder_layers; ++i) {
+            const std::string l = "s2s.transformer_encoder.layers." + std::to_string(i);
+            S2sEncLayerW w;
+            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = lin(l + ".self_attn.out_proj");
+            w.fc1 = lin(l + ".linear1"); w.fc2 = lin(l + ".linear2");
+            w.ln1 = norm(l + ".norm1"); w.ln2 = norm(l + ".norm2");
+            v.enc.push_back(w);
+        }
+        for (int i = 0; i < scfg.s2s_decoder_layers; ++i) {
+            const std::string l = "s2s.transformer_decoder.layers." + std::to_string(i);
+            S2sDecLayerW w;
+            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = lin(l + ".self_attn.out_proj");
+            w.q2 = in_proj(l + ".multihead_attn", 0, C); w.kv2 = in_proj(l + ".multihead_attn", C, 2 * C);
+            w.out2 = lin(l + ".multihead_attn.out_proj");
+            w.fc1 = lin(l + ".linear1"); w.fc2 = lin(l + ".linear2");
+            w.ln1 = norm(l + ".norm1"); w.ln2 = norm(l + ".norm2"); w.ln3 = norm(l + ".norm3");
+            v.dec.push_back(w);
+        }
+        {   // txtpredictor: the classifiers' padding to whole quads of rows, in a block of its own; the loaded tensors stay the ones read back
+            const int L = scfg.s2s_txt_classes, Lp = (L + 3) / 4 * 4;
+            const WTensor& w = keep("s2s.txtpredictor.weight");
+            const WTensor& b = keep("s2s.txtpredictor.bias");
+            float* dw = dev_alloc((size_t)Lp * C);
+            float* db = dev_alloc(Lp);
+            E2V_HIP(hipMemsetAsync(dw, 0, (size_t)Lp * C * sizeof(float), P.s));
+            E2V_HIP(hipMemsetAsync(db, 0, (size_t)Lp * sizeof(float), P.s));
+            copy_rows(w.d(), C, dw, C, L, C, P.s);
+            copy_rows(b.d(), L, db, L, 1, L, P.s);
+            v.txt = P.mk_lin(dw, db, C, Lp);
+        }
+        v.pred = lin("s2s.predictor");
+        P.f32_only = false;
+        s2s = std::move(v);
+    }
     alloc_part = -1;
     resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
@@ -814,6 +941,7 @@ void e2v_ctx::finalize(int which) {
             if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
             continue;
         }
+        if (part == 128) continue;               // every tensor of the Seq2Seq model is read where it was loaded
         const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
                            k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
                            k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
@@ -828,6 +956,7 @@ void e2v_ctx::finalize(int which) {
     if (which & 16) image_ready = true;
     if (which & 32) video_ready = true;
     if (which & 64) clipv_ready = true;
+    if (which & 128) s2s_ready = true;
 }
 
 // =====================================================================================================
@@ -1025,6 +1154,7 @@ struct LinOpt {
     const float* a1 = nullptr; int c1 = 0, lda1 = 0;         // second source: the last c1 of the K columns come from a1
     bool geglu = false;                                      // out[M][N/2]
     bool f32_io = false, out_f32 = false;                    // bf16-activation mode: see Runner::linear
+    bool relu = false;                                       // out = max(out, 0) after the bias
 };
 struct ConvOpt {
     const float* rowbias = nullptr; int rows_per_sample = 1;
@@ -1137,7 +1267,7 @@ struct Runner {
         IgemmArgs g;
         g.a0 = a; g.c0 = K0; g.lda0 = lda; g.a1 = o.a1; g.c1 = o.c1; g.lda1 = o.lda1;
         g.w = w.w; g.ldw = w.in; g.ldw16 = w.in16; g.out = out.p; g.ldc = out.C; g.bias = w.b;
-        g.resid = o.resid; g.ldr = o.ldr; g.M = (int)M; g.N = w.out; g.taps = 1; g.geglu = o.geglu ? 1 : 0;
+        g.resid = o.resid; g.ldr = o.ldr; g.M = (int)M; g.N = w.out; g.taps = 1; g.geglu = o.geglu ? 1 : 0; g.relu = o.relu ? 1 : 0;
         if (b16) { g.w16 = w16_of(w); g.a_bf16 = h16(); g.out_f32 = o.out_f32 ? 1 : 0; g.resid_bf16 = o.resid ? 1 : 0; }
         if (c->x3_compute && w.w3) { g.x3 = 1; g.w3 = w.w3; g.w3_plane = (long long)w.out * w.in; }
         Act skws = sk_setup(g);
@@ -1908,6 +2038,124 @@ void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float*
         tower_head_ln(R, clipv.post_ln, x.p, T * C, false, cls.p, ni, C, eps);
         Act emb = R.linear(clipv.proj, cls.p, C, ni, R.f32_rows());
         copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// myTransformer.forward in eval mode (my_autoregressive_transformer.py:151-192) and the slice its inference keeps (:383-384).
+//   windows   MyEEGNet_embedding of every window (eegnet_embed, then the Linear), + the sinusoid rows (:154,161)
+//   encoder   nn.TransformerEncoderLayer x L, post-LN, ReLU, no mask, no final norm (:171)
+//   text      txtpredictor of the mean over the window rows (:187,190)
+//   decoder   new_tgt starts as one zero row and never receives a position (:176); pass i runs the layers over rows 0 .. i under the
+//             causal mask and appends the last output row (:177-181).  Under that mask rows 0 .. i - 1 come out of every layer exactly as
+//             in the pass before, so pass i computes ROW i alone, against the keys and values each layer kept of the earlier rows --
+//             the reference's arithmetic for that row, 1 / (i + 1) of its work; the memory's keys and values of every layer are
+//             projected once per call.  Only the passes the requested tokens need are run.
+//   latents   predictor of the requested token rows (:190), in the caller's layout
+// fp32 rows and fp32 arithmetic whatever the context's compute mode (the linears go the way of the time-embedding MLP, no split-K:
+// the runner is of the large family), and every kernel computes a row from its own clip in an order fixed by the config: a clip's bits
+// depend neither on B nor on its place in the batch.
+// -----------------------------------------------------------------------------------------------------
+void e2v_ctx::seq2seq_latents(const EegnetArgs& eeg_in, int B, int first, int count, int layout, float* latents, float* txt_logits,
+                              float* tokens, hipStream_t s) {
+    E2V_REQUIRE(s2s_ready, E2V_ESTATE, "Seq2Seq weights are not finalized");
+    Runner R{this, s, false};
+    const int C = scfg.s2s_d_model, H = scfg.s2s_heads, Dh = C / H, W = scfg.s2s_windows, T1 = scfg.s2s_steps + 1;
+    const int feat = s2s_features(), L = scfg.s2s_txt_classes;
+    const float eps = scfg.s2s_norm_eps, scale = 1.0f / std::sqrt((float)Dh);
+    const bool decode = latents || tokens;
+    const int passes = decode ? first + count - 1 : 0;
+    const int64_t MW = (int64_t)B * W;
+    auto ln = [&](const NormW& w, const float* x, int ldx, float* y, int ldy, int rows) { layernorm(x, ldx, w.g, w.b, y, ldy, rows, C, eps, s); };
+    auto plus = [&](const float* r, int ldr) { LinOpt o = R.f32_rows(); o.resid = r; o.ldr = ldr; return o; };
+    LinOpt relu = R.f32_rows();
+    relu.relu = true;
+    auto attend = [&](const float* q, long long sq, int ldq, const float* k, const float* v, long long skv, int ldkv, float* o, long long so,
+                      int ldo, int Nq, int Nk, int pos0, bool causal) {
+        SeqAttnArgs a;
+        a.q = q; a.sq = sq; a.ldq = ldq; a.k = k; a.v = v; a.skv = skv; a.ldkv = ldkv; a.o = o; a.so = so; a.ldo = ldo;
+        a.B = B; a.heads = H; a.D = Dh; a.Nq = Nq; a.Nk = Nk; a.q_pos0 = pos0; a.causal = causal ? 1 : 0; a.scale = scale;
+        seq_attention(a, s);
+    };
+
+    // ---- windows -> encoder rows ----
+    Act x(pool, MW, C);
+    {
+        Act f(pool, MW, feat);
+        EegnetArgs e = eeg_in;
+        e.pack = s2s.eegnet; e.out = f.p; e.B = B; e.W = W; e.C = scfg.s2s_electrodes; e.T = scfg.s2s_samples;
+        e.F1 = scfg.s2s_f1; e.D = scfg.s2s_d; e.F2 = scfg.s2s_f2;
+        eegnet_embed(e, s);
+        Act emb = R.linear(s2s.embed, f.p, feat, MW, R.f32_rows());
+        video_embed(emb.p, s2s.pe, x.p, B, W, C, s);
+    }
+    for (const S2sEncLayerW& l : s2s.enc) {
+        Act qkv = R.linear(l.qkv, x.p, C, MW, R.f32_rows());
+        Act a(pool, MW, C);
+        attend(qkv.p, (long long)W * 3 * C, 3 * C, qkv.p + C, qkv.p + 2 * C, (long long)W * 3 * C, 3 * C, a.p, (long long)W * C, C, W, W, 0, false);
+        Act y = R.linear(l.out, a.p, C, MW, plus(x.p, C));
+        ln(l.ln1, y.p, C, x.p, C, (int)MW);
+        Act f = R.linear(l.fc1, x.p, C, MW, relu);
+        y = R.linear(l.fc2, f.p, scfg.s2s_ffn, MW, plus(x.p, C));
+        ln(l.ln2, y.p, C, x.p, C, (int)MW);
+    }
+    if (txt_logits) {
+        Act mean(pool, B, C);
+        token_mean(x.p, mean.p, B, W, C, s);
+        Act lg = R.linear(s2s.txt, mean.p, C, B, R.f32_rows());
+        copy_rows(lg.p, lg.C, txt_logits, L, B, L, s);
+    }
+    if (decode) {
+        const int rows = passes + 1;                             // token rows this call holds
+        Act tok(pool, (int64_t)B * rows, C);
+        E2V_HIP(hipMemsetAsync(tok.p, 0, tok.bytes(), s));       // row 0 of every clip: torch.zeros; the others are written below
+        const long long st = (long long)rows * C;                // clip stride of the token rows
+        std::vector<Act> memkv, cache;                           // per layer: k | v of the memory [B W][2C], of the token rows [B rows][2C]
+        for (const S2sDecLayerW& l : s2s.dec) {
+            if (passes > 0) {
+                memkv.push_back(R.linear(l.kv2, x.p, C, MW, R.f32_rows()));
+                cache.emplace_back(pool, (int64_t)B * passes, 2 * C);
+            }
+        }
+        for (int i = 0; i < passes; ++i) {
+            const float* h = tok.p + (size_t)i * C;              // row i of every clip
+            int ldh = (int)st;
+            Act cur;
+            for (size_t li = 0; li < s2s.dec.size(); ++li) {
+                const S2sDecLayerW& l = s2s.dec[li];
+                const long long sc = (long long)passes * 2 * C;
+                Act qkv = R.linear(l.qkv, h, ldh, B, R.f32_rows());
+                copy_rows(qkv.p + C, 3 * C, cache[li].p + (size_t)i * 2 * C, (int)sc, B, 2 * C, s);
+                Act a(pool, B, C);
+                attend(qkv.p, 3 * C, 3 * C, cache[li].p, cache[li].p + C, sc, 2 * C, a.p, C, C, 1, i + 1, i, true);
+                Act y = R.linear(l.out, a.p, C, B, plus(h, ldh));
+                Act h1(pool, B, C);
+                ln(l.ln1, y.p, C, h1.p, C, B);
+                Act q2 = R.linear(l.q2, h1.p, C, B, R.f32_rows());
+                attend(q2.p, C, C, memkv[li].p, memkv[li].p + C, (long long)W * 2 * C, 2 * C, a.p, C, C, 1, W, 0, false);
+                y = R.linear(l.out2, a.p, C, B, plus(h1.p, C));
+                Act h2(pool, B, C);
+                ln(l.ln2, y.p, C, h2.p, C, B);
+                Act f = R.linear(l.fc1, h2.p, C, B, relu);
+                y = R.linear(l.fc2, f.p, scfg.s2s_ffn, B, plus(h2.p, C));
+                if (li + 1 == s2s.dec.size()) {                  // the last layer's row IS the appended token
+                    ln(l.ln3, y.p, C, tok.p + (size_t)(i + 1) * C, (int)st, B);
+                } else {
+                    cur = Act(pool, B, C);
+                    ln(l.ln3, y.p, C, cur.p, C, B);
+                    h = cur.p; ldh = C;
+                }
+            }
+        }
+        if (tokens) copy_rows(tok.p, (int)st, tokens, T1 * C, B, rows * C, s);
+        if (latents) {
+            Act sel(pool, (int64_t)B * count, C);
+            copy_rows(tok.p + (size_t)first * C, (int)st, sel.p, count * C, B, count * C, s);
+            Act lat = R.linear(s2s.pred, sel.p, C, (int64_t)B * count, R.f32_rows());
+            if (layout == 0) E2V_HIP(hipMemcpyAsync(latents, lat.p, lat.bytes(), hipMemcpyDeviceToDevice, s));
+            else seq_latents_bcfhw(lat.p, latents, B, count, scfg.s2s_latent_channels, scfg.s2s_latent_h * scfg.s2s_latent_w, s);
+        }
     }
     E2V_HIP(hipGetLastError());
 }

@@ -136,6 +136,22 @@ struct ClipVW {
     LinW proj;                                                       // [projection_dim][C], no bias
 };
 
+// The Seq2Seq latent model (the reference's myTransformer, my_autoregressive_transformer.py:123-192; keys "s2s." + its state-dict
+// names): fp32 matrices only, every loaded tensor kept as it is.  nn.MultiheadAttention packs q | k | v as in_proj_weight [3C][C]: the
+// self-attention uses it whole, the cross-attention as its rows 0 .. C - 1 (q, from the token) and C .. 3C - 1 (k | v, from the memory)
+// -- two views of the one loaded block.
+struct S2sEncLayerW { NormW ln1, ln2; LinW qkv, out, fc1, fc2; };
+struct S2sDecLayerW { NormW ln1, ln2, ln3; LinW qkv, out, q2, kv2, out2, fc1, fc2; };
+struct S2sW {
+    const float* eegnet = nullptr;                                   // eegnet_pack (kernels.h): the convs with the three BatchNorms folded
+    const float* pe = nullptr;                                       // [windows][C]
+    LinW embed;                                                      // [C][F2 ((T / 4) / 8)]
+    std::vector<S2sEncLayerW> enc;
+    std::vector<S2sDecLayerW> dec;
+    LinW txt;                                                        // [classes rounded up to 4][C]
+    LinW pred;                                                       // [latent C h w][C]
+};
+
 // Where one raw state-dict tensor lives in the packed world of a finalized part (recorded by finalize(), used by e2v_update_tensor):
 //   RAW   the fp32 block the kernels read -- norm affines, plain biases (the uploaded block itself), a slice of a fused bias, the
 //         GEGLU bias (32-element groups interleaved);
@@ -204,8 +220,9 @@ struct e2v_ctx {
     e2v::ImageW image;
     e2v::VideoW video;
     e2v::ClipVW clipv;
+    e2v::S2sW s2s;
     bool unet_ready = false, vae_ready = false, sem_ready = false, text_ready = false, image_ready = false, video_ready = false;
-    bool clipv_ready = false;
+    bool clipv_ready = false, s2s_ready = false;
     float image_lut[3 * 256] = {};                               // the processor's pixel value of a byte, per channel (e2v_create)
     std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W)
     const e2v::ImagePrepPlan& prep_plan(int H, int W);
@@ -216,6 +233,9 @@ struct e2v_ctx {
     float clipv_lut[3 * 256] = {};                               // and for the CLIP vision tower's processor (bicubic tables)
     std::map<std::array<int, 2>, e2v::VideoPrepPlan> clipv_prep_plans;
     const e2v::VideoPrepPlan& clipv_prep_plan(int H, int W);
+    e2v_s2s_config scfg = {};                                    // the Seq2Seq model's config (e2v_create_ex); all zero: none
+    int s2s_features() const { return scfg.s2s_f2 * ((scfg.s2s_samples / 4) / 8); }     // the EEGNet embedding's flattened width
+    int s2s_latent() const { return scfg.s2s_latent_channels * scfg.s2s_latent_h * scfg.s2s_latent_w; }
     int conv_algo = 0;                                           // e2v_set_conv_algo: 0 auto, 1 direct, 2 / 3 Winograd F(2x2) / F(4x4) wherever it applies
     bool wino_f4 = true;                                         // auto: F(4x4,3x3) where min(Cin, Cout) >= wino4_min_c and the map, padded to
     int wino4_min_c = 128;                                       //   multiples of 4, grows by <= wino_f4_pad (E2V_WINO_F4 / _F4_MIN_C / _F4_PAD)
@@ -249,7 +269,7 @@ struct e2v_ctx {
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
     void enter_stream(hipStream_t s);
     // device blocks made by dev_alloc, per part (bit index of `which`), so that finalizing a part again frees what it replaces
-    std::vector<e2v::DevBlock> owned_part[7];
+    std::vector<e2v::DevBlock> owned_part[8];
     size_t weight_bytes() const;                                 // what the uploaded tensors and the parts' blocks hold (e2v_device_bytes)
     void* comm = nullptr; int comm_rank = 0, comm_world = 0;     // RCCL communicator of e2v_comm_init (comm.cpp)
     // e2v_op_unet_forward_taps (test aid): while set, unet_forward_cl copies the tensors the oracle exposes (emb, down0..3, mid,
@@ -307,11 +327,14 @@ struct e2v_ctx {
     // CLIPImageProcessor + CLIPVisionModelWithProjection over the n * F frames of `src`, walked in chunks of images;
     // embeds [n*F][clipv_projection_dim]: image_embeds, not normalised
     void clip_embed(const e2v::FrameSrc& src, int n, int F, int H, int W, float* embeds, hipStream_t s);
+    // myTransformer.forward in eval mode (see e2v_seq2seq_latents): tokens [first, first + count) of the steps + 1; any output may be null
+    void seq2seq_latents(const e2v::EegnetArgs& eeg, int B, int first, int count, int layout, float* latents, float* txt_logits, float* tokens,
+                         hipStream_t s);
     int clipv_tokens() const { const int g = vcfg.clipv_patch_size > 0 ? vcfg.clipv_image_size / vcfg.clipv_patch_size : 0; return g * g + 1; }
     // which finalize() part owns a state-dict key: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video
-    // classifier, 64 CLIP vision tower
+    // classifier, 64 CLIP vision tower, 128 Seq2Seq latent model
     static int key_part(const std::string& k) {
         return k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : k.rfind("text.", 0) == 0 ? 8 : k.rfind("image.", 0) == 0 ? 16 :
-               k.rfind("video.", 0) == 0 ? 32 : k.rfind("clipv.", 0) == 0 ? 64 : 1;
+               k.rfind("video.", 0) == 0 ? 32 : k.rfind("clipv.", 0) == 0 ? 64 : k.rfind("s2s.", 0) == 0 ? 128 : 1;
     }
 };

@@ -12,7 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import TEXT_ACTS, ClipVisionConfig, ImageConfig, SemanticConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig
+from .weights import (TEXT_ACTS, ClipVisionConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig, VAEConfig,
+                      VideoConfig)
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -31,20 +32,22 @@ class Engine:
     """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
     the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one, ``video_cfg``
     (``None``: no video classifier) the ``VideoMAEForVideoClassification`` one, ``clip_vision_cfg`` (``None``: no CLIP vision tower)
-    the ``CLIPVisionModelWithProjection`` one."""
+    the ``CLIPVisionModelWithProjection`` one, ``seq2seq_cfg`` (``None``: no Seq2Seq latent model) the reference's ``myTransformer``."""
 
     UNET, VAE, SEMANTIC, TEXT, IMAGE, VIDEO, CLIP_VISION = 1, 2, 4, 8, 16, 32, 64
+    SEQ2SEQ = 128
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
                  sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None,
                  image_cfg: Optional[ImageConfig] = None, video_cfg: Optional[VideoConfig] = None,
-                 clip_vision_cfg: Optional[ClipVisionConfig] = None):
+                 clip_vision_cfg: Optional[ClipVisionConfig] = None, seq2seq_cfg: Optional[Seq2SeqConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
         self.lib = _lib.load()
         self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
         self.image_cfg, self.video_cfg, self.clip_vision_cfg = image_cfg, video_cfg, clip_vision_cfg
+        self.seq2seq_cfg = seq2seq_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -78,7 +81,12 @@ class Engine:
             fill_video_config(cfg, video_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
-        if clip_vision_cfg is not None:                       # the tower's config is a struct of its own beside the e2v_config
+        if seq2seq_cfg is not None:                           # either optional part: structs of their own beside the e2v_config
+            self._clipv_cfg = clip_vision_config(clip_vision_cfg) if clip_vision_cfg is not None else None
+            self._s2s_cfg = seq2seq_config(seq2seq_cfg)
+            st = self.lib.e2v_create_ex(C.byref(cfg), C.byref(self._clipv_cfg) if self._clipv_cfg is not None else None,
+                                        C.byref(self._s2s_cfg), device, C.byref(ctx))
+        elif clip_vision_cfg is not None:                     # the tower's config is a struct of its own beside the e2v_config
             self._clipv_cfg = clip_vision_config(clip_vision_cfg)
             st = self.lib.e2v_create_clip_vision(C.byref(cfg), C.byref(self._clipv_cfg), device, C.byref(ctx))
         else:
@@ -213,7 +221,7 @@ class Engine:
                                              self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
         return out
 
-    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video.", 64: "clipv."}
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video.", 64: "clipv.", 128: "s2s."}
 
     def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
         """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE`` / ``VIDEO`` / ``CLIP_VISION``) as the device holds it NOW -- after any
@@ -227,7 +235,7 @@ class Engine:
         elif dev.type != "cpu":
             raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
         own = self._PART_PREFIX.get(part, "")
-        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO, self.CLIP_VISION) or prefix not in ("", own):
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO, self.CLIP_VISION, self.SEQ2SEQ) or prefix not in ("", own):
             raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
         foreign = tuple(self._PART_PREFIX.values())
         out = OrderedDict()
@@ -566,6 +574,65 @@ class Engine:
         self._check(self.lib.e2v_text_encode(self.ctx, ids.ctypes.data_as(_lib.c_int64_p), b, t, out.data_ptr(), _stream()))
         return out
 
+    def seq2seq_latents(self, eeg: torch.Tensor, *, strides: Optional[Tuple[int, int, int]] = None, batch: Optional[int] = None,
+                        scaler: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, first: int = 0, count: Optional[int] = None,
+                        layout: str = "bfchw", latents: bool = True, txt_logits: bool = False, tokens: bool = False,
+                        out: Optional[Dict[str, torch.Tensor]] = None):
+        """``myTransformer.forward`` in eval mode with the slice its inference keeps (``e2v_seq2seq_latents``).  ``eeg``: a contiguous fp32
+        tensor on the engine's device, by default stacked windows ``[B, windows, electrodes, samples]``; with ``strides`` = (clip, window,
+        channel) element strides and ``batch`` any buffer the strides describe -- a raw segment ``[B, electrodes, L]`` under sliding
+        windows of step ``s`` is ``(electrodes * L, s, L)``.  ``scaler``: ``(mean, scale)`` ``[windows, electrodes, samples]`` applied as
+        ``(x - mean) / scale``.  Tokens ``[first, first + count)`` of the ``steps + 1`` (``count=None``: ``steps - first``, i.e. the
+        reference's ``[:, :-1]`` from ``first = 0``); ``layout`` ``'bfchw'`` ``[B,count,C,h,w]`` or ``'bcfhw'`` ``[B,C,count,h,w]``.
+        Returns a dict with the outputs asked for: ``latents``, ``txt_logits`` ``[B,classes]``, ``tokens`` ``[B,steps+1,d_model]``
+        (rows past ``first + count - 1`` are zeros).  ``out``: contiguous fp32 tensors of those shapes to write instead, by name (a
+        ``tokens`` tensor given this way keeps its rows past ``first + count - 1``).  fp32 arithmetic whatever the compute dtype."""
+        sc = self.seq2seq_cfg
+        if sc is None:
+            raise RuntimeError("this engine was built without a Seq2Seq latent model (Engine(..., seq2seq_cfg=Seq2SeqConfig()))")
+        if layout not in ("bfchw", "bcfhw"):
+            raise ValueError(f"layout {layout!r}: 'bfchw' or 'bcfhw'")
+        if not isinstance(eeg, torch.Tensor) or eeg.device != self.device or eeg.dtype != torch.float32 or not eeg.is_contiguous():
+            raise ValueError(f"`eeg` has to be a contiguous float32 tensor on {self.device}")
+        if strides is None:
+            if tuple(eeg.shape[1:]) != (sc.windows, sc.electrodes, sc.samples):
+                raise ValueError(f"expected eeg [B,{sc.windows},{sc.electrodes},{sc.samples}], got {tuple(eeg.shape)}")
+            b = eeg.shape[0]
+            strides = (sc.windows * sc.electrodes * sc.samples, sc.electrodes * sc.samples, sc.samples)
+        else:
+            if batch is None:
+                raise ValueError("`strides` needs `batch`")
+            b = int(batch)
+            cs, ws, es = (int(v) for v in strides)
+            if min(cs, ws, es) < 0 or b < 1:
+                raise ValueError("strides are non-negative element counts, batch at least 1")
+            if (b - 1) * cs + (sc.windows - 1) * ws + (sc.electrodes - 1) * es + sc.samples > eeg.numel():
+                raise ValueError("the strides reach past the end of `eeg`")
+            strides = (cs, ws, es)
+        mean_p = scale_p = None
+        if scaler is not None:
+            mean, scale = (self._dev(t, "scaler") for t in scaler)
+            if tuple(mean.shape) != (sc.windows, sc.electrodes, sc.samples) or mean.shape != scale.shape:
+                raise ValueError(f"the scaler is (mean, scale), each [{sc.windows},{sc.electrodes},{sc.samples}]")
+            mean_p, scale_p = mean.data_ptr(), scale.data_ptr()
+        if count is None:
+            count = sc.steps - first
+        given, out = out or {}, {}
+        if latents:
+            shape = (b, count) + tuple(sc.latent) if layout == "bfchw" else (b, sc.latent[0], count) + tuple(sc.latent[1:])
+            shape = tuple(max(int(v), 0) for v in shape)
+            out["latents"] = self._op_out(given["latents"], shape) if "latents" in given else torch.empty(shape, device=self.device, dtype=torch.float32)
+        if txt_logits:
+            out["txt_logits"] = self._op_out(given.get("txt_logits"), (b, sc.txt_classes))
+        if tokens:
+            shape = (b, sc.steps + 1, sc.d_model)
+            out["tokens"] = self._op_out(given["tokens"], shape) if "tokens" in given else torch.zeros(shape, device=self.device, dtype=torch.float32)
+        ptr = lambda k: out[k].data_ptr() if k in out else None
+        self._check(self.lib.e2v_seq2seq_latents(self.ctx, eeg.data_ptr(), strides[0], strides[1], strides[2], mean_p, scale_p, b, int(first),
+                                                 int(count), 0 if layout == "bfchw" else 1, ptr("latents"), ptr("txt_logits"), ptr("tokens"),
+                                                 _stream()))
+        return out
+
     def dana_noise(self, x0: torch.Tensor, eps_div: torch.Tensor, eps_same: torch.Tensor, t: Sequence[int],
                    dynamic_beta: float, time_steps: int = 500) -> torch.Tensor:
         """``[B,F,C,H,W]`` Seq2Seq latents + the two noise draws -> noised latents in the pipeline layout ``[B,C,F,H,W]``."""
@@ -850,6 +917,53 @@ class Engine:
                                                      heads, _stream()))
         return out
 
+    def op_eegnet_embed(self, eeg, weights, *, B, W, C, T, F1, D, F2, strides=None, scaler=None, bn_eps=1e-5, out=None):
+        """``e2v_op_eegnet_embed``: the EEGNet embedding kernel on its own.  ``eeg``: a contiguous fp32 device tensor read through
+        ``strides`` = (clip, window, channel) element strides (``None``: stacked windows ``[B,W,C,T]``); ``weights``: the torch-layout
+        tensors ``dict(w1 [F1,1,1,64], bn1, w2 [F1 D,1,C,1], bn2, w3 [F1 D,1,1,16], w4 [F2,F1 D,1,1], bn3)``, each ``bn*`` a
+        ``[4, n]`` stack of weight, bias, running_mean, running_var; ``scaler``: ``(mean, scale)`` ``[W,C,T]``.
+        Returns ``[B * W, F2 * ((T // 4) // 8)]``."""
+        if not isinstance(eeg, torch.Tensor) or eeg.device != self.device or eeg.dtype != torch.float32 or not eeg.is_contiguous():
+            raise ValueError(f"`eeg` has to be a contiguous float32 tensor on {self.device}")
+        if strides is None:
+            strides = (W * C * T, C * T, T)
+        cs, ws, es = (int(v) for v in strides)
+        if min(cs, ws, es) < 0 or (B - 1) * cs + (W - 1) * ws + (C - 1) * es + T > eeg.numel():
+            raise ValueError("the strides are negative or reach past the end of `eeg`")
+        fd = F1 * D
+        want = {"w1": F1 * 64, "bn1": 4 * F1, "w2": fd * C, "bn2": 4 * fd, "w3": fd * 16, "w4": F2 * fd, "bn3": 4 * F2}
+        w = {}
+        for k, n in want.items():
+            w[k] = self._dev(weights[k], k)
+            if w[k].numel() != n:
+                raise ValueError(f"weights[{k!r}] has {w[k].numel()} elements, expected {n}")
+        mean_p = scale_p = None
+        if scaler is not None:
+            mean, scale = (self._dev(t, "scaler") for t in scaler)
+            if mean.numel() != W * C * T or scale.numel() != W * C * T:
+                raise ValueError("the scaler is (mean, scale), each [W,C,T]")
+            mean_p, scale_p = mean.data_ptr(), scale.data_ptr()
+        out = self._op_out(out, (B * W, F2 * ((T // 4) // 8)))
+        self._check(self.lib.e2v_op_eegnet_embed(self.ctx, eeg.data_ptr(), cs, ws, es, mean_p, scale_p, B, W, C, T, F1, D, F2,
+                                                 w["w1"].data_ptr(), w["bn1"].data_ptr(), w["w2"].data_ptr(), w["bn2"].data_ptr(),
+                                                 w["w3"].data_ptr(), w["w4"].data_ptr(), w["bn3"].data_ptr(), float(bn_eps), out.data_ptr(),
+                                                 _stream()))
+        return out
+
+    def op_seq_attention(self, q, k, v, *, B, heads, D, Nq, Nk, q_pos0=0, causal=False, out=None):
+        """``e2v_op_seq_attention``: ``q`` a 2-D view ``[B*Nq, heads*D]``, ``k``, ``v`` 2-D views ``[B*Nk, heads*D]`` of one row stride
+        (``.stride(0)``; unit column stride) -> ``[B*Nq, heads*D]``; ``causal``: query i sits at position ``q_pos0 + i``.
+        ``out``: a 2-D view with its own row stride."""
+        out = self._op_out(out, (B * Nq, heads * D), strided=True)
+        for name, t, rows in (("q", q, B * Nq), ("k", k, B * Nk), ("v", v, B * Nk)):
+            if tuple(t.shape) != (rows, heads * D) or t.stride(1) != 1 or t.dtype != torch.float32 or t.device != self.device:
+                raise ValueError(f"`{name}` has to be a float32 view [{rows}, {heads * D}] with unit column stride on {self.device}")
+        if k.stride(0) != v.stride(0):
+            raise ValueError("`k` and `v` share one row stride")
+        self._check(self.lib.e2v_op_seq_attention(self.ctx, q.data_ptr(), q.stride(0), k.data_ptr(), v.data_ptr(), k.stride(0), out.data_ptr(),
+                                                  out.stride(0), B, heads, D, Nq, Nk, int(q_pos0), int(bool(causal)), _stream()))
+        return out
+
     def op_image_preprocess(self, frames, *, size, patch, lut=None, channels_last=False, out=None):
         """``e2v_op_image_preprocess``: clips -> the patch rows ``[n*F*(size/patch)^2, 3*patch^2]`` of the classifier's preprocess.
         ``lut``: ``[3,256]`` fp32 pixel values of a byte per channel (``None``: the engine's image config)."""
@@ -1050,6 +1164,18 @@ def clip_vision_config(cv: ClipVisionConfig) -> "_lib.E2VClipVConfig":
     cfg.clipv_resize_edge, cfg.clipv_resample, cfg.clipv_rescale = cv.resize_edge, cv.resample, float(cv.rescale_factor)
     cfg.clipv_mean = (C.c_float * 3)(*[float(v) for v in cv.image_mean])
     cfg.clipv_std = (C.c_float * 3)(*[float(v) for v in cv.image_std])
+    return cfg
+
+
+def seq2seq_config(sc: Seq2SeqConfig) -> "_lib.E2VS2sConfig":
+    """The ``e2v_s2s_config`` of a ``Seq2SeqConfig`` (``e2v_create_ex``)."""
+    cfg = _lib.E2VS2sConfig()
+    cfg.s2s_electrodes, cfg.s2s_samples, cfg.s2s_windows = sc.electrodes, sc.samples, sc.windows
+    cfg.s2s_f1, cfg.s2s_d, cfg.s2s_f2 = sc.F1, sc.D, sc.F2
+    cfg.s2s_d_model, cfg.s2s_heads, cfg.s2s_ffn = sc.d_model, sc.heads, sc.ffn
+    cfg.s2s_encoder_layers, cfg.s2s_decoder_layers, cfg.s2s_steps = sc.encoder_layers, sc.decoder_layers, sc.steps
+    cfg.s2s_latent_channels, cfg.s2s_latent_h, cfg.s2s_latent_w = sc.latent
+    cfg.s2s_txt_classes, cfg.s2s_norm_eps, cfg.s2s_bn_eps = sc.txt_classes, sc.norm_eps, sc.bn_eps
     return cfg
 
 

@@ -277,6 +277,126 @@ def clip_vision_param_spec(cfg: ClipVisionConfig) -> "OrderedDict[str, Tuple[int
     return spec
 
 
+@dataclass(frozen=True)
+class Seq2SeqConfig:
+    """The reference's ``myTransformer`` (``EEG2Video_New/Seq2Seq/my_autoregressive_transformer.py:123-149``): an EEGNet embedding
+    (``electrodes`` x ``samples`` per window, ``F1`` / ``D`` / ``F2``) of each of ``windows`` EEG windows, a post-LN transformer
+    encoder and an autoregressive post-LN decoder (``d_model``, ``heads``, ``ffn``, ``encoder_layers`` / ``decoder_layers``; ``steps``
+    decoder passes give ``steps + 1`` tokens), a latent predictor (``latent`` = (C, h, w)) and a text-class predictor.  Defaults are
+    the values the reference hard-codes."""
+    electrodes: int = 62
+    samples: int = 100
+    windows: int = 7
+    F1: int = 16
+    D: int = 4
+    F2: int = 16
+    d_model: int = 512
+    heads: int = 4
+    ffn: int = 2048
+    encoder_layers: int = 2
+    decoder_layers: int = 4
+    steps: int = 6
+    latent: Tuple[int, int, int] = (4, 36, 64)
+    txt_classes: int = 13
+    norm_eps: float = 1e-5
+    bn_eps: float = 1e-5
+    num_embeddings: int = 10            # the unused nn.Embedding
+    pe_max_len: int = 5000              # rows of the positional buffer in a checkpoint
+
+    @property
+    def features(self) -> int:
+        """Width of the flattened EEGNet output (the reference's 48)."""
+        return self.F2 * ((self.samples // 4) // 8)
+
+    @property
+    def latent_size(self) -> int:
+        return self.latent[0] * self.latent[1] * self.latent[2]
+
+
+#: three windows of 5 x 40 and three decoder passes for a few tens of thousands of parameters
+TINY_SEQ2SEQ = Seq2SeqConfig(electrodes=5, samples=40, windows=3, d_model=64, heads=4, ffn=128, encoder_layers=1, decoder_layers=2,
+                             steps=3, latent=(4, 4, 6))
+
+#: the position table as the engine holds it (``[windows][d_model]``; a checkpoint has ``[1][pe_max_len][d_model]`` under the same name)
+SEQ2SEQ_PE_KEY = "positional_encoding.pe"
+
+
+def seq2seq_unused_key(name: str) -> bool:
+    """State-dict entries of ``myTransformer`` its inference never reads: the engine does not hold them."""
+    return name == "embedding.weight" or name.startswith("img_embedding.") or name.endswith(".num_batches_tracked")
+
+
+def seq2seq_param_spec(cfg: Seq2SeqConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of ``myTransformer().state_dict()`` in its order (125 entries at the default config), buffers included:
+    the BatchNorm statistics, ``num_batches_tracked`` (shape ``()``) and ``positional_encoding.pe`` ``[1, pe_max_len, d_model]``."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    c, fd = cfg.d_model, cfg.F1 * cfg.D
+
+    def bn(name, n):
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            spec[f"{name}.{leaf}"] = (n,)
+        spec[f"{name}.num_batches_tracked"] = ()
+
+    def mha(name):
+        spec[f"{name}.in_proj_weight"] = (3 * c, c)
+        spec[f"{name}.in_proj_bias"] = (3 * c,)
+        _lin(spec, f"{name}.out_proj", c, c)
+
+    spec["embedding.weight"] = (cfg.num_embeddings, c)
+    _lin(spec, "img_embedding", c, cfg.latent_size)
+    e = "eeg_embedding"
+    spec[f"{e}.block_1.1.weight"] = (cfg.F1, 1, 1, 64)
+    bn(f"{e}.block_1.2", cfg.F1)
+    spec[f"{e}.block_2.0.weight"] = (fd, 1, cfg.electrodes, 1)
+    bn(f"{e}.block_2.1", fd)
+    spec[f"{e}.block_3.1.weight"] = (fd, 1, 1, 16)
+    spec[f"{e}.block_3.2.weight"] = (cfg.F2, fd, 1, 1)
+    bn(f"{e}.block_3.3", cfg.F2)
+    _lin(spec, f"{e}.embedding", c, cfg.features)
+    for i in range(cfg.encoder_layers):
+        p = f"transformer_encoder.layers.{i}"
+        mha(f"{p}.self_attn")
+        _lin(spec, f"{p}.linear1", cfg.ffn, c)
+        _lin(spec, f"{p}.linear2", c, cfg.ffn)
+        _norm(spec, f"{p}.norm1", c)
+        _norm(spec, f"{p}.norm2", c)
+    for i in range(cfg.decoder_layers):
+        p = f"transformer_decoder.layers.{i}"
+        mha(f"{p}.self_attn")
+        mha(f"{p}.multihead_attn")
+        _lin(spec, f"{p}.linear1", cfg.ffn, c)
+        _lin(spec, f"{p}.linear2", c, cfg.ffn)
+        _norm(spec, f"{p}.norm1", c)
+        _norm(spec, f"{p}.norm2", c)
+        _norm(spec, f"{p}.norm3", c)
+    spec[SEQ2SEQ_PE_KEY] = (1, cfg.pe_max_len, c)
+    _lin(spec, "txtpredictor", cfg.txt_classes, c)
+    _lin(spec, "predictor", cfg.latent_size, c)
+    return spec
+
+
+def seq2seq_engine_spec(cfg: Seq2SeqConfig) -> "OrderedDict[str, Tuple[int, ...]]":
+    """What the engine expects under ``s2s.``: ``seq2seq_param_spec`` without the unused entries, the position table as the
+    ``[windows, d_model]`` rows that are read."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    for k, shape in seq2seq_param_spec(cfg).items():
+        if not seq2seq_unused_key(k):
+            spec[k] = (cfg.windows, cfg.d_model) if k == SEQ2SEQ_PE_KEY else shape
+    return spec
+
+
+def seq2seq_position_table(rows: int, d_model: int):
+    """The first ``rows`` rows of ``PositionalEncoding.pe`` (``my_autoregressive_transformer.py:97-107``) with the reference's own
+    fp32 torch expression, ``[rows, d_model]``."""
+    import torch
+    pe = torch.zeros(rows, d_model)
+    position = torch.arange(0, rows).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2) * -(math.log(10000.0) / d_model))
+    pe[:, 0::2] = torch.sin(position * div_term)
+    pe[:, 1::2] = torch.cos(position * div_term)
+    return pe
+
+
 #: how ``transformers`` 5 spells the per-layer tensors of the same model (``vit.layers.{i}.`` instead of ``vit.encoder.layer.{i}.``)
 _VIT_V5_NAMES = (("attention.q_proj.", "attention.attention.query."), ("attention.k_proj.", "attention.attention.key."),
                  ("attention.v_proj.", "attention.attention.value."), ("attention.o_proj.", "attention.output.dense."),
@@ -575,6 +695,8 @@ def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 42, mode: str = 
     neutral parameter in a parity test.
     """
     n = int(np.prod(shape))
+    if name.endswith("running_var"):       # a variance: positive, 0.5 .. 1.5
+        return (0.5 + counter_uniform(seed, name, n)).astype(np.float32).reshape(shape)
     if _is_norm(name):
         if mode == "reference_init":
             v = np.ones(n, np.float32) if name.endswith(".weight") else np.zeros(n, np.float32)
@@ -587,7 +709,7 @@ def synth_tensor(name: str, shape: Tuple[int, ...], seed: int = 42, mode: str = 
     if name.endswith(".weight"):
         fan_in = int(np.prod(shape[1:]))
     elif fan_in <= 0:                      # bias without a known sibling weight
-        fan_in = shape[0]
+        fan_in = shape[0] if shape else 1
     bound = 1.0 / math.sqrt(max(fan_in, 1))
     u = counter_uniform(seed, name, n) * 2.0 - 1.0
     return (u * bound).astype(np.float32).reshape(shape)

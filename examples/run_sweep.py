@@ -56,6 +56,9 @@ def main(argv=None, engine=None):
     ap.add_argument("--batch", type=int, default=8, help="clips per e2v_generate call")
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--dtype", default="fp32", choices=["fp32", "bf16", "fp16"])
+    ap.add_argument("--seq2seq", default="host", choices=["host", "native"],
+                    help="the Seq2Seq stage: host (default) -- the plain-torch look-alike of host_models --, or native -- the reference's "
+                         "myTransformer on the device (e2v_seq2seq_latents; synthetic weights, fp32 whatever --dtype)")
     ap.add_argument("--out", default="", help="directory for <concept>_<k>.gif (empty: frames are produced but not written)")
     ap.add_argument("--npy", action="store_true", help="write .npy instead of .gif")
     ap.add_argument("--score-against", default="", metavar="DIR",
@@ -82,8 +85,8 @@ def main(argv=None, engine=None):
     from eeg2video_amd.host_models import GLMNet, Seq2SeqLatents
     from eeg2video_amd.semantic import CLIP
     from eeg2video_amd.util import save_videos_grid
-    from eeg2video_amd.weights import (TINY_UNET, TINY_VAE, SemanticConfig, UNetConfig, VAEConfig, counter_normal, synth_state_dict,
-                                       unet_param_spec, vae_param_spec)
+    from eeg2video_amd.weights import (TINY_UNET, TINY_VAE, SemanticConfig, Seq2SeqConfig, UNetConfig, VAEConfig, counter_normal,
+                                       synth_state_dict, unet_param_spec, vae_param_spec)
 
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if world > 1:
@@ -93,11 +96,16 @@ def main(argv=None, engine=None):
     ucfg, vcfg, scfg = ((TINY_UNET, TINY_VAE, SemanticConfig(in_features=22, hidden=96, tokens=77)) if args.tiny
                         else (UNetConfig(), VAEConfig(), SemanticConfig()))
     F, h, w = (3, 4, 6) if args.tiny else (6, 36, 64)
+    # --seq2seq native: the reference's model over the sweep's [7, 62, 100] windows, its latent and steps those of the sweep
+    s2s_cfg = None
+    if args.seq2seq == "native":
+        s2s_cfg = (Seq2SeqConfig(d_model=64, heads=4, ffn=128, encoder_layers=1, decoder_layers=2, steps=F, latent=(4, h, w)) if args.tiny
+                   else Seq2SeqConfig(steps=F, latent=(4, h, w)))
     t_setup = time.perf_counter()
     if engine is not None:
         eng = engine
     else:
-        eng = Engine(ucfg, vcfg, local, sem_cfg=scfg)
+        eng = Engine(ucfg, vcfg, local, sem_cfg=scfg, seq2seq_cfg=s2s_cfg)
         eng.load_state_dict(synth_state_dict(unet_param_spec(ucfg), seed=42, mode="reference_init"))
         eng.load_state_dict(synth_state_dict(vae_param_spec(vcfg), seed=43, mode="reference_init"), prefix="vae.")
         eng.finalize(Engine.UNET | Engine.VAE)
@@ -109,7 +117,12 @@ def main(argv=None, engine=None):
     dev = eng.device
     torch.manual_seed(0)
     glm = GLMNet(out_dim=2, emb_dim=64, C=62, T=200).to(dev).eval()
-    s2s = Seq2SeqLatents(d_model=512 if not args.tiny else 64, latent_shape=(4, h, w), frames=F).to(dev).eval()
+    if s2s_cfg is None:
+        s2s = Seq2SeqLatents(d_model=512 if not args.tiny else 64, latent_shape=(4, h, w), frames=F).to(dev).eval()
+    else:                                                           # on the sweep's engine where it was built for the model, else on one of its own
+        from eeg2video_amd.seq2seq import myTransformer
+        native = myTransformer(s2s_cfg, engine=eng if eng.seq2seq_cfg == s2s_cfg else None, device=local).init_synthetic(47)
+        s2s = lambda x: native.predict_latents(x, layout="bfchw")   # [B, F, 4, h, w], as the host stage returns it
     t_setup = time.perf_counter() - t_setup
 
     total = args.concepts * args.per_concept

@@ -153,6 +153,31 @@ int64_t e2v_clipv_config_size(void);
 /* e2v_create with a CLIP vision tower: the context also expects the "clipv." keys (part 64 of e2v_finalize_weights) and serves
  * e2v_clip_embed.  clipv NULL or all zero: exactly e2v_create (no tower).  A bad tower config: E2V_EINVAL. */
 e2v_status e2v_create_clip_vision(const e2v_config* cfg, const e2v_clipv_config* clipv, int device, e2v_ctx** out);
+/* Seq2Seq latent model (the reference's myTransformer, EEG2Video_New/Seq2Seq/my_autoregressive_transformer.py:123-192: an EEGNet
+ * embedding of each EEG window, a post-LN nn.TransformerEncoder over the windows, a post-LN nn.TransformerDecoder run autoregressively
+ * from a zero token, a linear to the latent of every token and a linear on the mean encoder row).  A struct of its own, handed to
+ * e2v_create_ex; the reference's values: electrodes 62, samples 100, windows 7, F1 / D / F2 16 / 4 / 16, d_model 512, heads 4, ffn 2048,
+ * encoder / decoder layers 2 / 4, steps 6, latent 4 x 36 x 64, 13 text classes, both eps 1e-5 (e2v_default_s2s_config).  d_model is a
+ * multiple of heads and at most 1280 (the LayerNorm kernel), the head dim a multiple of 4 and at most 128 (the attention kernel),
+ * windows and steps + 1 at most 32 (one key per lane of half a wave), samples at least 32, and d_model, ffn, the EEGNet feature count
+ * F2 * ((samples / 4) / 8) and latent_channels * latent_h * latent_w multiples of 4; one window with its intermediates has to fit the
+ * embedding kernel's 156 KiB of LDS. */
+typedef struct {
+    int s2s_electrodes, s2s_samples, s2s_windows;      /* C, T of one window, windows per clip */
+    int s2s_f1, s2s_d, s2s_f2;                         /* MyEEGNet_embedding's F1, D, F2 */
+    int s2s_d_model, s2s_heads, s2s_ffn, s2s_encoder_layers, s2s_decoder_layers;
+    int s2s_steps;                                     /* decoder passes of the reference's forward: steps + 1 tokens */
+    int s2s_latent_channels, s2s_latent_h, s2s_latent_w;
+    int s2s_txt_classes;
+    float s2s_norm_eps, s2s_bn_eps;
+} e2v_s2s_config;
+void e2v_default_s2s_config(e2v_s2s_config* s2s);
+/* sizeof(e2v_s2s_config) as this build sees it: a binding asserts its own against it, as with e2v_config_size */
+int64_t e2v_s2s_config_size(void);
+/* e2v_create with either optional part: clipv as e2v_create_clip_vision takes it; s2s non-NULL and not all zero: the context also
+ * expects the "s2s." keys (part 128 of e2v_finalize_weights) and serves e2v_seq2seq_latents.  Both NULL: exactly e2v_create.  A bad
+ * config of either: E2V_EINVAL, with a message that names the limit. */
+e2v_status e2v_create_ex(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, int device, e2v_ctx** out);
 void e2v_destroy(e2v_ctx* ctx);
 const char* e2v_last_error(const e2v_ctx* ctx);      /* ctx may be NULL: last error of a failed e2v_create */
 
@@ -192,6 +217,18 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * "clipv.vision_model.encoder.layers.{i}." "self_attn.{q,k,v,out}_proj.*", "layer_norm{1,2}.*", "mlp.fc{1,2}.*", then
  * "clipv.vision_model.post_layernorm.*" and "clipv.visual_projection.weight" [projection_dim][C] (no bias); the position_ids
  * buffer of older checkpoints is not a weight and not expected).  fp32 matrices only.
+ * bit 7 (128) = Seq2Seq latent model (a context made by e2v_create_ex with an e2v_s2s_config -- on any other context the bit is outside
+ * the mask, E2V_EINVAL as before the part existed; the names of the reference's
+ * myTransformer state dict under the prefix "s2s.": "s2s.eeg_embedding.block_1.1.weight" [F1][1][1][64], "...block_1.2.{weight,bias,
+ * running_mean,running_var}", "...block_2.0.weight" [F1 D][1][C][1], "...block_2.1.*", "...block_3.1.weight" [F1 D][1][1][16],
+ * "...block_3.2.weight" [F2][F1 D][1][1], "...block_3.3.*", "s2s.eeg_embedding.embedding.*", per encoder layer
+ * "s2s.transformer_encoder.layers.{i}." "self_attn.in_proj_{weight,bias}", "self_attn.out_proj.*", "linear{1,2}.*", "norm{1,2}.*", per
+ * decoder layer the same with "multihead_attn.*" and "norm3.*", then "s2s.txtpredictor.*", "s2s.predictor.*", and one key that is
+ * ours: "s2s.positional_encoding.pe" [windows][d_model], the first rows of the reference's sinusoid buffer, supplied by the caller
+ * (it is fp32 torch arithmetic of the reference: the caller hands over its bits).  NOT expected, because inference never reads them:
+ * "embedding.weight", "img_embedding.*", every "num_batches_tracked", and the [1][5000][d_model] buffer itself.  Finalize folds the three
+ * BatchNorms (running statistics) into the embedding kernel's pack and keeps every loaded tensor: fp32 matrices only, and
+ * e2v_read_tensor returns every "s2s." key with the loaded bits.
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -211,6 +248,8 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * `text_encoder.requires_grad_(False)`); another text encoder is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 8).
  * An "image." key: E2V_EINVAL as well -- the classifier is a frozen yardstick (40_class_run_metrics.py:70-72 loads it and only
  * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32).
+ * An "s2s." key: E2V_EINVAL too -- the Seq2Seq model is trained by its own script and only called here, and its BatchNorms are folded
+ * at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128).
  * A "clipv." key (part 64) is updated like a UNet key: the fp32 form, and the bf16 / fp16 copy of a matrix (the layers' linears, the
  * patch embedding) once the tower has built it in a 16-bit mode (e2v_set_tower_dtype) -- every copy that exists is refreshed. */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
@@ -398,6 +437,32 @@ e2v_status e2v_semantic_predict(e2v_ctx* ctx, const float* eeg, int B, float* ou
  * No text config / text part not finalized / host-only context: E2V_ESTATE.  Stream-ordered, does not synchronise, allocates nothing
  * once the workspace of a (B, T) is cached. */
 e2v_status e2v_text_encode(e2v_ctx* ctx, const int64_t* host_ids, int B, int T, float* out, e2v_stream stream);
+
+/* rank 9 -- replaces myTransformer.forward in eval mode (EEG2Video_New/Seq2Seq/my_autoregressive_transformer.py:151-192) and the
+ * `out[:, :-1]` its inference keeps (:383-384): EEG windows in, the latents DANA or the pipeline takes out.
+ * eeg: device fp32, 4-byte aligned; sample t of electrode c of window w of clip b is eeg[b clip_stride + w window_stride +
+ * c channel_stride + t] (element strides, non-negative).  Stacked windows [B][windows][electrodes][samples] are (windows electrodes
+ * samples, electrodes samples, samples); a raw segment [B][electrodes][L] under the reference's sliding windows of `samples` with
+ * step s (:309-314: 100 and 50 over L = 400) is (electrodes L, s, L) -- no host-side windowing.
+ * mean, scale: device [windows][electrodes][samples] fp32, both or neither NULL: the input scaler (x - mean) / scale applied as a
+ * value is read, true division -- the reference's StandardScaler over the stacked windows (:320-330; its features run (electrode,
+ * sample, window): the caller reorders).
+ * The decoder starts from a zero token and appends one token per step; token j of the steps + 1 is the latent predictor's input j.
+ * first, count: the tokens [first, first + count) are returned; only first + count - 1 decoder steps run (each new token is one row
+ * against per-layer cached keys and values, the same arithmetic as the reference's recomputation of all rows under the causal mask).
+ * The reference's [:, :-1] is first = 0, count = steps: its last pass is never run.  Token 0 is predictor.bias for every clip.
+ * layout 0: latents [B][count][latent_channels][h][w] (what e2v_dana_noise takes as x0); 1: [B][latent_channels][count][h][w] (the
+ * pipeline's layout).  txt_logits: [B][txt_classes], txtpredictor of the mean encoder row.  tokens: [B][steps + 1][d_model], the decoder's
+ * token rows; rows 0 .. first + count - 1 are written, the rest left alone.  Any of the three may be NULL, not all; first / count /
+ * layout are checked whenever latents or tokens is given, and a call for txt_logits alone runs no decoder step.
+ * ARITHMETIC IS FP32 IN EVERY COMPUTE MODE, as e2v_text_encode; a clip's bits do not depend on B or on its place in the batch.
+ * Checked before anything is enqueued, in this order: NULL eeg / no output / mean without scale / a pointer off its alignment (eeg,
+ * mean, scale, txt_logits 4 bytes; latents, tokens 16) / negative stride / layout not 0 or 1 / first < 0, count < 1, first + count >
+ * steps + 1 / B < 1: E2V_EINVAL; then no Seq2Seq config, part 128 not finalized, host-only context: E2V_ESTATE.
+ * Stream-ordered, does not synchronise, allocates nothing once the workspace of a (B, first + count) is cached. */
+e2v_status e2v_seq2seq_latents(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
+                               const float* mean, const float* scale, int B, int first, int count, int layout, float* latents,
+                               float* txt_logits, float* tokens, e2v_stream stream);
 
 /* rank 2 -- replaces Diffusion.forward of DANA (EEG2Video/models/DANA_module.py:52-72) given its random draws, fused with
  * the latent layout fix 'a b c d e -> a c b d e' of inference_eeg2video.py:77,82:

@@ -254,6 +254,23 @@ e2v_status e2v_op_run_plan(e2v_ctx* ctx, const e2v_plan_op* ops, int n_ops, int 
                            const float* eps_u, const float* eps_c, int n_unet, const float* noise, int n_noise,
                            float guidance_scale, float* out, int64_t count, e2v_stream stream);
 
+/* Test aid: the EEGNet embedding kernel of e2v_seq2seq_latents on its own (MyEEGNet_embedding up to the flatten, eval mode), from
+ * torch-layout DEVICE tensors: w1 [F1][64], w2 [F1 D][C], w3 [F1 D][16], w4 [F2][F1 D], bn1 / bn2 / bn3 [4][n] = weight | bias |
+ * running_mean | running_var.  eeg, the three strides, mean and scale ([W][C][T], both or neither NULL) as e2v_seq2seq_latents takes
+ * them; out: [B * W][F2 * ((T / 4) / 8)].  The weights are folded on the host as finalize folds them: the call synchronises the stream.
+ * Needs no Seq2Seq config in the context.  T < 32 or a window that does not fit the kernel's LDS: E2V_ESHAPE. */
+e2v_status e2v_op_eegnet_embed(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
+                               const float* mean, const float* scale, int B, int W, int C, int T, int F1, int D, int F2, const float* w1,
+                               const float* bn1, const float* w2, const float* bn2, const float* w3, const float* w4, const float* bn3,
+                               float bn_eps, float* out, e2v_stream stream);
+
+/* Test aid: the attention kernel of e2v_seq2seq_latents on its own: Nq queries of every (clip, head) against Nk <= 32 keys, head dim D a
+ * multiple of 4 up to 128, scale D^-0.5.  q [B][Nq][ldq], k, v [B][Nk][ldkv], out [B][Nq][ldo] (row strides in elements, multiples of 4;
+ * heads * D columns used; clips Nq ldq / Nk ldkv / Nq ldo apart).  causal != 0: query i sits at absolute position q_pos0 + i and sees
+ * keys 0 .. q_pos0 + i.  Needs no Seq2Seq config in the context. */
+e2v_status e2v_op_seq_attention(e2v_ctx* ctx, const float* q, int ldq, const float* k, const float* v, int ldkv, float* out, int ldo, int B,
+                                int heads, int D, int Nq, int Nk, int q_pos0, int causal, e2v_stream stream);
+
 #ifdef __cplusplus
 }
 #endif
