@@ -13,19 +13,15 @@ of the hub model made elsewhere.  A full CLIP checkpoint's text tower, ``logit_s
 """
 from __future__ import annotations
 
-import json
-import os
 from typing import Optional
 
 import torch
 
+from ._tower_model import PROCESSOR_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, _TowerModel
 from .engine import Engine, named_tensors
 from .unet import FrozenDict, _load_checkpoint
 from .weights import TEXT_ACTS, ClipVisionConfig, UNetConfig, VAEConfig, clip_vision_param_spec, synth_state_dict
 
-SAFETENSORS_NAME = "model.safetensors"        # transformers.utils.SAFE_WEIGHTS_NAME
-WEIGHTS_NAME = "pytorch_model.bin"            # transformers.utils.WEIGHTS_NAME
-PROCESSOR_NAME = "preprocessor_config.json"   # transformers.utils.IMAGE_PROCESSOR_NAME
 _RESAMPLES = (2, 3)                           # PIL.Image.Resampling.BILINEAR / BICUBIC: the filters the resize tables have
 _MAX_TOKENS = 288                             # kImageAttnMaxT: the attention kernel keeps K and V of an image's head in LDS
 
@@ -48,7 +44,9 @@ class CLIPVisionModelOutput:
         return (self.image_embeds,)
 
 
-class CLIPVisionModelWithProjection:
+class CLIPVisionModelWithProjection(_TowerModel):
+    _PART = Engine.CLIP_VISION
+
     def __init__(self, config: ClipVisionConfig = ClipVisionConfig(), *, engine: Optional[Engine] = None, device: int = 0):
         self.ccfg = config
         self._internal_dict = FrozenDict(hidden_size=config.hidden, num_attention_heads=config.heads, num_hidden_layers=config.layers,
@@ -59,39 +57,6 @@ class CLIPVisionModelWithProjection:
             raise RuntimeError(f"the engine was created for a CLIP vision tower of {engine.clip_vision_cfg}, this one is {config}: "
                                "create the engine with clip_vision_cfg=CLIPVisionModelWithProjection.config_from_dir(<dir>)")
         self.engine = engine if engine is not None else Engine(UNetConfig(), VAEConfig(), device, clip_vision_cfg=config)
-
-    @property
-    def config(self) -> FrozenDict:
-        return self._internal_dict
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return torch.float32
-
-    @property
-    def device(self) -> torch.device:
-        return self.engine.device
-
-    def to(self, *a, **k):          # the weights live on the engine's GPU; the arithmetic is chosen by set_compute_dtype alone
-        return self
-
-    @property
-    def compute_dtype(self) -> str:
-        """``'fp32'`` (the default), ``'bf16'`` or ``'fp16'``: the arithmetic of this model on its engine (``Engine.tower_dtype``)."""
-        return self.engine.tower_dtype(Engine.CLIP_VISION)
-
-    def set_compute_dtype(self, dtype):
-        """Opt into 16-bit arithmetic for this model alone: ``'fp16'`` (what the reference runs it in,
-        ``40_class_run_metrics.py``: ``.to(device, torch.float16)``), ``'bf16'``, or back to ``'fp32'`` -- a name or a ``torch.dtype``
-        (``Engine.set_tower_dtype``).  The outputs stay fp32; ``torch_dtype=`` and ``.to()`` do not select it."""
-        self.engine.set_tower_dtype(Engine.CLIP_VISION, dtype)
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag: bool = False):
-        return self
 
     # -- weights -----------------------------------------------------------------------------
     def state_dict_spec(self):
@@ -136,9 +101,7 @@ class CLIPVisionModelWithProjection:
                 "do_normalize": True, "do_convert_rgb": True, "size": {"shortest_edge": c.resize_edge},
                 "crop_size": {"height": c.image_size, "width": c.image_size}, "resample": c.resample, "rescale_factor": c.rescale_factor,
                 "image_mean": list(c.image_mean), "image_std": list(c.image_std)}
-        with open(os.path.join(save_directory, PROCESSOR_NAME), "w") as f:
-            json.dump(proc, f, indent=2, sort_keys=True)
-            f.write("\n")
+        self._write_processor(save_directory, proc)
 
     def init_synthetic(self, seed: int = 46, mode: str = "perturbed"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
@@ -147,14 +110,7 @@ class CLIPVisionModelWithProjection:
     def config_from_dir(path: str) -> ClipVisionConfig:
         """``config.json`` (``CLIPVisionConfig``, or ``CLIPConfig`` with its ``vision_config``) + ``preprocessor_config.json`` of a
         ``transformers`` CLIP directory -> ``ClipVisionConfig``.  Refuses what the kernels cannot do."""
-        cfg_file, proc_file = os.path.join(path, "config.json"), os.path.join(path, PROCESSOR_NAME)
-        for f in (cfg_file, proc_file):
-            if not os.path.isfile(f):
-                raise RuntimeError(f"{f} does not exist")
-        with open(cfg_file) as f:
-            cj = json.load(f)
-        with open(proc_file) as f:
-            pj = json.load(f)
+        cj, pj = _TowerModel._read_configs(path)
         d = ClipVisionConfig()
         top = cj
         if "vision_config" in cj:                                # a full CLIPConfig: projection_dim sits at the top as well
@@ -205,12 +161,9 @@ class CLIPVisionModelWithProjection:
         """LOCAL directory only.  ``torch_dtype`` and ``cache_dir`` are accepted for drop-in use: checkpoints of any float type are
         widened to fp32, and nothing is ever fetched.  ``compute_dtype``: ``set_compute_dtype`` on the built model (``None``: fp32)."""
         path = str(pretrained_model_path)
-        if not os.path.isdir(path):
-            raise RuntimeError(f"{path!r} is not a directory: this model loads from a local checkpoint directory only and never "
-                               "reads the network (download 'openai/clip-vit-base-patch32' elsewhere and pass its directory)")
+        cls._require_dir(path, "model", "openai/clip-vit-base-patch32")
         config = cls.config_from_dir(path)
-        if not os.path.isfile(os.path.join(path, WEIGHTS_NAME)) and not os.path.isfile(os.path.join(path, SAFETENSORS_NAME)):
-            raise RuntimeError(f"{os.path.join(path, SAFETENSORS_NAME)} does not exist")
+        cls._require_weights(path)
         model = cls(config, engine=engine, device=device)
         if compute_dtype is not None:
             model.set_compute_dtype(compute_dtype)

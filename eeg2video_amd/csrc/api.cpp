@@ -35,6 +35,24 @@ e2v_status guarded(e2v_ctx* ctx, Fn&& fn) {
     }
 }
 
+// The skeleton of an entry point that answers a malformed call on ANY context: a null context is E2V_EINVAL; `check` holds the
+// argument and state checks and makes no HIP call, so a host-only context gets the same answer -- its Error's text and code; `run` is
+// the work, under guarded().
+template <typename Check, typename Run>
+e2v_status entry(e2v_ctx* c, Check&& check, Run&& run) {
+    if (!c) return E2V_EINVAL;
+    try {
+        check();
+    } catch (const Error& e) {
+        c->err = e.what();
+        return e.code;
+    }
+    return guarded(c, run);
+}
+
+// the frames of an entry point as the kernels take them: `kind` is E2V_FRAMES_U8 | E2V_FRAMES_CHANNELS_LAST bits
+FrameSrc frame_src(const void* frames, int kind) { return FrameSrc{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0}; }
+
 float half_to_float(uint16_t h) {
     const uint32_t sign = (uint32_t)(h & 0x8000) << 16;
     uint32_t exp = (h >> 10) & 0x1F, man = h & 0x3FF, bits;
@@ -372,9 +390,7 @@ const WTensor& updatable(e2v_ctx* c, const char* key) {
     auto it = c->raw.find(key);
     E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
     const std::string k(key);
-    const int part = e2v_ctx::key_part(k);
-    const bool ready = part == 4 ? c->sem_ready : part == 2 ? c->vae_ready : part == 8 ? c->text_ready : part == 16 ? c->image_ready : part == 32 ? c->video_ready : part == 64 ? c->clipv_ready : part == 128 ? c->s2s_ready : c->unet_ready;
-    E2V_REQUIRE(ready, E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
+    E2V_REQUIRE(c->ready[e2v_ctx::key_part(k)], E2V_ESTATE, "the part that owns " + k + " is not finalized: upload it with e2v_load_tensor, then e2v_finalize_weights");
     return it->second;
 }
 }  // namespace
@@ -383,26 +399,12 @@ extern "C" {
 
 e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_dtype dtype, int on_device, const int64_t* shape,
                              int ndim, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    if (!key || !data || !shape) { c->err = "null argument"; return E2V_EINVAL; }
-    if (dtype != E2V_F32 && dtype != E2V_F16 && dtype != E2V_BF16) { c->err = "e2v_update_tensor: the source is fp32, fp16 or bf16"; return E2V_EINVAL; }
-    if (e2v_ctx::key_part(key) == 8) {
-        c->err = "e2v_update_tensor: the text encoder is frozen on this path (train_finetune_videodiffusion.py:115); load a new one with e2v_load_tensor + e2v_finalize_weights";
-        return E2V_EINVAL;
-    }
-    if (e2v_ctx::key_part(key) == 16) {
-        c->err = "e2v_update_tensor: the image classifier is a frozen yardstick (40_class_run_metrics.py:88-90); load a new one with e2v_load_tensor + e2v_finalize_weights";
-        return E2V_EINVAL;
-    }
-    if (e2v_ctx::key_part(key) == 32) {
-        c->err = "e2v_update_tensor: the video classifier is a frozen yardstick (40_class_run_metrics.py:113-118); load a new one with e2v_load_tensor + e2v_finalize_weights";
-        return E2V_EINVAL;
-    }
-    if (e2v_ctx::key_part(key) == 128) {
-        c->err = "e2v_update_tensor: the Seq2Seq model is only called here and its BatchNorms are folded at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128)";
-        return E2V_EINVAL;
-    }
-    return guarded(c, [&] {
+    return entry(c, [&] {
+        E2V_REQUIRE(key && data && shape, E2V_EINVAL, "null argument");
+        E2V_REQUIRE(dtype == E2V_F32 || dtype == E2V_F16 || dtype == E2V_BF16, E2V_EINVAL, "e2v_update_tensor: the source is fp32, fp16 or bf16");
+        const char* frozen = e2v_ctx::kParts[e2v_ctx::key_part(key)].frozen;
+        E2V_REQUIRE(!frozen, E2V_EINVAL, std::string("e2v_update_tensor: ") + frozen);
+    }, [&] {
         E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no weights in a dry run");
         const WTensor& t = updatable(c, key);
         bool same = (int)t.shape.size() == ndim;
@@ -414,10 +416,8 @@ e2v_status e2v_update_tensor(e2v_ctx* c, const char* key, const void* data, e2v_
 
 e2v_status e2v_read_tensor(e2v_ctx* c, const char* key, int form, void* out, e2v_dtype dtype, int on_device, const int64_t* shape,
                            int ndim, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    if (!key || !out || !shape) { c->err = "null argument"; return E2V_EINVAL; }
-    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
-    try {
+    return entry(c, [&] {
+        E2V_REQUIRE(key && out && shape, E2V_EINVAL, "null argument");
         auto it = c->raw.find(key);
         E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, std::string("unexpected state-dict key: ") + key);
         const WTensor& t = it->second;
@@ -432,20 +432,14 @@ e2v_status e2v_read_tensor(e2v_ctx* c, const char* key, int form, void* out, e2v
                     "e2v_read_tensor: the conv kernel layouts, the Winograd domains and the UP2 forms have no index-map inverse; read E2V_FORM_F32");
         updatable(c, key);
         c->read_source(key, form);
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         E2V_REQUIRE(!dry_run(), E2V_ESTATE, "no weights in a dry run");
         c->read_tensor(key, form, out, dtype, on_device != 0, S(c, stream));
     });
 }
 
 e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
-    if (!c) return E2V_EINVAL;
-    if (!key || !mask) { c->err = "null argument"; return E2V_EINVAL; }
-    return guarded(c, [&] {
+    return entry(c, [&] { E2V_REQUIRE(key && mask, E2V_EINVAL, "null argument"); }, [&] {
         updatable(c, key);
         *mask = c->weight_forms(key);
     });
@@ -493,7 +487,7 @@ e2v_status e2v_set_ddim_schedule(e2v_ctx* c, const float* t, int n, int steps_of
 e2v_status e2v_semantic_predict(e2v_ctx* c, const float* eeg, int B, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(c->sem_ready, E2V_ESTATE, "semantic predictor weights are not finalized");
+        c->require_ready(e2v_ctx::SEM);
         E2V_REQUIRE(eeg && out && B > 0, E2V_EINVAL, "bad arguments");
         hipStream_t s = S(c, stream);
         const bool b16 = c->bf16_compute;                        // bf16-activation mode: bf16 rows between the layers, fp32 result
@@ -537,8 +531,8 @@ e2v_status e2v_semantic_predict(e2v_ctx* c, const float* eeg, int B, float* out,
 e2v_status e2v_text_encode(e2v_ctx* c, const int64_t* host_ids, int B, int T, float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        E2V_REQUIRE(c->cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
-        E2V_REQUIRE(c->text_ready, E2V_ESTATE, "text encoder weights are not finalized");
+        c->require_part(e2v_ctx::TEXT);
+        c->require_ready(e2v_ctx::TEXT);
         E2V_REQUIRE(host_ids && out && (reinterpret_cast<uintptr_t>(out) & 15) == 0, E2V_EINVAL, "null or misaligned argument (out: 16 bytes)");
         E2V_REQUIRE(B > 0 && T >= 1 && T <= c->cfg.text_max_positions, E2V_ESHAPE,
                     "input_ids must be [B >= 1][1 <= T <= text_max_positions = " + std::to_string(c->cfg.text_max_positions) + "]");
@@ -561,8 +555,7 @@ e2v_status e2v_text_encode(e2v_ctx* c, const int64_t* host_ids, int B, int T, fl
 e2v_status e2v_seq2seq_latents(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
                                const float* mean, const float* scale, int B, int first, int count, int layout, float* latents,
                                float* txt_logits, float* tokens, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         auto off = [](const void* p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; };
         E2V_REQUIRE(eeg, E2V_EINVAL, "e2v_seq2seq_latents: eeg is NULL");
         E2V_REQUIRE(latents || txt_logits || tokens, E2V_EINVAL, "e2v_seq2seq_latents: no output asked for (latents, txt_logits and tokens are all NULL)");
@@ -578,15 +571,11 @@ e2v_status e2v_seq2seq_latents(e2v_ctx* c, const float* eeg, int64_t clip_stride
                         "e2v_seq2seq_latents: tokens [first, first + count) must lie in [0, s2s_steps + 1) with count >= 1");
         }
         E2V_REQUIRE(B >= 1, E2V_EINVAL, "e2v_seq2seq_latents: B must be at least 1");
-        E2V_REQUIRE(c->scfg.s2s_d_model > 0, E2V_ESTATE, "the context has no Seq2Seq latent model (e2v_create_ex)");
-        E2V_REQUIRE(c->s2s_ready, E2V_ESTATE, "Seq2Seq weights are not finalized");
+        c->require_part(e2v_ctx::S2S);
+        c->require_ready(e2v_ctx::S2S);
         E2V_REQUIRE((long long)B * std::max(c->scfg.s2s_windows, c->scfg.s2s_steps + 1) * std::max(c->scfg.s2s_ffn, 3 * c->scfg.s2s_d_model) <= 0x7FFFFFFFLL &&
                         (long long)B * (c->scfg.s2s_steps + 1) <= (1 << 20), E2V_ESHAPE, "e2v_seq2seq_latents: B is too large for one call");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         EegnetArgs e;
         e.eeg = eeg; e.clip_stride = clip_stride; e.window_stride = window_stride; e.channel_stride = channel_stride; e.mean = mean; e.scale = scale;
         c->seq2seq_latents(e, B, first, count, layout, latents, txt_logits, tokens, S(c, stream));
@@ -636,9 +625,7 @@ e2v_status e2v_frames_to_uint8(e2v_ctx* c, const float* videos, uint8_t* out, in
 
 e2v_status e2v_frame_metrics(e2v_ctx* c, const void* a, int a_kind, const void* b, int b_kind, int n, int F, int C, int H, int W,
                              float* ssim, float* mse, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
-    try {
+    return entry(c, [&] {
         const int known = E2V_FRAMES_U8 | E2V_FRAMES_CHANNELS_LAST;
         E2V_REQUIRE(a && b, E2V_EINVAL, "e2v_frame_metrics: null argument");
         E2V_REQUIRE(ssim || mse, E2V_EINVAL, "e2v_frame_metrics: ssim and mse are both NULL");
@@ -647,15 +634,11 @@ e2v_status e2v_frame_metrics(e2v_ctx* c, const void* a, int a_kind, const void* 
         E2V_REQUIRE(C >= 1 && C <= 4, E2V_ESHAPE, "e2v_frame_metrics: 1 to 4 channels");
         E2V_REQUIRE(H >= 7 && W >= 7, E2V_ESHAPE, "e2v_frame_metrics: the 7x7 window exceeds the image");
         E2V_REQUIRE((double)n * F * (double)frame_metrics_tiles(H, W) < 2147483648.0, E2V_ESHAPE, "e2v_frame_metrics: too many tiles for one call");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
         Act partials(c->pool, (int64_t)(frame_metrics_partials_bytes(n, F, H, W) / 4), 1);
-        const FrameSrc sa{a, (a_kind & E2V_FRAMES_U8) == 0, (a_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
-        const FrameSrc sb{b, (b_kind & E2V_FRAMES_U8) == 0, (b_kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc sa = frame_src(a, a_kind);
+        const FrameSrc sb = frame_src(b, b_kind);
         frame_metrics(sa, sb, n, F, C, H, W, partials.p, ssim, mse, s);
         E2V_HIP(hipGetLastError());
     });
@@ -682,23 +665,17 @@ extern "C" {
 // ViTImageProcessor + ViTForImageClassification + softmax + top 3 of every frame (img_classify_metric's classifier half)
 e2v_status e2v_image_classify(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* logits, float* probs,
                               int32_t* top3, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    // what is wrong with the call itself is answered without a HIP call, so a host-only context answers it too
-    try {
+    return entry(c, [&] {
         check_frames("e2v_image_classify", frames, kind, n, F, H, W);
         E2V_REQUIRE(logits || probs || top3, E2V_EINVAL, "e2v_image_classify: logits, probs and top3 are all NULL");
         E2V_REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(top3)) & 3) == 0,
                     E2V_EINVAL, "e2v_image_classify: misaligned output (4 bytes)");
-        E2V_REQUIRE(c->cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
+        c->require_part(e2v_ctx::IMAGE);
         E2V_REQUIRE(c->prep_plan(H, W).band >= 1, E2V_ESHAPE,
                     "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
-        E2V_REQUIRE(c->image_ready, E2V_ESTATE, "image classifier weights are not finalized");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->require_ready(e2v_ctx::IMAGE);
+    }, [&] {
+        const FrameSrc src = frame_src(frames, kind);
         c->image_classify(src, n, F, H, W, logits, probs, top3, S(c, stream));
     });
 }
@@ -730,25 +707,19 @@ e2v_status e2v_image_resize_table_filter(int in_size, int out_size, int filter, 
 // the preprocess of e2v_image_classify on its own, at any (S, P) and with the caller's pixel table
 e2v_status e2v_op_image_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch,
                                    const float* host_lut, float* rows, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
     ImagePrepPlan plan;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_op_image_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_image_preprocess: null or misaligned rows");
         E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0, E2V_ESHAPE, "e2v_op_image_preprocess: 1 <= S <= 4096, a multiple of P >= 1");
         E2V_REQUIRE(host_lut || c->cfg.vit_layers > 0, E2V_ESTATE, "e2v_op_image_preprocess: no pixel table given and the config has no image classifier");
         plan = image_prep_plan(H, W, size, patch, host_lut ? host_lut : c->image_lut);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_image_preprocess: the source rows of one output row do not fit the kernel's LDS band");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
-        Act tables(c->pool, (int64_t)plan.words.size(), 1);
-        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        Act tables = upload_plan(c->pool, plan, s);
         E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc src = frame_src(frames, kind);
         const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
         for (long long i0 = 0; i0 < total; i0 += 4096) {
             const int ni = (int)std::min<long long>(4096, total - i0);
@@ -760,18 +731,13 @@ e2v_status e2v_op_image_preprocess(e2v_ctx* c, const void* frames, int kind, int
 
 // fp32 in every compute mode, as e2v_image_classify runs it
 e2v_status e2v_op_image_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
         E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && T <= kImageAttnMaxT, E2V_ESHAPE, "image attention: B, heads >= 1 and 1 <= T <= " + std::to_string(kImageAttnMaxT));
         E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldqkv % 4 == 0 && ldo >= heads * 64 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(out) & 3) == 0,
                     E2V_EINVAL, "image attention: qkv rows of q | k | v (16-byte aligned, ldqkv a multiple of 4), out rows of heads * 64 columns");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         OpRecord rec;
         image_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
         E2V_HIP(hipGetLastError());
@@ -781,8 +747,7 @@ e2v_status e2v_op_image_attention(e2v_ctx* c, const float* qkv, int ldqkv, float
 // VideoMAEImageProcessor + VideoMAEForVideoClassification + softmax + top 3 of every clip (video_classify_metric's classifier half)
 e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* logits, float* probs,
                               int32_t* top3, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_video_classify", frames, kind, n, F, H, W);
         E2V_REQUIRE(logits || probs || top3, E2V_EINVAL, "e2v_video_classify: logits, probs and top3 are all NULL");
         E2V_REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(top3)) & 3) == 0,
@@ -794,14 +759,10 @@ e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, i
             E2V_REQUIRE(c->video_prep_plan(H, W).band >= 1, E2V_ESHAPE,
                         "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
         }
-        E2V_REQUIRE(c->cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
-        E2V_REQUIRE(c->video_ready, E2V_ESTATE, "video classifier weights are not finalized");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->require_part(e2v_ctx::VIDEO);
+        c->require_ready(e2v_ctx::VIDEO);
+    }, [&] {
+        const FrameSrc src = frame_src(frames, kind);
         c->video_classify(src, n, F, H, W, logits, probs, top3, S(c, stream));
     });
 }
@@ -809,9 +770,8 @@ e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, i
 // the preprocess of e2v_video_classify on its own, at any (S, P, ts, edge) and with the caller's pixel table
 e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int ts, int edge,
                                    const float* host_lut, float* rows, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
     VideoPrepPlan plan;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_op_video_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_video_preprocess: null or misaligned rows");
         E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0 && edge >= size && edge <= 4096, E2V_ESHAPE,
@@ -820,16 +780,11 @@ e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int
         E2V_REQUIRE(host_lut || c->cfg.vmae_layers > 0, E2V_ESTATE, "e2v_op_video_preprocess: no pixel table given and the config has no video classifier");
         plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->video_lut);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_video_preprocess: the source rows of one output row do not fit the kernel's LDS band");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
-        Act tables(c->pool, (int64_t)plan.words.size(), 1);
-        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        Act tables = upload_plan(c->pool, plan, s);
         E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc src = frame_src(frames, kind);
         const long long per = (long long)(F / ts) * (size / patch) * (size / patch) * 3 * ts * patch * patch;
         const int step = std::max(1, 4096 / F);
         for (int i0 = 0; i0 < n; i0 += step)
@@ -840,28 +795,22 @@ e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int
 
 // CLIPImageProcessor + CLIPVisionModelWithProjection.image_embeds of every frame (the model half of clip_score)
 e2v_status e2v_clip_embed(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, float* embeds, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_clip_embed", frames, kind, n, F, H, W);
         E2V_REQUIRE(embeds && (reinterpret_cast<uintptr_t>(embeds) & 3) == 0, E2V_EINVAL, "e2v_clip_embed: null or misaligned embeds (4 bytes)");
-        E2V_REQUIRE(c->vcfg.clipv_layers > 0, E2V_ESTATE, "the context has no CLIP vision tower (e2v_create_clip_vision)");
+        c->require_part(e2v_ctx::CLIPV);
         E2V_REQUIRE(c->clipv_prep_plan(H, W).band >= 1, E2V_ESHAPE,
                     "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
-        E2V_REQUIRE(c->clipv_ready, E2V_ESTATE, "CLIP vision tower weights are not finalized");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        c->require_ready(e2v_ctx::CLIPV);
+    }, [&] {
+        const FrameSrc src = frame_src(frames, kind);
         c->clip_embed(src, n, F, H, W, embeds, S(c, stream));
     });
 }
 
 // torch.nn.functional.cosine_similarity(a, b, dim=-1, eps=1e-8) of rows, pairwise or as a matrix
 e2v_status e2v_clip_similarity(e2v_ctx* c, const float* a, int na, const float* b, int nb, int D, int matrix, float* out, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         E2V_REQUIRE(a && b && out, E2V_EINVAL, "e2v_clip_similarity: null argument");
         E2V_REQUIRE(matrix == 0 || matrix == 1, E2V_EINVAL, "e2v_clip_similarity: matrix is 0 (pairs) or 1");
         E2V_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 3) == 0,
@@ -870,11 +819,7 @@ e2v_status e2v_clip_similarity(e2v_ctx* c, const float* a, int na, const float* 
         E2V_REQUIRE(matrix || na == nb, E2V_ESHAPE, "e2v_clip_similarity: the pair form takes as many rows of a as of b");
         E2V_REQUIRE(!matrix || (na + 15) / 16 <= 65535, E2V_ESHAPE, "e2v_clip_similarity: at most 65535 * 16 rows of a in the matrix form");
         E2V_REQUIRE(c->device >= 0, E2V_ESTATE, "e2v_clip_similarity: a host-only context has no device");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         clip_similarity(a, na, b, nb, D, matrix != 0, 1e-8f, out, S(c, stream));
         E2V_HIP(hipGetLastError());
     });
@@ -883,9 +828,8 @@ e2v_status e2v_clip_similarity(e2v_ctx* c, const float* a, int na, const float* 
 // the preprocess of e2v_clip_embed on its own, at any (S, P, edge, filter) and with the caller's pixel table
 e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int edge,
                                   int filter, const float* host_lut, float* rows, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
     VideoPrepPlan plan;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_op_clip_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_clip_preprocess: null or misaligned rows");
         E2V_REQUIRE(filter == kResizeBilinear || filter == kResizeBicubic, E2V_EINVAL, "e2v_op_clip_preprocess: filter 2 (BILINEAR) or 3 (BICUBIC)");
@@ -894,16 +838,11 @@ e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int 
         E2V_REQUIRE(host_lut || c->vcfg.clipv_layers > 0, E2V_ESTATE, "e2v_op_clip_preprocess: no pixel table given and the context has no CLIP vision tower");
         plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->clipv_lut, filter);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_clip_preprocess: the source rows of one output row do not fit the kernel's LDS band");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
-        Act tables(c->pool, (int64_t)plan.words.size(), 1);
-        E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        Act tables = upload_plan(c->pool, plan, s);
         E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc src = frame_src(frames, kind);
         const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
         for (long long i0 = 0; i0 < total; i0 += 4096) {
             const int ni = (int)std::min<long long>(4096, total - i0);
@@ -915,18 +854,13 @@ e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int 
 
 // fp32 in every compute mode, as e2v_video_classify runs it
 e2v_status e2v_op_token_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
         E2V_REQUIRE(B > 0 && heads > 0 && T >= 1, E2V_ESHAPE, "token attention: B, heads, T >= 1");
         E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldqkv % 4 == 0 && ldo >= heads * 64 && ldo % 4 == 0 && (reinterpret_cast<uintptr_t>(qkv) & 15) == 0 &&
                         (reinterpret_cast<uintptr_t>(out) & 15) == 0,
                     E2V_EINVAL, "token attention: qkv rows of q | k | v, out rows of heads * 64 columns, both 16-byte aligned with strides that are multiples of 4");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         OpRecord rec;
         token_attention(qkv, ldqkv, out, ldo, B, T, heads, S(c, stream));
         E2V_HIP(hipGetLastError());
@@ -936,9 +870,6 @@ e2v_status e2v_op_token_attention(e2v_ctx* c, const float* qkv, int ldqkv, float
 // ---- the metric towers in a 16-bit mode (e2v_set_tower_dtype) and the pieces of that path on their own ----------------------------
 namespace {
 int tower_mode_of(int dtype) { return dtype == E2V_BF16 ? H16_BF16 : dtype == E2V_F16 ? H16_FP16 : dtype == E2V_F32 ? H16_NONE : -1; }
-bool tower_exists(const e2v_ctx* c, int part) {
-    return part == 16 ? c->cfg.vit_layers > 0 : part == 32 ? c->cfg.vmae_layers > 0 : part == 64 ? c->vcfg.clipv_layers > 0 : false;
-}
 void require_h16(const char* who, int dtype) {
     E2V_REQUIRE(dtype == E2V_BF16 || dtype == E2V_F16, E2V_EINVAL, std::string(who) + ": dtype is E2V_BF16 or E2V_F16");
 }
@@ -946,12 +877,12 @@ void require_h16(const char* who, int dtype) {
 
 e2v_status e2v_set_tower_dtype(e2v_ctx* c, int part, int dtype) {
     if (!c) return E2V_EINVAL;
-    const int slot = e2v_ctx::tower_slot(part), mode = tower_mode_of(dtype);
+    const int slot = e2v_ctx::tower_part(part), mode = tower_mode_of(dtype);
     if (slot < 0 || mode < 0) {
         c->err = "e2v_set_tower_dtype: part is 16 (image classifier), 32 (video classifier) or 64 (CLIP vision tower); dtype is E2V_F32, E2V_BF16 or E2V_F16";
         return E2V_EINVAL;
     }
-    if (!tower_exists(c, part)) {
+    if (!c->has_part((e2v_ctx::Part)slot)) {
         c->err = "e2v_set_tower_dtype: the context has no such tower (part " + std::to_string(part) + ")";
         return E2V_ESTATE;
     }
@@ -960,7 +891,7 @@ e2v_status e2v_set_tower_dtype(e2v_ctx* c, int part, int dtype) {
 }
 
 int e2v_tower_dtype(const e2v_ctx* c, int part) {
-    const int slot = e2v_ctx::tower_slot(part);
+    const int slot = e2v_ctx::tower_part(part);
     if (!c || slot < 0) return -1;
     const int m = c->tower_h16[slot];
     return m == H16_BF16 ? E2V_BF16 : m == H16_FP16 ? E2V_F16 : E2V_F32;
@@ -970,10 +901,9 @@ int e2v_tower_dtype(const e2v_ctx* c, int part) {
 // the caller's fp32 `rows`: tower = 16 (image_preprocess), 32 (video_preprocess: ts, edge) or 64 (frame_preprocess: edge, filter).
 e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void* frames, int kind, int n, int F, int H, int W, int size,
                                    int patch, int ts, int edge, int filter, const float* host_lut, float* rows, e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
     ImagePrepPlan iplan;
     VideoPrepPlan vplan;
-    try {
+    return entry(c, [&] {
         check_frames("e2v_op_tower_preprocess", frames, kind, n, F, H, W);
         require_h16("e2v_op_tower_preprocess", dtype);
         E2V_REQUIRE(tower == 16 || tower == 32 || tower == 64, E2V_EINVAL, "e2v_op_tower_preprocess: tower is 16, 32 or 64");
@@ -985,19 +915,13 @@ e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void*
         if (tower == 16) iplan = image_prep_plan(H, W, size, patch, host_lut);
         else vplan = video_prep_plan(H, W, edge, size, patch, host_lut, tower == 64 ? filter : kResizeBilinear);
         E2V_REQUIRE((tower == 16 ? iplan.band : vplan.band) >= 1, E2V_ESHAPE, "e2v_op_tower_preprocess: the source rows of one output row do not fit the kernel's LDS band");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
         const int mode = tower_mode_of(dtype);
-        const std::vector<int>& words = tower == 16 ? iplan.words : vplan.words;
-        Act tables(c->pool, (int64_t)words.size(), 1);
-        E2V_HIP(hipMemcpyAsync(tables.p, words.data(), words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        Act tables = upload_plan(c->pool, tower == 16 ? iplan : vplan, s);
         E2V_HIP(hipStreamSynchronize(s));                    // (the plans are locals: a test aid may wait)
         const int* tab = reinterpret_cast<const int*>(tables.p);
-        const FrameSrc src{frames, (kind & E2V_FRAMES_U8) == 0, (kind & E2V_FRAMES_CHANNELS_LAST) != 0};
+        const FrameSrc src = frame_src(frames, kind);
         const int tsz = tower == 32 ? ts : 1;
         const long long np2 = (long long)(size / patch) * (size / patch);
         const int K = 3 * tsz * patch * patch;
@@ -1021,17 +945,12 @@ e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void*
 // flash_attention on the 16-bit rows (mode 1, F = 1, Nq = Nk = T, head dim 64, scale 1/8), the 16-bit output widened exactly.
 e2v_status e2v_op_tower_attention(e2v_ctx* c, int dtype, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads,
                                   e2v_stream stream) {
-    if (!c) return E2V_EINVAL;
-    try {
+    return entry(c, [&] {
         require_h16("e2v_op_tower_attention", dtype);
         E2V_REQUIRE(qkv && out, E2V_EINVAL, "null argument");
         E2V_REQUIRE(B > 0 && heads > 0 && T >= 1 && (double)B * T < 2147483648.0, E2V_ESHAPE, "tower attention: B, heads, T >= 1");
         E2V_REQUIRE(ldqkv >= 3 * heads * 64 && ldo >= heads * 64, E2V_EINVAL, "tower attention: qkv rows of q | k | v, out rows of heads * 64 columns");
-    } catch (const Error& e) {
-        c->err = e.what();
-        return e.code;
-    }
-    return guarded(c, [&] {
+    }, [&] {
         hipStream_t s = S(c, stream);
         const int mode = tower_mode_of(dtype), C = heads * 64;
         const int64_t M = (int64_t)B * T;
@@ -1137,7 +1056,7 @@ int64_t e2v_profile_end(e2v_ctx* c, char* json, int64_t cap) {
 
 e2v_status e2v_set_compute_dtype(e2v_ctx* c, int dtype) {
     if (!c || (dtype != E2V_F32 && dtype != E2V_BF16 && dtype != E2V_F16 && dtype != E2V_F32X3)) return E2V_EINVAL;
-    if (dtype == E2V_F32X3 && (c->unet_ready || c->vae_ready || c->sem_ready)) {
+    if (dtype == E2V_F32X3 && (c->ready[e2v_ctx::UNET] || c->ready[e2v_ctx::VAE] || c->ready[e2v_ctx::SEM])) {
         c->err = "E2V_F32X3 needs the split weights: select it before e2v_finalize_weights";
         return E2V_ESTATE;
     }
@@ -1557,7 +1476,7 @@ e2v_status e2v_op_describe_dispatch(e2v_ctx* c, int dtype, int B, int F, int h, 
         ~Dry() { dry_run() = false; dry_log().clear(); }
     } dry;
     e2v_status st = guarded(c, [&] {
-        if (!c->unet_ready || !c->vae_ready) c->finalize(3);
+        if (!c->ready[e2v_ctx::UNET] || !c->ready[e2v_ctx::VAE]) c->finalize(3);
     });
     if (st != E2V_OK) return st;
     const int was_mode = c->h16_mode;

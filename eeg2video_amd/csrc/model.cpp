@@ -58,6 +58,19 @@ struct KeySink {
         for (const char* n : {"query", "key", "value", "proj_attn"}) lin(a + "." + n, ch, ch);
         resnet3d(p + ".resnets.1", ch, ch, 0);
     }
+    // one encoder layer under transformers' ViT / VideoMAE names ("image.", "video.") and one CLIPEncoderLayer ("text.", "clipv."),
+    // each in its checkpoint's own order
+    void hf_vit_layer(const std::string& l, int C, int I) {
+        for (const char* n : {"query", "key", "value"}) lin(l + ".attention.attention." + n, C, C);
+        lin(l + ".attention.output.dense", C, C);
+        lin(l + ".intermediate.dense", I, C); lin(l + ".output.dense", C, I);
+        norm(l + ".layernorm_before", C); norm(l + ".layernorm_after", C);
+    }
+    void clip_layer(const std::string& l, int C, int I) {
+        for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) lin(l + ".self_attn." + n, C, C);
+        norm(l + ".layer_norm1", C); norm(l + ".layer_norm2", C);
+        lin(l + ".mlp.fc1", I, C); lin(l + ".mlp.fc2", C, I);
+    }
 };
 
 std::string idx(const std::string& a, int i, const std::string& b, int j) {
@@ -65,6 +78,20 @@ std::string idx(const std::string& a, int i, const std::string& b, int j) {
 }
 
 }  // namespace
+
+bool e2v_ctx::has_part(Part p) const {
+    switch (p) {
+        case UNET: case VAE: return true;
+        case SEM: return cfg.sem_in_features > 0 && cfg.sem_hidden > 0;
+        case TEXT: return cfg.text_layers > 0;
+        case IMAGE: return cfg.vit_layers > 0;
+        case VIDEO: return cfg.vmae_layers > 0;
+        case CLIPV: return vcfg.clipv_layers > 0;
+        case S2S: return scfg.s2s_d_model > 0;
+        case N_PARTS: break;
+    }
+    return false;
+}
 
 void e2v_ctx::expected_keys() {
     KeySink s{this};
@@ -133,78 +160,56 @@ void e2v_ctx::expected_keys() {
     s.conv("vae.post_quant_conv", lat, lat, 1);
 
     // ---- Semantic Predictor ("semantic." prefix; nn.Sequential indices of train_semantic_predictor.py:14-28) ----
-    if (cfg.sem_in_features > 0 && cfg.sem_hidden > 0) {
+    if (has_part(SEM)) {
         const int dims[6] = {cfg.sem_in_features, cfg.sem_hidden, cfg.sem_hidden, cfg.sem_hidden, cfg.sem_hidden,
                              cfg.sem_tokens * cfg.cross_attention_dim};
         for (int i = 0; i < 5; ++i) s.lin("semantic.mlp." + std::to_string(2 * i), dims[i + 1], dims[i]);
     }
 
     // ---- CLIP text encoder ("text." prefix; the keys of the SD-v1-4 text_encoder checkpoint, transformers CLIPTextModel) ----
-    if (cfg.text_layers > 0) {
+    if (has_part(TEXT)) {
         const int C = cfg.text_hidden, I = cfg.text_intermediate;
         const std::string m = "text.text_model.";
         s.add(m + "embeddings.token_embedding.weight", {cfg.text_vocab_size, C});
         s.add(m + "embeddings.position_embedding.weight", {cfg.text_max_positions, C});
-        for (int i = 0; i < cfg.text_layers; ++i) {
-            const std::string l = m + "encoder.layers." + std::to_string(i);
-            for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) s.lin(l + ".self_attn." + n, C, C);
-            s.norm(l + ".layer_norm1", C); s.norm(l + ".layer_norm2", C);
-            s.lin(l + ".mlp.fc1", I, C); s.lin(l + ".mlp.fc2", C, I);
-        }
+        for (int i = 0; i < cfg.text_layers; ++i) s.clip_layer(m + "encoder.layers." + std::to_string(i), C, I);
         s.norm(m + "final_layer_norm", C);
     }
 
     // ---- ViT image classifier ("image." prefix; the keys of the google/vit-base-patch16-224 checkpoint, ViTForImageClassification) ----
-    if (cfg.vit_layers > 0) {
+    if (has_part(IMAGE)) {
         const int C = cfg.vit_hidden, I = cfg.vit_intermediate, P = cfg.vit_patch_size;
         const std::string m = "image.vit.";
         s.add(m + "embeddings.cls_token", {1, 1, C});
         s.add(m + "embeddings.position_embeddings", {1, image_tokens(), C});
         s.conv(m + "embeddings.patch_embeddings.projection", C, 3, P);
-        for (int i = 0; i < cfg.vit_layers; ++i) {
-            const std::string l = m + "encoder.layer." + std::to_string(i);
-            for (const char* n : {"query", "key", "value"}) s.lin(l + ".attention.attention." + n, C, C);
-            s.lin(l + ".attention.output.dense", C, C);
-            s.lin(l + ".intermediate.dense", I, C); s.lin(l + ".output.dense", C, I);
-            s.norm(l + ".layernorm_before", C); s.norm(l + ".layernorm_after", C);
-        }
+        for (int i = 0; i < cfg.vit_layers; ++i) s.hf_vit_layer(m + "encoder.layer." + std::to_string(i), C, I);
         s.norm(m + "layernorm", C);
         s.lin("image.classifier", cfg.vit_num_labels, C);
     }
 
     // ---- VideoMAE video classifier ("video." prefix; the names of transformers' VideoMAEForVideoClassification state dict, and the
     // fixed position table -- a buffer transformers builds at construction -- as a key of our own) ----
-    if (cfg.vmae_layers > 0) {
+    if (has_part(VIDEO)) {
         const int C = cfg.vmae_hidden, I = cfg.vmae_intermediate, P = cfg.vmae_patch_size;
         const std::string m = "video.videomae.";
         s.add(m + "embeddings.position_embeddings", {video_tokens(), C});
         s.conv(m + "embeddings.patch_embeddings.projection", C, 3 * cfg.vmae_tubelet_size, P);      // Conv3d [C][3][ts][P][P], axes 1 and 2 merged
-        for (int i = 0; i < cfg.vmae_layers; ++i) {
-            const std::string l = m + "encoder.layer." + std::to_string(i);
-            for (const char* n : {"query", "key", "value"}) s.lin(l + ".attention.attention." + n, C, C);
-            s.lin(l + ".attention.output.dense", C, C);
-            s.lin(l + ".intermediate.dense", I, C); s.lin(l + ".output.dense", C, I);
-            s.norm(l + ".layernorm_before", C); s.norm(l + ".layernorm_after", C);
-        }
+        for (int i = 0; i < cfg.vmae_layers; ++i) s.hf_vit_layer(m + "encoder.layer." + std::to_string(i), C, I);
         s.norm("video.fc_norm", C);
         s.lin("video.classifier", cfg.vmae_num_labels, C);
     }
 
     // ---- CLIP vision tower ("clipv." prefix; the keys of a CLIPVisionModelWithProjection checkpoint -- "pre_layrnorm" is the
     // checkpoint's own spelling; the position_ids buffer of older checkpoints is not a weight) ----
-    if (vcfg.clipv_layers > 0) {
+    if (has_part(CLIPV)) {
         const int C = vcfg.clipv_hidden, I = vcfg.clipv_intermediate, P = vcfg.clipv_patch_size;
         const std::string m = "clipv.vision_model.";
         s.add(m + "embeddings.class_embedding", {C});
         s.add(m + "embeddings.patch_embedding.weight", {C, 3, P, P});
         s.add(m + "embeddings.position_embedding.weight", {clipv_tokens(), C});
         s.norm(m + "pre_layrnorm", C);
-        for (int i = 0; i < vcfg.clipv_layers; ++i) {
-            const std::string l = m + "encoder.layers." + std::to_string(i);
-            for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) s.lin(l + ".self_attn." + n, C, C);
-            s.norm(l + ".layer_norm1", C); s.norm(l + ".layer_norm2", C);
-            s.lin(l + ".mlp.fc1", I, C); s.lin(l + ".mlp.fc2", C, I);
-        }
+        for (int i = 0; i < vcfg.clipv_layers; ++i) s.clip_layer(m + "encoder.layers." + std::to_string(i), C, I);
         s.norm(m + "post_layernorm", C);
         s.lin("clipv.visual_projection", vcfg.clipv_projection_dim, C, false);
     }
@@ -212,7 +217,7 @@ void e2v_ctx::expected_keys() {
     // ---- Seq2Seq latent model ("s2s." prefix; the names of the reference's myTransformer state dict in its order, without what
     // inference never reads -- embedding.weight, img_embedding.*, every num_batches_tracked -- and with the position table as the
     // [windows][d_model] rows that are read, not the [1][5000][d_model] buffer) ----
-    if (scfg.s2s_d_model > 0) {
+    if (has_part(S2S)) {
         const int C = scfg.s2s_d_model, I = scfg.s2s_ffn, FD = scfg.s2s_f1 * scfg.s2s_d;
         const std::string e = "s2s.eeg_embedding.";
         auto bn = [&](const std::string& n, int ch) {
@@ -431,7 +436,8 @@ namespace {
 struct Packer {
     e2v_ctx* c;
     hipStream_t s = nullptr;
-    bool f32_only = false;           // the text encoder: a linear keeps its fp32 matrix and nothing else, in every compute mode
+    bool f32_only = false;           // the part's PartRow::f32_only: a linear keeps its fp32 matrix and nothing else, in every compute mode
+    std::vector<std::string> superseded;     // raw keys whose torch-layout tensor was re-laid out into a block of the part: finalize() releases them
     const WTensor& t(const std::string& k) {
         auto it = c->raw.find(k);
         E2V_REQUIRE(it != c->raw.end(), E2V_ENOWEIGHT, "unknown key " + k);
@@ -533,7 +539,8 @@ struct Packer {
             copy_rows(w.d(), in, d + (size_t)r * in, in, (int)w.shape[0], in, s);
             if (bias) copy_rows(t(n + ".bias").d(), (int)w.shape[0], b + r, (int)w.shape[0], 1, (int)w.shape[0], s);
             bind_lin(n + ".weight", d, r);
-            if (bias) bind_raw(n + ".bias", b + r, 1, (int)w.shape[0]);
+            superseded.push_back(n + ".weight");
+            if (bias) { bind_raw(n + ".bias", b + r, 1, (int)w.shape[0]); superseded.push_back(n + ".bias"); }
             r += (int)w.shape[0];
         }
         return mk_lin(d, b, in, out);
@@ -548,6 +555,7 @@ struct Packer {
         geglu_interleave(w.d(), bsrc.d(), half, in, d, b, s);
         bind_lin(n + ".weight", d, 0, half);
         bind_raw(n + ".bias", b, out / 32, 32, half / 32);       // 32-element groups, interleaved one by one
+        superseded.push_back(n + ".weight"); superseded.push_back(n + ".bias");
         return mk_lin(d, b, in, out);
     }
     ResW resnet(const std::string& p, bool temb) {
@@ -583,267 +591,221 @@ struct Packer {
         w.C = w.norm.c;
         return w;
     }
-};
+    // ---- pieces the towers share ----
+    // a plain table (class token, position rows, token embedding) read where it was loaded
+    const float* table(const std::string& k, int rows, int cols) {
+        const float* d = t(k).d();
+        bind_raw(k, d, rows, cols);
+        return d;
+    }
+    // a patch / tubelet convolution [C][3][(ts)][P][P] is the linear [C][K] over the patch rows as it stands
+    LinW patch_linear(const std::string& n, int C, int K, bool bias) {
+        const WTensor& w = t(n + ".weight");
+        bind_matrix(n + ".weight", w.d(), C, K);
+        if (bias) bind_raw(n + ".bias", t(n + ".bias").d(), 1, C);
+        return mk_lin(w.d(), bias ? t(n + ".bias").d() : nullptr, K, C);
+    }
+    // a head [L][C] + [L] in a block of its own with rows of zeros appended up to a multiple of 4: the linear kernels store quads.
+    // bound: the raw keys are bound to that block, which supersedes them (the classifiers); else they stay bound where they were
+    // loaded (s2s.txtpredictor: the loaded tensors are the ones read back)
+    LinW padded_head(const std::string& wk, const std::string& bk, int L, int C, bool bound) {
+        const int Lp = (L + 3) / 4 * 4;
+        float* d = c->dev_alloc((size_t)Lp * C);
+        float* b = c->dev_alloc(Lp);
+        E2V_HIP(hipMemsetAsync(d, 0, (size_t)Lp * C * sizeof(float), s));
+        E2V_HIP(hipMemsetAsync(b, 0, (size_t)Lp * sizeof(float), s));
+        copy_rows(t(wk).d(), C, d, C, L, C, s);
+        copy_rows(t(bk).d(), L, b, L, 1, L, s);
+        if (bound) {
+            bind_lin(wk, d, 0);
+            bind_raw(bk, b, 1, L);
+            superseded.push_back(wk); superseded.push_back(bk);
+        }
+        return mk_lin(d, b, C, Lp);
+    }
+    LinW classifier(const std::string& n, int L, int C) {
+        return L % 4 == 0 ? lin(n) : padded_head(n + ".weight", n + ".bias", L, C, true);
+    }
+    // a CLIPEncoderLayer under its checkpoint names (text., clipv.) and a transformers ViT / VideoMAE layer (image., video.): one packing
+    TextLayerW clip_layer(const std::string& l) {
+        TextLayerW w;
+        w.ln1 = norm(l + ".layer_norm1"); w.ln2 = norm(l + ".layer_norm2");
+        w.qkv = fuse_rows({l + ".self_attn.q_proj", l + ".self_attn.k_proj", l + ".self_attn.v_proj"}, true);
+        w.out = lin(l + ".self_attn.out_proj");
+        w.fc1 = lin(l + ".mlp.fc1"); w.fc2 = lin(l + ".mlp.fc2");
+        return w;
+    }
+    TextLayerW encoder_layer(const std::string& l) {
+        TextLayerW w;
+        w.ln1 = norm(l + ".layernorm_before"); w.ln2 = norm(l + ".layernorm_after");
+        w.qkv = fuse_rows({l + ".attention.attention.query", l + ".attention.attention.key", l + ".attention.attention.value"}, true);
+        w.out = lin(l + ".attention.output.dense");
+        w.fc1 = lin(l + ".intermediate.dense"); w.fc2 = lin(l + ".output.dense");
+        return w;
+    }
 
-}  // namespace
-
-void e2v_ctx::finalize(int which) {
-    Packer P{this};
-    const int L = cfg.layers_per_block;
-    AllocPart part_guard(this, -1);                  // (an error below leaves no part selected)
-    // everything that can refuse the call is checked BEFORE a part is freed: a failed finalize leaves the context as it was
-    E2V_REQUIRE(!(which & 4) || (cfg.sem_in_features > 0 && cfg.sem_hidden > 0), E2V_ESTATE, "the config has no semantic predictor");
-    E2V_REQUIRE(!(which & 8) || cfg.text_layers > 0, E2V_ESTATE, "the config has no text encoder (text_layers = 0)");
-    E2V_REQUIRE(!(which & 16) || cfg.vit_layers > 0, E2V_ESTATE, "the config has no image classifier (vit_layers = 0)");
-    E2V_REQUIRE(!(which & 32) || cfg.vmae_layers > 0, E2V_ESTATE, "the config has no video classifier (vmae_layers = 0)");
-    E2V_REQUIRE(!(which & 64) || vcfg.clipv_layers > 0, E2V_ESTATE, "the context has no CLIP vision tower (e2v_create_clip_vision)");
-    E2V_REQUIRE(!(which & 128) || !dry_run(), E2V_ESTATE, "the Seq2Seq latent model has no dry run");
-    for (const auto& k : keys)
-        if (which & key_part(k)) P.t(k);
-    E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
-    if (which & 1) {
-        free_part(0);
-        alloc_part = 0;
+    // ---- one packing function per part (e2v_ctx::kParts; finalize() dispatches through pack) ----
+    void pack_unet() {
+        const int L = c->cfg.layers_per_block;
         UNetW u;
-        u.conv_in = P.conv3("conv_in");
-        u.te1 = P.lin("time_embedding.linear_1"); u.te2 = P.lin("time_embedding.linear_2");
+        u.conv_in = conv3("conv_in");
+        u.te1 = lin("time_embedding.linear_1"); u.te2 = lin("time_embedding.linear_2");
         for (int i = 0; i < 4; ++i) {
             UNetW::Block b;
             for (int j = 0; j < L; ++j) {
-                b.res.push_back(P.resnet(idx("down_blocks", i, "resnets", j), true));
-                if (i < 3) b.attn.push_back(P.transformer(idx("down_blocks", i, "attentions", j)));
+                b.res.push_back(resnet(idx("down_blocks", i, "resnets", j), true));
+                if (i < 3) b.attn.push_back(transformer(idx("down_blocks", i, "attentions", j)));
             }
-            if (i != 3) { b.resample = true; b.rs = P.conv3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
+            if (i != 3) { b.resample = true; b.rs = conv3("down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
             u.down.push_back(std::move(b));
         }
-        u.mid_r0 = P.resnet("mid_block.resnets.0", true);
-        u.mid_attn = P.transformer("mid_block.attentions.0");
-        u.mid_r1 = P.resnet("mid_block.resnets.1", true);
+        u.mid_r0 = resnet("mid_block.resnets.0", true);
+        u.mid_attn = transformer("mid_block.attentions.0");
+        u.mid_r1 = resnet("mid_block.resnets.1", true);
         for (int i = 0; i < 4; ++i) {
             UNetW::Block b;
             for (int j = 0; j < L + 1; ++j) {
-                b.res.push_back(P.resnet(idx("up_blocks", i, "resnets", j), true));
-                if (i > 0) b.attn.push_back(P.transformer(idx("up_blocks", i, "attentions", j)));
+                b.res.push_back(resnet(idx("up_blocks", i, "resnets", j), true));
+                if (i > 0) b.attn.push_back(transformer(idx("up_blocks", i, "attentions", j)));
             }
-            if (i != 3) { b.resample = true; b.rs = P.conv3("up_blocks." + std::to_string(i) + ".upsamplers.0.conv"); }
+            if (i != 3) { b.resample = true; b.rs = conv3("up_blocks." + std::to_string(i) + ".upsamplers.0.conv"); }
             u.up.push_back(std::move(b));
         }
-        u.norm_out = P.norm("conv_norm_out");
-        u.conv_out = P.conv3("conv_out");
-        unet = std::move(u);
+        u.norm_out = norm("conv_norm_out");
+        u.conv_out = conv3("conv_out");
+        c->unet = std::move(u);
     }
-    if (which & 2) {
-        free_part(1);
-        alloc_part = 1;
+    void pack_vae() {
         VAEW v;
-        const int VL = cfg.vae_layers_per_block;
-        v.post_quant = P.lin("vae.post_quant_conv");
-        v.dec_in = P.conv3("vae.decoder.conv_in");
-        v.dec_mid0 = P.resnet("vae.decoder.mid_block.resnets.0", false);
-        v.dec_attn = P.vae_attn("vae.decoder.mid_block.attentions.0");
-        v.dec_mid1 = P.resnet("vae.decoder.mid_block.resnets.1", false);
+        const int VL = c->cfg.vae_layers_per_block;
+        v.post_quant = lin("vae.post_quant_conv");
+        v.dec_in = conv3("vae.decoder.conv_in");
+        v.dec_mid0 = resnet("vae.decoder.mid_block.resnets.0", false);
+        v.dec_attn = vae_attn("vae.decoder.mid_block.attentions.0");
+        v.dec_mid1 = resnet("vae.decoder.mid_block.resnets.1", false);
         for (int i = 0; i < 4; ++i) {
             VAEW::Block b;
-            for (int j = 0; j < VL + 1; ++j) b.res.push_back(P.resnet(idx("vae.decoder.up_blocks", i, "resnets", j), false));
-            if (i != 3) { b.resample = true; b.rs = P.conv3("vae.decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv"); }
+            for (int j = 0; j < VL + 1; ++j) b.res.push_back(resnet(idx("vae.decoder.up_blocks", i, "resnets", j), false));
+            if (i != 3) { b.resample = true; b.rs = conv3("vae.decoder.up_blocks." + std::to_string(i) + ".upsamplers.0.conv"); }
             v.dec_up.push_back(std::move(b));
         }
-        v.dec_norm_out = P.norm("vae.decoder.conv_norm_out");
-        v.dec_out = P.conv3("vae.decoder.conv_out");
-        v.quant = P.lin("vae.quant_conv");
-        v.enc_in = P.conv3("vae.encoder.conv_in");
+        v.dec_norm_out = norm("vae.decoder.conv_norm_out");
+        v.dec_out = conv3("vae.decoder.conv_out");
+        v.quant = lin("vae.quant_conv");
+        v.enc_in = conv3("vae.encoder.conv_in");
         for (int i = 0; i < 4; ++i) {
             VAEW::Block b;
-            for (int j = 0; j < VL; ++j) b.res.push_back(P.resnet(idx("vae.encoder.down_blocks", i, "resnets", j), false));
-            if (i != 3) { b.resample = true; b.rs = P.conv3("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
+            for (int j = 0; j < VL; ++j) b.res.push_back(resnet(idx("vae.encoder.down_blocks", i, "resnets", j), false));
+            if (i != 3) { b.resample = true; b.rs = conv3("vae.encoder.down_blocks." + std::to_string(i) + ".downsamplers.0.conv"); }
             v.enc_down.push_back(std::move(b));
         }
-        v.enc_mid0 = P.resnet("vae.encoder.mid_block.resnets.0", false);
-        v.enc_attn = P.vae_attn("vae.encoder.mid_block.attentions.0");
-        v.enc_mid1 = P.resnet("vae.encoder.mid_block.resnets.1", false);
-        v.enc_norm_out = P.norm("vae.encoder.conv_norm_out");
-        v.enc_out = P.conv3("vae.encoder.conv_out");
-        vae = std::move(v);
+        v.enc_mid0 = resnet("vae.encoder.mid_block.resnets.0", false);
+        v.enc_attn = vae_attn("vae.encoder.mid_block.attentions.0");
+        v.enc_mid1 = resnet("vae.encoder.mid_block.resnets.1", false);
+        v.enc_norm_out = norm("vae.encoder.conv_norm_out");
+        v.enc_out = conv3("vae.encoder.conv_out");
+        c->vae = std::move(v);
     }
-    if (which & 4) {
-        free_part(2);
-        alloc_part = 2;
-        sem.clear();
+    void pack_sem() {
+        const e2v_config& cfg = c->cfg;
+        c->sem.clear();
         // the first layer's K (310) is padded to a multiple of 8 (320 -> 312 would do for fp32's 16-byte rows, but the bf16
         // tile reads 8-element pieces): pad FIRST, then derive the bf16 / split copies from the padded matrix so that every
-        // form of the layer has the same row length
-        sem_in_pad = (cfg.sem_in_features + 7) / 8 * 8;
+        // form of the layer has the same row length.  The loaded matrix stays: nothing of this part is superseded.
+        c->sem_in_pad = (cfg.sem_in_features + 7) / 8 * 8;
         for (int i = 0; i < 5; ++i) {
             const std::string n = "semantic.mlp." + std::to_string(2 * i);
-            if (i == 0 && sem_in_pad != cfg.sem_in_features) {
-                const WTensor& w = P.t(n + ".weight");
+            if (i == 0 && c->sem_in_pad != cfg.sem_in_features) {
+                const WTensor& w = t(n + ".weight");
                 const int out = (int)w.shape[0];
-                float* wp = dev_alloc((size_t)out * sem_in_pad);
-                pad_cols(w.d(), cfg.sem_in_features, wp, sem_in_pad, out, nullptr);
-                P.bind_lin(n + ".weight", wp, 0);
-                P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, out);
-                sem.push_back(P.mk_lin(wp, P.t(n + ".bias").d(), sem_in_pad, out));
+                float* wp = c->dev_alloc((size_t)out * c->sem_in_pad);
+                pad_cols(w.d(), cfg.sem_in_features, wp, c->sem_in_pad, out, nullptr);
+                bind_lin(n + ".weight", wp, 0);
+                bind_raw(n + ".bias", t(n + ".bias").d(), 1, out);
+                c->sem.push_back(mk_lin(wp, t(n + ".bias").d(), c->sem_in_pad, out));
             } else {
-                sem.push_back(P.lin(n));
+                c->sem.push_back(lin(n));
             }
         }
     }
-    // a CLIPEncoderLayer under its checkpoint names: the text tower's (part 8) and the vision tower's (part 64)
-    auto clip_layer = [&](const std::string& l) {
-        TextLayerW w;
-        w.ln1 = P.norm(l + ".layer_norm1"); w.ln2 = P.norm(l + ".layer_norm2");
-        w.qkv = P.fuse_rows({l + ".self_attn.q_proj", l + ".self_attn.k_proj", l + ".self_attn.v_proj"}, true);
-        w.out = P.lin(l + ".self_attn.out_proj");
-        w.fc1 = P.lin(l + ".mlp.fc1"); w.fc2 = P.lin(l + ".mlp.fc2");
-        return w;
-    };
-    if (which & 8) {
-        free_part(3);
-        alloc_part = 3;
-        P.f32_only = true;
-        TextW t;
+    void pack_text() {
+        const e2v_config& cfg = c->cfg;
+        TextW w;
         const std::string m = "text.text_model.";
-        const WTensor& tok = P.t(m + "embeddings.token_embedding.weight");
-        const WTensor& pos = P.t(m + "embeddings.position_embedding.weight");
-        t.tok = tok.d(); t.pos = pos.d();
-        P.bind_raw(m + "embeddings.token_embedding.weight", tok.d(), (int)tok.shape[0], (int)tok.shape[1]);
-        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), (int)pos.shape[0], (int)pos.shape[1]);
-        for (int i = 0; i < cfg.text_layers; ++i) t.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
-        t.ln_f = P.norm(m + "final_layer_norm");
-        P.f32_only = false;
-        text = std::move(t);
+        w.tok = table(m + "embeddings.token_embedding.weight", cfg.text_vocab_size, cfg.text_hidden);
+        w.pos = table(m + "embeddings.position_embedding.weight", cfg.text_max_positions, cfg.text_hidden);
+        for (int i = 0; i < cfg.text_layers; ++i) w.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
+        w.ln_f = norm(m + "final_layer_norm");
+        c->text = std::move(w);
     }
-    // what the two classifiers (parts 16 and 32) share: a transformers encoder layer in the text tower's packing, and the classifier
-    // [L][C] as a linear whose row count is a multiple of 4 -- rows of zeros appended: the linear kernels store quads
-    auto encoder_layer = [&](const std::string& l) {
-        TextLayerW w;
-        w.ln1 = P.norm(l + ".layernorm_before"); w.ln2 = P.norm(l + ".layernorm_after");
-        w.qkv = P.fuse_rows({l + ".attention.attention.query", l + ".attention.attention.key", l + ".attention.attention.value"}, true);
-        w.out = P.lin(l + ".attention.output.dense");
-        w.fc1 = P.lin(l + ".intermediate.dense"); w.fc2 = P.lin(l + ".output.dense");
-        return w;
-    };
-    auto classifier_head = [&](const std::string& n, int L, int C) {
-        if (L % 4 == 0) return P.lin(n);
-        const int Lp = (L + 3) / 4 * 4;
-        const WTensor& w = P.t(n + ".weight");
-        float* d = dev_alloc((size_t)Lp * C);
-        float* b = dev_alloc(Lp);
-        E2V_HIP(hipMemsetAsync(d, 0, (size_t)Lp * C * sizeof(float), P.s));
-        E2V_HIP(hipMemsetAsync(b, 0, (size_t)Lp * sizeof(float), P.s));
-        copy_rows(w.d(), C, d, C, L, C, P.s);
-        copy_rows(P.t(n + ".bias").d(), L, b, L, 1, L, P.s);
-        P.bind_lin(n + ".weight", d, 0);
-        P.bind_raw(n + ".bias", b, 1, L);
-        return P.mk_lin(d, b, C, Lp);
-    };
-    if (which & 16) {
-        free_part(4);
-        alloc_part = 4;
-        P.f32_only = true;
-        ImageW v;
+    void pack_image() {
+        const e2v_config& cfg = c->cfg;
+        VisionTowerW v;
         const std::string m = "image.vit.";
-        const int C = cfg.vit_hidden, T = image_tokens(), K = 3 * cfg.vit_patch_size * cfg.vit_patch_size, L = cfg.vit_num_labels;
-        const WTensor& cls = P.t(m + "embeddings.cls_token");
-        const WTensor& pos = P.t(m + "embeddings.position_embeddings");
-        v.cls = cls.d(); v.pos = pos.d();
-        P.bind_raw(m + "embeddings.cls_token", cls.d(), 1, C);
-        P.bind_raw(m + "embeddings.position_embeddings", pos.d(), T, C);
-        {   // the patch convolution [C][3][P][P] is the linear [C][3 P P] over the patch rows as it stands
-            const std::string n = m + "embeddings.patch_embeddings.projection";
-            const WTensor& w = P.t(n + ".weight");
-            P.bind_matrix(n + ".weight", w.d(), C, K);
-            P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
-            v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
-        }
-        for (int i = 0; i < cfg.vit_layers; ++i) {
-            v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
-        }
-        v.ln_f = P.norm(m + "layernorm");
-        v.head = classifier_head("image.classifier", L, C);
-        P.f32_only = false;
-        image = std::move(v);
+        const int C = cfg.vit_hidden;
+        v.cls = table(m + "embeddings.cls_token", 1, C);
+        v.pos = table(m + "embeddings.position_embeddings", c->image_tokens(), C);
+        v.patch = patch_linear(m + "embeddings.patch_embeddings.projection", C, 3 * cfg.vit_patch_size * cfg.vit_patch_size, true);
+        for (int i = 0; i < cfg.vit_layers; ++i) v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
+        v.head_ln = norm(m + "layernorm");
+        v.head = classifier("image.classifier", cfg.vit_num_labels, C);
+        c->image = std::move(v);
     }
-    if (which & 32) {
-        free_part(5);
-        alloc_part = 5;
-        P.f32_only = true;
-        VideoW v;
+    void pack_video() {
+        const e2v_config& cfg = c->cfg;
+        VisionTowerW v;
         const std::string m = "video.videomae.";
-        const int C = cfg.vmae_hidden, T = video_tokens(), L = cfg.vmae_num_labels;
-        const int K = 3 * cfg.vmae_tubelet_size * cfg.vmae_patch_size * cfg.vmae_patch_size;
-        const WTensor& pos = P.t(m + "embeddings.position_embeddings");
-        v.pos = pos.d();
-        P.bind_raw(m + "embeddings.position_embeddings", pos.d(), T, C);
-        {   // the tubelet convolution [C][3][ts][P][P] is the linear [C][3 ts P P] over the patch rows as it stands
-            const std::string n = m + "embeddings.patch_embeddings.projection";
-            const WTensor& w = P.t(n + ".weight");
-            P.bind_matrix(n + ".weight", w.d(), C, K);
-            P.bind_raw(n + ".bias", P.t(n + ".bias").d(), 1, C);
-            v.patch = P.mk_lin(w.d(), P.t(n + ".bias").d(), K, C);
-        }
-        for (int i = 0; i < cfg.vmae_layers; ++i) {
-            v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
-        }
-        v.fc_norm = P.norm("video.fc_norm");
-        v.head = classifier_head("video.classifier", L, C);
-        P.f32_only = false;
-        video = std::move(v);
+        const int C = cfg.vmae_hidden;
+        v.pos = table(m + "embeddings.position_embeddings", c->video_tokens(), C);
+        v.patch = patch_linear(m + "embeddings.patch_embeddings.projection", C,
+                               3 * cfg.vmae_tubelet_size * cfg.vmae_patch_size * cfg.vmae_patch_size, true);
+        for (int i = 0; i < cfg.vmae_layers; ++i) v.layers.push_back(encoder_layer(m + "encoder.layer." + std::to_string(i)));
+        v.head_ln = norm("video.fc_norm");
+        v.head = classifier("video.classifier", cfg.vmae_num_labels, C);
+        c->video = std::move(v);
     }
-    if (which & 64) {
-        free_part(6);
-        alloc_part = 6;
-        P.f32_only = true;
-        ClipVW v;
+    void pack_clipv() {
+        const e2v_clipv_config& cfg = c->vcfg;
+        VisionTowerW v;
         const std::string m = "clipv.vision_model.";
-        const int C = vcfg.clipv_hidden, T = clipv_tokens(), K = 3 * vcfg.clipv_patch_size * vcfg.clipv_patch_size;
-        const WTensor& cls = P.t(m + "embeddings.class_embedding");
-        const WTensor& pos = P.t(m + "embeddings.position_embedding.weight");
-        v.cls = cls.d(); v.pos = pos.d();
-        P.bind_raw(m + "embeddings.class_embedding", cls.d(), 1, C);
-        P.bind_raw(m + "embeddings.position_embedding.weight", pos.d(), T, C);
-        {   // the patch convolution [C][3][P][P] (no bias) is the linear [C][3 P P] over the patch rows as it stands
-            const WTensor& w = P.t(m + "embeddings.patch_embedding.weight");
-            P.bind_matrix(m + "embeddings.patch_embedding.weight", w.d(), C, K);
-            v.patch = P.mk_lin(w.d(), nullptr, K, C);
-        }
-        v.pre_ln = P.norm(m + "pre_layrnorm");
-        for (int i = 0; i < vcfg.clipv_layers; ++i) v.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
-        v.post_ln = P.norm(m + "post_layernorm");
-        v.proj = P.lin("clipv.visual_projection", false);
-        P.f32_only = false;
-        clipv = std::move(v);
+        const int C = cfg.clipv_hidden;
+        v.cls = table(m + "embeddings.class_embedding", 1, C);
+        v.pos = table(m + "embeddings.position_embedding.weight", c->clipv_tokens(), C);
+        v.patch = patch_linear(m + "embeddings.patch_embedding", C, 3 * cfg.clipv_patch_size * cfg.clipv_patch_size, false);
+        v.pre_ln = norm(m + "pre_layrnorm");
+        for (int i = 0; i < cfg.clipv_layers; ++i) v.layers.push_back(clip_layer(m + "encoder.layers." + std::to_string(i)));
+        v.head_ln = norm(m + "post_layernorm");
+        v.head = lin("clipv.visual_projection", false);
+        c->clipv = std::move(v);
     }
-    if (which & 128) {
-        free_part(7);
-        alloc_part = 7;
-        P.f32_only = true;
+    void pack_s2s() {
+        const e2v_s2s_config& scfg = c->scfg;
         S2sW v;
         const int C = scfg.s2s_d_model, F1 = scfg.s2s_f1, D = scfg.s2s_d, F2 = scfg.s2s_f2, E = scfg.s2s_electrodes;
         // every tensor stays where e2v_load_tensor put it and is read back from there: a matrix is used as it stands, in_proj as views
         auto keep = [&](const std::string& k) -> const WTensor& {
-            const WTensor& t = P.t(k);
-            const int rows = t.shape.size() > 1 ? (int)t.shape[0] : 1;
-            P.bind_raw(k, t.d(), rows, (int)(t.numel / (size_t)rows));
-            return t;
+            const WTensor& w = t(k);
+            const int rows = w.shape.size() > 1 ? (int)w.shape[0] : 1;
+            bind_raw(k, w.d(), rows, (int)(w.numel / (size_t)rows));
+            return w;
         };
-        auto lin = [&](const std::string& n) {
+        auto klin = [&](const std::string& n) {
             const WTensor& w = keep(n + ".weight");
-            return P.mk_lin(w.d(), keep(n + ".bias").d(), (int)w.shape[1], (int)w.shape[0]);
+            return mk_lin(w.d(), keep(n + ".bias").d(), (int)w.shape[1], (int)w.shape[0]);
         };
-        auto norm = [&](const std::string& n) { return NormW{keep(n + ".weight").d(), keep(n + ".bias").d(), C}; };
+        auto knorm = [&](const std::string& n) { return NormW{keep(n + ".weight").d(), keep(n + ".bias").d(), C}; };
         {   // the EEGNet embedding: the four convs and the three BatchNorms (eval mode: running statistics) folded on the host
             const std::string e = "s2s.eeg_embedding.";
             auto host = [&](const std::string& k) {
-                const WTensor& t = keep(k);
-                std::vector<float> h(t.numel);
-                E2V_HIP(hipMemcpy(h.data(), t.d(), t.numel * sizeof(float), hipMemcpyDeviceToHost));
+                const WTensor& w = keep(k);
+                std::vector<float> h(w.numel);
+                E2V_HIP(hipMemcpy(h.data(), w.d(), w.numel * sizeof(float), hipMemcpyDeviceToHost));
                 return h;
             };
             auto host_bn = [&](const std::string& n) {
                 std::vector<float> h;
-                for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) {
-                    const std::vector<float> part = host(n + t);
+                for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) {
+                    const std::vector<float> part = host(n + f);
                     h.insert(h.end(), part.begin(), part.end());
                 }
                 return h;
@@ -859,104 +821,87 @@ void e2v_ctx::finalize(int which) {
                 E2V_REQUIRE(bn3[3 * F2 + i] + scfg.s2s_bn_eps > 0.f, E2V_EINVAL, "s2s.eeg_embedding.block_3.3.running_var + eps must be positive");
             const std::vector<float> pk = eegnet_pack(EegnetHostW{w1.data(), bn1.data(), w2.data(), bn2.data(), w3.data(), w4.data(), bn3.data()},
                                                       E, F1, D, F2, scfg.s2s_bn_eps);
-            float* d = dev_alloc(pk.size());
+            float* d = c->dev_alloc(pk.size());
             E2V_HIP(hipMemcpy(d, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
             v.eegnet = d;
-            v.embed = lin(e + "embedding");
+            v.embed = klin(e + "embedding");
         }
         v.pe = keep("s2s.positional_encoding.pe").d();
         // nn.MultiheadAttention: in_proj whole (self-attention) or as its q rows and its k | v rows (cross-attention)
         auto in_proj = [&](const std::string& n, int row0, int rows) {
             const WTensor& w = keep(n + ".in_proj_weight");
             const WTensor& b = keep(n + ".in_proj_bias");
-            return P.mk_lin(w.d() + (size_t)row0 * C, b.d() + row0, C, rows);
+            return mk_lin(w.d() + (size_t)row0 * C, b.d() + row0, C, rows);
         };
         for (int i = 0; i < scfg.s2s_encoder_layers; ++i) {
             const std::string l = "s2s.transformer_encoder.layers." + std::to_string(i);
             S2sEncLayerW w;
-            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = lin(l + ".self_attn.out_proj");
-            w.fc1 = lin(l + ".linear1"); w.fc2 = lin(l + ".linear2");
-            w.ln1 = norm(l + ".norm1"); w.ln2 = norm(l + ".norm2");
+            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = klin(l + ".self_attn.out_proj");
+            w.fc1 = klin(l + ".linear1"); w.fc2 = klin(l + ".linear2");
+            w.ln1 = knorm(l + ".norm1"); w.ln2 = knorm(l + ".norm2");
             v.enc.push_back(w);
         }
         for (int i = 0; i < scfg.s2s_decoder_layers; ++i) {
             const std::string l = "s2s.transformer_decoder.layers." + std::to_string(i);
             S2sDecLayerW w;
-            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = lin(l + ".self_attn.out_proj");
+            w.qkv = in_proj(l + ".self_attn", 0, 3 * C); w.out = klin(l + ".self_attn.out_proj");
             w.q2 = in_proj(l + ".multihead_attn", 0, C); w.kv2 = in_proj(l + ".multihead_attn", C, 2 * C);
-            w.out2 = lin(l + ".multihead_attn.out_proj");
-            w.fc1 = lin(l + ".linear1"); w.fc2 = lin(l + ".linear2");
-            w.ln1 = norm(l + ".norm1"); w.ln2 = norm(l + ".norm2"); w.ln3 = norm(l + ".norm3");
+            w.out2 = klin(l + ".multihead_attn.out_proj");
+            w.fc1 = klin(l + ".linear1"); w.fc2 = klin(l + ".linear2");
+            w.ln1 = knorm(l + ".norm1"); w.ln2 = knorm(l + ".norm2"); w.ln3 = knorm(l + ".norm3");
             v.dec.push_back(w);
         }
-        {   // txtpredictor: the classifiers' padding to whole quads of rows, in a block of its own; the loaded tensors stay the ones read back
-            const int L = scfg.s2s_txt_classes, Lp = (L + 3) / 4 * 4;
-            const WTensor& w = keep("s2s.txtpredictor.weight");
-            const WTensor& b = keep("s2s.txtpredictor.bias");
-            float* dw = dev_alloc((size_t)Lp * C);
-            float* db = dev_alloc(Lp);
-            E2V_HIP(hipMemsetAsync(dw, 0, (size_t)Lp * C * sizeof(float), P.s));
-            E2V_HIP(hipMemsetAsync(db, 0, (size_t)Lp * sizeof(float), P.s));
-            copy_rows(w.d(), C, dw, C, L, C, P.s);
-            copy_rows(b.d(), L, db, L, 1, L, P.s);
-            v.txt = P.mk_lin(dw, db, C, Lp);
+        keep("s2s.txtpredictor.weight"); keep("s2s.txtpredictor.bias");
+        v.txt = padded_head("s2s.txtpredictor.weight", "s2s.txtpredictor.bias", scfg.s2s_txt_classes, C, false);
+        v.pred = klin("s2s.predictor");
+        c->s2s = std::move(v);
+    }
+    void pack(e2v_ctx::Part p) {
+        switch (p) {
+            case e2v_ctx::UNET: pack_unet(); break;
+            case e2v_ctx::VAE: pack_vae(); break;
+            case e2v_ctx::SEM: pack_sem(); break;
+            case e2v_ctx::TEXT: pack_text(); break;
+            case e2v_ctx::IMAGE: pack_image(); break;
+            case e2v_ctx::VIDEO: pack_video(); break;
+            case e2v_ctx::CLIPV: pack_clipv(); break;
+            case e2v_ctx::S2S: pack_s2s(); break;
+            case e2v_ctx::N_PARTS: break;
         }
-        v.pred = lin("s2s.predictor");
-        P.f32_only = false;
-        s2s = std::move(v);
+    }
+};
+
+}  // namespace
+
+void e2v_ctx::finalize(int which) {
+    Packer P{this};
+    AllocPart part_guard(this, -1);                  // (an error below leaves no part selected)
+    // everything that can refuse the call is checked BEFORE a part is freed: a failed finalize leaves the context as it was
+    for (int p = 0; p < N_PARTS; ++p)
+        if (which & kParts[p].bit) require_part((Part)p);
+    E2V_REQUIRE(!(which & kParts[S2S].bit) || !dry_run(), E2V_ESTATE, "the Seq2Seq latent model has no dry run");
+    for (const auto& k : keys)
+        if (which & kParts[key_part(k)].bit) P.t(k);
+    E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
+    for (int p = 0; p < N_PARTS; ++p) {
+        if (!(which & kParts[p].bit)) continue;
+        free_part(p);
+        alloc_part = p;
+        P.f32_only = kParts[p].f32_only;
+        P.pack((Part)p);
     }
     alloc_part = -1;
     resolve_bindings();
     E2V_HIP(hipStreamSynchronize(nullptr));
     E2V_HIP(hipGetLastError());
-    if (dry_run()) {                                         // nothing was allocated: nothing to drop
-        if (which & 1) unet_ready = true;
-        if (which & 2) vae_ready = true;
-        return;
-    }
-    // the torch-layout copies of re-laid-out tensors are no longer needed
-    auto drop = [&](const std::string& k) {
-        auto it = raw.find(k);
-        if (it != raw.end() && it->second.mem) {
-            it->second.mem.release();
-            it->second.loaded = false;
+    if (dry_run()) which &= kParts[UNET].bit | kParts[VAE].bit;      // nothing was allocated, nothing to drop; a dry run describes these two only
+    else
+        for (const std::string& k : P.superseded) {  // the torch-layout copies of re-laid-out tensors are no longer needed
+            WTensor& w = raw.at(k);
+            if (w.mem) { w.mem.release(); w.loaded = false; }
         }
-    };
-    for (const auto& k : keys) {
-        const int part = key_part(k);
-        if (part == 4 || !(which & part)) continue;
-        if (part == 8) {                         // q / k / v projections live on in the fused matrix and bias
-            if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
-            continue;
-        }
-        if (part == 16) {                        // the same for query / key / value, and for a classifier that was padded
-            if (k.find(".attention.attention.") != std::string::npos || (k.rfind("image.classifier.", 0) == 0 && cfg.vit_num_labels % 4 != 0)) drop(k);
-            continue;
-        }
-        if (part == 32) {
-            if (k.find(".attention.attention.") != std::string::npos || (k.rfind("video.classifier.", 0) == 0 && cfg.vmae_num_labels % 4 != 0)) drop(k);
-            continue;
-        }
-        if (part == 64) {                        // as the text tower
-            if (k.find(".q_proj.") != std::string::npos || k.find(".k_proj.") != std::string::npos || k.find(".v_proj.") != std::string::npos) drop(k);
-            continue;
-        }
-        if (part == 128) continue;               // every tensor of the Seq2Seq model is read where it was loaded
-        const bool fused = k.find(".to_q.") != std::string::npos || k.find(".to_k.") != std::string::npos ||
-                           k.find(".to_v.") != std::string::npos || k.find(".ff.net.0.proj.") != std::string::npos ||
-                           k.find(".query.") != std::string::npos || k.find(".key.") != std::string::npos ||
-                           k.find(".value.") != std::string::npos;
-        const bool keep_q = k.find(".attn2.to_q.") != std::string::npos;
-        if (fused && !keep_q) drop(k);          // (3x3 conv weights stay: their kernel layouts are derived from them on first use)
-    }
-    if (which & 1) unet_ready = true;
-    if (which & 2) vae_ready = true;
-    if (which & 4) sem_ready = true;
-    if (which & 8) text_ready = true;
-    if (which & 16) image_ready = true;
-    if (which & 32) video_ready = true;
-    if (which & 64) clipv_ready = true;
-    if (which & 128) s2s_ready = true;
+    for (int p = 0; p < N_PARTS; ++p)
+        if (which & kParts[p].bit) ready[p] = true;
 }
 
 // =====================================================================================================
@@ -1003,12 +948,10 @@ void e2v_ctx::resolve_bindings() {
     visit(vae, fl, fc);
     for (auto& l : sem) fl(l);
     for (auto& l : text.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
-    for (auto& l : image.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
-    fl(image.patch); fl(image.head);
-    for (auto& l : video.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
-    fl(video.patch); fl(video.head);
-    for (auto& l : clipv.layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
-    fl(clipv.patch); fl(clipv.proj);
+    for (VisionTowerW* v : {&image, &video, &clipv}) {
+        for (auto& l : v->layers) { fl(l.qkv); fl(l.out); fl(l.fc1); fl(l.fc2); }
+        fl(v->patch); fl(v->head);
+    }
     for (auto& kv : bind) {
         WBind& b = kv.second;
         if (b.kind == WBind::LIN) { auto it = lins.find(b.anchor); b.lin = it != lins.end() ? it->second : nullptr; }
@@ -1536,7 +1479,7 @@ int down_size(int x) { return (x - 1) / 2 + 1; }     // 3x3, stride 2, padding 1
 // -----------------------------------------------------------------------------------------------------
 Act e2v_ctx::unet_forward_cl(const float* sample_cl, const int64_t* host_t, int n_t, const float* cond, int N, int F,
                              int H, int W, int T, hipStream_t s, bool cfg_pair, const float* host_tf) {
-    E2V_REQUIRE(unet_ready, E2V_ESTATE, "UNet weights are not finalized");
+    require_ready(UNET);
     E2V_REQUIRE(n_t == 1 || n_t == N, E2V_EINVAL, "timesteps must have 1 or N entries");
     // cfg_pair: `sample_cl` holds N / 2 samples standing for [x ; x] (one timestep): everything before the first use of the
     // conditioning -- conv_in, the first resnet, the first transformer block up to its cross-attention -- is computed once
@@ -1710,7 +1653,7 @@ void e2v_ctx::build_step_caches(const EvalTime* ev, int steps, const float* cond
 // AutoencoderKL (diffusers 0.11.1).  Images are independent: "samples" = frames, F = 1.
 // -----------------------------------------------------------------------------------------------------
 void e2v_ctx::vae_decode_frames(const float* z_cl, int nf, int h, int w, float* out_cl, hipStream_t s, bool small) {
-    E2V_REQUIRE(vae_ready, E2V_ESTATE, "VAE weights are not finalized");
+    require_ready(VAE);
     Runner R{this, s, small};                                 // the CALL decodes at most four clips (the caller knows: a pass may be a call's ragged last group)
     const int g = cfg.vae_norm_num_groups;
     const float eps = cfg.vae_norm_eps;
@@ -1752,7 +1695,7 @@ void e2v_ctx::vae_decode_frames(const float* z_cl, int nf, int h, int w, float* 
 }
 
 void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, float* moments_cl, hipStream_t s) {
-    E2V_REQUIRE(vae_ready, E2V_ESTATE, "VAE weights are not finalized");
+    require_ready(VAE);
     Runner R{this, s, n <= 12};                               // frames, whatever E2V_SMALL_FAMILY_CLIPS says (ADVICE.md finding 2 would derive it from the knob)
     const int g = cfg.vae_norm_num_groups;
     const float eps = cfg.vae_norm_eps;
@@ -1789,7 +1732,8 @@ void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, flo
 
 // -----------------------------------------------------------------------------------------------------
 // The encoder layers of a metric tower (parts 16 / 32 / 64: pre-LN, no mask, head dim 64) over n sequences of T token rows, in the
-// mode of the tower the runner serves (Runner::tower, e2v_set_tower_dtype) -- ONE body for the three modes:
+// mode of the tower the runner serves (Runner::tower, e2v_set_tower_dtype) -- ONE body for the three modes, and in its fp32 form, with
+// the causal kernel as `attn32`, the layers of the text encoder (text_encode):
 //   fp32 (0)    fp32 rows, the linears as the time-embedding MLP takes them (f32_rows), attention by `attn32` (the tower's fp32 kernel);
 //   bf16 / fp16 the token rows live in HBM as 16-bit; LayerNorm is the 16-bit kernel (fp32 statistics, the tower's eps); the linears
 //               are 16-bit MFMA with fp32 accumulation, fp32 bias and residual added before the one store rounding; the activation is
@@ -1846,29 +1790,118 @@ void tower_head_ln(const Runner& R, const NormW& w, const float* x, int ldx, boo
 // time-embedding MLP), so the same ids give the same bits in every mode.
 // -----------------------------------------------------------------------------------------------------
 void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t s) {
-    E2V_REQUIRE(text_ready, E2V_ESTATE, "text encoder weights are not finalized");
+    require_ready(TEXT);
     Runner R{this, s, false};
-    const int C = cfg.text_hidden, I = cfg.text_intermediate;
+    R.tower = H16_NONE;                                          // tower_layers in its fp32 form: fp32 rows, the fp32 LayerNorm and activation
+    const int C = cfg.text_hidden;                               // = 64 * text_heads (e2v_create refuses any other): the width tower_layers derives
     const int64_t M = (int64_t)B * T;
-    const float eps = cfg.text_norm_eps;
-    auto ln = [&](const NormW& w, const float* x, float* y) { layernorm(x, C, w.g, w.b, y, C, (int)M, C, eps, s); };
-    auto plus = [&](const Act& x) { LinOpt o = R.f32_rows(); o.resid = x.p; o.ldr = C; return o; };
     Act x(pool, M, C);
     text_embed(ids, text.tok, text.pos, x.p, (int)M, T, C, s);
-    for (const TextLayerW& l : text.layers) {
-        Act h(pool, M, C);
-        ln(l.ln1, x.p, h.p);
-        Act qkv = R.linear(l.qkv, h.p, C, M, R.f32_rows());
-        Act a(pool, M, C);
-        text_causal_attention(qkv.p, 3 * C, a.p, C, B, T, cfg.text_heads, s);
-        x = R.linear(l.out, a.p, C, M, plus(x));
-        ln(l.ln2, x.p, h.p);
-        Act f = R.linear(l.fc1, h.p, C, M, R.f32_rows());
-        text_activation(f.p, M * I, cfg.text_act, s);
-        x = R.linear(l.fc2, f.p, I, M, plus(x));
-    }
-    ln(text.ln_f, x.p, out);
+    x = tower_layers(R, text.layers, std::move(x), B, T, cfg.text_heads, cfg.text_intermediate, cfg.text_norm_eps, cfg.text_act,
+                     [&](const float* qkv, float* a) { text_causal_attention(qkv, 3 * C, a, C, B, T, cfg.text_heads, s); });
+    layernorm(x.p, C, text.ln_f.g, text.ln_f.b, out, C, (int)M, C, cfg.text_norm_eps, s);
     E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// The frame-input metric towers (image_classify, video_classify, clip_embed below) are one runner.  A tower is a VisionTowerW, its
+// sizes (TowerDims, filled from the config at the call site) and what the call site passes as lambdas: the preprocess call, the fp32
+// attention kernel, and what is done with the head's rows.  Whether a class token is embedded, the LayerNorm in front of the layers
+// and class-row or token-mean pooling follow from the weights (cls, pre_ln.g).
+// -----------------------------------------------------------------------------------------------------
+namespace {
+
+// the host resize tables of a preprocess per (H, W), at most 64 sizes
+template <class Plan, class Make>
+const Plan& prep_cached(std::map<std::array<int, 2>, Plan>& cache, int H, int W, Make make) {
+    const std::array<int, 2> key{H, W};
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        if (cache.size() >= 64) cache.clear();
+        it = cache.emplace(key, make()).first;
+    }
+    return it->second;
+}
+
+struct TowerDims { int C, I, P, T, K, heads; float eps, head_eps; int act; };      // K: patch row length; head_eps: of the LayerNorm in front of the head
+
+template <class Plan>
+struct TowerRun {
+    Runner R;                 // in the tower's own mode
+    const Plan& plan;
+    Act tables;               // plan.words on the device
+    int chunk;                // sequences per pass
+    const int* tab() const { return reinterpret_cast<const int*>(tables.p); }
+};
+
+// what the three share before the first launch, in this order: the ready check, the 16-bit mode's limit on K (`k_what` names K in the
+// tower's terms), the plan of this frame size and its band check, the upload of its tables, the chunk knob
+template <class PlanFn>
+auto tower_begin(e2v_ctx* c, e2v_ctx::Part part, const std::string& who, const char* k_what, int K, PlanFn plan_of, int chunk_knob, hipStream_t s) {
+    c->require_ready(part);
+    Runner R{c, s, false};
+    R.tower = c->tower_h16[part];
+    E2V_REQUIRE(!R.h16() || K % 8 == 0, E2V_ESHAPE, who + ": a 16-bit tower needs " + k_what + " to be a multiple of 8");
+    const auto& plan = plan_of();
+    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, who + ": the source rows of one output row do not fit the preprocess kernel's LDS band");
+    return TowerRun<std::decay_t<decltype(plan)>>{R, plan, upload_plan(c->pool, plan, s), std::min(std::max(chunk_knob, 1), 4096)};      // (the plan lives in the context)
+}
+
+// One pass of ni sequences: prep(rows) fills the patch rows; the patch linear; the token rows (with the class token where the tower has
+// one, through pre_ln where it has one); the layers; the class rows, or the mean over the tokens, through head_ln -- fp32 from there
+// on -- and the fp32 head, whose rows [ni][head.out] go to finish.
+template <class Prep, class Attn32, class Finish>
+void tower_chunk(Runner& R, const VisionTowerW& w, const TowerDims& d, int ni, Prep prep, Attn32 attn32, Finish finish) {
+    Pool& pool = R.pool();
+    hipStream_t s = R.s;
+    const int h16 = R.h16(), C = d.C, T = d.T;
+    const int64_t M = (int64_t)ni * T, Mp = (int64_t)ni * (w.cls ? T - 1 : T);
+    Act x(pool, M, C, R.bf());
+    {
+        Act rows(pool, Mp, d.K, R.bf());
+        prep(rows.p);
+        Act patches = R.linear(w.patch, rows.p, d.K, Mp, tower_rows(R));
+        Act tok;                                                // the token rows in front of pre_ln
+        if (w.pre_ln.g) tok = Act(pool, M, C, R.bf());
+        float* e = w.pre_ln.g ? tok.p : x.p;
+        if (w.cls) image_embed(patches.p, w.cls, w.pos, e, ni, T, C, s, h16);
+        else video_embed(patches.p, w.pos, e, ni, T, C, s, h16);
+        if (w.pre_ln.g) layernorm(tok.p, C, w.pre_ln.g, w.pre_ln.b, x.p, C, (int)M, C, d.eps, s, h16);
+    }
+    x = tower_layers(R, w.layers, std::move(x), ni, T, d.heads, d.I, d.eps, d.act, attn32);
+    Act mean;                                                   // fp32 from here on: the mean reads the 16-bit rows of a 16-bit tower
+    if (!w.cls) mean = Act(pool, ni, C);
+    Act pooled(pool, ni, C);
+    if (w.cls) {                                                // head_ln on the class rows only (row stride T * C)
+        tower_head_ln(R, w.head_ln, x.p, T * C, false, pooled.p, ni, C, d.head_eps);
+    } else {
+        token_mean(x.p, mean.p, ni, T, C, s, h16);
+        tower_head_ln(R, w.head_ln, mean.p, C, true, pooled.p, ni, C, d.head_eps);
+    }
+    Act out = R.linear(w.head, pooled.p, C, ni, R.f32_rows());
+    finish(out);
+}
+
+}  // namespace
+
+Act e2v::upload_plan(Pool& pool, const ImagePrepPlan& plan, hipStream_t s) {
+    Act tables(pool, (int64_t)plan.words.size(), 1);
+    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    return tables;
+}
+
+const ImagePrepPlan& e2v_ctx::prep_plan(int H, int W) {
+    return prep_cached(prep_plans, H, W, [&] { return image_prep_plan(H, W, cfg.vit_image_size, cfg.vit_patch_size, image_lut); });
+}
+const VideoPrepPlan& e2v_ctx::video_prep_plan(int H, int W) {
+    return prep_cached(video_prep_plans, H, W, [&] {
+        return e2v::video_prep_plan(H, W, cfg.vmae_resize_edge, cfg.vmae_image_size, cfg.vmae_patch_size, video_lut);
+    });
+}
+const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
+    return prep_cached(clipv_prep_plans, H, W, [&] {
+        return e2v::video_prep_plan(H, W, vcfg.clipv_resize_edge, vcfg.clipv_image_size, vcfg.clipv_patch_size, clipv_lut, vcfg.clipv_resample);
+    });
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -1880,49 +1913,22 @@ void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t 
 // here computes a row from that row's image alone and in an order that does not depend on the row count, so the chunking does not
 // show in the result.
 // -----------------------------------------------------------------------------------------------------
-const ImagePrepPlan& e2v_ctx::prep_plan(int H, int W) {
-    const std::array<int, 2> key{H, W};
-    auto it = prep_plans.find(key);
-    if (it == prep_plans.end()) {
-        if (prep_plans.size() >= 64) prep_plans.clear();
-        it = prep_plans.emplace(key, image_prep_plan(H, W, cfg.vit_image_size, cfg.vit_patch_size, image_lut)).first;
-    }
-    return it->second;
-}
-
 void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, float* logits, float* probs, int* top3, hipStream_t s) {
-    E2V_REQUIRE(image_ready, E2V_ESTATE, "image classifier weights are not finalized");
-    Runner R{this, s, false};
-    R.tower = tower_h16[tower_slot(16)];
-    const int h16 = R.h16();
-    const int C = cfg.vit_hidden, I = cfg.vit_intermediate, P = cfg.vit_patch_size, L = cfg.vit_num_labels;
-    const int T = image_tokens(), K = 3 * P * P;
-    const float eps = cfg.vit_norm_eps;
-    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_image_classify: a 16-bit tower needs 3 * patch_size^2 to be a multiple of 8");
-    const ImagePrepPlan& plan = prep_plan(H, W);
-    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
-    Act tables(pool, (int64_t)plan.words.size(), 1);
-    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
     static const int* const chunk_knob = knob("E2V_VIT_CHUNK", 64);
-    const int chunk = std::min(std::max(*chunk_knob, 1), 4096);
+    const int P = cfg.vit_patch_size, L = cfg.vit_num_labels;
+    const TowerDims d{cfg.vit_hidden, cfg.vit_intermediate, P, image_tokens(), 3 * P * P, cfg.vit_heads, cfg.vit_norm_eps, cfg.vit_norm_eps, 1};
+    auto t = tower_begin(this, IMAGE, "e2v_image_classify", "3 * patch_size^2", d.K, [&]() -> const ImagePrepPlan& { return prep_plan(H, W); }, *chunk_knob, s);
+    const int h16 = t.R.h16();
     const long long total = (long long)n * F;
-    for (long long i0 = 0; i0 < total; i0 += chunk) {
-        const int ni = (int)std::min<long long>(chunk, total - i0);
-        const int64_t M = (int64_t)ni * T;
-        Act x(pool, M, C, R.bf());
-        {
-            Act rows(pool, (int64_t)ni * (T - 1), K, R.bf());
-            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
-            Act patches = R.linear(image.patch, rows.p, K, (int64_t)ni * (T - 1), tower_rows(R));
-            image_embed(patches.p, image.cls, image.pos, x.p, ni, T, C, s, h16);
-        }
-        x = tower_layers(R, image.layers, std::move(x), ni, T, cfg.vit_heads, I, eps, 1,
-                         [&](const float* qkv, float* a) { image_attention(qkv, 3 * C, a, C, ni, T, cfg.vit_heads, s); });
-        Act cls(pool, ni, C);                                   // the final LayerNorm on the class rows only (row stride T * C): fp32 from here on
-        tower_head_ln(R, image.ln_f, x.p, T * C, false, cls.p, ni, C, eps);
-        Act lg = R.linear(image.head, cls.p, C, ni, R.f32_rows());
-        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
-                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+    for (long long i0 = 0; i0 < total; i0 += t.chunk) {
+        const int ni = (int)std::min<long long>(t.chunk, total - i0);
+        tower_chunk(t.R, image, d, ni,
+                    [&](float* rows) { image_preprocess(src, n, F, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](const float* qkv, float* a) { image_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
+                    [&](const Act& lg) {
+                        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
+                                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+                    });
     }
     E2V_HIP(hipGetLastError());
 }
@@ -1935,50 +1941,25 @@ void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, fl
 // Clips are walked in chunks of E2V_VMAE_CHUNK (16): every kernel here computes a row from that row's clip alone and in an order
 // that does not depend on the row count, so the chunking does not show in the result.
 // -----------------------------------------------------------------------------------------------------
-const VideoPrepPlan& e2v_ctx::video_prep_plan(int H, int W) {
-    const std::array<int, 2> key{H, W};
-    auto it = video_prep_plans.find(key);
-    if (it == video_prep_plans.end()) {
-        if (video_prep_plans.size() >= 64) video_prep_plans.clear();
-        it = video_prep_plans.emplace(key, e2v::video_prep_plan(H, W, cfg.vmae_resize_edge, cfg.vmae_image_size, cfg.vmae_patch_size, video_lut)).first;
-    }
-    return it->second;
-}
-
 void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, float* logits, float* probs, int* top3, hipStream_t s) {
-    E2V_REQUIRE(video_ready, E2V_ESTATE, "video classifier weights are not finalized");
+    require_ready(VIDEO);
     E2V_REQUIRE(F == cfg.vmae_num_frames, E2V_ESHAPE, "e2v_video_classify: F must be vmae_num_frames");
-    Runner R{this, s, false};
-    R.tower = tower_h16[tower_slot(32)];
-    const int h16 = R.h16();
-    const int C = cfg.vmae_hidden, I = cfg.vmae_intermediate, P = cfg.vmae_patch_size, ts = cfg.vmae_tubelet_size, L = cfg.vmae_num_labels;
-    const int T = video_tokens(), K = 3 * ts * P * P;
-    const float eps = cfg.vmae_norm_eps;
-    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_video_classify: a 16-bit tower needs 3 * tubelet_size * patch_size^2 to be a multiple of 8");
-    const VideoPrepPlan& plan = video_prep_plan(H, W);
-    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band");
-    Act tables(pool, (int64_t)plan.words.size(), 1);
-    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
     static const int* const chunk_knob = knob("E2V_VMAE_CHUNK", 16);
-    const int chunk = std::min(std::min(std::max(*chunk_knob, 1), 4096), 65535 / F);
+    const int P = cfg.vmae_patch_size, ts = cfg.vmae_tubelet_size, L = cfg.vmae_num_labels;
+    const TowerDims d{cfg.vmae_hidden, cfg.vmae_intermediate, P, video_tokens(), 3 * ts * P * P, cfg.vmae_heads, cfg.vmae_norm_eps,
+                      1e-5f, 1};                                 // fc_norm = nn.LayerNorm(hidden): the default eps
+    auto t = tower_begin(this, VIDEO, "e2v_video_classify", "3 * tubelet_size * patch_size^2", d.K,
+                         [&]() -> const VideoPrepPlan& { return video_prep_plan(H, W); }, *chunk_knob, s);
+    const int h16 = t.R.h16(), chunk = std::min(t.chunk, 65535 / F);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int ni = std::min(chunk, n - i0);
-        const int64_t M = (int64_t)ni * T;
-        Act x(pool, M, C, R.bf());
-        {
-            Act rows(pool, M, K, R.bf());
-            video_preprocess(src, n, F, ts, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
-            Act patches = R.linear(video.patch, rows.p, K, M, tower_rows(R));
-            video_embed(patches.p, video.pos, x.p, ni, T, C, s, h16);
-        }
-        x = tower_layers(R, video.layers, std::move(x), ni, T, cfg.vmae_heads, I, eps, 1,
-                         [&](const float* qkv, float* a) { token_attention(qkv, 3 * C, a, C, ni, T, cfg.vmae_heads, s); });
-        Act mean(pool, ni, C), pooled(pool, ni, C);             // fp32 from here on: the mean reads the 16-bit rows of a 16-bit tower
-        token_mean(x.p, mean.p, ni, T, C, s, h16);
-        tower_head_ln(R, video.fc_norm, mean.p, C, true, pooled.p, ni, C, 1e-5f);                   // fc_norm = nn.LayerNorm(hidden): the default eps
-        Act lg = R.linear(video.head, pooled.p, C, ni, R.f32_rows());
-        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
-                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+        tower_chunk(t.R, video, d, ni,
+                    [&](float* rows) { video_preprocess(src, n, F, ts, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](const float* qkv, float* a) { token_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
+                    [&](const Act& lg) {
+                        image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
+                                   top3 ? top3 + (size_t)i0 * 3 : nullptr, s);
+                    });
     }
     E2V_HIP(hipGetLastError());
 }
@@ -1993,51 +1974,20 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
 // GEMM then sees 12800 rows, about the 64 x 197 = 12608 of the image classifier's chunk); every kernel here computes a row from
 // that row's image alone and in an order that does not depend on the row count, so the chunking does not show in the result.
 // -----------------------------------------------------------------------------------------------------
-const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
-    const std::array<int, 2> key{H, W};
-    auto it = clipv_prep_plans.find(key);
-    if (it == clipv_prep_plans.end()) {
-        if (clipv_prep_plans.size() >= 64) clipv_prep_plans.clear();
-        it = clipv_prep_plans.emplace(key, e2v::video_prep_plan(H, W, vcfg.clipv_resize_edge, vcfg.clipv_image_size, vcfg.clipv_patch_size, clipv_lut,
-                                                                vcfg.clipv_resample)).first;
-    }
-    return it->second;
-}
-
 void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float* embeds, hipStream_t s) {
-    E2V_REQUIRE(clipv_ready, E2V_ESTATE, "CLIP vision tower weights are not finalized");
-    Runner R{this, s, false};
-    R.tower = tower_h16[tower_slot(64)];
-    const int h16 = R.h16();
-    const int C = vcfg.clipv_hidden, I = vcfg.clipv_intermediate, P = vcfg.clipv_patch_size, E = vcfg.clipv_projection_dim;
-    const int T = clipv_tokens(), K = 3 * P * P;
-    const float eps = vcfg.clipv_norm_eps;
-    E2V_REQUIRE(!h16 || K % 8 == 0, E2V_ESHAPE, "e2v_clip_embed: a 16-bit tower needs 3 * patch_size^2 to be a multiple of 8");
-    const VideoPrepPlan& plan = clipv_prep_plan(H, W);
-    E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band");
-    Act tables(pool, (int64_t)plan.words.size(), 1);
-    E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));   // (the plan lives in the context)
     static const int* const chunk_knob = knob("E2V_CLIPV_CHUNK", 256);
-    const int chunk = std::min(std::max(*chunk_knob, 1), 4096);
+    const int P = vcfg.clipv_patch_size, E = vcfg.clipv_projection_dim;
+    const TowerDims d{vcfg.clipv_hidden, vcfg.clipv_intermediate, P, clipv_tokens(), 3 * P * P, vcfg.clipv_heads, vcfg.clipv_norm_eps,
+                      vcfg.clipv_norm_eps, vcfg.clipv_act};
+    auto t = tower_begin(this, CLIPV, "e2v_clip_embed", "3 * patch_size^2", d.K, [&]() -> const VideoPrepPlan& { return clipv_prep_plan(H, W); }, *chunk_knob, s);
+    const int h16 = t.R.h16();
     const long long total = (long long)n * F;
-    for (long long i0 = 0; i0 < total; i0 += chunk) {
-        const int ni = (int)std::min<long long>(chunk, total - i0);
-        const int64_t M = (int64_t)ni * T;
-        Act x(pool, M, C, R.bf());
-        {
-            Act rows(pool, (int64_t)ni * (T - 1), K, R.bf());
-            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), P, rows.p, s, h16);
-            Act patches = R.linear(clipv.patch, rows.p, K, (int64_t)ni * (T - 1), tower_rows(R));
-            Act tok(pool, M, C, R.bf());
-            image_embed(patches.p, clipv.cls, clipv.pos, tok.p, ni, T, C, s, h16);
-            layernorm(tok.p, C, clipv.pre_ln.g, clipv.pre_ln.b, x.p, C, (int)M, C, eps, s, h16);
-        }
-        x = tower_layers(R, clipv.layers, std::move(x), ni, T, vcfg.clipv_heads, I, eps, vcfg.clipv_act,
-                         [&](const float* qkv, float* a) { image_attention(qkv, 3 * C, a, C, ni, T, vcfg.clipv_heads, s); });
-        Act cls(pool, ni, C);                                   // post_layernorm on the class rows only (row stride T * C): fp32 from here on
-        tower_head_ln(R, clipv.post_ln, x.p, T * C, false, cls.p, ni, C, eps);
-        Act emb = R.linear(clipv.proj, cls.p, C, ni, R.f32_rows());
-        copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s);
+    for (long long i0 = 0; i0 < total; i0 += t.chunk) {
+        const int ni = (int)std::min<long long>(t.chunk, total - i0);
+        tower_chunk(t.R, clipv, d, ni,
+                    [&](float* rows) { frame_preprocess(src, n, F, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](const float* qkv, float* a) { image_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
+                    [&](const Act& emb) { copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s); });
     }
     E2V_HIP(hipGetLastError());
 }
@@ -2059,7 +2009,7 @@ void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float*
 // -----------------------------------------------------------------------------------------------------
 void e2v_ctx::seq2seq_latents(const EegnetArgs& eeg_in, int B, int first, int count, int layout, float* latents, float* txt_logits,
                               float* tokens, hipStream_t s) {
-    E2V_REQUIRE(s2s_ready, E2V_ESTATE, "Seq2Seq weights are not finalized");
+    require_ready(S2S);
     Runner R{this, s, false};
     const int C = scfg.s2s_d_model, H = scfg.s2s_heads, Dh = C / H, W = scfg.s2s_windows, T1 = scfg.s2s_steps + 1;
     const int feat = s2s_features(), L = scfg.s2s_txt_classes;

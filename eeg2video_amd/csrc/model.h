@@ -103,37 +103,21 @@ struct TextW {
     NormW ln_f;
 };
 
-// ViTForImageClassification (transformers; keys "image.vit....", "image.classifier...."): the text tower's layer packing -- fp32 matrices
-// only, query | key | value fused -- behind a patch embedding and a class token, with a classifier on the class row
-struct ImageW {
-    const float* cls = nullptr; const float* pos = nullptr;          // [C], [T][C]
-    LinW patch;                                                      // the patch convolution as [C][3 P P]
-    std::vector<TextLayerW> layers;
-    NormW ln_f;
-    LinW head;                                                       // [labels rounded up to 4][C]: the linear kernels store quads
-};
-
-// VideoMAEForVideoClassification (transformers; keys "video.videomae....", "video.fc_norm.*", "video.classifier.*"): the image
-// classifier's layers behind a tubelet embedding and a fixed position table, without a class token; the classifier reads fc_norm
-// of the mean over the tokens
-struct VideoW {
+// A frame-input metric tower: the text tower's layer packing -- fp32 matrices only, q | k | v fused -- behind a patch embedding.
+//   image  ViTForImageClassification (transformers; keys "image.vit....", "image.classifier...."): a class token, the final LayerNorm
+//          and a classifier on the class row
+//   video  VideoMAEForVideoClassification (keys "video.videomae....", "video.fc_norm.*", "video.classifier.*"): a tubelet embedding and
+//          a fixed position table, no class token; the classifier reads fc_norm of the mean over the tokens
+//   clipv  CLIPVisionModelWithProjection (keys "clipv.vision_model....", "clipv.visual_projection.weight"): a LayerNorm in front of the
+//          layers, a patch embedding without bias, and a projection without bias in place of the classifier
+struct VisionTowerW {
+    const float* cls = nullptr;                                      // [C]; null: no class token
     const float* pos = nullptr;                                      // [T][C]
-    LinW patch;                                                      // the tubelet convolution as [C][3 ts P P]
+    LinW patch;                                                      // the patch / tubelet convolution as [C][3 (ts) P P]
+    NormW pre_ln;                                                    // g == nullptr: none
     std::vector<TextLayerW> layers;
-    NormW fc_norm;
-    LinW head;                                                       // [labels rounded up to 4][C]
-};
-
-// CLIPVisionModelWithProjection (transformers; keys "clipv.vision_model....", "clipv.visual_projection.weight"): the image
-// classifier's token rows and layers with a LayerNorm in front of the layers, a patch embedding without bias, and a projection
-// without bias in place of the classifier
-struct ClipVW {
-    const float* cls = nullptr;                                      // [C]
-    const float* pos = nullptr;                                      // [T][C]
-    LinW patch;                                                      // the patch convolution as [C][3 P P], no bias
-    NormW pre_ln, post_ln;
-    std::vector<TextLayerW> layers;
-    LinW proj;                                                       // [projection_dim][C], no bias
+    NormW head_ln;                                                   // the final LayerNorm / fc_norm / post_layernorm
+    LinW head;                                                       // [labels rounded up to 4][C] (the linear kernels store quads) / [projection_dim][C]
 };
 
 // The Seq2Seq latent model (the reference's myTransformer, my_autoregressive_transformer.py:123-192; keys "s2s." + its state-dict
@@ -200,10 +184,51 @@ void conv3_wino(e2v_ctx* c, const Conv3& d, int m, const float* U, const void* U
 void geglu_interleave(const float* w, const float* b, int half, int in, float* dw, float* db, hipStream_t s);
 // ask for `want` split-K runs of launch g: where it is eligible the workspace is attached and returned (alive until the launch is queued)
 Act splitk_attach(Pool& pool, IgemmArgs& g, int want);
+// the tables of a preprocess plan (plan.words) in a pool block, copied on stream s: `plan` must live until the copy has run
+Act upload_plan(Pool& pool, const ImagePrepPlan& plan, hipStream_t s);
 
 }  // namespace e2v
 
 struct e2v_ctx {
+    // THE part table.  A model part is one row: its slot (the enum: owned_part, alloc_part, ready), its bit of e2v_finalize_weights'
+    // `which`, the prefix of its state-dict keys, what a context without it / a call before its finalize() is told, whether it is a
+    // metric tower (e2v_set_tower_dtype), whether its linears keep fp32 matrices only (Packer::f32_only) and, where e2v_update_tensor refuses its keys, why.  has_part() (model.cpp) is the one
+    // switch next to it: the config fields that say whether this context holds the part.
+    enum Part { UNET, VAE, SEM, TEXT, IMAGE, VIDEO, CLIPV, S2S, N_PARTS };
+    struct PartRow {
+        int bit; const char* prefix; const char* absent; const char* not_ready; bool tower; bool f32_only; const char* frozen;
+        bool owns(const std::string& k) const { return *prefix && k.rfind(prefix, 0) == 0; }
+    };
+    static constexpr PartRow kParts[N_PARTS] = {
+        {1, "", nullptr, "UNet weights are not finalized", false, false, nullptr},
+        {2, "vae.", nullptr, "VAE weights are not finalized", false, false, nullptr},
+        {4, "semantic.", "the config has no semantic predictor", "semantic predictor weights are not finalized", false, false, nullptr},
+        {8, "text.", "the config has no text encoder (text_layers = 0)", "text encoder weights are not finalized", false, true,
+         "the text encoder is frozen on this path (train_finetune_videodiffusion.py:115); load a new one with e2v_load_tensor + e2v_finalize_weights"},
+        {16, "image.", "the config has no image classifier (vit_layers = 0)", "image classifier weights are not finalized", true, true,
+         "the image classifier is a frozen yardstick (40_class_run_metrics.py:88-90); load a new one with e2v_load_tensor + e2v_finalize_weights"},
+        {32, "video.", "the config has no video classifier (vmae_layers = 0)", "video classifier weights are not finalized", true, true,
+         "the video classifier is a frozen yardstick (40_class_run_metrics.py:113-118); load a new one with e2v_load_tensor + e2v_finalize_weights"},
+        {64, "clipv.", "the context has no CLIP vision tower (e2v_create_clip_vision)", "CLIP vision tower weights are not finalized", true, true, nullptr},
+        {128, "s2s.", "the context has no Seq2Seq latent model (e2v_create_ex)", "Seq2Seq weights are not finalized", false, true,
+         "the Seq2Seq model is only called here and its BatchNorms are folded at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128)"},
+    };
+    // which part owns a state-dict key: the one whose prefix it carries, else the UNet
+    static Part key_part(const std::string& k) {
+        for (int p = 0; p < N_PARTS; ++p)
+            if (kParts[p].owns(k)) return (Part)p;
+        return UNET;
+    }
+    static int tower_part(int bit) {                             // the API's 16 / 32 / 64 -> Part; -1: not a metric tower's bit
+        for (int p = 0; p < N_PARTS; ++p)
+            if (kParts[p].tower && kParts[p].bit == bit) return p;
+        return -1;
+    }
+    bool has_part(Part p) const;                                 // does this context's config hold the part
+    bool ready[N_PARTS] = {};                                    // finalize() has put the part in place
+    void require_part(Part p) const { E2V_REQUIRE(has_part(p), E2V_ESTATE, kParts[p].absent); }
+    void require_ready(Part p) const { E2V_REQUIRE(ready[p], E2V_ESTATE, kParts[p].not_ready); }
+
     e2v_config cfg;
     int device = 0;
     std::string err;
@@ -217,14 +242,10 @@ struct e2v_ctx {
     e2v::UNetW unet;
     e2v::VAEW vae;
     e2v::TextW text;
-    e2v::ImageW image;
-    e2v::VideoW video;
-    e2v::ClipVW clipv;
+    e2v::VisionTowerW image, video, clipv;
     e2v::S2sW s2s;
-    bool unet_ready = false, vae_ready = false, sem_ready = false, text_ready = false, image_ready = false, video_ready = false;
-    bool clipv_ready = false, s2s_ready = false;
     float image_lut[3 * 256] = {};                               // the processor's pixel value of a byte, per channel (e2v_create)
-    std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W)
+    std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W): prep_cached (model.cpp)
     const e2v::ImagePrepPlan& prep_plan(int H, int W);
     float video_lut[3 * 256] = {};                               // the same two for the video classifier
     std::map<std::array<int, 2>, e2v::VideoPrepPlan> video_prep_plans;
@@ -247,9 +268,8 @@ struct e2v_ctx {
     int h16_mode = 0;                                            // ... and which: 0 none, 1 bf16 (E2V_BF16), 2 fp16 (E2V_F16) -- the flag every 16-bit launch carries (h16.h)
     void set_h16_mode(int m) { h16_mode = m; bf16_compute = m != 0; }
     // e2v_set_tower_dtype: the arithmetic of the three metric towers, each on its own and whatever the mode above -- 0 fp32 (the
-    // default), 1 bf16, 2 fp16 (h16.h), indexed by tower_slot(part)
-    int tower_h16[3] = {0, 0, 0};
-    static int tower_slot(int part) { return part == 16 ? 0 : part == 32 ? 1 : part == 64 ? 2 : -1; }
+    // default), 1 bf16, 2 fp16 (h16.h), indexed by Part (the towers' entries are the ones used)
+    int tower_h16[N_PARTS] = {};
     std::vector<e2v::LinW> sem;                                  // semantic predictor layers (first one K-padded to 4)
     int sem_in_pad = 0;
     std::vector<float> alphas;                                   // host alpha-bar table
@@ -268,8 +288,8 @@ struct e2v_ctx {
     // stream of the previous call (workspace reuse is stream-ordered): see enter_stream
     hipStream_t last_stream = nullptr; bool has_last_stream = false; hipEvent_t stream_ev = nullptr;
     void enter_stream(hipStream_t s);
-    // device blocks made by dev_alloc, per part (bit index of `which`), so that finalizing a part again frees what it replaces
-    std::vector<e2v::DevBlock> owned_part[8];
+    // device blocks made by dev_alloc, per part, so that finalizing a part again frees what it replaces
+    std::vector<e2v::DevBlock> owned_part[N_PARTS];
     size_t weight_bytes() const;                                 // what the uploaded tensors and the parts' blocks hold (e2v_device_bytes)
     void* comm = nullptr; int comm_rank = 0, comm_world = 0;     // RCCL communicator of e2v_comm_init (comm.cpp)
     // e2v_op_unet_forward_taps (test aid): while set, unet_forward_cl copies the tensors the oracle exposes (emb, down0..3, mid,
@@ -331,10 +351,4 @@ struct e2v_ctx {
     void seq2seq_latents(const e2v::EegnetArgs& eeg, int B, int first, int count, int layout, float* latents, float* txt_logits, float* tokens,
                          hipStream_t s);
     int clipv_tokens() const { const int g = vcfg.clipv_patch_size > 0 ? vcfg.clipv_image_size / vcfg.clipv_patch_size : 0; return g * g + 1; }
-    // which finalize() part owns a state-dict key: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video
-    // classifier, 64 CLIP vision tower, 128 Seq2Seq latent model
-    static int key_part(const std::string& k) {
-        return k.rfind("semantic.", 0) == 0 ? 4 : k.rfind("vae.", 0) == 0 ? 2 : k.rfind("text.", 0) == 0 ? 8 : k.rfind("image.", 0) == 0 ? 16 :
-               k.rfind("video.", 0) == 0 ? 32 : k.rfind("clipv.", 0) == 0 ? 64 : k.rfind("s2s.", 0) == 0 ? 128 : 1;
-    }
 };

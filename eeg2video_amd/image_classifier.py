@@ -13,19 +13,15 @@ Nothing here reads the network: a checkpoint is a LOCAL directory (``config.json
 """
 from __future__ import annotations
 
-import json
-import os
 from typing import Optional
 
 import torch
 
+from ._tower_model import PROCESSOR_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, _TowerModel
 from .engine import Engine
 from .unet import FrozenDict, _load_checkpoint
 from .weights import ImageConfig, UNetConfig, VAEConfig, image_checkpoint_key, image_param_spec, synth_state_dict
 
-SAFETENSORS_NAME = "model.safetensors"        # transformers.utils.SAFE_WEIGHTS_NAME
-WEIGHTS_NAME = "pytorch_model.bin"            # transformers.utils.WEIGHTS_NAME
-PROCESSOR_NAME = "preprocessor_config.json"   # transformers.utils.IMAGE_PROCESSOR_NAME
 _BILINEAR = 2                                 # PIL.Image.Resampling.BILINEAR, the only resample implemented
 
 
@@ -46,7 +42,9 @@ class ImageClassifierOutput:
         return (self.logits,)
 
 
-class ViTForImageClassification:
+class ViTForImageClassification(_TowerModel):
+    _PART = Engine.IMAGE
+
     def __init__(self, config: ImageConfig = ImageConfig(), *, engine: Optional[Engine] = None, device: int = 0):
         self.icfg = config
         self._internal_dict = FrozenDict(hidden_size=config.hidden, num_attention_heads=config.heads, num_hidden_layers=config.layers,
@@ -57,39 +55,6 @@ class ViTForImageClassification:
             raise RuntimeError(f"the engine was created for an image classifier of {engine.image_cfg}, this one is {config}: create "
                                "the engine with image_cfg=ViTForImageClassification.config_from_dir(<dir>)")
         self.engine = engine if engine is not None else Engine(UNetConfig(), VAEConfig(), device, image_cfg=config)
-
-    @property
-    def config(self) -> FrozenDict:
-        return self._internal_dict
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return torch.float32
-
-    @property
-    def device(self) -> torch.device:
-        return self.engine.device
-
-    def to(self, *a, **k):          # the weights live on the engine's GPU; the arithmetic is chosen by set_compute_dtype alone
-        return self
-
-    @property
-    def compute_dtype(self) -> str:
-        """``'fp32'`` (the default), ``'bf16'`` or ``'fp16'``: the arithmetic of this model on its engine (``Engine.tower_dtype``)."""
-        return self.engine.tower_dtype(Engine.IMAGE)
-
-    def set_compute_dtype(self, dtype):
-        """Opt into 16-bit arithmetic for this model alone: ``'fp16'`` (what the reference runs it in,
-        ``40_class_run_metrics.py``: ``.to(device, torch.float16)``), ``'bf16'``, or back to ``'fp32'`` -- a name or a ``torch.dtype``
-        (``Engine.set_tower_dtype``).  The outputs stay fp32; ``torch_dtype=`` and ``.to()`` do not select it."""
-        self.engine.set_tower_dtype(Engine.IMAGE, dtype)
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag: bool = False):
-        return self
 
     # -- weights -----------------------------------------------------------------------------
     def state_dict_spec(self):
@@ -126,9 +91,7 @@ class ViTForImageClassification:
         proc = {"image_processor_type": "ViTImageProcessor", "do_resize": True, "do_rescale": True, "do_normalize": True,
                 "size": {"height": c.image_size, "width": c.image_size}, "resample": _BILINEAR, "rescale_factor": c.rescale_factor,
                 "image_mean": list(c.image_mean), "image_std": list(c.image_std)}
-        with open(os.path.join(save_directory, PROCESSOR_NAME), "w") as f:
-            json.dump(proc, f, indent=2, sort_keys=True)
-            f.write("\n")
+        self._write_processor(save_directory, proc)
 
     def init_synthetic(self, seed: int = 45, mode: str = "perturbed"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
@@ -136,14 +99,7 @@ class ViTForImageClassification:
     @staticmethod
     def config_from_dir(path: str) -> ImageConfig:
         """``config.json`` + ``preprocessor_config.json`` of a ``transformers`` ViT directory -> ``ImageConfig``."""
-        cfg_file, proc_file = os.path.join(path, "config.json"), os.path.join(path, PROCESSOR_NAME)
-        for f in (cfg_file, proc_file):
-            if not os.path.isfile(f):
-                raise RuntimeError(f"{f} does not exist")
-        with open(cfg_file) as f:
-            cj = json.load(f)
-        with open(proc_file) as f:
-            pj = json.load(f)
+        cj, pj = _TowerModel._read_configs(path)
         d = ImageConfig()
         if cj.get("hidden_act", "gelu") != "gelu":
             raise NotImplementedError(f"hidden_act={cj['hidden_act']!r}: the image classifier implements the erf 'gelu'")
@@ -181,12 +137,9 @@ class ViTForImageClassification:
         """LOCAL directory only.  ``torch_dtype`` and ``cache_dir`` are accepted for drop-in use: checkpoints of any float type are
         widened to fp32, and nothing is ever fetched.  ``compute_dtype``: ``set_compute_dtype`` on the built model (``None``: fp32)."""
         path = str(pretrained_model_path)
-        if not os.path.isdir(path):
-            raise RuntimeError(f"{path!r} is not a directory: this classifier loads from a local checkpoint directory only and never "
-                               "reads the network (download 'google/vit-base-patch16-224' elsewhere and pass its directory)")
+        cls._require_dir(path, "classifier", "google/vit-base-patch16-224")
         model = cls(cls.config_from_dir(path), engine=engine, device=device)
-        if not os.path.isfile(os.path.join(path, WEIGHTS_NAME)) and not os.path.isfile(os.path.join(path, SAFETENSORS_NAME)):
-            raise RuntimeError(f"{os.path.join(path, SAFETENSORS_NAME)} does not exist")
+        cls._require_weights(path)
         if compute_dtype is not None:
             model.set_compute_dtype(compute_dtype)
         return model.load_state_dict(_load_checkpoint(path, SAFETENSORS_NAME, WEIGHTS_NAME), strict=False)

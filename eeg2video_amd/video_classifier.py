@@ -17,16 +17,15 @@ Nothing here reads the network: a checkpoint is a LOCAL directory (``config.json
 """
 from __future__ import annotations
 
-import json
-import os
 from collections import OrderedDict
 from typing import Optional
 
 import numpy as np
 import torch
 
+from ._tower_model import PROCESSOR_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, _TowerModel
 from .engine import Engine
-from .image_classifier import PROCESSOR_NAME, SAFETENSORS_NAME, WEIGHTS_NAME, ImageClassifierOutput, _BILINEAR
+from .image_classifier import ImageClassifierOutput, _BILINEAR
 from .unet import FrozenDict, _load_checkpoint
 from .weights import (VIDEO_POSITION_KEY, UNetConfig, VAEConfig, VideoConfig, synth_state_dict, video_checkpoint_rename,
                       video_checkpoint_spec, video_engine_shape, video_param_spec, video_position_table)
@@ -34,7 +33,9 @@ from .weights import (VIDEO_POSITION_KEY, UNetConfig, VAEConfig, VideoConfig, sy
 HUB_NAME = "MCG-NJU/videomae-base-finetuned-kinetics"
 
 
-class VideoMAEForVideoClassification:
+class VideoMAEForVideoClassification(_TowerModel):
+    _PART = Engine.VIDEO
+
     def __init__(self, config: VideoConfig = VideoConfig(), *, engine: Optional[Engine] = None, device: int = 0):
         self.vcfg = config
         self._internal_dict = FrozenDict(hidden_size=config.hidden, num_attention_heads=config.heads, num_hidden_layers=config.layers,
@@ -46,39 +47,6 @@ class VideoMAEForVideoClassification:
             raise RuntimeError(f"the engine was created for a video classifier of {engine.video_cfg}, this one is {config}: create "
                                "the engine with video_cfg=VideoMAEForVideoClassification.config_from_dir(<dir>)")
         self.engine = engine if engine is not None else Engine(UNetConfig(), VAEConfig(), device, video_cfg=config)
-
-    @property
-    def config(self) -> FrozenDict:
-        return self._internal_dict
-
-    @property
-    def dtype(self) -> torch.dtype:
-        return torch.float32
-
-    @property
-    def device(self) -> torch.device:
-        return self.engine.device
-
-    def to(self, *a, **k):          # the weights live on the engine's GPU; the arithmetic is chosen by set_compute_dtype alone
-        return self
-
-    @property
-    def compute_dtype(self) -> str:
-        """``'fp32'`` (the default), ``'bf16'`` or ``'fp16'``: the arithmetic of this model on its engine (``Engine.tower_dtype``)."""
-        return self.engine.tower_dtype(Engine.VIDEO)
-
-    def set_compute_dtype(self, dtype):
-        """Opt into 16-bit arithmetic for this model alone: ``'fp16'`` (what the reference runs it in,
-        ``40_class_run_metrics.py``: ``.to(device, torch.float16)``), ``'bf16'``, or back to ``'fp32'`` -- a name or a ``torch.dtype``
-        (``Engine.set_tower_dtype``).  The outputs stay fp32; ``torch_dtype=`` and ``.to()`` do not select it."""
-        self.engine.set_tower_dtype(Engine.VIDEO, dtype)
-        return self
-
-    def eval(self):
-        return self
-
-    def requires_grad_(self, flag: bool = False):
-        return self
 
     # -- weights -----------------------------------------------------------------------------
     def state_dict_spec(self):
@@ -132,9 +100,7 @@ class VideoMAEForVideoClassification:
         proc = {"image_processor_type": "VideoMAEImageProcessor", "do_resize": True, "do_center_crop": True, "do_rescale": True,
                 "do_normalize": True, "size": {"shortest_edge": c.resize_edge}, "crop_size": {"height": c.image_size, "width": c.image_size},
                 "resample": _BILINEAR, "rescale_factor": c.rescale_factor, "image_mean": list(c.image_mean), "image_std": list(c.image_std)}
-        with open(os.path.join(save_directory, PROCESSOR_NAME), "w") as f:
-            json.dump(proc, f, indent=2, sort_keys=True)
-            f.write("\n")
+        self._write_processor(save_directory, proc)
 
     def init_synthetic(self, seed: int = 46, mode: str = "perturbed"):
         return self.load_state_dict(synth_state_dict(self.state_dict_spec(), seed=seed, mode=mode))
@@ -143,14 +109,7 @@ class VideoMAEForVideoClassification:
     def config_from_dir(path: str, num_frames: Optional[int] = None) -> VideoConfig:
         """``config.json`` + ``preprocessor_config.json`` of a ``transformers`` VideoMAE directory -> ``VideoConfig``;
         ``num_frames`` overrides the config's, as the keyword of ``from_pretrained`` does in ``transformers``."""
-        cfg_file, proc_file = os.path.join(path, "config.json"), os.path.join(path, PROCESSOR_NAME)
-        for f in (cfg_file, proc_file):
-            if not os.path.isfile(f):
-                raise RuntimeError(f"{f} does not exist")
-        with open(cfg_file) as f:
-            cj = json.load(f)
-        with open(proc_file) as f:
-            pj = json.load(f)
+        cj, pj = _TowerModel._read_configs(path)
         d = VideoConfig()
         if cj.get("hidden_act", "gelu") != "gelu":
             raise NotImplementedError(f"hidden_act={cj['hidden_act']!r}: the video classifier implements the erf 'gelu'")
@@ -194,15 +153,12 @@ class VideoMAEForVideoClassification:
         token count and the position table follow it; the weights do not depend on it.  ``torch_dtype`` and ``cache_dir`` are accepted
         for drop-in use: checkpoints of any float type are widened to fp32, and nothing is ever fetched.  ``compute_dtype``: ``set_compute_dtype`` on the built model (``None``: fp32)."""
         path = str(pretrained_model_path)
-        if not os.path.isdir(path):
-            raise RuntimeError(f"{path!r} is not a directory: this classifier loads from a local checkpoint directory only and never "
-                               f"reads the network (download {HUB_NAME!r} elsewhere and pass its directory)")
+        cls._require_dir(path, "classifier", HUB_NAME)
         config = cls.config_from_dir(path, num_frames)
         if config.num_frames < 1 or config.num_frames % config.tubelet_size:
             raise ValueError(f"num_frames={config.num_frames} is not a positive multiple of tubelet_size={config.tubelet_size}")
         model = cls(config, engine=engine, device=device)
-        if not os.path.isfile(os.path.join(path, WEIGHTS_NAME)) and not os.path.isfile(os.path.join(path, SAFETENSORS_NAME)):
-            raise RuntimeError(f"{os.path.join(path, SAFETENSORS_NAME)} does not exist")
+        cls._require_weights(path)
         if compute_dtype is not None:
             model.set_compute_dtype(compute_dtype)
         return model.load_state_dict(_load_checkpoint(path, SAFETENSORS_NAME, WEIGHTS_NAME), strict=False)
