@@ -14,17 +14,19 @@ Layout (only what the path needs):
   the video N-way accuracy (``video_classify_metric``) over ``video_classifier``, its ``VideoMAEForVideoClassification``, and the
   CLIP score (``clip_score``, ``clip_score_only``, ``n_way_scores``) over ``clip_vision``, its ``CLIPVisionModelWithProjection``
 * ``seq2seq``   the reference's Seq2Seq latent model ``myTransformer`` on the library: EEG windows in, UNet latents out
+* ``features``  the reference's ``DE_PSD`` features of raw EEG on the library (``DE_PSD``, batched ``de_psd``)
+* ``glmnet``    the reference's GLMNet pair ``glfnet`` / ``glfnet_mlp`` on the library: raw EEG or DE features in, logits / labels out
 * ``host_models``   GLMNet / Seq2Seq as plain host-side torch modules (BASELINE configs[4] driver: ``examples/run_sweep.py``)
 * ``weights``    state-dict key scheme + counter-RNG synthetic weights
 * ``dist``       sharding of clips over ranks and the all-gather of decoded frames
 
 The compute path has no CPU fallback: without the built library or without a GPU it raises.
 """
-from .weights import (TINY_CLIP_VISION, TINY_IMAGE, TINY_SEMANTIC, TINY_SEQ2SEQ, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO,  # noqa: F401
-                      ClipVisionConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig)
+from .weights import (TINY_CLIP_VISION, TINY_GLMNET, TINY_IMAGE, TINY_SEMANTIC, TINY_SEQ2SEQ, TINY_TEXT, TINY_UNET, TINY_VAE, TINY_VIDEO,  # noqa: F401
+                      ClipVisionConfig, GLMNetConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig, VAEConfig, VideoConfig)
 
 __all__ = ["UNetConfig", "VAEConfig", "TINY_UNET", "TINY_VAE", "Engine", "UNet3DConditionModel", "AutoencoderKL", "CLIPTextModel", "TextConfig", "ViTForImageClassification", "ImageConfig", "VideoMAEForVideoClassification", "VideoConfig", "CLIPVisionModelWithProjection", "ClipVisionConfig",
-           "myTransformer", "Seq2Seq", "Seq2SeqConfig",
+           "myTransformer", "Seq2Seq", "Seq2SeqConfig", "glfnet", "glfnet_mlp", "GLMNetConfig", "DE_PSD", "de_psd",
            "DDIMScheduler", "PNDMScheduler", "LMSDiscreteScheduler", "EulerDiscreteScheduler", "EulerAncestralDiscreteScheduler",
            "DPMSolverMultistepScheduler", "TuneAVideoPipeline", "build_pipeline", "save_videos_grid"]
 
@@ -51,6 +53,12 @@ def __getattr__(name):          # lazy: importing the package must not need torc
     if name in ("myTransformer", "Seq2Seq"):
         from .seq2seq import myTransformer
         return myTransformer
+    if name in ("glfnet", "glfnet_mlp"):
+        from . import glmnet
+        return getattr(glmnet, name)
+    if name in ("DE_PSD", "de_psd"):
+        from . import features
+        return getattr(features, name)
     if name == "AutoencoderKL":
         from .vae import AutoencoderKL
         return AutoencoderKL

@@ -66,6 +66,16 @@ class E2VS2sConfig(C.Structure):
     ]
 
 
+class E2VGlmConfig(C.Structure):
+    """``e2v_glm_config`` of include/eeg2video_hip.h (field order is the ABI): the GLMNet pair, handed to ``e2v_create_ex2``."""
+    _fields_ = [
+        ("glm_electrodes", C.c_int), ("glm_samples", C.c_int), ("glm_occ_first", C.c_int), ("glm_occ_count", C.c_int),
+        ("glm_filters", C.c_int), ("glm_taps", C.c_int), ("glm_pool", C.c_int), ("glm_pool_stride", C.c_int),
+        ("glm_bands", C.c_int), ("glm_hidden1", C.c_int), ("glm_hidden2", C.c_int), ("glm_emb", C.c_int),
+        ("glm_raw_out", C.c_int), ("glm_mlp_out", C.c_int), ("glm_bn_eps", C.c_float),
+    ]
+
+
 class E2VPlanOp(C.Structure):
     """``e2v_plan_op`` of include/eeg2video_hip.h (field order is the ABI)."""
     _fields_ = [
@@ -101,6 +111,9 @@ SIGNATURES = {
     "e2v_default_s2s_config": (None, [C.POINTER(E2VS2sConfig)]),
     "e2v_s2s_config_size": (_i64, []),
     "e2v_create_ex": (_i, [C.POINTER(E2VConfig), C.POINTER(E2VClipVConfig), C.POINTER(E2VS2sConfig), _i, C.POINTER(_ctx)]),
+    "e2v_default_glm_config": (None, [C.POINTER(E2VGlmConfig)]),
+    "e2v_glm_config_size": (_i64, []),
+    "e2v_create_ex2": (_i, [C.POINTER(E2VConfig), C.POINTER(E2VClipVConfig), C.POINTER(E2VS2sConfig), C.POINTER(E2VGlmConfig), _i, C.POINTER(_ctx)]),
     "e2v_destroy": (None, [_ctx]),
     "e2v_last_error": (C.c_char_p, [_ctx]),
     "e2v_load_tensor": (_i, [_ctx, C.c_char_p, _p, _i, c_int64_p, _i]),
@@ -124,7 +137,10 @@ SIGNATURES = {
     "e2v_semantic_predict": (_i, [_ctx, _p, _i, _p, _stream]),
     "e2v_text_encode": (_i, [_ctx, c_int64_p, _i, _i, _p, _stream]),
     "e2v_seq2seq_latents": (_i, [_ctx, _p, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _p, _p, _p, _stream]),
-    "e2v_dana_noise": (_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
+    "e2v_eeg_de_psd": (_i, [_ctx, _p, _i64, _i64, _i64, _i, _i, _i, _i, _i, _p, _p, _p, _p, _stream]),
+    "e2v_glmnet_raw": (_i, [_ctx, _p, _i64, _i64, _i, _p, _p, _p, _p, _p, _stream]),
+    "e2v_glmnet_mlp": (_i, [_ctx, _p, _i, _p, _p, _p, _stream]),
+    "e2v_dana_noise":(_i, [_ctx, _p, _p, _p, c_int64_p, _i, _f, _i, _i, _i, _i, _i, _p, _stream]),
     "e2v_frames_to_uint8": (_i, [_ctx, _p, _p, _i64, _stream]),
     "e2v_frame_metrics": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _stream]),
     "e2v_image_classify": (_i, [_ctx, _p, _i, _i, _i, _i, _i, _p, _p, _p, _stream]),
@@ -172,6 +188,7 @@ SIGNATURES = {
     "e2v_op_tower_activation": (_i, [_ctx, _i, _p, _i64, _i, _p, _stream]),
     "e2v_op_tower_embed": (_i, [_ctx, _i, _p, _p, _p, _i, _i, _i, _p, _stream]),
     "e2v_op_eegnet_embed": (_i, [_ctx, _p, _i64, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _f, _p, _stream]),
+    "e2v_op_shallownet": (_i, [_ctx, _p, _i64, _i64, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _f, _p, _stream]),
     "e2v_op_seq_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _stream]),
     "e2v_op_to_channels_last": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _stream]),
     "e2v_op_from_channels_last": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _stream]),
@@ -217,6 +234,9 @@ def load() -> C.CDLL:
                           "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     if lib.e2v_s2s_config_size() != C.sizeof(E2VS2sConfig):
         raise ImportError(f"{LIB_PATH}: e2v_s2s_config is {lib.e2v_s2s_config_size()} bytes in the library, {C.sizeof(E2VS2sConfig)} in "
+                          "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
+    if lib.e2v_glm_config_size() != C.sizeof(E2VGlmConfig):
+        raise ImportError(f"{LIB_PATH}: e2v_glm_config is {lib.e2v_glm_config_size()} bytes in the library, {C.sizeof(E2VGlmConfig)} in "
                           "this binding (include/eeg2video_hip.h and eeg2video_amd/_lib.py disagree)")
     if lib.e2v_plan_op_size() != C.sizeof(E2VPlanOp):
         raise ImportError(f"{LIB_PATH}: e2v_plan_op is {lib.e2v_plan_op_size()} bytes in the library, {C.sizeof(E2VPlanOp)} in this binding "

@@ -187,6 +187,39 @@ void check_s2s_config(const e2v_s2s_config* v) {
     E2V_REQUIRE(lat % 4 == 0 && (v->s2s_latent_h * (long long)v->s2s_latent_w) % 4 == 0 && lat <= (1 << 24), E2V_EINVAL,
                 "s2s_latent_h * s2s_latent_w must be a multiple of 4 (the linear and layout kernels store quads), a latent at most 2^24 values");
 }
+// what e2v_create_ex2 refuses of a GLMNet config (glm_raw_out or glm_mlp_out != 0): each message names the limit it enforces
+void check_glm_config(const e2v_glm_config* v) {
+    E2V_REQUIRE(v->glm_raw_out >= 0 && v->glm_mlp_out >= 0 && (v->glm_raw_out > 0 || v->glm_mlp_out > 0), E2V_EINVAL,
+                "bad GLMNet config: glm_raw_out and glm_mlp_out are the widths of the two heads, 0 for an absent model, not both 0");
+    E2V_REQUIRE(v->glm_electrodes > 0 && v->glm_samples > 0 && v->glm_occ_first >= 0 && v->glm_occ_count > 0 && v->glm_filters > 0 && v->glm_taps > 0 &&
+                    v->glm_pool > 0 && v->glm_pool_stride > 0 && v->glm_bands > 0 && v->glm_hidden1 > 0 && v->glm_hidden2 > 0 && v->glm_emb > 0 &&
+                    v->glm_bn_eps > 0.f,
+                E2V_EINVAL, "bad GLMNet config: every size and the eps must be positive");
+    E2V_REQUIRE(v->glm_electrodes <= 4096 && v->glm_samples <= 65536 && v->glm_filters <= 1024 && v->glm_taps <= 1024 && v->glm_pool <= 65536 &&
+                    v->glm_bands <= 64 && v->glm_hidden1 <= 65536 && v->glm_hidden2 <= 65536 && v->glm_emb <= 65536 && v->glm_raw_out <= 65536 &&
+                    v->glm_mlp_out <= 65536,
+                E2V_EINVAL, "bad GLMNet config: sizes are bounded (electrodes 4096, filters and taps 1024, the rest 65536, bands 64)");
+    E2V_REQUIRE((long long)v->glm_occ_first + v->glm_occ_count <= v->glm_electrodes, E2V_EINVAL,
+                "the occipital electrodes glm_occ_first .. glm_occ_first + glm_occ_count - 1 must lie inside glm_electrodes");
+    E2V_REQUIRE(v->glm_emb % 4 == 0 && v->glm_hidden1 % 4 == 0 && v->glm_hidden2 % 4 == 0, E2V_EINVAL,
+                "glm_emb, glm_hidden1 and glm_hidden2 must be multiples of 4 (the linear kernels read and store quads)");
+    if (v->glm_raw_out > 0) {
+        const int cols = shallownet_columns(v->glm_samples, v->glm_taps, v->glm_pool, v->glm_pool_stride);
+        E2V_REQUIRE(cols >= 1, E2V_EINVAL, "glm_samples must be at least glm_taps + glm_pool - 1: the pool has to leave one column");
+        const long long width = (long long)v->glm_filters * cols;
+        // the reference sizes its linear 1040 * (T // 200) whatever the pool leaves: only T = 200 .. 204 agree (T = 205 and T = 400 fail inside it)
+        if (v->glm_filters == 40 && v->glm_taps == 25 && v->glm_pool == 51 && v->glm_pool_stride == 5)
+            E2V_REQUIRE(width == 1040LL * (v->glm_samples / 200), E2V_EINVAL,
+                        "at the reference's sizes glm_filters * pooled columns (" + std::to_string(width) + " at glm_samples = " + std::to_string(v->glm_samples) +
+                            ") must equal the `out` linear's width 1040 * (glm_samples / 200) = " + std::to_string(1040LL * (v->glm_samples / 200)) +
+                            ": samples 200 .. 204");
+        E2V_REQUIRE(width % 4 == 0 && width <= (1 << 24), E2V_EINVAL,
+                    "glm_filters * pooled columns, the `out` linear's width, must be a multiple of 4 (the linear kernels read quads), at most 2^24");
+        E2V_REQUIRE(shallownet_lds_bytes(v->glm_electrodes, v->glm_samples, v->glm_taps) <= (size_t)kShallowMaxLdsBytes, E2V_EINVAL,
+                    "one clip glm_electrodes x glm_samples with a filter group's columns must fit the ShallowNet kernel's " + std::to_string(kShallowMaxLdsBytes) +
+                        " bytes of LDS (this config: " + std::to_string(shallownet_lds_bytes(v->glm_electrodes, v->glm_samples, v->glm_taps)) + ")");
+    }
+}
 }  // namespace
 
 extern "C" {
@@ -217,6 +250,26 @@ void e2v_default_s2s_config(e2v_s2s_config* s) {      // myTransformer() as the 
 }
 
 e2v_status e2v_create_ex(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, int device, e2v_ctx** out) {
+    return e2v_create_ex2(cfg, clipv, s2s, nullptr, device, out);
+}
+
+int64_t e2v_glm_config_size(void) { return (int64_t)sizeof(e2v_glm_config); }
+
+void e2v_default_glm_config(e2v_glm_config* g) {      // glfnet(2, 64, 62, 200) and glfnet_mlp(40, 64, 310) as the reference's scripts construct them
+    std::memset(g, 0, sizeof(*g));
+    g->glm_electrodes = 62; g->glm_samples = 200; g->glm_occ_first = 50; g->glm_occ_count = 12;
+    g->glm_filters = 40; g->glm_taps = 25; g->glm_pool = 51; g->glm_pool_stride = 5;
+    g->glm_bands = 5; g->glm_hidden1 = 512; g->glm_hidden2 = 256; g->glm_emb = 64;
+    g->glm_raw_out = 2; g->glm_mlp_out = 40;
+    g->glm_bn_eps = 1e-5f;
+}
+
+e2v_status e2v_create_ex2(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, const e2v_glm_config* glm, int device,
+                          e2v_ctx** out) {
+    if (glm) {                                                   // (all zero: no GLMNet)
+        static const e2v_glm_config none = {};
+        if (std::memcmp(glm, &none, sizeof(none)) == 0) glm = nullptr;
+    }
     if (clipv && clipv->clipv_layers == 0) clipv = nullptr;      // (all zero: no tower)
     if (s2s) {                                                   // (all zero: no Seq2Seq model)
         static const e2v_s2s_config none = {};
@@ -293,11 +346,13 @@ e2v_status e2v_create_ex(const e2v_config* cfg, const e2v_clipv_config* clipv, c
         }
         if (clipv) check_clipv_config(clipv);
         if (s2s) check_s2s_config(s2s);
+        if (glm) check_glm_config(glm);
         c = new e2v_ctx();
         c->cfg = *cfg;
         c->device = device;
         if (clipv) c->vcfg = *clipv;
         if (s2s) c->scfg = *s2s;
+        if (glm) c->gcfg = *glm;
         for (int ch = 0; ch < 3 && c->vcfg.clipv_layers > 0; ++ch) // CLIPImageProcessor: as the image processor's table
             for (int b = 0; b < 256; ++b) {
                 const float x = (float)((double)b * c->vcfg.clipv_rescale);
@@ -448,10 +503,13 @@ e2v_status e2v_op_weight_forms(e2v_ctx* c, const char* key, int* mask) {
 e2v_status e2v_finalize_weights(e2v_ctx* c, int which) {
     if (!c) return E2V_EINVAL;
     return guarded(c, [&] {
-        // (bit 7 belongs to the mask of a context that was made with a Seq2Seq config; on any other it is out of range, as it always was)
-        E2V_REQUIRE(which >= 1 && which <= (c->scfg.s2s_d_model > 0 ? 255 : 127), E2V_EINVAL,
+        // (bits 7 and 8 belong to the mask of a context that was made with a Seq2Seq / a GLMNet config; on any other they are out of range,
+        // as they always were)
+        const int mask = 127 | (c->has_part(e2v_ctx::S2S) ? 128 : 0) | (c->has_part(e2v_ctx::GLM) ? 256 : 0);
+        E2V_REQUIRE(which >= 1 && (which & ~mask) == 0, E2V_EINVAL,
                     "which is a bit mask: 1 UNet, 2 VAE, 4 semantic predictor, 8 text encoder, 16 image classifier, 32 video classifier, 64 CLIP vision tower, "
-                    "128 Seq2Seq latent model (a context made by e2v_create_ex with an e2v_s2s_config only)");
+                    "128 Seq2Seq latent model (a context made by e2v_create_ex with an e2v_s2s_config only), 256 GLMNet (a context made by "
+                    "e2v_create_ex2 with an e2v_glm_config only)");
         c->finalize(which);
     });
 }
@@ -580,6 +638,80 @@ e2v_status e2v_seq2seq_latents(e2v_ctx* c, const float* eeg, int64_t clip_stride
         e.eeg = eeg; e.clip_stride = clip_stride; e.window_stride = window_stride; e.channel_stride = channel_stride; e.mean = mean; e.scale = scale;
         c->seq2seq_latents(e, B, first, count, layout, latents, txt_logits, tokens, S(c, stream));
     });
+}
+
+// DE_PSD of every (clip, window, electrode) row.  No weights: any context with a device serves it.  What is wrong with the call itself
+// is answered first and without a HIP call (E2V_EINVAL, a host-only context included); nothing is enqueued before that passed.
+e2v_status e2v_eeg_de_psd(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride, int B,
+                          int windows, int electrodes, int samples, int fs, const float* de_mean, const float* de_scale, float* de,
+                          float* psd, e2v_stream stream) {
+    DePsdArgs a;
+    return entry(c, [&] {
+        auto off = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+        E2V_REQUIRE(eeg, E2V_EINVAL, "e2v_eeg_de_psd: eeg is NULL");
+        E2V_REQUIRE(de || psd, E2V_EINVAL, "e2v_eeg_de_psd: no output asked for (de and psd are both NULL)");
+        E2V_REQUIRE((de_mean == nullptr) == (de_scale == nullptr), E2V_EINVAL, "e2v_eeg_de_psd: the DE scaler is a mean AND a scale, or neither");
+        E2V_REQUIRE(!off(eeg) && !off(de_mean) && !off(de_scale) && !off(de) && !off(psd), E2V_EINVAL,
+                    "e2v_eeg_de_psd: eeg, de_mean, de_scale, de and psd must be 4-byte aligned");
+        E2V_REQUIRE(clip_stride >= 0 && window_stride >= 0 && channel_stride >= 0, E2V_EINVAL, "e2v_eeg_de_psd: strides are non-negative element counts");
+        E2V_REQUIRE(B >= 1, E2V_EINVAL, "e2v_eeg_de_psd: B must be at least 1");
+        E2V_REQUIRE(windows >= 1 && electrodes >= 1 && samples >= 1 && samples <= 65536, E2V_EINVAL,
+                    "e2v_eeg_de_psd: windows, electrodes and samples must be at least 1, samples at most 65536");
+        E2V_REQUIRE(de_psd_bands(fs, a.first, a.last), E2V_EINVAL,
+                    "e2v_eeg_de_psd: at sampling rate " + std::to_string(fs) + " a band's first bin int(fStart / fs * 200) is below 1 or its last "
+                    "int(fEnd / fs * 200) above 100: the reference would index from the end of the spectrum or past its half (fs = 200 is its rate)");
+        E2V_REQUIRE((long long)B * windows * electrodes <= 0x7FFFFFFFLL, E2V_ESHAPE, "e2v_eeg_de_psd: B * windows * electrodes must stay below 2^31");
+    }, [&] {
+        hipStream_t s = S(c, stream);
+        const std::vector<float>& plan = c->de_psd_plan(samples);      // (lives in the context)
+        Act dp(c->pool, (int64_t)plan.size(), 1);
+        E2V_HIP(hipMemcpyAsync(dp.p, plan.data(), plan.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        a.eeg = eeg; a.clip_stride = clip_stride; a.window_stride = window_stride; a.channel_stride = channel_stride;
+        a.plan = dp.p; a.de_mean = de_mean; a.de_scale = de_scale; a.de = de; a.psd = psd;
+        a.B = B; a.W = windows; a.C = electrodes; a.n = std::min(samples, kDePsdN);
+        a.bins = *std::max_element(a.last, a.last + kDePsdBands) + 1;
+        eeg_de_psd(a, s);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// glfnet.forward + what its callers take from it.  Argument checks first and without a HIP call, then the state of the context.
+e2v_status e2v_glmnet_raw(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t channel_stride, int B, const float* in_mean,
+                          const float* in_scale, float* logits, float* features, int32_t* labels, e2v_stream stream) {
+    return entry(c, [&] {
+        auto off = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+        E2V_REQUIRE(eeg, E2V_EINVAL, "e2v_glmnet_raw: eeg is NULL");
+        E2V_REQUIRE(logits || features || labels, E2V_EINVAL, "e2v_glmnet_raw: no output asked for (logits, features and labels are all NULL)");
+        E2V_REQUIRE((in_mean == nullptr) == (in_scale == nullptr), E2V_EINVAL, "e2v_glmnet_raw: the input scaler is a mean AND a scale, or neither");
+        E2V_REQUIRE(!off(eeg) && !off(in_mean) && !off(in_scale) && !off(logits) && !off(features) && !off(labels), E2V_EINVAL,
+                    "e2v_glmnet_raw: every pointer must be 4-byte aligned");
+        E2V_REQUIRE(clip_stride >= 0 && channel_stride >= 0, E2V_EINVAL, "e2v_glmnet_raw: strides are non-negative element counts");
+        E2V_REQUIRE(B >= 1, E2V_EINVAL, "e2v_glmnet_raw: B must be at least 1");
+        c->require_part(e2v_ctx::GLM);
+        E2V_REQUIRE(c->gcfg.glm_raw_out > 0, E2V_ESTATE, "the context's GLMNet config has no raw model (glm_raw_out = 0)");
+        c->require_ready(e2v_ctx::GLM);
+        E2V_REQUIRE((long long)B * std::max(c->glm_raw_features(), c->gcfg.glm_filters) <= 0x7FFFFFFFLL, E2V_ESHAPE, "e2v_glmnet_raw: B is too large for one call");
+    }, [&] {
+        ShallowArgs a;
+        a.eeg = eeg; a.clip_stride = clip_stride; a.channel_stride = channel_stride; a.mean = in_mean; a.scale = in_scale;
+        c->glmnet_raw(a, B, logits, features, labels, S(c, stream));
+    });
+}
+
+// glfnet_mlp.forward over DE features on the device
+e2v_status e2v_glmnet_mlp(e2v_ctx* c, const float* de, int B, float* logits, float* features, int32_t* labels, e2v_stream stream) {
+    return entry(c, [&] {
+        auto off = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) != 0; };
+        E2V_REQUIRE(de, E2V_EINVAL, "e2v_glmnet_mlp: de is NULL");
+        E2V_REQUIRE(logits || features || labels, E2V_EINVAL, "e2v_glmnet_mlp: no output asked for (logits, features and labels are all NULL)");
+        E2V_REQUIRE(!off(de) && !off(logits) && !off(features) && !off(labels), E2V_EINVAL, "e2v_glmnet_mlp: every pointer must be 4-byte aligned");
+        E2V_REQUIRE(B >= 1, E2V_EINVAL, "e2v_glmnet_mlp: B must be at least 1");
+        c->require_part(e2v_ctx::GLM);
+        E2V_REQUIRE(c->gcfg.glm_mlp_out > 0, E2V_ESTATE, "the context's GLMNet config has no feature model (glm_mlp_out = 0)");
+        c->require_ready(e2v_ctx::GLM);
+        E2V_REQUIRE((long long)B * std::max(c->gcfg.glm_hidden1, c->gcfg.glm_electrodes * c->gcfg.glm_bands + 4) <= 0x7FFFFFFFLL, E2V_ESHAPE,
+                    "e2v_glmnet_mlp: B is too large for one call");
+    }, [&] { c->glmnet_mlp(de, B, logits, features, labels, S(c, stream)); });
 }
 
 e2v_status e2v_dana_noise(e2v_ctx* c, const float* x0, const float* ed, const float* es, const int64_t* host_t, int steps,
@@ -1932,6 +2064,41 @@ e2v_status e2v_op_eegnet_embed(e2v_ctx* c, const float* eeg, int64_t clip_stride
         a.eeg = eeg; a.clip_stride = clip_stride; a.window_stride = window_stride; a.channel_stride = channel_stride; a.mean = mean; a.scale = scale;
         a.pack = dp.p; a.out = out; a.B = B; a.W = W; a.C = C; a.T = T; a.F1 = F1; a.D = D; a.F2 = F2;
         eegnet_embed(a, s);
+        E2V_HIP(hipStreamSynchronize(s));                        // (pk is pageable host memory: the copy has to have left it)
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+// the ShallowNet kernel of e2v_glmnet_raw from torch-layout device tensors (folded on the host, as finalize does)
+e2v_status e2v_op_shallownet(e2v_ctx* c, const float* eeg, int64_t clip_stride, int64_t channel_stride, const float* mean, const float* scale,
+                             int B, int C, int T, int F, int K, int P, int S_, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* bn, float bn_eps, float* out, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(B >= 1 && C >= 1 && C <= 4096 && T >= 1 && T <= 65536 && F >= 1 && F <= 1024 && K >= 1 && K <= 1024 && P >= 1 && P <= 65536 && S_ >= 1 &&
+                        shallownet_columns(T, K, P, S_) >= 1,
+                    E2V_ESHAPE, "ShallowNet: positive, bounded sizes and at least taps + pool - 1 samples");
+        E2V_REQUIRE(eeg && out && w1 && b1 && w2 && b2 && bn, E2V_EINVAL, "null argument");
+        E2V_REQUIRE((mean == nullptr) == (scale == nullptr), E2V_EINVAL, "the scaler is a mean AND a scale, or neither");
+        E2V_REQUIRE(clip_stride >= 0 && channel_stride >= 0 && bn_eps > 0.f, E2V_EINVAL, "negative stride or eps");
+        hipStream_t s = S(c, stream);
+        auto host = [&](const float* d, size_t n) {
+            std::vector<float> h(n);
+            E2V_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(float), hipMemcpyDeviceToHost, s));
+            return h;
+        };
+        const std::vector<float> h1 = host(w1, (size_t)F * K), hb1 = host(b1, F), h2 = host(w2, (size_t)F * F * C), hb2 = host(b2, F), hbn = host(bn, 4 * (size_t)F);
+        E2V_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < F; ++i) E2V_REQUIRE(hbn[3 * F + i] + bn_eps > 0.f, E2V_EINVAL, "running_var + eps must be positive");
+        const std::vector<float> pk = shallownet_fold(ShallowHostW{h1.data(), hb1.data(), h2.data(), hb2.data(), hbn.data()}, C, F, K, bn_eps);
+        Act dp(c->pool, (int64_t)pk.size(), 1);
+        E2V_HIP(hipMemcpyAsync(dp.p, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice, s));
+        ShallowArgs a;
+        a.eeg = eeg; a.clip_stride = clip_stride; a.channel_stride = channel_stride; a.mean = mean; a.scale = scale;
+        a.w = dp.p; a.c = dp.p + pk.size() - shallownet_fold_floats(0, F, 0);
+        a.out = out; a.ldo = F * shallownet_columns(T, K, P, S_);
+        a.B = B; a.C = C; a.T = T; a.F = F; a.K = K; a.P = P; a.S = S_;
+        shallownet(a, s);
         E2V_HIP(hipStreamSynchronize(s));                        // (pk is pageable host memory: the copy has to have left it)
         E2V_HIP(hipGetLastError());
     });

@@ -389,6 +389,58 @@ void seq_attention(const SeqAttnArgs& a, hipStream_t s);
 void seq_latents_bcfhw(const float* in, float* out, int B, int F, int C, int HW, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------
+// EEG front end (eeg.hip; e2v_eeg_de_psd): the reference's DE_PSD of every (clip, window, electrode) row, fp32 in every compute mode.
+// ---------------------------------------------------------------------------------------
+constexpr int kDePsdN = 200;                         // the transform length, STFTN of DE_PSD.py:27, whatever the row length
+constexpr int kDePsdBands = 5;                       // delta, theta, alpha, beta, gamma
+constexpr int kDePsdThreads = 128;                   // one thread per bin of the half spectrum (at most 100)
+constexpr int kDePsdPlanFloats = 3 * kDePsdN;        // the Hann row [200] | cos, sin (2 pi j / 200) interleaved [200][2]
+std::vector<float> de_psd_plan(int m);               // of rows of m samples: host arithmetic in double, rounded once
+// first[p] .. last[p], the bins band p sums at sampling rate fs (the reference's arithmetic); false: outside bins 0 .. 99
+bool de_psd_bands(int fs, int* first, int* last);
+// One workgroup per row: de / psd [B][W][C][5] (either may be null).  Sample t of electrode c of window w of clip b is eeg[b clip_stride +
+// w window_stride + c channel_stride + t] (element strides; 4-byte alignment is all a load assumes); n = min(samples, 200) of them are
+// read.  bins = the largest last[] + 1.  de_mean / de_scale [C][5]: the optional scaler (de - mean) / scale, both or neither.
+struct DePsdArgs {
+    const float* eeg = nullptr; long long clip_stride = 0, window_stride = 0, channel_stride = 0;
+    const float* plan = nullptr;                     // de_psd_plan, on the device
+    const float* de_mean = nullptr; const float* de_scale = nullptr;
+    float* de = nullptr; float* psd = nullptr;
+    int B = 0, W = 0, C = 0, n = 0, bins = 0;
+    int first[kDePsdBands] = {}, last[kDePsdBands] = {};
+};
+void eeg_de_psd(const DePsdArgs& a, hipStream_t s);
+// shallownet (EEG2Video/models/models.py:105-123) up to the flatten, its two convolutions and the BatchNorm folded into one filter:
+// one workgroup per (clip, kShallowGroup output filters); the clip [C][T] and the group's columns [kShallowGroup][T - K + 1] in LDS
+constexpr int kShallowGroup = 4;
+constexpr int kShallowThreads = 256;
+constexpr int kShallowMaxLdsBytes = 156 * 1024;      // of the CU's 160 KiB; the reference's clip (62 x 200) with its columns takes 52 KiB
+E2V_SCHED_HD inline int shallownet_columns(int T, int K, int P, int S) { const int tc = T - K + 1; return tc >= P ? (tc - P) / S + 1 : 0; }
+E2V_SCHED_HD inline size_t shallownet_lds_bytes(int C, int T, int K) {
+    return ((((size_t)C * T + 3) / 4) * 4 + (size_t)kShallowGroup * (T - K + 1)) * sizeof(float);
+}
+// the torch-layout tensors of one shallownet on the HOST: net.0 [F][1][1][K] + bias, net.1 [F][F][C][1] + bias, net.2 as weight | bias |
+// running_mean | running_var, F values each
+struct ShallowHostW { const float* w1; const float* b1; const float* w2; const float* b2; const float* bn; };
+// w [groups][C K][kShallowGroup] | c [groups kShallowGroup] (groups = ceil(F / kShallowGroup), zeros past F); shallownet_fold_floats of them
+std::vector<float> shallownet_fold(const ShallowHostW& h, int C, int F, int K, float bn_eps);
+inline size_t shallownet_fold_floats(int C, int F, int K) { return (size_t)((F + kShallowGroup - 1) / kShallowGroup) * kShallowGroup * ((size_t)C * K + 1); }
+// Sample t of electrode c of clip b is eeg[b clip_stride + c channel_stride + t] (element strides; 4-byte alignment is all a load
+// assumes) -- the occipital net starts `first` electrodes into the same clip.  mean / scale [C][T]: the optional input scaler
+// (x - mean) / scale, both or neither.  out[b ldo + f cols + j]: the pooled maps in the reference's flatten order.
+struct ShallowArgs {
+    const float* eeg = nullptr; long long clip_stride = 0, channel_stride = 0;
+    const float* mean = nullptr; const float* scale = nullptr;
+    const float* w = nullptr; const float* c = nullptr;      // shallownet_fold, on the device (16-byte aligned): its filters, its constants
+    float* out = nullptr; int ldo = 0;
+    int B = 0, C = 0, T = 0, F = 0, K = 0, P = 0, S = 0;
+};
+void shallownet(const ShallowArgs& a, hipStream_t s);
+// head [B][ldh] (L of its columns are logits), feat [B][E2] -> logits [B][L], features [B][E2], labels [B] (int32: argmax, the lowest
+// index among equal maxima); any of the three may be null
+void glm_outputs(const float* head, int ldh, const float* feat, int E2, int L, int B, float* logits, float* features, int* labels, hipStream_t s);
+
+// ---------------------------------------------------------------------------------------
 // element-wise / layout (misc.hip)
 // ---------------------------------------------------------------------------------------
 void ncfhw_to_cl(const float* in, float* out, int n, int C, int Cpad, int FHW, float scale, hipStream_t s, int out_bf16 = 0);

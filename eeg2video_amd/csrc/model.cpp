@@ -88,6 +88,7 @@ bool e2v_ctx::has_part(Part p) const {
         case VIDEO: return cfg.vmae_layers > 0;
         case CLIPV: return vcfg.clipv_layers > 0;
         case S2S: return scfg.s2s_d_model > 0;
+        case GLM: return gcfg.glm_raw_out > 0 || gcfg.glm_mlp_out > 0;
         case N_PARTS: break;
     }
     return false;
@@ -247,6 +248,31 @@ void e2v_ctx::expected_keys() {
         s.add("s2s.positional_encoding.pe", {scfg.s2s_windows, C});
         s.lin("s2s.txtpredictor", scfg.s2s_txt_classes, C);
         s.lin("s2s.predictor", s2s_latent(), C);
+    }
+
+    // ---- GLMNet ("glm.raw." + the names of the reference's glfnet state dict, "glm.mlp." + glfnet_mlp's, each in its order and only
+    // if the model is configured; num_batches_tracked is not a weight and not expected) ----
+    if (has_part(GLM)) {
+        const int F = gcfg.glm_filters, E = gcfg.glm_emb;
+        if (gcfg.glm_raw_out > 0) {
+            for (const auto& net : {std::make_pair(std::string("glm.raw.globalnet"), gcfg.glm_electrodes),
+                                    std::make_pair(std::string("glm.raw.occipital_localnet"), gcfg.glm_occ_count)}) {
+                s.add(net.first + ".net.0.weight", {F, 1, 1, gcfg.glm_taps}); s.add(net.first + ".net.0.bias", {F});
+                s.add(net.first + ".net.1.weight", {F, F, net.second, 1}); s.add(net.first + ".net.1.bias", {F});
+                for (const char* t : {".weight", ".bias", ".running_mean", ".running_var"}) s.add(net.first + ".net.2" + t, {F});
+                s.lin(net.first + ".out", E, glm_raw_features());
+            }
+            s.lin("glm.raw.out", gcfg.glm_raw_out, 2 * E);
+        }
+        if (gcfg.glm_mlp_out > 0) {
+            for (const auto& net : {std::make_pair(std::string("glm.mlp.globalnet"), gcfg.glm_electrodes),
+                                    std::make_pair(std::string("glm.mlp.occipital_localnet"), gcfg.glm_occ_count)}) {
+                s.lin(net.first + ".net.1", gcfg.glm_hidden1, net.second * gcfg.glm_bands);
+                s.lin(net.first + ".net.3", gcfg.glm_hidden2, gcfg.glm_hidden1);
+                s.lin(net.first + ".net.5", E, gcfg.glm_hidden2);
+            }
+            s.lin("glm.mlp.out", gcfg.glm_mlp_out, 2 * E);
+        }
     }
 }
 
@@ -856,6 +882,78 @@ struct Packer {
         v.pred = klin("s2s.predictor");
         c->s2s = std::move(v);
     }
+    void pack_glm() {
+        const e2v_glm_config& g = c->gcfg;
+        GlmW v;
+        const int F = g.glm_filters, K = g.glm_taps, E = g.glm_emb;
+        // every tensor stays where e2v_load_tensor put it and is read back from there (pack_s2s)
+        auto keep = [&](const std::string& k) -> const WTensor& {
+            const WTensor& w = t(k);
+            const int rows = w.shape.size() > 1 ? (int)w.shape[0] : 1;
+            bind_raw(k, w.d(), rows, (int)(w.numel / (size_t)rows));
+            return w;
+        };
+        auto klin = [&](const std::string& n) {
+            const WTensor& w = keep(n + ".weight");
+            return mk_lin(w.d(), keep(n + ".bias").d(), (int)w.shape[1], (int)w.shape[0]);
+        };
+        auto head = [&](const std::string& n, int L) {
+            keep(n + ".weight"); keep(n + ".bias");
+            return padded_head(n + ".weight", n + ".bias", L, 2 * E, false);
+        };
+        auto host = [&](const std::string& k) {
+            const WTensor& w = keep(k);
+            std::vector<float> h(w.numel);
+            E2V_HIP(hipMemcpy(h.data(), w.d(), w.numel * sizeof(float), hipMemcpyDeviceToHost));
+            return h;
+        };
+        // shallownet: the two convolutions and the BatchNorm (eval mode: running statistics) folded on the host
+        auto shallow = [&](const std::string& n, int C) {
+            GlmNetW w;
+            const std::vector<float> w1 = host(n + ".net.0.weight"), b1 = host(n + ".net.0.bias"), w2 = host(n + ".net.1.weight"), b2 = host(n + ".net.1.bias");
+            std::vector<float> bn;
+            for (const char* f : {".weight", ".bias", ".running_mean", ".running_var"}) {
+                const std::vector<float> part = host(n + ".net.2" + f);
+                bn.insert(bn.end(), part.begin(), part.end());
+            }
+            for (int i = 0; i < F; ++i) E2V_REQUIRE(bn[3 * F + i] + g.glm_bn_eps > 0.f, E2V_EINVAL, n + ".net.2.running_var + eps must be positive");
+            const std::vector<float> pk = shallownet_fold(ShallowHostW{w1.data(), b1.data(), w2.data(), b2.data(), bn.data()}, C, F, K, g.glm_bn_eps);
+            float* d = c->dev_alloc(pk.size());
+            E2V_HIP(hipMemcpy(d, pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+            w.fold = d;
+            w.out = klin(n + ".out");
+            return w;
+        };
+        // mlpnet: the first linear's K (electrodes * bands: 310) padded to a multiple of 4 with zero columns, in a block of its own
+        auto mlp = [&](const std::string& n, int in) {
+            GlmMlpW w;
+            w.in = in;
+            const int inp = (in + 3) / 4 * 4;
+            if (inp == in) {
+                w.l1 = klin(n + ".net.1");
+            } else {
+                const WTensor& m = keep(n + ".net.1.weight");
+                const int out = (int)m.shape[0];
+                float* wp = c->dev_alloc((size_t)out * inp);
+                pad_cols(m.d(), in, wp, inp, out, s);
+                w.l1 = mk_lin(wp, keep(n + ".net.1.bias").d(), inp, out);
+            }
+            w.l2 = klin(n + ".net.3");
+            w.l3 = klin(n + ".net.5");
+            return w;
+        };
+        if (g.glm_raw_out > 0) {
+            v.raw_global = shallow("glm.raw.globalnet", g.glm_electrodes);
+            v.raw_occ = shallow("glm.raw.occipital_localnet", g.glm_occ_count);
+            v.raw_head = head("glm.raw.out", g.glm_raw_out);
+        }
+        if (g.glm_mlp_out > 0) {
+            v.mlp_global = mlp("glm.mlp.globalnet", g.glm_electrodes * g.glm_bands);
+            v.mlp_occ = mlp("glm.mlp.occipital_localnet", g.glm_occ_count * g.glm_bands);
+            v.mlp_head = head("glm.mlp.out", g.glm_mlp_out);
+        }
+        c->glm = std::move(v);
+    }
     void pack(e2v_ctx::Part p) {
         switch (p) {
             case e2v_ctx::UNET: pack_unet(); break;
@@ -866,6 +964,7 @@ struct Packer {
             case e2v_ctx::VIDEO: pack_video(); break;
             case e2v_ctx::CLIPV: pack_clipv(); break;
             case e2v_ctx::S2S: pack_s2s(); break;
+            case e2v_ctx::GLM: pack_glm(); break;
             case e2v_ctx::N_PARTS: break;
         }
     }
@@ -880,6 +979,7 @@ void e2v_ctx::finalize(int which) {
     for (int p = 0; p < N_PARTS; ++p)
         if (which & kParts[p].bit) require_part((Part)p);
     E2V_REQUIRE(!(which & kParts[S2S].bit) || !dry_run(), E2V_ESTATE, "the Seq2Seq latent model has no dry run");
+    E2V_REQUIRE(!(which & kParts[GLM].bit) || !dry_run(), E2V_ESTATE, "GLMNet has no dry run");
     for (const auto& k : keys)
         if (which & kParts[key_part(k)].bit) P.t(k);
     E2V_HIP(hipDeviceSynchronize());                 // a part finalized before may still be in use by queued work
@@ -1904,6 +2004,10 @@ const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
     });
 }
 
+const std::vector<float>& e2v_ctx::de_psd_plan(int samples) {
+    return prep_cached(de_psd_plans, samples, 0, [&] { return e2v::de_psd_plan(samples); });
+}
+
 // -----------------------------------------------------------------------------------------------------
 // ViTImageProcessor + ViTForImageClassification.forward(pixel_values).logits (transformers: ViTEmbeddings -- patch convolution,
 // class token, position embeddings --, pre-LN encoder layers without a mask, the final LayerNorm, the classifier on the class row),
@@ -2107,5 +2211,67 @@ void e2v_ctx::seq2seq_latents(const EegnetArgs& eeg_in, int B, int first, int co
             else seq_latents_bcfhw(lat.p, latents, B, count, scfg.s2s_latent_channels, scfg.s2s_latent_h * scfg.s2s_latent_w, s);
         }
     }
+    E2V_HIP(hipGetLastError());
+}
+
+// -----------------------------------------------------------------------------------------------------
+// glfnet.forward in eval mode (EEG2Video/models/models.py:352-373): the global shallownet over all electrodes and the occipital one
+// over electrodes occ_first .. occ_first + occ_count - 1 of the same clip (read through the electrode stride, no gathered copy), each
+// the ShallowNet kernel and its linear; the head over the concatenated embeddings.  fp32 rows and fp32 arithmetic whatever the
+// context's compute mode, every value in an order fixed by the config: a clip's bits depend neither on B nor on its place in the batch.
+// -----------------------------------------------------------------------------------------------------
+namespace {
+void glm_finish(Runner& R, const LinW& head, const Act& a, const Act& b, int E, int L, int B, float* logits, float* features, int* labels) {
+    Act feat(R.pool(), B, 2 * E);
+    copy_rows(a.p, a.C, feat.p, 2 * E, B, E, R.s);
+    copy_rows(b.p, b.C, feat.p + E, 2 * E, B, E, R.s);
+    Act lg = R.linear(head, feat.p, 2 * E, B, R.f32_rows());
+    glm_outputs(lg.p, lg.C, feat.p, 2 * E, L, B, logits, features, labels, R.s);
+}
+}  // namespace
+
+void e2v_ctx::glmnet_raw(const ShallowArgs& eeg_in, int B, float* logits, float* features, int* labels, hipStream_t s) {
+    require_ready(GLM);
+    Runner R{this, s, false};
+    const int E = gcfg.glm_emb, feat = glm_raw_features();
+    auto net = [&](const GlmNetW& w, int first, int count) {
+        Act maps(pool, B, feat);
+        ShallowArgs a = eeg_in;
+        a.eeg += (long long)first * a.channel_stride;
+        if (a.mean) { a.mean += (size_t)first * gcfg.glm_samples; a.scale += (size_t)first * gcfg.glm_samples; }
+        a.w = w.fold;
+        a.c = w.fold + shallownet_fold_floats(count, gcfg.glm_filters, gcfg.glm_taps) - shallownet_fold_floats(0, gcfg.glm_filters, 0);      // (the constants close the pack)
+        a.out = maps.p; a.ldo = feat;
+        a.B = B; a.C = count; a.T = gcfg.glm_samples; a.F = gcfg.glm_filters; a.K = gcfg.glm_taps; a.P = gcfg.glm_pool; a.S = gcfg.glm_pool_stride;
+        shallownet(a, s);
+        return R.linear(w.out, maps.p, feat, B, R.f32_rows());
+    };
+    Act g = net(glm.raw_global, 0, gcfg.glm_electrodes);
+    Act o = net(glm.raw_occ, gcfg.glm_occ_first, gcfg.glm_occ_count);
+    glm_finish(R, glm.raw_head, g, o, E, gcfg.glm_raw_out, B, logits, features, labels);
+    E2V_HIP(hipGetLastError());
+}
+
+// glfnet_mlp.forward (EEG2Video/models/models.py:375-413): two mlpnets (Linear, erf GELU, Linear, GELU, Linear) over the flattened
+// [electrodes][bands] features and over their occipital rows, the same head.  The rows are copied into K-padded buffers of their own
+// first: 310 is no multiple of 4, and the occipital rows start 1000 bytes into a row.
+void e2v_ctx::glmnet_mlp(const float* de, int B, float* logits, float* features, int* labels, hipStream_t s) {
+    require_ready(GLM);
+    Runner R{this, s, false};
+    const int E = gcfg.glm_emb, bands = gcfg.glm_bands, row = gcfg.glm_electrodes * bands;
+    auto net = [&](const GlmMlpW& w, int first) {
+        const int inp = w.l1.in;
+        Act x(pool, B, inp);
+        if (inp != w.in) E2V_HIP(hipMemsetAsync(x.p, 0, x.bytes(), s));
+        copy_rows(de + (size_t)first * bands, row, x.p, inp, B, w.in, s);
+        Act h1 = R.linear(w.l1, x.p, inp, B, R.f32_rows());
+        text_activation(h1.p, (long long)B * h1.C, 1, s);
+        Act h2 = R.linear(w.l2, h1.p, h1.C, B, R.f32_rows());
+        text_activation(h2.p, (long long)B * h2.C, 1, s);
+        return R.linear(w.l3, h2.p, h2.C, B, R.f32_rows());
+    };
+    Act g = net(glm.mlp_global, 0);
+    Act o = net(glm.mlp_occ, gcfg.glm_occ_first);
+    glm_finish(R, glm.mlp_head, g, o, E, gcfg.glm_mlp_out, B, logits, features, labels);
     E2V_HIP(hipGetLastError());
 }

@@ -136,6 +136,16 @@ struct S2sW {
     LinW pred;                                                       // [latent C h w][C]
 };
 
+// The GLMNet pair (the reference's glfnet and glfnet_mlp, EEG2Video/models/models.py:352-413; keys "glm.raw." / "glm.mlp." + their
+// state-dict names): fp32 matrices only, every loaded tensor kept as it is.  Each model is a global and an occipital net and a head
+// over the concatenated embeddings; either model may be absent (head.w == nullptr).
+struct GlmNetW { const float* fold = nullptr; LinW out; };              // shallownet: shallownet_fold (kernels.h) and the linear behind the flatten
+struct GlmMlpW { LinW l1, l2, l3; int in = 0; };                        // mlpnet: l1's K padded to a multiple of 4 (zero columns)
+struct GlmW {
+    GlmNetW raw_global, raw_occ; LinW raw_head;                         // heads: [out rounded up to 4][2 emb]
+    GlmMlpW mlp_global, mlp_occ; LinW mlp_head;
+};
+
 // Where one raw state-dict tensor lives in the packed world of a finalized part (recorded by finalize(), used by e2v_update_tensor):
 //   RAW   the fp32 block the kernels read -- norm affines, plain biases (the uploaded block itself), a slice of a fused bias, the
 //         GEGLU bias (32-element groups interleaved);
@@ -194,7 +204,7 @@ struct e2v_ctx {
     // `which`, the prefix of its state-dict keys, what a context without it / a call before its finalize() is told, whether it is a
     // metric tower (e2v_set_tower_dtype), whether its linears keep fp32 matrices only (Packer::f32_only) and, where e2v_update_tensor refuses its keys, why.  has_part() (model.cpp) is the one
     // switch next to it: the config fields that say whether this context holds the part.
-    enum Part { UNET, VAE, SEM, TEXT, IMAGE, VIDEO, CLIPV, S2S, N_PARTS };
+    enum Part { UNET, VAE, SEM, TEXT, IMAGE, VIDEO, CLIPV, S2S, GLM, N_PARTS };
     struct PartRow {
         int bit; const char* prefix; const char* absent; const char* not_ready; bool tower; bool f32_only; const char* frozen;
         bool owns(const std::string& k) const { return *prefix && k.rfind(prefix, 0) == 0; }
@@ -212,6 +222,8 @@ struct e2v_ctx {
         {64, "clipv.", "the context has no CLIP vision tower (e2v_create_clip_vision)", "CLIP vision tower weights are not finalized", true, true, nullptr},
         {128, "s2s.", "the context has no Seq2Seq latent model (e2v_create_ex)", "Seq2Seq weights are not finalized", false, true,
          "the Seq2Seq model is only called here and its BatchNorms are folded at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128)"},
+        {256, "glm.", "the context has no GLMNet (e2v_create_ex2)", "GLMNet weights are not finalized", false, true,
+         "the GLMNet models are only called here and their BatchNorms are folded at finalize; load new ones with e2v_load_tensor + e2v_finalize_weights(ctx, 256)"},
     };
     // which part owns a state-dict key: the one whose prefix it carries, else the UNet
     static Part key_part(const std::string& k) {
@@ -244,6 +256,7 @@ struct e2v_ctx {
     e2v::TextW text;
     e2v::VisionTowerW image, video, clipv;
     e2v::S2sW s2s;
+    e2v::GlmW glm;
     float image_lut[3 * 256] = {};                               // the processor's pixel value of a byte, per channel (e2v_create)
     std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W): prep_cached (model.cpp)
     const e2v::ImagePrepPlan& prep_plan(int H, int W);
@@ -257,6 +270,11 @@ struct e2v_ctx {
     e2v_s2s_config scfg = {};                                    // the Seq2Seq model's config (e2v_create_ex); all zero: none
     int s2s_features() const { return scfg.s2s_f2 * ((scfg.s2s_samples / 4) / 8); }     // the EEGNet embedding's flattened width
     int s2s_latent() const { return scfg.s2s_latent_channels * scfg.s2s_latent_h * scfg.s2s_latent_w; }
+    std::map<std::array<int, 2>, std::vector<float>> de_psd_plans; // host Hann row and twiddles of e2v_eeg_de_psd per row length: prep_cached (model.cpp)
+    const std::vector<float>& de_psd_plan(int samples);
+    e2v_glm_config gcfg = {};                                    // the GLMNet pair's config (e2v_create_ex2); all zero: none
+    int glm_columns() const { return e2v::shallownet_columns(gcfg.glm_samples, gcfg.glm_taps, gcfg.glm_pool, gcfg.glm_pool_stride); }
+    int glm_raw_features() const { return gcfg.glm_filters * glm_columns(); }      // width of a shallownet's flattened maps (the reference's 1040)
     int conv_algo = 0;                                           // e2v_set_conv_algo: 0 auto, 1 direct, 2 / 3 Winograd F(2x2) / F(4x4) wherever it applies
     bool wino_f4 = true;                                         // auto: F(4x4,3x3) where min(Cin, Cout) >= wino4_min_c and the map, padded to
     int wino4_min_c = 128;                                       //   multiples of 4, grows by <= wino_f4_pad (E2V_WINO_F4 / _F4_MIN_C / _F4_PAD)
@@ -350,5 +368,8 @@ struct e2v_ctx {
     // myTransformer.forward in eval mode (see e2v_seq2seq_latents): tokens [first, first + count) of the steps + 1; any output may be null
     void seq2seq_latents(const e2v::EegnetArgs& eeg, int B, int first, int count, int layout, float* latents, float* txt_logits, float* tokens,
                          hipStream_t s);
+    // glfnet / glfnet_mlp in eval mode (see e2v_glmnet_raw / e2v_glmnet_mlp); any output may be null
+    void glmnet_raw(const e2v::ShallowArgs& eeg, int B, float* logits, float* features, int* labels, hipStream_t s);
+    void glmnet_mlp(const float* de, int B, float* logits, float* features, int* labels, hipStream_t s);
     int clipv_tokens() const { const int g = vcfg.clipv_patch_size > 0 ? vcfg.clipv_image_size / vcfg.clipv_patch_size : 0; return g * g + 1; }
 };

@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import (TEXT_ACTS, ClipVisionConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig, VAEConfig,
-                      VideoConfig)
+from .weights import (TEXT_ACTS, ClipVisionConfig, GLMNetConfig, ImageConfig, SemanticConfig, Seq2SeqConfig, TextConfig, UNetConfig,
+                      VAEConfig, VideoConfig)
 
 _ERRORS = {
     _lib.E2V_EINVAL: ValueError,
@@ -32,15 +32,18 @@ class Engine:
     """Owns one ``e2v_ctx``.  ``unet_cfg`` / ``vae_cfg`` mirror the reference configs; ``text_cfg`` (``None``: no text encoder)
     the ``CLIPTextModel`` one, ``image_cfg`` (``None``: no image classifier) the ``ViTForImageClassification`` one, ``video_cfg``
     (``None``: no video classifier) the ``VideoMAEForVideoClassification`` one, ``clip_vision_cfg`` (``None``: no CLIP vision tower)
-    the ``CLIPVisionModelWithProjection`` one, ``seq2seq_cfg`` (``None``: no Seq2Seq latent model) the reference's ``myTransformer``."""
+    the ``CLIPVisionModelWithProjection`` one, ``seq2seq_cfg`` (``None``: no Seq2Seq latent model) the reference's ``myTransformer``,
+    ``glmnet_cfg`` (``None``: no GLMNet) its ``glfnet`` / ``glfnet_mlp`` pair."""
 
     UNET, VAE, SEMANTIC, TEXT, IMAGE, VIDEO, CLIP_VISION = 1, 2, 4, 8, 16, 32, 64
     SEQ2SEQ = 128
+    GLM = 256
 
     def __init__(self, unet_cfg: UNetConfig = UNetConfig(), vae_cfg: VAEConfig = VAEConfig(), device: int = 0,
                  sem_cfg: SemanticConfig = SemanticConfig(), text_cfg: Optional[TextConfig] = None,
                  image_cfg: Optional[ImageConfig] = None, video_cfg: Optional[VideoConfig] = None,
-                 clip_vision_cfg: Optional[ClipVisionConfig] = None, seq2seq_cfg: Optional[Seq2SeqConfig] = None):
+                 clip_vision_cfg: Optional[ClipVisionConfig] = None, seq2seq_cfg: Optional[Seq2SeqConfig] = None,
+                 glmnet_cfg: Optional[GLMNetConfig] = None):
         if not torch.cuda.is_available():
             raise RuntimeError("eeg2video_amd needs an AMD GPU (torch.cuda.is_available() is False); "
                                "there is no CPU path")
@@ -48,6 +51,7 @@ class Engine:
         self.unet_cfg, self.vae_cfg, self.sem_cfg, self.text_cfg = unet_cfg, vae_cfg, sem_cfg, text_cfg
         self.image_cfg, self.video_cfg, self.clip_vision_cfg = image_cfg, video_cfg, clip_vision_cfg
         self.seq2seq_cfg = seq2seq_cfg
+        self.glmnet_cfg = glmnet_cfg
         self.device = torch.device("cuda", device)
         torch.cuda.set_device(self.device)
         torch.zeros(1, device=self.device)          # make sure torch has initialised the device's context
@@ -81,7 +85,14 @@ class Engine:
             fill_video_config(cfg, video_cfg)
         self._cfg = cfg
         ctx = C.c_void_p()
-        if seq2seq_cfg is not None:                           # either optional part: structs of their own beside the e2v_config
+        if glmnet_cfg is not None:                            # any optional part: structs of their own beside the e2v_config
+            self._clipv_cfg = clip_vision_config(clip_vision_cfg) if clip_vision_cfg is not None else None
+            self._s2s_cfg = seq2seq_config(seq2seq_cfg) if seq2seq_cfg is not None else None
+            self._glm_cfg = glmnet_config(glmnet_cfg)
+            st = self.lib.e2v_create_ex2(C.byref(cfg), C.byref(self._clipv_cfg) if self._clipv_cfg is not None else None,
+                                         C.byref(self._s2s_cfg) if self._s2s_cfg is not None else None, C.byref(self._glm_cfg), device,
+                                         C.byref(ctx))
+        elif seq2seq_cfg is not None:
             self._clipv_cfg = clip_vision_config(clip_vision_cfg) if clip_vision_cfg is not None else None
             self._s2s_cfg = seq2seq_config(seq2seq_cfg)
             st = self.lib.e2v_create_ex(C.byref(cfg), C.byref(self._clipv_cfg) if self._clipv_cfg is not None else None,
@@ -221,7 +232,7 @@ class Engine:
                                              self._UPDATE_DTYPES[dtype], on_device, cshape, len(shape), stream.cuda_stream))
         return out
 
-    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video.", 64: "clipv.", 128: "s2s."}
+    _PART_PREFIX = {4: "semantic.", 2: "vae.", 8: "text.", 16: "image.", 32: "video.", 64: "clipv.", 128: "s2s.", 256: "glm."}
 
     def state_dict(self, part: int, prefix: str = "", dtype: torch.dtype = torch.float32, device="cuda"):
         """Every tensor of one finalized part (``Engine.UNET`` / ``VAE`` / ``SEMANTIC`` / ``TEXT`` / ``IMAGE`` / ``VIDEO`` / ``CLIP_VISION``) as the device holds it NOW -- after any
@@ -235,7 +246,7 @@ class Engine:
         elif dev.type != "cpu":
             raise ValueError(f"state_dict(device={device!r}): 'cuda' or 'cpu'")
         own = self._PART_PREFIX.get(part, "")
-        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO, self.CLIP_VISION, self.SEQ2SEQ) or prefix not in ("", own):
+        if part not in (self.UNET, self.VAE, self.SEMANTIC, self.TEXT, self.IMAGE, self.VIDEO, self.CLIP_VISION, self.SEQ2SEQ, self.GLM) or prefix not in ("", own):
             raise ValueError(f"state_dict(part={part!r}, prefix={prefix!r}): one part, and the prefix load_state_dict adds for it ({own!r})")
         foreign = tuple(self._PART_PREFIX.values())
         out = OrderedDict()
@@ -633,6 +644,130 @@ class Engine:
                                                  _stream()))
         return out
 
+    def eeg_de_psd(self, eeg: torch.Tensor, *, samples: Optional[int] = None, strides: Optional[Tuple[int, int, int]] = None,
+                   batch: Optional[int] = None, windows: Optional[int] = None, electrodes: Optional[int] = None, fs: int = 200,
+                   scaler: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, de: bool = True, psd: bool = True,
+                   out: Optional[Dict[str, torch.Tensor]] = None):
+        """The reference's ``DE_PSD`` of every row (``e2v_eeg_de_psd``).  ``eeg``: a contiguous fp32 tensor on the engine's device, by
+        default stacked windows ``[B, windows, electrodes, samples]``; with ``strides`` = (clip, window, electrode) element strides,
+        ``batch``, ``windows``, ``electrodes`` and ``samples`` any buffer the strides describe -- the ``step``-spaced windows of a raw
+        segment ``[B, electrodes, L]`` are ``(electrodes * L, step, L)``.  The transform length is 200 whatever ``samples`` is (longer
+        rows are truncated after the Hann window, as the reference does).  ``scaler``: ``(mean, scale)``, ``electrodes * 5`` values each,
+        applied to DE as ``(de - mean) / scale``.  Returns ``(de, psd)``, each ``[B, windows, electrodes, 5]`` or ``None`` where not asked
+        for; ``out``: contiguous fp32 tensors of that shape to write instead, by name.  An all-zero row gives ``psd`` 0 and ``de``
+        ``-inf``.  fp32 arithmetic whatever the compute dtype."""
+        if not isinstance(eeg, torch.Tensor) or eeg.device != self.device or eeg.dtype != torch.float32 or not eeg.is_contiguous():
+            raise ValueError(f"`eeg` has to be a contiguous float32 tensor on {self.device}")
+        if strides is None:
+            if eeg.dim() != 4 or min(eeg.shape) < 1:
+                raise ValueError(f"expected eeg [B,windows,electrodes,samples], got {tuple(eeg.shape)}")
+            b, w, c, m = (int(v) for v in eeg.shape)
+            if any(given is not None and int(given) != have for given, have in ((batch, b), (windows, w), (electrodes, c), (samples, m))):
+                raise ValueError("without `strides` the sizes are the shape of `eeg`")
+            strides = (w * c * m, c * m, m)
+        else:
+            if None in (samples, batch, windows, electrodes):
+                raise ValueError("`strides` needs `batch`, `windows`, `electrodes` and `samples`")
+            b, w, c, m = int(batch), int(windows), int(electrodes), int(samples)
+            cs, ws, es = (int(v) for v in strides)
+            if min(cs, ws, es) < 0 or min(b, w, c, m) < 1:
+                raise ValueError("strides are non-negative element counts, sizes at least 1")
+            if (b - 1) * cs + (w - 1) * ws + (c - 1) * es + m > eeg.numel():
+                raise ValueError("the strides reach past the end of `eeg`")
+            strides = (cs, ws, es)
+        mean_p = scale_p = None
+        if scaler is not None:
+            mean, scale = (self._dev(t, "scaler") for t in scaler)
+            if mean.numel() != c * 5 or scale.numel() != c * 5:
+                raise ValueError(f"the scaler is (mean, scale), each electrodes * 5 = {c * 5} values")
+            mean_p, scale_p = mean.data_ptr(), scale.data_ptr()
+        given = out or {}
+        de_t = self._op_out(given.get("de"), (b, w, c, 5)) if de else None
+        psd_t = self._op_out(given.get("psd"), (b, w, c, 5)) if psd else None
+        self._check(self.lib.e2v_eeg_de_psd(self.ctx, eeg.data_ptr(), strides[0], strides[1], strides[2], b, w, c, m, int(fs), mean_p, scale_p,
+                                            de_t.data_ptr() if de else None, psd_t.data_ptr() if psd else None, _stream()))
+        return de_t, psd_t
+
+    def _glm_outputs(self, b, width, logits, features, labels, out):
+        given, res = out or {}, {}
+        if logits:
+            res["logits"] = self._op_out(given.get("logits"), (b, width))
+        if features:
+            res["features"] = self._op_out(given.get("features"), (b, 2 * self.glmnet_cfg.emb))
+        if labels:
+            lab = given.get("labels")
+            if lab is None:
+                lab = torch.empty(b, device=self.device, dtype=torch.int32)
+            elif not isinstance(lab, torch.Tensor) or lab.device != self.device or lab.dtype != torch.int32 or tuple(lab.shape) != (b,) or not lab.is_contiguous():
+                raise ValueError(f"`labels` has to be a contiguous int32 tensor [{b}] on {self.device}")
+            res["labels"] = lab
+        return res
+
+    def glmnet_raw(self, eeg: torch.Tensor, *, strides: Optional[Tuple[int, int]] = None, batch: Optional[int] = None,
+                   scaler: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, logits: bool = True, features: bool = False,
+                   labels: bool = False, out: Optional[Dict[str, torch.Tensor]] = None):
+        """``glfnet.forward`` in eval mode (``e2v_glmnet_raw``).  ``eeg``: a contiguous fp32 tensor on the engine's device, by default
+        ``[B, electrodes, samples]`` (or the reference's ``[B, 1, electrodes, samples]``); with ``strides`` = (clip, electrode) element
+        strides and ``batch`` any buffer the strides describe -- the first ``samples`` of raw segments ``[B, electrodes, L]`` are
+        ``(electrodes * L, L)``.  ``scaler``: ``(mean, scale)`` ``[electrodes, samples]`` applied as ``(x - mean) / scale``.  Returns a
+        dict with the outputs asked for: ``logits`` ``[B, raw_out]``, ``features`` ``[B, 2 emb]`` (the concatenated embeddings),
+        ``labels`` ``[B]`` int32 (argmax, the lowest index among equal maxima).  ``out``: tensors of those shapes to write instead, by
+        name.  fp32 arithmetic whatever the compute dtype."""
+        gc = self.glmnet_cfg
+        if gc is None:
+            raise RuntimeError("this engine was built without a GLMNet (Engine(..., glmnet_cfg=GLMNetConfig()))")
+        if gc.raw_out <= 0:
+            raise RuntimeError("this engine's GLMNet config has no raw model (raw_out = 0)")
+        if not isinstance(eeg, torch.Tensor) or eeg.device != self.device or eeg.dtype != torch.float32 or not eeg.is_contiguous():
+            raise ValueError(f"`eeg` has to be a contiguous float32 tensor on {self.device}")
+        if strides is None:
+            if eeg.dim() == 4 and eeg.shape[1] == 1:
+                eeg = eeg[:, 0]
+            if eeg.dim() != 3 or tuple(eeg.shape[1:]) != (gc.electrodes, gc.samples) or eeg.shape[0] < 1:
+                raise ValueError(f"expected eeg [B,{gc.electrodes},{gc.samples}] or [B,1,{gc.electrodes},{gc.samples}], got {tuple(eeg.shape)}")
+            b = int(eeg.shape[0])
+            strides = (gc.electrodes * gc.samples, gc.samples)
+        else:
+            if batch is None:
+                raise ValueError("`strides` needs `batch`")
+            b = int(batch)
+            cs, es = (int(v) for v in strides)
+            if min(cs, es) < 0 or b < 1:
+                raise ValueError("strides are non-negative element counts, batch at least 1")
+            if (b - 1) * cs + (gc.electrodes - 1) * es + gc.samples > eeg.numel():
+                raise ValueError("the strides reach past the end of `eeg`")
+            strides = (cs, es)
+        mean_p = scale_p = None
+        if scaler is not None:
+            mean, scale = (self._dev(t, "scaler") for t in scaler)
+            if tuple(mean.shape) != (gc.electrodes, gc.samples) or mean.shape != scale.shape:
+                raise ValueError(f"the scaler is (mean, scale), each [{gc.electrodes},{gc.samples}]")
+            mean_p, scale_p = mean.data_ptr(), scale.data_ptr()
+        res = self._glm_outputs(b, gc.raw_out, logits, features, labels, out)
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        self._check(self.lib.e2v_glmnet_raw(self.ctx, eeg.data_ptr(), strides[0], strides[1], b, mean_p, scale_p, ptr("logits"), ptr("features"),
+                                            ptr("labels"), _stream()))
+        return res
+
+    def glmnet_mlp(self, de: torch.Tensor, *, logits: bool = True, features: bool = False, labels: bool = False,
+                   out: Optional[Dict[str, torch.Tensor]] = None):
+        """``glfnet_mlp.forward`` (``e2v_glmnet_mlp``).  ``de``: a contiguous fp32 tensor ``[B, electrodes, bands]`` on the engine's
+        device, for instance one window of ``eeg_de_psd``.  Outputs as ``glmnet_raw``, ``logits`` ``[B, mlp_out]``."""
+        gc = self.glmnet_cfg
+        if gc is None:
+            raise RuntimeError("this engine was built without a GLMNet (Engine(..., glmnet_cfg=GLMNetConfig()))")
+        if gc.mlp_out <= 0:
+            raise RuntimeError("this engine's GLMNet config has no feature model (mlp_out = 0)")
+        if not isinstance(de, torch.Tensor) or de.device != self.device or de.dtype != torch.float32 or not de.is_contiguous():
+            raise ValueError(f"`de` has to be a contiguous float32 tensor on {self.device}")
+        if de.dim() != 3 or tuple(de.shape[1:]) != (gc.electrodes, gc.bands) or de.shape[0] < 1:
+            raise ValueError(f"expected de [B,{gc.electrodes},{gc.bands}], got {tuple(de.shape)}")
+        b = int(de.shape[0])
+        res = self._glm_outputs(b, gc.mlp_out, logits, features, labels, out)
+        ptr = lambda k: res[k].data_ptr() if k in res else None
+        self._check(self.lib.e2v_glmnet_mlp(self.ctx, de.data_ptr(), b, ptr("logits"), ptr("features"), ptr("labels"), _stream()))
+        return res
+
     def dana_noise(self, x0: torch.Tensor, eps_div: torch.Tensor, eps_same: torch.Tensor, t: Sequence[int],
                    dynamic_beta: float, time_steps: int = 500) -> torch.Tensor:
         """``[B,F,C,H,W]`` Seq2Seq latents + the two noise draws -> noised latents in the pipeline layout ``[B,C,F,H,W]``."""
@@ -950,6 +1085,38 @@ class Engine:
                                                  _stream()))
         return out
 
+    def op_shallownet(self, eeg, weights, *, B, C, T, F, K, P, S, strides=None, scaler=None, bn_eps=1e-5, out=None):
+        """``e2v_op_shallownet``: the ShallowNet kernel on its own.  ``eeg``: a contiguous fp32 device tensor read through ``strides`` =
+        (clip, electrode) element strides (``None``: ``[B,C,T]``); ``weights``: the torch-layout tensors ``dict(w1 [F,1,1,K], b1 [F],
+        w2 [F,F,C,1], b2 [F], bn [4,F])``, ``bn`` the stack of weight, bias, running_mean, running_var; ``scaler``: ``(mean, scale)``
+        ``[C,T]``.  Returns the pooled maps ``[B, F * columns]``, filter-major."""
+        if not isinstance(eeg, torch.Tensor) or eeg.device != self.device or eeg.dtype != torch.float32 or not eeg.is_contiguous():
+            raise ValueError(f"`eeg` has to be a contiguous float32 tensor on {self.device}")
+        if strides is None:
+            strides = (C * T, T)
+        cs, es = (int(v) for v in strides)
+        if min(cs, es) < 0 or (B - 1) * cs + (C - 1) * es + T > eeg.numel():
+            raise ValueError("the strides are negative or reach past the end of `eeg`")
+        want = {"w1": F * K, "b1": F, "w2": F * F * C, "b2": F, "bn": 4 * F}
+        w = {}
+        for k, n in want.items():
+            w[k] = self._dev(weights[k], k)
+            if w[k].numel() != n:
+                raise ValueError(f"weights[{k!r}] has {w[k].numel()} elements, expected {n}")
+        mean_p = scale_p = None
+        if scaler is not None:
+            mean, scale = (self._dev(t, "scaler") for t in scaler)
+            if mean.numel() != C * T or scale.numel() != C * T:
+                raise ValueError("the scaler is (mean, scale), each [C,T]")
+            mean_p, scale_p = mean.data_ptr(), scale.data_ptr()
+        tc = T - K + 1
+        cols = (tc - P) // S + 1 if tc >= P else 0
+        out = self._op_out(out, (B, F * cols))
+        self._check(self.lib.e2v_op_shallownet(self.ctx, eeg.data_ptr(), cs, es, mean_p, scale_p, B, C, T, F, K, P, S, w["w1"].data_ptr(),
+                                               w["b1"].data_ptr(), w["w2"].data_ptr(), w["b2"].data_ptr(), w["bn"].data_ptr(), float(bn_eps),
+                                               out.data_ptr(), _stream()))
+        return out
+
     def op_seq_attention(self, q, k, v, *, B, heads, D, Nq, Nk, q_pos0=0, causal=False, out=None):
         """``e2v_op_seq_attention``: ``q`` a 2-D view ``[B*Nq, heads*D]``, ``k``, ``v`` 2-D views ``[B*Nk, heads*D]`` of one row stride
         (``.stride(0)``; unit column stride) -> ``[B*Nq, heads*D]``; ``causal``: query i sits at position ``q_pos0 + i``.
@@ -1176,6 +1343,16 @@ def seq2seq_config(sc: Seq2SeqConfig) -> "_lib.E2VS2sConfig":
     cfg.s2s_encoder_layers, cfg.s2s_decoder_layers, cfg.s2s_steps = sc.encoder_layers, sc.decoder_layers, sc.steps
     cfg.s2s_latent_channels, cfg.s2s_latent_h, cfg.s2s_latent_w = sc.latent
     cfg.s2s_txt_classes, cfg.s2s_norm_eps, cfg.s2s_bn_eps = sc.txt_classes, sc.norm_eps, sc.bn_eps
+    return cfg
+
+
+def glmnet_config(gc: GLMNetConfig) -> "_lib.E2VGlmConfig":
+    """The ``e2v_glm_config`` of a ``GLMNetConfig`` (``e2v_create_ex2``)."""
+    cfg = _lib.E2VGlmConfig()
+    cfg.glm_electrodes, cfg.glm_samples, cfg.glm_occ_first, cfg.glm_occ_count = gc.electrodes, gc.samples, gc.occ_first, gc.occ_count
+    cfg.glm_filters, cfg.glm_taps, cfg.glm_pool, cfg.glm_pool_stride = gc.filters, gc.taps, gc.pool, gc.pool_stride
+    cfg.glm_bands, (cfg.glm_hidden1, cfg.glm_hidden2), cfg.glm_emb = gc.bands, gc.hidden, gc.emb
+    cfg.glm_raw_out, cfg.glm_mlp_out, cfg.glm_bn_eps = gc.raw_out, gc.mlp_out, gc.bn_eps
     return cfg
 
 

@@ -2,6 +2,9 @@
 "the GLMNet EEG encoder and Seq2Seq latent predictor stay as lightweight PyTorch-ROCm host code").  They exist so that the
 end-to-end driver (``examples/run_sweep.py``) can feed the accelerated path with tensors of the right shapes and measure the
 host stages' share; weights are random-init (no checkpoints offline), so nothing here is parity-tested against the reference.
+The reference's own models now run on the library: ``eeg2video_amd.glmnet`` (``glfnet``, ``glfnet_mlp``) and ``eeg2video_amd.seq2seq``
+(``myTransformer``), each checked against a fixture its reference module wrote; ``examples/run_sweep.py --glmnet native --seq2seq
+native`` selects them.  The modules below stay the sweep's default stages.
 
 Architectures (written from the shapes the reference documents, not copied):
 * ``GLMNet``  -- ``glfnet`` of ``EEG2Video/models/models.py:352-375``: a global ShallowNet over all 62 channels and a local one

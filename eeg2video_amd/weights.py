@@ -397,6 +397,85 @@ def seq2seq_position_table(rows: int, d_model: int):
     return pe
 
 
+@dataclass(frozen=True)
+class GLMNetConfig:
+    """The reference's GLMNet pair (``EEG2Video/models/models.py:105-123, 352-413``): ``glfnet(raw_out, emb, electrodes, samples)`` over
+    raw EEG -- a global ``shallownet`` over all electrodes and one over the occipital electrodes ``occ_first .. occ_first + occ_count -
+    1``, each ``filters`` temporal filters of ``taps`` taps, a spatial mix, BatchNorm, ELU and an average pool ``pool`` / ``pool_stride``
+    -- and ``glfnet_mlp(mlp_out, emb, electrodes * bands)`` over DE features, two ``mlpnet`` (``hidden`` = (512, 256)).  ``raw_out`` /
+    ``mlp_out`` 0: that model is absent.  Defaults are the values the reference hard-codes and the sizes its scripts construct."""
+    electrodes: int = 62
+    samples: int = 200
+    occ_first: int = 50
+    occ_count: int = 12
+    filters: int = 40
+    taps: int = 25
+    pool: int = 51
+    pool_stride: int = 5
+    bands: int = 5
+    hidden: Tuple[int, int] = (512, 256)
+    emb: int = 64
+    raw_out: int = 2
+    mlp_out: int = 40
+    bn_eps: float = 1e-5
+
+    @property
+    def pooled_columns(self) -> int:
+        """Columns the pool leaves of ``samples - taps + 1`` (the reference's 26; 0 where the row is too short)."""
+        t = self.samples - self.taps + 1
+        return (t - self.pool) // self.pool_stride + 1 if t >= self.pool else 0
+
+    @property
+    def raw_features(self) -> int:
+        """Width of a ``shallownet``'s flattened maps (the reference's 1040)."""
+        return self.filters * self.pooled_columns
+
+
+#: 5 electrodes (occipital 2..4) of 40 samples, 8 filters of 5 taps, pool 7 / 3: ten pooled columns
+TINY_GLMNET = GLMNetConfig(electrodes=5, samples=40, occ_first=2, occ_count=3, filters=8, taps=5, pool=7, pool_stride=3, hidden=(32, 16),
+                           emb=8, raw_out=2, mlp_out=6)
+
+
+def glmnet_param_spec(cfg: GLMNetConfig, model: str) -> "OrderedDict[str, Tuple[int, ...]]":
+    """name -> shape of ``glfnet(...).state_dict()`` (``model="raw"``, 24 entries) or ``glfnet_mlp(...).state_dict()`` (``"mlp"``, 14) in
+    the module's order, ``num_batches_tracked`` (shape ``()``) included."""
+    spec: "OrderedDict[str, Tuple[int, ...]]" = OrderedDict()
+    if model == "raw":
+        f = cfg.filters
+        for name, c in (("globalnet", cfg.electrodes), ("occipital_localnet", cfg.occ_count)):
+            spec[f"{name}.net.0.weight"] = (f, 1, 1, cfg.taps)
+            spec[f"{name}.net.0.bias"] = (f,)
+            spec[f"{name}.net.1.weight"] = (f, f, c, 1)
+            spec[f"{name}.net.1.bias"] = (f,)
+            for leaf in ("weight", "bias", "running_mean", "running_var"):
+                spec[f"{name}.net.2.{leaf}"] = (f,)
+            spec[f"{name}.net.2.num_batches_tracked"] = ()
+            _lin(spec, f"{name}.out", cfg.emb, cfg.raw_features)
+        _lin(spec, "out", cfg.raw_out, 2 * cfg.emb)
+    elif model == "mlp":
+        for name, c in (("globalnet", cfg.electrodes), ("occipital_localnet", cfg.occ_count)):
+            _lin(spec, f"{name}.net.1", cfg.hidden[0], c * cfg.bands)
+            _lin(spec, f"{name}.net.3", cfg.hidden[1], cfg.hidden[0])
+            _lin(spec, f"{name}.net.5", cfg.emb, cfg.hidden[1])
+        _lin(spec, "out", cfg.mlp_out, 2 * cfg.emb)
+    else:
+        raise ValueError(f"model {model!r}: 'raw' (glfnet) or 'mlp' (glfnet_mlp)")
+    return spec
+
+
+def glmnet_synth_state_dict(cfg: GLMNetConfig, model: str, seed: int = 42) -> "OrderedDict[str, np.ndarray]":
+    """``synth_state_dict(..., mode="perturbed")`` of one model with BatchNorm statistics that show: gamma in 0.75 .. 1.25 (the generic
+    draw for a name ``net.2.weight`` would straddle zero), running_mean within +-0.16, running_var 0.5 .. 1.5, ``num_batches_tracked``
+    an int64 zero as torch keeps it."""
+    sd = synth_state_dict(glmnet_param_spec(cfg, model), seed=seed, mode="perturbed")
+    for k in sd:
+        if k.endswith("net.2.weight"):
+            sd[k] = (0.75 + 0.5 * counter_uniform(seed, k, sd[k].size)).astype(np.float32)
+        if k.endswith("num_batches_tracked"):
+            sd[k] = np.zeros((), np.int64)
+    return sd
+
+
 #: how ``transformers`` 5 spells the per-layer tensors of the same model (``vit.layers.{i}.`` instead of ``vit.encoder.layer.{i}.``)
 _VIT_V5_NAMES = (("attention.q_proj.", "attention.attention.query."), ("attention.k_proj.", "attention.attention.key."),
                  ("attention.v_proj.", "attention.attention.value."), ("attention.o_proj.", "attention.output.dense."),

@@ -2,8 +2,8 @@
 40-concept sweep" -- the whole generation flow of the reference (EEG2Video/inference_eeg2video.py:60-98 with the Seq2Seq / DANA
 latents of EEG2Video_New) over 40 concepts x 5 clips, batched and shardable over ranks:
 
-    raw EEG [B,62,200] ----GLMNet (host torch)------> fast / slow label -> DANA's dynamic_beta (0.3 / 0.2)
-    DE features [B,310] ---Semantic Predictor (HIP)--> cond [B,77,768]
+    raw EEG [B,62,200] ----GLMNet (host torch; --glmnet native: HIP)--> fast / slow label -> DANA's dynamic_beta (0.3 / 0.2)
+    DE features [B,310] ---Semantic Predictor (HIP)--> cond [B,77,768]      (--features native: DE of the clip's raw [62,400] segment, HIP)
     EEG windows [B,7,62,100] --Seq2Seq (host torch)--> latents [B,6,4,36,64] --DANA noise + layout fix (HIP)--> [B,4,6,36,64]
     e2v_generate (HIP: 50 x [UNet3D on 2B samples, CFG, DDIM] + VAE decode) -> frames -> uint8 (HIP) -> GIF / NPY writer (host)
 
@@ -59,6 +59,13 @@ def main(argv=None, engine=None):
     ap.add_argument("--seq2seq", default="host", choices=["host", "native"],
                     help="the Seq2Seq stage: host (default) -- the plain-torch look-alike of host_models --, or native -- the reference's "
                          "myTransformer on the device (e2v_seq2seq_latents; synthetic weights, fp32 whatever --dtype)")
+    ap.add_argument("--glmnet", default="host", choices=["host", "native"],
+                    help="the GLMNet stage: host (default) -- the plain-torch look-alike of host_models --, or native -- the reference's "
+                         "glfnet on the device (e2v_glmnet_raw; synthetic weights, fp32 whatever --dtype)")
+    ap.add_argument("--features", default="synthetic", choices=["synthetic", "native"],
+                    help="the Semantic Predictor's input: synthetic (default) -- a noise draw per clip --, or native -- the DE features of the "
+                         "clip's own synthetic raw 2-s segment [62, 400] (e2v_eeg_de_psd, a fixed seeded scaler), whose first 200 samples then "
+                         "serve the GLMNet stage; adds a `features` stage; under --tiny the semantic predictor takes 310 inputs")
     ap.add_argument("--out", default="", help="directory for <concept>_<k>.gif (empty: frames are produced but not written)")
     ap.add_argument("--npy", action="store_true", help="write .npy instead of .gif")
     ap.add_argument("--score-against", default="", metavar="DIR",
@@ -85,15 +92,16 @@ def main(argv=None, engine=None):
     from eeg2video_amd.host_models import GLMNet, Seq2SeqLatents
     from eeg2video_amd.semantic import CLIP
     from eeg2video_amd.util import save_videos_grid
-    from eeg2video_amd.weights import (TINY_UNET, TINY_VAE, SemanticConfig, Seq2SeqConfig, UNetConfig, VAEConfig, counter_normal,
-                                       synth_state_dict, unet_param_spec, vae_param_spec)
+    from eeg2video_amd.weights import (TINY_UNET, TINY_VAE, GLMNetConfig, SemanticConfig, Seq2SeqConfig, UNetConfig, VAEConfig, counter_normal,
+                                       counter_uniform, synth_state_dict, unet_param_spec, vae_param_spec)
 
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local)
         dist.init_process_group("nccl", device_id=torch.device("cuda", local))
-    ucfg, vcfg, scfg = ((TINY_UNET, TINY_VAE, SemanticConfig(in_features=22, hidden=96, tokens=77)) if args.tiny
+    native_de = args.features == "native"
+    ucfg, vcfg, scfg = ((TINY_UNET, TINY_VAE, SemanticConfig(in_features=310 if native_de else 22, hidden=96, tokens=77)) if args.tiny
                         else (UNetConfig(), VAEConfig(), SemanticConfig()))
     F, h, w = (3, 4, 6) if args.tiny else (6, 36, 64)
     # --seq2seq native: the reference's model over the sweep's [7, 62, 100] windows, its latent and steps those of the sweep
@@ -101,11 +109,13 @@ def main(argv=None, engine=None):
     if args.seq2seq == "native":
         s2s_cfg = (Seq2SeqConfig(d_model=64, heads=4, ffn=128, encoder_layers=1, decoder_layers=2, steps=F, latent=(4, h, w)) if args.tiny
                    else Seq2SeqConfig(steps=F, latent=(4, h, w)))
+    # --glmnet native: the reference's glfnet(2, 64, 62, 200) alone (no feature model)
+    glm_cfg = GLMNetConfig(mlp_out=0) if args.glmnet == "native" else None
     t_setup = time.perf_counter()
     if engine is not None:
         eng = engine
     else:
-        eng = Engine(ucfg, vcfg, local, sem_cfg=scfg, seq2seq_cfg=s2s_cfg)
+        eng = Engine(ucfg, vcfg, local, sem_cfg=scfg, seq2seq_cfg=s2s_cfg, glmnet_cfg=glm_cfg)
         eng.load_state_dict(synth_state_dict(unet_param_spec(ucfg), seed=42, mode="reference_init"))
         eng.load_state_dict(synth_state_dict(vae_param_spec(vcfg), seed=43, mode="reference_init"), prefix="vae.")
         eng.finalize(Engine.UNET | Engine.VAE)
@@ -116,7 +126,15 @@ def main(argv=None, engine=None):
     eng.set_compute_dtype(args.dtype)
     dev = eng.device
     torch.manual_seed(0)
-    glm = GLMNet(out_dim=2, emb_dim=64, C=62, T=200).to(dev).eval()
+    t_ = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    if glm_cfg is None:
+        glm = GLMNet(out_dim=2, emb_dim=64, C=62, T=200).to(dev).eval()
+    else:                                                           # on the sweep's engine where it was built for the model, else on one of its own
+        from eeg2video_amd.glmnet import glfnet
+        glm = glfnet(2, 64, 62, 200, config=glm_cfg, engine=eng if eng.glmnet_cfg == glm_cfg else None, device=local).init_synthetic(48)
+    de_scaler = None
+    if native_de:                                                   # a StandardScaler's mean_ / scale_ over the 310 features, fixed and seeded
+        de_scaler = (t_(10.0 + counter_normal(45, "de_mean", (310,))).to(dev), t_(1.0 + counter_uniform(46, "de_scale", 310)).to(dev))
     if s2s_cfg is None:
         s2s = Seq2SeqLatents(d_model=512 if not args.tiny else 64, latent_shape=(4, h, w), frames=F).to(dev).eval()
     else:                                                           # on the sweep's engine where it was built for the model, else on one of its own
@@ -131,6 +149,8 @@ def main(argv=None, engine=None):
     neg = t(counter_normal(2, "neg", (1, scfg.tokens, ucfg.cross_attention_dim))).to(dev)
     stage = {"glmnet": 0.0, "seq2seq": 0.0, "semantic": 0.0, "dana": 0.0, "generate": 0.0, "uint8_d2h": 0.0, "write": 0.0}
     mine, scores, classes, video_classes, clip_embeds = [], [], [], [], []
+    if native_de:
+        stage["features"] = 0.0
     if args.score_against:
         stage["score"] = 0.0
     vit = None
@@ -160,12 +180,23 @@ def main(argv=None, engine=None):
         ids = list(range(b0, min(b0 + args.batch, hi)))
         B = len(ids)
         # synthetic "sub1" recordings of these clips (seeded by the clip id: any rank reproduces any clip)
-        raw = torch.stack([t(counter_normal(1000 + k, "raw", (62, 200))) for k in ids]).to(dev)
         win = torch.stack([t(counter_normal(2000 + k, "win", (7, 62, 100))) for k in ids]).to(dev)
-        de = torch.stack([t(counter_normal(3000 + k, "de", (scfg.in_features,))) for k in ids]).to(dev)
+        if native_de:                                               # the clip's 2-s segment: its DE features, and its first 200 samples below
+            seg = torch.stack([t(counter_normal(1000 + k, "segment", (62, 400))) for k in ids]).to(dev)
+            t0 = time.perf_counter()
+            de = eng.eeg_de_psd(seg, samples=400, strides=(62 * 400, 0, 400), batch=B, windows=1, electrodes=62, scaler=de_scaler,
+                                psd=False)[0].reshape(B, 310)
+            tick("features", t0)
+            raw = seg[:, :, :200].contiguous() if glm_cfg is None else seg
+        else:
+            raw = torch.stack([t(counter_normal(1000 + k, "raw", (62, 200))) for k in ids]).to(dev)
+            de = torch.stack([t(counter_normal(3000 + k, "de", (scfg.in_features,))) for k in ids]).to(dev)
         t0 = time.perf_counter()
-        with torch.no_grad():
-            fast = glm(raw[:, None]).argmax(1).bool()               # fast / slow optical-flow class -> dynamic_beta
+        if glm_cfg is None:
+            with torch.no_grad():
+                fast = glm(raw[:, None]).argmax(1).bool()           # fast / slow optical-flow class -> dynamic_beta
+        else:
+            fast = glm.predict(raw).bool()                          # (a segment is read through its electrode stride: the first 200 samples)
         tick("glmnet", t0)
         t0 = time.perf_counter()
         lat_s2s = s2s(win).float()                                  # [B, F, 4, h, w]

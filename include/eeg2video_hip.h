@@ -178,6 +178,34 @@ int64_t e2v_s2s_config_size(void);
  * expects the "s2s." keys (part 128 of e2v_finalize_weights) and serves e2v_seq2seq_latents.  Both NULL: exactly e2v_create.  A bad
  * config of either: E2V_EINVAL, with a message that names the limit. */
 e2v_status e2v_create_ex(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, int device, e2v_ctx** out);
+/* The GLMNet pair (the reference's EEG2Video/models/models.py:105-123, 352-413).  glfnet(raw_out, emb, electrodes, samples) over raw
+ * EEG: a global shallownet over all electrodes and one over the occipital electrodes occ_first .. occ_first + occ_count - 1 -- each
+ * Conv2d(1, filters, (1, taps)), Conv2d(filters, filters, (C, 1)), BatchNorm2d on running statistics, ELU, AvgPool2d((1, pool), (1,
+ * pool_stride)), flatten, Linear(-> emb) -- and Linear(2 emb, raw_out) on the concatenation.  glfnet_mlp(mlp_out, emb, electrodes *
+ * bands) over DE features: two mlpnets -- Linear(-> hidden1), erf GELU, Linear(-> hidden2), GELU, Linear(-> emb) -- over the flattened
+ * [electrodes][bands] block and its occipital rows, and Linear(2 emb, mlp_out).  A struct of its own, handed to e2v_create_ex2; the
+ * reference's values: electrodes 62, samples 200, occipital 50 / 12, filters 40, taps 25, pool 51 / 5, bands 5, hidden 512 / 256, emb
+ * 64, raw_out 2, mlp_out 40, eps 1e-5 (e2v_default_glm_config).  raw_out / mlp_out 0: that model is absent (not both).  Refused, each
+ * with a message that names the limit: an occipital range outside the electrodes; emb, hidden1 or hidden2 not a multiple of 4; with a raw
+ * model, samples below taps + pool - 1, a width filters * pooled columns that is not a multiple of 4, at the reference's filter and
+ * pool sizes a width other than the reference's own 1040 * (samples / 200) (it sizes its linear that way: only samples 200 .. 204
+ * agree, 205 and 400 fail inside the reference), and a clip that does not fit the ShallowNet kernel's 156 KiB of LDS. */
+typedef struct {
+    int glm_electrodes, glm_samples;                   /* C, T of one clip */
+    int glm_occ_first, glm_occ_count;                  /* the occipital electrodes */
+    int glm_filters, glm_taps, glm_pool, glm_pool_stride;
+    int glm_bands, glm_hidden1, glm_hidden2;           /* glfnet_mlp: features per electrode, the two hidden widths */
+    int glm_emb;                                       /* width of each net's embedding */
+    int glm_raw_out, glm_mlp_out;                      /* width of glfnet's / glfnet_mlp's head; 0: the model is absent */
+    float glm_bn_eps;
+} e2v_glm_config;
+void e2v_default_glm_config(e2v_glm_config* glm);
+/* sizeof(e2v_glm_config) as this build sees it: a binding asserts its own against it, as with e2v_config_size */
+int64_t e2v_glm_config_size(void);
+/* e2v_create_ex with the GLMNet pair beside the other optional parts: glm non-NULL and not all zero: the context also expects the
+ * "glm." keys (part 256 of e2v_finalize_weights) and serves e2v_glmnet_raw / e2v_glmnet_mlp.  glm NULL: exactly e2v_create_ex. */
+e2v_status e2v_create_ex2(const e2v_config* cfg, const e2v_clipv_config* clipv, const e2v_s2s_config* s2s, const e2v_glm_config* glm,
+                          int device, e2v_ctx** out);
 void e2v_destroy(e2v_ctx* ctx);
 const char* e2v_last_error(const e2v_ctx* ctx);      /* ctx may be NULL: last error of a failed e2v_create */
 
@@ -229,6 +257,13 @@ const char* e2v_expected_key(const e2v_ctx* ctx, int64_t i, int64_t* shape4, int
  * "embedding.weight", "img_embedding.*", every "num_batches_tracked", and the [1][5000][d_model] buffer itself.  Finalize folds the three
  * BatchNorms (running statistics) into the embedding kernel's pack and keeps every loaded tensor: fp32 matrices only, and
  * e2v_read_tensor returns every "s2s." key with the loaded bits.
+ * bit 8 (256) = the GLMNet pair (a context made by e2v_create_ex2 with an e2v_glm_config -- on any other context the bit is outside the
+ * mask, E2V_EINVAL as before the part existed): "glm.raw." + the names of the reference's glfnet state dict -- per net n in
+ * {globalnet, occipital_localnet}: "n.net.0.{weight [F][1][1][taps], bias}", "n.net.1.{weight [F][F][C][1], bias}",
+ * "n.net.2.{weight, bias, running_mean, running_var}", "n.out.*"; then "out.*" -- and "glm.mlp." + glfnet_mlp's -- per net
+ * "n.net.{1,3,5}.*", then "out.*" --, each set only if its model is configured.  NOT expected: "num_batches_tracked".  Finalize folds
+ * each net's two convolutions and its BatchNorm into one filter and keeps every loaded tensor: fp32 only, and e2v_read_tensor returns
+ * every "glm." key with the loaded bits.
  * every expected key of the selected parts must have been loaded. */
 e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
 /* replaces: optimizer.step() as the validation pipeline sees it (train_finetune_videodiffusion.py:117-121,196-200,320-335: the
@@ -250,6 +285,7 @@ e2v_status e2v_finalize_weights(e2v_ctx* ctx, int which);
  * calls it); another one is loaded with e2v_load_tensor + e2v_finalize_weights(ctx, 16).  A "video." key: the same (part 32).
  * An "s2s." key: E2V_EINVAL too -- the Seq2Seq model is trained by its own script and only called here, and its BatchNorms are folded
  * at finalize; load a new one with e2v_load_tensor + e2v_finalize_weights(ctx, 128).
+ * A "glm." key: E2V_EINVAL as well, for the same reason (its BatchNorms are folded at finalize); reload and e2v_finalize_weights(ctx, 256).
  * A "clipv." key (part 64) is updated like a UNet key: the fp32 form, and the bf16 / fp16 copy of a matrix (the layers' linears, the
  * patch embedding) once the tower has built it in a 16-bit mode (e2v_set_tower_dtype) -- every copy that exists is refreshed. */
 e2v_status e2v_update_tensor(e2v_ctx* ctx, const char* key, const void* data, e2v_dtype dtype, int on_device,
@@ -463,6 +499,49 @@ e2v_status e2v_text_encode(e2v_ctx* ctx, const int64_t* host_ids, int B, int T, 
 e2v_status e2v_seq2seq_latents(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride,
                                const float* mean, const float* scale, int B, int first, int count, int layout, float* latents,
                                float* txt_logits, float* tokens, e2v_stream stream);
+
+/* rank 10 -- replaces DE_PSD (EEG_preprocessing/DE_PSD.py:8-71) and the loops of its three extractors over clips, windows and
+ * electrodes: differential entropy and power spectral density of the five bands of every EEG row.  No weights: any context with a
+ * device serves it.
+ * eeg: device fp32, 4-byte aligned; sample t of electrode c of window w of clip b is eeg[b clip_stride + w window_stride +
+ * c channel_stride + t] (element strides, non-negative).  The one 2-s window of a raw segment [B][62][400] is windows = 1, samples = 400,
+ * strides (24800, 0, 400); its seven 500-ms windows are windows = 7, samples = 100, strides (24800, 50, 400) -- no host-side windowing.
+ * Per row, as the reference: the Hann row 0.5 - 0.5 cos(2 pi k / (samples + 1)), k = 1 .. samples; the 200-point transform of the
+ * windowed row WHATEVER samples is -- a row of more than 200 samples is truncated to its first 200 windowed samples, a shorter one
+ * zero-padded; band p = (1,4), (4,8), (8,14), (14,31), (31,99) Hz is the mean of |X[j]|^2 over bins int(fStart / fs * 200) - 1 ..
+ * int(fEnd / fs * 200) - 1 (at fs = 200: 0..3, 3..7, 7..13, 13..30, 30..98; the bands overlap); psd = that mean E, de = log2(100 E).
+ * de, psd: [B][windows][electrodes][5] fp32, either may be NULL, not both.  de_mean, de_scale: device [electrodes * 5] fp32, both or
+ * neither NULL: the per-feature scaler (de - mean) / scale applied to de on the way out, true division -- the StandardScaler of
+ * train_semantic_predictor.py:46-47 over the 310 features of a window.
+ * The one deviation: a band with E = 0 (an all-zero row) gives psd 0 and de -inf; the reference raises ValueError in math.log there.
+ * ARITHMETIC IS FP32 IN EVERY COMPUTE MODE (tables made in double on the host, sums in index order): a row's bits depend on the row,
+ * samples and fs alone, not on B, its place in the batch or the compute dtype.
+ * Checked before anything is enqueued, in this order: NULL eeg / no output / mean without scale / a pointer off 4-byte alignment /
+ * negative stride / B < 1 / windows, electrodes, samples < 1 or samples > 65536 / an fs at which a band's first bin would be below 0
+ * or its last above 99, where the reference indexes from the end of the spectrum or past its half (fs = 100 and fs = 256 do):
+ * E2V_EINVAL; then a host-only context: E2V_ESTATE.
+ * Stream-ordered, does not synchronise, allocates nothing once one call has been made. */
+e2v_status e2v_eeg_de_psd(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t window_stride, int64_t channel_stride, int B,
+                          int windows, int electrodes, int samples, int fs, const float* de_mean, const float* de_scale, float* de,
+                          float* psd, e2v_stream stream);
+
+/* rank 10 -- replaces glfnet.forward in eval mode (EEG2Video/models/models.py:352-373), whose fast / slow label selects DANA's
+ * dynamic_beta.  eeg: device fp32, 4-byte aligned; sample t of electrode c of clip b is eeg[b clip_stride + c channel_stride + t] (element
+ * strides, non-negative): a contiguous [B][electrodes][samples] is (electrodes samples, samples); the first 200 samples of a raw 2-s
+ * segment [B][62][400] are (24800, 400).  The occipital net reads its electrodes of the same clip through the stride.
+ * in_mean, in_scale: device [electrodes][samples] fp32, both or neither NULL: the input scaler (x - mean) / scale applied as a value
+ * is read, true division.  logits [B][raw_out] fp32; features [B][2 emb] fp32, the concatenated embeddings the head reads; labels [B]
+ * int32, argmax of the logits (the lowest index among equal maxima).  Any of the three may be NULL, not all.
+ * ARITHMETIC IS FP32 IN EVERY COMPUTE MODE; a clip's bits do not depend on B or on its place in the batch.
+ * Checked before anything is enqueued, in this order: NULL eeg / no output / mean without scale / a pointer off 4-byte alignment /
+ * negative stride / B < 1: E2V_EINVAL; then no GLMNet config, no raw model in it, part 256 not finalized, host-only context: E2V_ESTATE.
+ * Stream-ordered, does not synchronise, allocates nothing once the workspace of a B is cached. */
+e2v_status e2v_glmnet_raw(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t channel_stride, int B, const float* in_mean,
+                          const float* in_scale, float* logits, float* features, int32_t* labels, e2v_stream stream);
+/* rank 10 -- replaces glfnet_mlp.forward (EEG2Video/models/models.py:375-413).  de: device [B][electrodes][bands] fp32, 4-byte aligned,
+ * for instance the output of e2v_eeg_de_psd for one window.  logits [B][mlp_out], features [B][2 emb], labels [B] as e2v_glmnet_raw;
+ * the same arithmetic contract, checks (NULL de / no output / alignment / B < 1, then the state) and stream behaviour. */
+e2v_status e2v_glmnet_mlp(e2v_ctx* ctx, const float* de, int B, float* logits, float* features, int32_t* labels, e2v_stream stream);
 
 /* rank 2 -- replaces Diffusion.forward of DANA (EEG2Video/models/DANA_module.py:52-72) given its random draws, fused with
  * the latent layout fix 'a b c d e -> a c b d e' of inference_eeg2video.py:77,82:

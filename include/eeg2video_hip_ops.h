@@ -264,6 +264,15 @@ e2v_status e2v_op_eegnet_embed(e2v_ctx* ctx, const float* eeg, int64_t clip_stri
                                const float* bn1, const float* w2, const float* bn2, const float* w3, const float* w4, const float* bn3,
                                float bn_eps, float* out, e2v_stream stream);
 
+/* Test aid: the ShallowNet kernel of e2v_glmnet_raw on its own (shallownet up to the flatten, eval mode), from torch-layout DEVICE
+ * tensors: w1 [F][K] and b1 [F] (net.0), w2 [F][F][C] and b2 [F] (net.1), bn [4][F] = weight | bias | running_mean | running_var
+ * (net.2).  eeg, the two strides, mean and scale ([C][T], both or neither NULL) as e2v_glmnet_raw takes them; out: [B][F * columns],
+ * columns = (T - K + 1 - P) / S + 1, filter-major.  The weights are folded on the host as finalize folds them: the call synchronises
+ * the stream.  Needs no GLMNet config in the context.  T < K + P - 1 or a clip that does not fit the kernel's LDS: E2V_ESHAPE. */
+e2v_status e2v_op_shallownet(e2v_ctx* ctx, const float* eeg, int64_t clip_stride, int64_t channel_stride, const float* mean, const float* scale,
+                             int B, int C, int T, int F, int K, int P, int S, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* bn, float bn_eps, float* out, e2v_stream stream);
+
 /* Test aid: the attention kernel of e2v_seq2seq_latents on its own: Nq queries of every (clip, head) against Nk <= 32 keys, head dim D a
  * multiple of 4 up to 128, scale D^-0.5.  q [B][Nq][ldq], k, v [B][Nk][ldkv], out [B][Nq][ldo] (row strides in elements, multiples of 4;
  * heads * D columns used; clips Nq ldq / Nk ldkv / Nq ldo apart).  causal != 0: query i sits at absolute position q_pos0 + i and sees
