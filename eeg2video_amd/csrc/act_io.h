@@ -144,4 +144,22 @@ __device__ __forceinline__ float lanes_allreduce(float x) {
     return x;
 }
 
+// What the two attention kernels with the keys resident in LDS share (vit.hip: no mask; text.hip: the causal mask): K and V rows of
+// 64 floats at a stride of 68 -- a 64-float row spans all 64 banks, so lanes reading the same column of different rows with
+// ds_read_b128 would all hit one slot; at 68 the 16 lanes of a group start 4 banks apart --, 8 waves per workgroup, and the wave ops.
+constexpr int kKeyLd = 68;          // LDS row stride in floats
+constexpr int kKeyWaves = 8;
+
+__device__ __forceinline__ float wave_max(float v) {
+    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
+    return v;
+}
+__device__ __forceinline__ float wave_sum(float v) {
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+__device__ __forceinline__ float lane_value(float v, int lane) {      // v of `lane` (wave-uniform) as a scalar
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
+}
+
 }  // namespace e2v

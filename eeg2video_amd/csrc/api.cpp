@@ -790,6 +790,29 @@ void check_frames(const char* who, const void* frames, int kind, int n, int F, i
     E2V_REQUIRE(F >= 1 && H >= 1 && W >= 1, E2V_ESHAPE, w + ": F, H and W must be at least 1");
     E2V_REQUIRE((double)n * F < 2147483648.0, E2V_ESHAPE, w + ": too many images for one call");
 }
+
+// What the preprocess ops do once their arguments are checked and their plan is made: the plan's tables onto the device, then launches of
+// `step` frames (whole tubelets of ts) under the profile class `name`.  mode != 0 (H16_BF16 / H16_FP16): into 16-bit patch rows of that
+// type, widened exactly into `rows`.
+void run_preprocess(e2v_ctx* c, const char* name, const PrepPlan& plan, const void* frames, int kind, int n, int F, int ts, long long step,
+                    int patch, int mode, float* rows, hipStream_t s) {
+    Act tables = upload_plan(c->pool, plan, s);
+    E2V_HIP(hipStreamSynchronize(s));                        // (`plan` is the caller's local: a test aid may wait)
+    const int* tab = reinterpret_cast<const int*>(tables.p);
+    const FrameSrc src = frame_src(frames, kind);
+    const int K = 3 * ts * patch * patch;
+    const long long per_img = (long long)(plan.S / patch) * (plan.S / patch) * 3 * patch * patch;      // row elements one frame contributes
+    const long long total = (long long)n * F;
+    for (long long i0 = 0; i0 < total; i0 += step) {
+        const int ni = (int)std::min<long long>(step, total - i0);
+        if (!mode) { frame_preprocess(src, n, F, ts, i0, ni, plan, tab, patch, rows + i0 * per_img, name, s); continue; }
+        const long long nrows = (long long)ni * per_img / K;
+        Act r16(c->pool, nrows, K, true);
+        frame_preprocess(src, n, F, ts, i0, ni, plan, tab, patch, r16.p, name, s, mode);
+        cvt_rows(r16.p, K, mode, rows + i0 * per_img, K, 0, nrows, K, K, s);
+    }
+    E2V_HIP(hipGetLastError());
+}
 }  // namespace
 
 extern "C" {
@@ -803,7 +826,7 @@ e2v_status e2v_image_classify(e2v_ctx* c, const void* frames, int kind, int n, i
         E2V_REQUIRE(((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(probs) | reinterpret_cast<uintptr_t>(top3)) & 3) == 0,
                     E2V_EINVAL, "e2v_image_classify: misaligned output (4 bytes)");
         c->require_part(e2v_ctx::IMAGE);
-        E2V_REQUIRE(c->prep_plan(H, W).band >= 1, E2V_ESHAPE,
+        E2V_REQUIRE(c->prep_plan(e2v_ctx::IMAGE, H, W).band >= 1, E2V_ESHAPE,
                     "e2v_image_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
         c->require_ready(e2v_ctx::IMAGE);
     }, [&] {
@@ -839,25 +862,16 @@ e2v_status e2v_image_resize_table_filter(int in_size, int out_size, int filter, 
 // the preprocess of e2v_image_classify on its own, at any (S, P) and with the caller's pixel table
 e2v_status e2v_op_image_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch,
                                    const float* host_lut, float* rows, e2v_stream stream) {
-    ImagePrepPlan plan;
+    PrepPlan plan;
     return entry(c, [&] {
         check_frames("e2v_op_image_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_image_preprocess: null or misaligned rows");
         E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0, E2V_ESHAPE, "e2v_op_image_preprocess: 1 <= S <= 4096, a multiple of P >= 1");
         E2V_REQUIRE(host_lut || c->cfg.vit_layers > 0, E2V_ESTATE, "e2v_op_image_preprocess: no pixel table given and the config has no image classifier");
-        plan = image_prep_plan(H, W, size, patch, host_lut ? host_lut : c->image_lut);
+        plan = prep_plan(H, W, PrepWindow{size, size, 0, 0}, size, patch, host_lut ? host_lut : c->image_lut, kResizeBilinear);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_image_preprocess: the source rows of one output row do not fit the kernel's LDS band");
     }, [&] {
-        hipStream_t s = S(c, stream);
-        Act tables = upload_plan(c->pool, plan, s);
-        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src = frame_src(frames, kind);
-        const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
-        for (long long i0 = 0; i0 < total; i0 += 4096) {
-            const int ni = (int)std::min<long long>(4096, total - i0);
-            image_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
-        }
-        E2V_HIP(hipGetLastError());
+        run_preprocess(c, "image_preprocess", plan, frames, kind, n, F, 1, 4096, patch, 0, rows, S(c, stream));
     });
 }
 
@@ -888,7 +902,7 @@ e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, i
             E2V_REQUIRE(F == c->cfg.vmae_num_frames, E2V_ESHAPE,
                         "e2v_video_classify: F = " + std::to_string(F) + " frames per clip, the model takes vmae_num_frames = " +
                             std::to_string(c->cfg.vmae_num_frames) + " (the position table and the token count are sized by it)");
-            E2V_REQUIRE(c->video_prep_plan(H, W).band >= 1, E2V_ESHAPE,
+            E2V_REQUIRE(c->prep_plan(e2v_ctx::VIDEO, H, W).band >= 1, E2V_ESHAPE,
                         "e2v_video_classify: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
         }
         c->require_part(e2v_ctx::VIDEO);
@@ -902,7 +916,7 @@ e2v_status e2v_video_classify(e2v_ctx* c, const void* frames, int kind, int n, i
 // the preprocess of e2v_video_classify on its own, at any (S, P, ts, edge) and with the caller's pixel table
 e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int ts, int edge,
                                    const float* host_lut, float* rows, e2v_stream stream) {
-    VideoPrepPlan plan;
+    PrepPlan plan;
     return entry(c, [&] {
         check_frames("e2v_op_video_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_video_preprocess: null or misaligned rows");
@@ -910,18 +924,10 @@ e2v_status e2v_op_video_preprocess(e2v_ctx* c, const void* frames, int kind, int
                     "e2v_op_video_preprocess: 1 <= S <= edge <= 4096, S a multiple of P >= 1");
         E2V_REQUIRE(ts >= 1 && F % ts == 0 && F <= 4096, E2V_ESHAPE, "e2v_op_video_preprocess: F must be a multiple of ts >= 1, at most 4096");
         E2V_REQUIRE(host_lut || c->cfg.vmae_layers > 0, E2V_ESTATE, "e2v_op_video_preprocess: no pixel table given and the config has no video classifier");
-        plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->video_lut);
+        plan = prep_plan(H, W, video_crop(H, W, edge, size), size, patch, host_lut ? host_lut : c->video_lut, kResizeBilinear);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_video_preprocess: the source rows of one output row do not fit the kernel's LDS band");
     }, [&] {
-        hipStream_t s = S(c, stream);
-        Act tables = upload_plan(c->pool, plan, s);
-        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src = frame_src(frames, kind);
-        const long long per = (long long)(F / ts) * (size / patch) * (size / patch) * 3 * ts * patch * patch;
-        const int step = std::max(1, 4096 / F);
-        for (int i0 = 0; i0 < n; i0 += step)
-            video_preprocess(src, n, F, ts, i0, std::min(step, n - i0), plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
-        E2V_HIP(hipGetLastError());
+        run_preprocess(c, "video_preprocess", plan, frames, kind, n, F, ts, (long long)std::max(1, 4096 / F) * F, patch, 0, rows, S(c, stream));      // (whole clips)
     });
 }
 
@@ -931,7 +937,7 @@ e2v_status e2v_clip_embed(e2v_ctx* c, const void* frames, int kind, int n, int F
         check_frames("e2v_clip_embed", frames, kind, n, F, H, W);
         E2V_REQUIRE(embeds && (reinterpret_cast<uintptr_t>(embeds) & 3) == 0, E2V_EINVAL, "e2v_clip_embed: null or misaligned embeds (4 bytes)");
         c->require_part(e2v_ctx::CLIPV);
-        E2V_REQUIRE(c->clipv_prep_plan(H, W).band >= 1, E2V_ESHAPE,
+        E2V_REQUIRE(c->prep_plan(e2v_ctx::CLIPV, H, W).band >= 1, E2V_ESHAPE,
                     "e2v_clip_embed: the source rows of one output row do not fit the preprocess kernel's LDS band (downscale too strong)");
         c->require_ready(e2v_ctx::CLIPV);
     }, [&] {
@@ -960,7 +966,7 @@ e2v_status e2v_clip_similarity(e2v_ctx* c, const float* a, int na, const float* 
 // the preprocess of e2v_clip_embed on its own, at any (S, P, edge, filter) and with the caller's pixel table
 e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int n, int F, int H, int W, int size, int patch, int edge,
                                   int filter, const float* host_lut, float* rows, e2v_stream stream) {
-    VideoPrepPlan plan;
+    PrepPlan plan;
     return entry(c, [&] {
         check_frames("e2v_op_clip_preprocess", frames, kind, n, F, H, W);
         E2V_REQUIRE(rows && (reinterpret_cast<uintptr_t>(rows) & 3) == 0, E2V_EINVAL, "e2v_op_clip_preprocess: null or misaligned rows");
@@ -968,19 +974,10 @@ e2v_status e2v_op_clip_preprocess(e2v_ctx* c, const void* frames, int kind, int 
         E2V_REQUIRE(size >= 1 && size <= 4096 && patch >= 1 && size % patch == 0 && edge >= size && edge <= 4096, E2V_ESHAPE,
                     "e2v_op_clip_preprocess: 1 <= S <= edge <= 4096, S a multiple of P >= 1");
         E2V_REQUIRE(host_lut || c->vcfg.clipv_layers > 0, E2V_ESTATE, "e2v_op_clip_preprocess: no pixel table given and the context has no CLIP vision tower");
-        plan = video_prep_plan(H, W, edge, size, patch, host_lut ? host_lut : c->clipv_lut, filter);
+        plan = prep_plan(H, W, video_crop(H, W, edge, size), size, patch, host_lut ? host_lut : c->clipv_lut, filter);
         E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_clip_preprocess: the source rows of one output row do not fit the kernel's LDS band");
     }, [&] {
-        hipStream_t s = S(c, stream);
-        Act tables = upload_plan(c->pool, plan, s);
-        E2V_HIP(hipStreamSynchronize(s));                    // (`plan` is a local: a test aid may wait)
-        const FrameSrc src = frame_src(frames, kind);
-        const long long total = (long long)n * F, per = (long long)(size / patch) * (size / patch) * 3 * patch * patch;
-        for (long long i0 = 0; i0 < total; i0 += 4096) {
-            const int ni = (int)std::min<long long>(4096, total - i0);
-            frame_preprocess(src, n, F, i0, ni, plan, reinterpret_cast<const int*>(tables.p), patch, rows + i0 * per, s);
-        }
-        E2V_HIP(hipGetLastError());
+        run_preprocess(c, "video_preprocess", plan, frames, kind, n, F, 1, 4096, patch, 0, rows, S(c, stream));
     });
 }
 
@@ -1029,12 +1026,11 @@ int e2v_tower_dtype(const e2v_ctx* c, int part) {
     return m == H16_BF16 ? E2V_BF16 : m == H16_FP16 ? E2V_F16 : E2V_F32;
 }
 
-// The three preprocess kernels storing 16-bit patch rows (what a tower in that mode feeds its patch linear), widened exactly into
-// the caller's fp32 `rows`: tower = 16 (image_preprocess), 32 (video_preprocess: ts, edge) or 64 (frame_preprocess: edge, filter).
+// The preprocess storing 16-bit patch rows (what a tower in that mode feeds its patch linear), widened exactly into the caller's
+// fp32 `rows`: tower = 16 (the image classifier's: the whole frame), 32 (the video classifier's: ts, edge) or 64 (CLIP's: edge, filter).
 e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void* frames, int kind, int n, int F, int H, int W, int size,
                                    int patch, int ts, int edge, int filter, const float* host_lut, float* rows, e2v_stream stream) {
-    ImagePrepPlan iplan;
-    VideoPrepPlan vplan;
+    PrepPlan plan;
     return entry(c, [&] {
         check_frames("e2v_op_tower_preprocess", frames, kind, n, F, H, W);
         require_h16("e2v_op_tower_preprocess", dtype);
@@ -1044,32 +1040,13 @@ e2v_status e2v_op_tower_preprocess(e2v_ctx* c, int tower, int dtype, const void*
         if (tower == 32) E2V_REQUIRE(ts >= 1 && F % ts == 0 && F <= 4096, E2V_ESHAPE, "e2v_op_tower_preprocess: F must be a multiple of ts >= 1, at most 4096");
         if (tower != 16) E2V_REQUIRE(edge >= size && edge <= 4096, E2V_ESHAPE, "e2v_op_tower_preprocess: S <= edge <= 4096");
         if (tower == 64) E2V_REQUIRE(filter == kResizeBilinear || filter == kResizeBicubic, E2V_EINVAL, "e2v_op_tower_preprocess: filter 2 (BILINEAR) or 3 (BICUBIC)");
-        if (tower == 16) iplan = image_prep_plan(H, W, size, patch, host_lut);
-        else vplan = video_prep_plan(H, W, edge, size, patch, host_lut, tower == 64 ? filter : kResizeBilinear);
-        E2V_REQUIRE((tower == 16 ? iplan.band : vplan.band) >= 1, E2V_ESHAPE, "e2v_op_tower_preprocess: the source rows of one output row do not fit the kernel's LDS band");
+        plan = prep_plan(H, W, tower == 16 ? PrepWindow{size, size, 0, 0} : video_crop(H, W, edge, size), size, patch, host_lut,
+                         tower == 64 ? filter : kResizeBilinear);
+        E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, "e2v_op_tower_preprocess: the source rows of one output row do not fit the kernel's LDS band");
     }, [&] {
-        hipStream_t s = S(c, stream);
-        const int mode = tower_mode_of(dtype);
-        Act tables = upload_plan(c->pool, tower == 16 ? iplan : vplan, s);
-        E2V_HIP(hipStreamSynchronize(s));                    // (the plans are locals: a test aid may wait)
-        const int* tab = reinterpret_cast<const int*>(tables.p);
-        const FrameSrc src = frame_src(frames, kind);
-        const int tsz = tower == 32 ? ts : 1;
-        const long long np2 = (long long)(size / patch) * (size / patch);
-        const int K = 3 * tsz * patch * patch;
-        const long long per_img = np2 * 3 * patch * patch;      // row elements one frame contributes
-        const long long total = (long long)n * F;
         const long long step = tower == 32 ? (long long)std::max(1, 4096 / F) * F : 4096;     // frames per launch (whole clips for the tubelets)
-        for (long long i0 = 0; i0 < total; i0 += step) {
-            const int ni = (int)std::min<long long>(step, total - i0);
-            const long long nrows = (long long)ni * per_img / K;
-            Act r16(c->pool, nrows, K, true);
-            if (tower == 16) image_preprocess(src, n, F, i0, ni, iplan, tab, patch, r16.p, s, mode);
-            else if (tower == 32) video_preprocess(src, n, F, ts, i0 / F, ni / F, vplan, tab, patch, r16.p, s, mode);
-            else frame_preprocess(src, n, F, i0, ni, vplan, tab, patch, r16.p, s, mode);
-            cvt_rows(r16.p, K, mode, rows + i0 * per_img, K, 0, nrows, K, K, s);
-        }
-        E2V_HIP(hipGetLastError());
+        run_preprocess(c, tower == 16 ? "image_preprocess" : "video_preprocess", plan, frames, kind, n, F, tower == 32 ? ts : 1, step, patch,
+                       tower_mode_of(dtype), rows, S(c, stream));
     });
 }
 
@@ -1151,8 +1128,8 @@ e2v_status e2v_op_tower_activation(e2v_ctx* c, int dtype, const float* x, int64_
     });
 }
 
-// The token rows of a tower in 16-bit mode: patches [nimg*(T-1)][C] (cls != NULL: a class row in front, image_embed) or [nimg*T][C]
-// (cls == NULL: video_embed) fp32 rounded once to `dtype`; cls [C] and pos [T][C] stay fp32; out [nimg*T][C] fp32 = the stored rows widened.
+// The token rows of a tower in 16-bit mode (token_embed): patches [nimg*(T-1)][C] (cls != NULL: a class row in front) or [nimg*T][C]
+// (cls == NULL) fp32 rounded once to `dtype`; cls [C] and pos [T][C] stay fp32; out [nimg*T][C] fp32 = the stored rows widened.
 e2v_status e2v_op_tower_embed(e2v_ctx* c, int dtype, const float* patches, const float* cls, const float* pos, int nimg, int T, int C,
                               float* out, e2v_stream stream) {
     if (!c) return E2V_EINVAL;
@@ -1165,8 +1142,7 @@ e2v_status e2v_op_tower_embed(e2v_ctx* c, int dtype, const float* patches, const
         const int64_t prow = (int64_t)nimg * (cls ? T - 1 : T), M = (int64_t)nimg * T;
         Act p16(c->pool, prow, C, true), x16(c->pool, M, C, true);
         cvt_rows(patches, C, 0, p16.p, C, mode, prow, C, C, s);
-        if (cls) image_embed(p16.p, cls, pos, x16.p, nimg, T, C, s, mode);
-        else video_embed(p16.p, pos, x16.p, nimg, T, C, s, mode);
+        token_embed(p16.p, cls, pos, x16.p, nimg, T, C, s, mode);
         cvt_rows(x16.p, C, mode, out, C, 0, M, C, C, s);
         E2V_HIP(hipGetLastError());
     });

@@ -237,8 +237,8 @@ void text_causal_attention(const float* qkv, int ldqkv, float* out, int ldo, int
 void text_activation(float* x, long long count, int act, hipStream_t s, int h16 = 0);
 
 // ---------------------------------------------------------------------------------------
-// ViT image classifier (vit.hip; e2v_image_classify): fp32 whatever the context's mode; `h16` selects the tower's 16-bit rows.  LayerNorm, the linears and the GELU are
-// norm.hip's, igemm.hip's and text.hip's.
+// ViT image classifier (vit.hip; e2v_image_classify): fp32 whatever the context's mode.  LayerNorm, the linears and the GELU are
+// norm.hip's, igemm.hip's and text.hip's; the preprocess and the token rows are video.hip's (below).
 // ---------------------------------------------------------------------------------------
 struct FrameSrc;                            // (below: the input description e2v_frame_metrics shares)
 // One axis of Pillow's antialiased resize as a table (host arithmetic; e2v_image_resize_table, e2v_image_resize_table_filter).
@@ -250,25 +250,6 @@ struct ResizeAxis {
     std::vector<int> coeff;                 // [out][ksize], 22-bit fixed point
 };
 ResizeAxis resize_axis(int in_size, int out_size, int filter = kResizeBilinear);
-// The tables of one (H, W) -> S x S resize and the pixel table, as the preprocess kernel reads them: one block of 32-bit words,
-// [hfirst S | hcount S | vfirst S | vcount S | hcoeff S * kh | vcoeff S * kv | lut 3 * 256 floats]
-struct ImagePrepPlan {
-    int H = 0, W = 0, S = 0, kh = 0, kv = 0;
-    bool vfirst = false;                    // Pillow resizes an image more than 100 times as tall as wide vertically first
-    int band = 0, band_rows = 0;            // output rows per workgroup and the most source rows such a band reads (0: does not fit)
-    std::vector<int> words;
-};
-constexpr int kImagePrepLdsBytes = 48 * 1024;     // the band of horizontally resized rows a workgroup keeps
-ImagePrepPlan image_prep_plan(int H, int W, int S, int P, const float* lut768);
-// frames (FrameSrc: fp32 quantised at load or bytes, planar [n,3,F,H,W] or channels-last [n,F,H,W,3]) -> rows [n*F*(S/P)^2][3*P*P];
-// `plan_dev`: plan.words on the device
-// h16 = 1 / 2: `rows` is bf16 / fp16 storage -- the pixel table's fp32 value rounded once at the store (the integer arithmetic in
-// front of the table is the same)
-void image_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const ImagePrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s, int h16 = 0);
-// x[i][0][:] = cls + pos[0], x[i][1 + p][:] = patches[i * (T - 1) + p][:] + pos[1 + p]   (C a multiple of 4)
-// h16 = 1 / 2: patches and x are bf16 / fp16 rows (cls and pos stay fp32; fp32 sum, one rounding at the store)
-void image_embed(const float* patches, const float* cls, const float* pos, float* x, int nimg, int T, int C, hipStream_t s, int h16 = 0);
 // non-causal self-attention over each of B images of T tokens, head dim 64, scale 64^-0.5; layouts as text_causal_attention.
 // K and V of an (image, head) live in LDS at the 68-float stride, which bounds T:
 constexpr int kImageAttnMaxT = 288;     // 2 x 288 rows x 272 bytes = 153 KiB of the CU's 160; up to five keys per lane
@@ -281,27 +262,39 @@ void image_head(const float* logits, int ld, int L, int nimg, float* logits_out,
 // VideoMAE video classifier (video.hip; e2v_video_classify): fp32 whatever the context's mode; `h16` as above.  The encoder layers are the image
 // classifier's; the head's softmax / top 3 is image_head.
 // ---------------------------------------------------------------------------------------
-// VideoMAEImageProcessor's geometry: the shortest edge resized to `edge` with the aspect ratio kept, then the centre crop of S x S
-struct VideoCrop { int nh = 0, nw = 0, top = 0, left = 0; };
-VideoCrop video_crop(int H, int W, int edge, int S);
-// The tables of the (H, W) -> (nh, nw) resize restricted to the crop window, in ImagePrepPlan's layout (S entries per axis, `first`
-// in source coordinates), and the source columns [c0, c0 + cw) the window's horizontal taps read (the vertical-first order keeps
-// only those).  band = 0: does not fit.
-struct VideoPrepPlan : ImagePrepPlan {
-    VideoCrop crop;
+// The frame preprocess of the three towers (Pillow's antialiased resize, of which only a window is computed, fused with the pixel
+// table and the patch layout) and their token rows.
+// A resize target (nh, nw) and the S x S window of it that is kept, from (top, left)
+struct PrepWindow { int nh = 0, nw = 0, top = 0, left = 0; };
+// VideoMAEImageProcessor's geometry (the CLIP processor's too): the shortest edge resized to `edge` with the aspect ratio kept, then
+// the centre crop of S x S
+PrepWindow video_crop(int H, int W, int edge, int S);
+// The tables of the (H, W) -> (nh, nw) resize restricted to the window and the pixel table, as the preprocess kernel reads them: one
+// block of 32-bit words, [hfirst S | hcount S | vfirst S | vcount S | hcoeff S * kh | vcoeff S * kv | lut 3 * 256 floats] (`first` in
+// source coordinates), and the source columns [c0, c0 + cw) the window's horizontal taps read (the vertical-first order keeps only those)
+struct PrepPlan {
+    int H = 0, W = 0, S = 0, kh = 0, kv = 0;
+    bool vfirst = false;                    // Pillow resizes an image more than 100 times as tall as wide vertically first
+    int band = 0, band_rows = 0;            // output rows per workgroup and the most source rows such a band reads (0: does not fit)
     int c0 = 0, cw = 0;
+    std::vector<int> words;
 };
-VideoPrepPlan video_prep_plan(int H, int W, int edge, int S, int P, const float* lut768, int filter = kResizeBilinear);
-// clips clip0 .. clip0 + nclips - 1 of `src` ([n][F] frames of plan.H x plan.W) -> rows [nclips*(F/ts)*(S/P)^2][3*ts*P*P]: frame
-// ts*t + dt of a clip writes columns ((c*ts + dt)*P + y)*P + x of the clip's token rows (t, py, px)
-void video_preprocess(const FrameSrc& src, int n, int F, int ts, long long clip0, int nclips, const VideoPrepPlan& plan, const int* plan_dev,
-                      int P, float* rows, hipStream_t s, int h16 = 0);     // h16: as image_preprocess
-// the same at ts = 1 for frames img0 .. img0 + nimg - 1 of the [n][F] source, every frame an image of its own (a range may start
-// and end inside a clip) -> rows [nimg*(S/P)^2][3*P*P]: the patch layout of image_preprocess
-void frame_preprocess(const FrameSrc& src, int n, int F, long long img0, int nimg, const VideoPrepPlan& plan, const int* plan_dev, int P,
-                      float* rows, hipStream_t s, int h16 = 0);
-// x[b*T + t][:] = patches[b*T + t][:] + pos[t][:]   (C a multiple of 4; no class row)
-void video_embed(const float* patches, const float* pos, float* x, int B, int T, int C, hipStream_t s, int h16 = 0);     // h16: as image_embed
+constexpr int kImagePrepLdsBytes = 48 * 1024;     // the band of resized rows a workgroup keeps
+// `filter`: the processor's resample code.  The image classifier's processor: win = {S, S, 0, 0}, bilinear; the video classifier's
+// and CLIP's: video_crop(H, W, edge, S), bilinear / the config's.
+PrepPlan prep_plan(int H, int W, const PrepWindow& win, int S, int P, const float* lut768, int filter);
+// frames img0 .. img0 + nimg - 1 of `src` (FrameSrc: fp32 quantised at load or bytes, planar [n,3,F,H,W] or channels-last [n,F,H,W,3],
+// frames of plan.H x plan.W) -> rows [(nimg/ts)*(S/P)^2][3*ts*P*P]: frame ts*t + dt of a clip writes columns ((c*ts + dt)*P + y)*P + x
+// of token rows (t, py, px).  ts >= 1 divides F, img0 and nimg (whole tubelets; at ts = 1 every frame is an image of its own and a range
+// may start and end inside a clip), nimg <= 65535.  `plan_dev`: plan.words on the device; `name`: the profile class.
+// h16 = 1 / 2: `rows` is bf16 / fp16 storage -- the pixel table's fp32 value rounded once at the store (the integer arithmetic in
+// front of the table is the same)
+void frame_preprocess(const FrameSrc& src, int n, int F, int ts, long long img0, int nimg, const PrepPlan& plan, const int* plan_dev, int P,
+                      float* rows, const char* name, hipStream_t s, int h16 = 0);
+// x[b*T + t][:] = (cls ? (t == 0 ? cls : patches[b*(T - 1) + t - 1]) : patches[b*T + t])[:] + pos[t][:]   (C a multiple of 4)
+// h16 = 1 / 2: patches and x are bf16 / fp16 rows (cls and pos stay fp32; fp32 sum, one rounding at the store).  Profile class:
+// image_embed with a class row, video_embed without.
+void token_embed(const float* patches, const float* cls, const float* pos, float* x, int B, int T, int C, hipStream_t s, int h16 = 0);
 // non-causal self-attention over each of B sequences of T tokens (any T >= 1), head dim 64, scale 64^-0.5; q | k | v in one row matrix
 // as image_attention takes them (16-byte aligned rows, strides multiples of 4).  K and V are read per key tile, never resident.
 void token_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s);
@@ -311,7 +304,7 @@ void token_mean(const float* x, float* out, int B, int T, int C, hipStream_t s, 
 
 // ---------------------------------------------------------------------------------------
 // CLIP vision tower and CLIP score (clip.hip; e2v_clip_embed, e2v_clip_similarity): the similarity is fp32 always, the tower as the classifiers.  The processor is
-// video_preprocess at ts = 1 over a bicubic plan (every frame its own image: rows [images * patches][3 P P]); the token rows, the
+// frame_preprocess at ts = 1 over a bicubic plan (every frame its own image: rows [images * patches][3 P P]); the token rows, the
 // attention and the layers are the image classifier's.
 // ---------------------------------------------------------------------------------------
 // torch.nn.functional.cosine_similarity(a, b, dim=-1, eps): dot(a, b) / (max(|a|, eps) * max(|b|, eps)).  a [na][D], b [nb][D],
@@ -322,7 +315,7 @@ void clip_similarity(const float* a, int na, const float* b, int nb, int D, bool
 
 // ---------------------------------------------------------------------------------------
 // Seq2Seq latent model (seq2seq.hip; e2v_seq2seq_latents): fp32 in every compute mode.  The linears, LayerNorm, the positions, the mean
-// over the window rows and the appended rows are igemm, layernorm, video_embed, token_mean and copy_rows.
+// over the window rows and the appended rows are igemm, layernorm, token_embed, token_mean and copy_rows.
 // ---------------------------------------------------------------------------------------
 // Where the EEGNet kernel keeps things, in floats (every offset a multiple of 4): the pack of folded weights -- w1 [F1][64], w2 [FD][C],
 // a2 / c2 [FD], w3 [FD][16], w4 [F2][FD], a3 / c3 [F2], offsets relative to `pack` -- and, behind it in LDS, the window xs [C][T], the

@@ -1911,10 +1911,9 @@ void e2v_ctx::text_encode(const int* ids, int B, int T, float* out, hipStream_t 
 // -----------------------------------------------------------------------------------------------------
 namespace {
 
-// the host resize tables of a preprocess per (H, W), at most 64 sizes
-template <class Plan, class Make>
-const Plan& prep_cached(std::map<std::array<int, 2>, Plan>& cache, int H, int W, Make make) {
-    const std::array<int, 2> key{H, W};
+// host tables per key (the resize tables of a tower's preprocess per (part, H, W)), at most 64 of them
+template <class Key, class Plan, class Make>
+const Plan& prep_cached(std::map<Key, Plan>& cache, const Key& key, Make make) {
     auto it = cache.find(key);
     if (it == cache.end()) {
         if (cache.size() >= 64) cache.clear();
@@ -1925,10 +1924,9 @@ const Plan& prep_cached(std::map<std::array<int, 2>, Plan>& cache, int H, int W,
 
 struct TowerDims { int C, I, P, T, K, heads; float eps, head_eps; int act; };      // K: patch row length; head_eps: of the LayerNorm in front of the head
 
-template <class Plan>
 struct TowerRun {
     Runner R;                 // in the tower's own mode
-    const Plan& plan;
+    const PrepPlan& plan;
     Act tables;               // plan.words on the device
     int chunk;                // sequences per pass
     const int* tab() const { return reinterpret_cast<const int*>(tables.p); }
@@ -1936,15 +1934,14 @@ struct TowerRun {
 
 // what the three share before the first launch, in this order: the ready check, the 16-bit mode's limit on K (`k_what` names K in the
 // tower's terms), the plan of this frame size and its band check, the upload of its tables, the chunk knob
-template <class PlanFn>
-auto tower_begin(e2v_ctx* c, e2v_ctx::Part part, const std::string& who, const char* k_what, int K, PlanFn plan_of, int chunk_knob, hipStream_t s) {
+TowerRun tower_begin(e2v_ctx* c, e2v_ctx::Part part, const std::string& who, const char* k_what, int K, int H, int W, int chunk_knob, hipStream_t s) {
     c->require_ready(part);
     Runner R{c, s, false};
     R.tower = c->tower_h16[part];
     E2V_REQUIRE(!R.h16() || K % 8 == 0, E2V_ESHAPE, who + ": a 16-bit tower needs " + k_what + " to be a multiple of 8");
-    const auto& plan = plan_of();
+    const PrepPlan& plan = c->prep_plan(part, H, W);
     E2V_REQUIRE(plan.band >= 1, E2V_ESHAPE, who + ": the source rows of one output row do not fit the preprocess kernel's LDS band");
-    return TowerRun<std::decay_t<decltype(plan)>>{R, plan, upload_plan(c->pool, plan, s), std::min(std::max(chunk_knob, 1), 4096)};      // (the plan lives in the context)
+    return TowerRun{R, plan, upload_plan(c->pool, plan, s), std::min(std::max(chunk_knob, 1), 4096)};      // (the plan lives in the context)
 }
 
 // One pass of ni sequences: prep(rows) fills the patch rows; the patch linear; the token rows (with the class token where the tower has
@@ -1964,8 +1961,7 @@ void tower_chunk(Runner& R, const VisionTowerW& w, const TowerDims& d, int ni, P
         Act tok;                                                // the token rows in front of pre_ln
         if (w.pre_ln.g) tok = Act(pool, M, C, R.bf());
         float* e = w.pre_ln.g ? tok.p : x.p;
-        if (w.cls) image_embed(patches.p, w.cls, w.pos, e, ni, T, C, s, h16);
-        else video_embed(patches.p, w.pos, e, ni, T, C, s, h16);
+        token_embed(patches.p, w.cls, w.pos, e, ni, T, C, s, h16);
         if (w.pre_ln.g) layernorm(tok.p, C, w.pre_ln.g, w.pre_ln.b, x.p, C, (int)M, C, d.eps, s, h16);
     }
     x = tower_layers(R, w.layers, std::move(x), ni, T, d.heads, d.I, d.eps, d.act, attn32);
@@ -1984,28 +1980,28 @@ void tower_chunk(Runner& R, const VisionTowerW& w, const TowerDims& d, int ni, P
 
 }  // namespace
 
-Act e2v::upload_plan(Pool& pool, const ImagePrepPlan& plan, hipStream_t s) {
+Act e2v::upload_plan(Pool& pool, const PrepPlan& plan, hipStream_t s) {
     Act tables(pool, (int64_t)plan.words.size(), 1);
     E2V_HIP(hipMemcpyAsync(tables.p, plan.words.data(), plan.words.size() * sizeof(int), hipMemcpyHostToDevice, s));
     return tables;
 }
 
-const ImagePrepPlan& e2v_ctx::prep_plan(int H, int W) {
-    return prep_cached(prep_plans, H, W, [&] { return image_prep_plan(H, W, cfg.vit_image_size, cfg.vit_patch_size, image_lut); });
-}
-const VideoPrepPlan& e2v_ctx::video_prep_plan(int H, int W) {
-    return prep_cached(video_prep_plans, H, W, [&] {
-        return e2v::video_prep_plan(H, W, cfg.vmae_resize_edge, cfg.vmae_image_size, cfg.vmae_patch_size, video_lut);
-    });
-}
-const VideoPrepPlan& e2v_ctx::clipv_prep_plan(int H, int W) {
-    return prep_cached(clipv_prep_plans, H, W, [&] {
-        return e2v::video_prep_plan(H, W, vcfg.clipv_resize_edge, vcfg.clipv_image_size, vcfg.clipv_patch_size, clipv_lut, vcfg.clipv_resample);
+const PrepPlan& e2v_ctx::prep_plan(Part tower, int H, int W) {
+    return prep_cached(prep_plans, std::array<int, 3>{(int)tower, H, W}, [&] {
+        if (tower == IMAGE) {                                    // ViTImageProcessor: the whole frame to S x S, no crop
+            const int S = cfg.vit_image_size;
+            return e2v::prep_plan(H, W, PrepWindow{S, S, 0, 0}, S, cfg.vit_patch_size, image_lut, kResizeBilinear);
+        }
+        if (tower == VIDEO)
+            return e2v::prep_plan(H, W, video_crop(H, W, cfg.vmae_resize_edge, cfg.vmae_image_size), cfg.vmae_image_size, cfg.vmae_patch_size,
+                                  video_lut, kResizeBilinear);
+        return e2v::prep_plan(H, W, video_crop(H, W, vcfg.clipv_resize_edge, vcfg.clipv_image_size), vcfg.clipv_image_size,
+                              vcfg.clipv_patch_size, clipv_lut, vcfg.clipv_resample);
     });
 }
 
 const std::vector<float>& e2v_ctx::de_psd_plan(int samples) {
-    return prep_cached(de_psd_plans, samples, 0, [&] { return e2v::de_psd_plan(samples); });
+    return prep_cached(de_psd_plans, std::array<int, 2>{samples, 0}, [&] { return e2v::de_psd_plan(samples); });
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -2021,13 +2017,13 @@ void e2v_ctx::image_classify(const FrameSrc& src, int n, int F, int H, int W, fl
     static const int* const chunk_knob = knob("E2V_VIT_CHUNK", 64);
     const int P = cfg.vit_patch_size, L = cfg.vit_num_labels;
     const TowerDims d{cfg.vit_hidden, cfg.vit_intermediate, P, image_tokens(), 3 * P * P, cfg.vit_heads, cfg.vit_norm_eps, cfg.vit_norm_eps, 1};
-    auto t = tower_begin(this, IMAGE, "e2v_image_classify", "3 * patch_size^2", d.K, [&]() -> const ImagePrepPlan& { return prep_plan(H, W); }, *chunk_knob, s);
+    auto t = tower_begin(this, IMAGE, "e2v_image_classify", "3 * patch_size^2", d.K, H, W, *chunk_knob, s);
     const int h16 = t.R.h16();
     const long long total = (long long)n * F;
     for (long long i0 = 0; i0 < total; i0 += t.chunk) {
         const int ni = (int)std::min<long long>(t.chunk, total - i0);
         tower_chunk(t.R, image, d, ni,
-                    [&](float* rows) { image_preprocess(src, n, F, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](float* rows) { frame_preprocess(src, n, F, 1, i0, ni, t.plan, t.tab(), P, rows, "image_preprocess", s, h16); },
                     [&](const float* qkv, float* a) { image_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
                     [&](const Act& lg) {
                         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
@@ -2052,13 +2048,12 @@ void e2v_ctx::video_classify(const FrameSrc& src, int n, int F, int H, int W, fl
     const int P = cfg.vmae_patch_size, ts = cfg.vmae_tubelet_size, L = cfg.vmae_num_labels;
     const TowerDims d{cfg.vmae_hidden, cfg.vmae_intermediate, P, video_tokens(), 3 * ts * P * P, cfg.vmae_heads, cfg.vmae_norm_eps,
                       1e-5f, 1};                                 // fc_norm = nn.LayerNorm(hidden): the default eps
-    auto t = tower_begin(this, VIDEO, "e2v_video_classify", "3 * tubelet_size * patch_size^2", d.K,
-                         [&]() -> const VideoPrepPlan& { return video_prep_plan(H, W); }, *chunk_knob, s);
+    auto t = tower_begin(this, VIDEO, "e2v_video_classify", "3 * tubelet_size * patch_size^2", d.K, H, W, *chunk_knob, s);
     const int h16 = t.R.h16(), chunk = std::min(t.chunk, 65535 / F);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int ni = std::min(chunk, n - i0);
         tower_chunk(t.R, video, d, ni,
-                    [&](float* rows) { video_preprocess(src, n, F, ts, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](float* rows) { frame_preprocess(src, n, F, ts, (long long)i0 * F, ni * F, t.plan, t.tab(), P, rows, "video_preprocess", s, h16); },
                     [&](const float* qkv, float* a) { token_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
                     [&](const Act& lg) {
                         image_head(lg.p, lg.C, L, ni, logits ? logits + (size_t)i0 * L : nullptr, probs ? probs + (size_t)i0 * L : nullptr,
@@ -2083,13 +2078,13 @@ void e2v_ctx::clip_embed(const FrameSrc& src, int n, int F, int H, int W, float*
     const int P = vcfg.clipv_patch_size, E = vcfg.clipv_projection_dim;
     const TowerDims d{vcfg.clipv_hidden, vcfg.clipv_intermediate, P, clipv_tokens(), 3 * P * P, vcfg.clipv_heads, vcfg.clipv_norm_eps,
                       vcfg.clipv_norm_eps, vcfg.clipv_act};
-    auto t = tower_begin(this, CLIPV, "e2v_clip_embed", "3 * patch_size^2", d.K, [&]() -> const VideoPrepPlan& { return clipv_prep_plan(H, W); }, *chunk_knob, s);
+    auto t = tower_begin(this, CLIPV, "e2v_clip_embed", "3 * patch_size^2", d.K, H, W, *chunk_knob, s);
     const int h16 = t.R.h16();
     const long long total = (long long)n * F;
     for (long long i0 = 0; i0 < total; i0 += t.chunk) {
         const int ni = (int)std::min<long long>(t.chunk, total - i0);
         tower_chunk(t.R, clipv, d, ni,
-                    [&](float* rows) { frame_preprocess(src, n, F, i0, ni, t.plan, t.tab(), P, rows, s, h16); },
+                    [&](float* rows) { frame_preprocess(src, n, F, 1, i0, ni, t.plan, t.tab(), P, rows, "video_preprocess", s, h16); },
                     [&](const float* qkv, float* a) { image_attention(qkv, 3 * d.C, a, d.C, ni, d.T, d.heads, s); },
                     [&](const Act& emb) { copy_rows(emb.p, emb.C, embeds + (size_t)i0 * E, E, ni, E, s); });
     }
@@ -2142,7 +2137,7 @@ void e2v_ctx::seq2seq_latents(const EegnetArgs& eeg_in, int B, int first, int co
         e.F1 = scfg.s2s_f1; e.D = scfg.s2s_d; e.F2 = scfg.s2s_f2;
         eegnet_embed(e, s);
         Act emb = R.linear(s2s.embed, f.p, feat, MW, R.f32_rows());
-        video_embed(emb.p, s2s.pe, x.p, B, W, C, s);
+        token_embed(emb.p, nullptr, s2s.pe, x.p, B, W, C, s);
     }
     for (const S2sEncLayerW& l : s2s.enc) {
         Act qkv = R.linear(l.qkv, x.p, C, MW, R.f32_rows());

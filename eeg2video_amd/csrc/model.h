@@ -195,7 +195,7 @@ void geglu_interleave(const float* w, const float* b, int half, int in, float* d
 // ask for `want` split-K runs of launch g: where it is eligible the workspace is attached and returned (alive until the launch is queued)
 Act splitk_attach(Pool& pool, IgemmArgs& g, int want);
 // the tables of a preprocess plan (plan.words) in a pool block, copied on stream s: `plan` must live until the copy has run
-Act upload_plan(Pool& pool, const ImagePrepPlan& plan, hipStream_t s);
+Act upload_plan(Pool& pool, const PrepPlan& plan, hipStream_t s);
 
 }  // namespace e2v
 
@@ -258,15 +258,11 @@ struct e2v_ctx {
     e2v::S2sW s2s;
     e2v::GlmW glm;
     float image_lut[3 * 256] = {};                               // the processor's pixel value of a byte, per channel (e2v_create)
-    std::map<std::array<int, 2>, e2v::ImagePrepPlan> prep_plans; // host resize tables of the classifier's preprocess per (H, W): prep_cached (model.cpp)
-    const e2v::ImagePrepPlan& prep_plan(int H, int W);
-    float video_lut[3 * 256] = {};                               // the same two for the video classifier
-    std::map<std::array<int, 2>, e2v::VideoPrepPlan> video_prep_plans;
-    const e2v::VideoPrepPlan& video_prep_plan(int H, int W);
+    float video_lut[3 * 256] = {};                               // the same for the video classifier
     e2v_clipv_config vcfg = {};                                  // the CLIP vision tower's config (e2v_create_clip_vision); all zero: none
     float clipv_lut[3 * 256] = {};                               // and for the CLIP vision tower's processor (bicubic tables)
-    std::map<std::array<int, 2>, e2v::VideoPrepPlan> clipv_prep_plans;
-    const e2v::VideoPrepPlan& clipv_prep_plan(int H, int W);
+    std::map<std::array<int, 3>, e2v::PrepPlan> prep_plans;      // host resize tables of a tower's preprocess per (part, H, W): prep_cached (model.cpp)
+    const e2v::PrepPlan& prep_plan(Part tower, int H, int W);    // IMAGE, VIDEO or CLIPV, by the tower's config and pixel table
     e2v_s2s_config scfg = {};                                    // the Seq2Seq model's config (e2v_create_ex); all zero: none
     int s2s_features() const { return scfg.s2s_f2 * ((scfg.s2s_samples / 4) / 8); }     // the EEGNet embedding's flattened width
     int s2s_latent() const { return scfg.s2s_latent_channels * scfg.s2s_latent_h * scfg.s2s_latent_w; }

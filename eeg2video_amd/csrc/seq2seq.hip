@@ -1,7 +1,7 @@
 // Kernels of the Seq2Seq latent model (the reference's myTransformer, EEG2Video_New/Seq2Seq/my_autoregressive_transformer.py:16-192,
 // behind e2v_seq2seq_latents) that the rest of the library has no counterpart for: the EEGNet embedding of one EEG window, attention
 // over the handful of tokens the model ever holds, and the latent layout.  LayerNorm and the linears are norm.hip's and igemm.hip's;
-// positions, the mean over the window rows and the appended rows are video_embed, token_mean and copy_rows.  fp32 in every compute mode.
+// positions, the mean over the window rows and the appended rows are token_embed, token_mean and copy_rows.  fp32 in every compute mode.
 #include <cmath>
 
 #include "kernels.h"

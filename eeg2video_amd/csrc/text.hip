@@ -35,30 +35,14 @@ void text_embed(const int* ids, const float* tok, const float* pos, float* out, 
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Causal self-attention over one prompt (CLIPAttention with the triu mask, head dim 64): one workgroup per (prompt, head).
-// K and V of the head are staged in LDS once ([T][68] fp32 each: a 64-float row spans all 64 banks, so lanes reading the same
-// column of different rows with ds_read_b128 would all hit one slot; at a stride of 68 floats the 16 lanes of a group start
-// 4 banks apart).  A wave takes the queries i = w, w + 8, ...; for query i
+// K and V of the head are staged in LDS once ([T][68] fp32 each: act_io.h, with the wave ops, shared with the image classifier's
+// kernel in vit.hip, which is this one without the triangle).  A wave takes the queries i = w, w + 8, ...; for query i
 //   scores   lane j (and j + 64) holds s_j = q_i . k_j for j <= i -- the query's 64 values are read lane by lane into scalar
 //            registers, the key row comes from LDS 16 bytes at a time; keys past i are never read (no -inf is added);
 //   softmax  fp32, the maximum over the wave subtracted, butterfly reductions over the 64 lanes;
 //   output   lane d accumulates sum_j p_j v_j[d] over j = 0 .. i in order (p_j read from its lane), divided by the sum at the end.
 // Nothing of a query depends on a later row of the prompt, and the summation order of a row does not depend on T or B.
 // ---------------------------------------------------------------------------------------------------------------------------
-constexpr int kTextLd = 68;          // LDS row stride in floats
-constexpr int kTextWaves = 8;
-
-__device__ __forceinline__ float wave_max(float v) {
-    for (int m = 32; m >= 1; m >>= 1) v = fmaxf(v, __shfl_xor(v, m, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ float lane_value(float v, int lane) {      // v of `lane` (wave-uniform) as a scalar
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane));
-}
-
 // s = q . K[j] for this lane's key row (qv: the query, one value per lane).  Called by all 64 lanes: a lane without a key of
 // its own is given row i again (a row the query may read) and its score is dropped by the caller.
 __device__ __forceinline__ float text_score(const float* __restrict__ krow, float qv) {
@@ -74,47 +58,47 @@ __device__ __forceinline__ float text_score(const float* __restrict__ krow, floa
     return acc * 0.125f;                                                           // 64^-0.5
 }
 
-__global__ __launch_bounds__(64 * kTextWaves) void text_causal_attn_kernel(const float* __restrict__ qkv, int ldqkv, float* __restrict__ out,
+__global__ __launch_bounds__(64 * kKeyWaves) void text_causal_attn_kernel(const float* __restrict__ qkv, int ldqkv, float* __restrict__ out,
                                                                            int ldo, int T, int heads) {
     extern __shared__ __attribute__((aligned(16))) char text_smem[];
     float* Ks = reinterpret_cast<float*>(text_smem);
-    float* Vs = Ks + (size_t)T * kTextLd;
+    float* Vs = Ks + (size_t)T * kKeyLd;
     const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
     const int C = heads * 64;
     const float* base = qkv + (size_t)b * T * ldqkv + h * 64;
-    for (int i = threadIdx.x; i < T * 16; i += 64 * kTextWaves) {
+    for (int i = threadIdx.x; i < T * 16; i += 64 * kKeyWaves) {
         const int r = i >> 4, c = (i & 15) * 4;
         const float* src = base + (size_t)r * ldqkv + c;
-        *reinterpret_cast<f32x4*>(Ks + r * kTextLd + c) = *reinterpret_cast<const f32x4*>(src + C);
-        *reinterpret_cast<f32x4*>(Vs + r * kTextLd + c) = *reinterpret_cast<const f32x4*>(src + 2 * C);
+        *reinterpret_cast<f32x4*>(Ks + r * kKeyLd + c) = *reinterpret_cast<const f32x4*>(src + C);
+        *reinterpret_cast<f32x4*>(Vs + r * kKeyLd + c) = *reinterpret_cast<const f32x4*>(src + 2 * C);
     }
     __syncthreads();
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    for (int i = w; i < T; i += kTextWaves) {
+    for (int i = w; i < T; i += kKeyWaves) {
         const float qv = base[(size_t)i * ldqkv + lane];
         const bool on0 = lane <= i, on1 = lane + 64 <= i;
-        float s0 = text_score(Ks + (on0 ? lane : i) * kTextLd, qv), s1 = 0.f;
-        if (i >= 64) s1 = text_score(Ks + (on1 ? lane + 64 : i) * kTextLd, qv);     // (wave-uniform: every lane is in)
+        float s0 = text_score(Ks + (on0 ? lane : i) * kKeyLd, qv), s1 = 0.f;
+        if (i >= 64) s1 = text_score(Ks + (on1 ? lane + 64 : i) * kKeyLd, qv);     // (wave-uniform: every lane is in)
         const float m = wave_max(fmaxf(on0 ? s0 : -INFINITY, on1 ? s1 : -INFINITY));
         const float p0 = on0 ? expf(s0 - m) : 0.f, p1 = on1 ? expf(s1 - m) : 0.f;
         const float l = wave_sum(p0 + p1);
         float acc = 0.f;
         const int n0 = i < 63 ? i + 1 : 64;
-        for (int j = 0; j < n0; ++j) acc = fmaf(lane_value(p0, j), Vs[j * kTextLd + lane], acc);
-        for (int j = 64; j <= i; ++j) acc = fmaf(lane_value(p1, j - 64), Vs[j * kTextLd + lane], acc);
+        for (int j = 0; j < n0; ++j) acc = fmaf(lane_value(p0, j), Vs[j * kKeyLd + lane], acc);
+        for (int j = 64; j <= i; ++j) acc = fmaf(lane_value(p1, j - 64), Vs[j * kKeyLd + lane], acc);
         out[((size_t)b * T + i) * ldo + h * 64 + lane] = acc / l;
     }
 }
 
 void text_causal_attention(const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, hipStream_t s) {
     E2V_REQUIRE(T >= 1 && T <= kTextAttnMaxT, E2V_ESHAPE, "causal attention: 1 <= T <= " + std::to_string(kTextAttnMaxT));
-    const size_t smem = (size_t)2 * T * kTextLd * sizeof(float);
+    const size_t smem = (size_t)2 * T * kKeyLd * sizeof(float);
     const double pairs = (double)B * heads * T * (T + 1) / 2;                  // (query, key) pairs of the causal triangle
     std::string pname = "text_causal_attn";
     if (prof_detail()) pname += " B" + std::to_string(B) + " T" + std::to_string(T) + " h" + std::to_string(heads);
     ProfScope ps(pname.c_str(), 4.0 * 64 * pairs, 4.0 * 4.0 * 64 * B * heads * T, s);
-    E2V_KATTR(text_causal_attn_kernel, (size_t)2 * kTextAttnMaxT * kTextLd * sizeof(float));
-    E2V_KLAUNCH(text_causal_attn_kernel, dim3(B * heads), dim3(64 * kTextWaves), smem, s, qkv, ldqkv, out, ldo, T, heads);
+    E2V_KATTR(text_causal_attn_kernel, (size_t)2 * kTextAttnMaxT * kKeyLd * sizeof(float));
+    E2V_KLAUNCH(text_causal_attn_kernel, dim3(B * heads), dim3(64 * kKeyWaves), smem, s, qkv, ldqkv, out, ldo, T, heads);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

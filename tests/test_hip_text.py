@@ -115,7 +115,7 @@ def test_shapes_vs_restatement(tiny, tiny_ref, b, t):
     check(tiny[0](ids)[0], ref, f"tiny B={b} T={t}")
 
 
-@pytest.mark.parametrize("t", T_CASES)
+@pytest.mark.parametrize("t", T_CASES + (65, 127))          # and the second key block with one and with 63 live lanes
 @pytest.mark.parametrize("heads", [1, 2, 3])
 def test_op_causal_attention(tiny, heads, t):
     b = 2
