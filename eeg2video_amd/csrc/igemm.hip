@@ -509,33 +509,41 @@ static void launch_igemm_x3(const IgemmArgs& a, int ntiles, hipStream_t s) {
 }
 
 // -----------------------------------------------------------------------------------------------------
-// The fp32 tile for taps == 1 (linears, Winograd-domain GEMMs: 95 % of the igemm time) with 16-k stages.  LDS drops to 40 KB
-// per workgroup, so THREE workgroups fit a CU (3 waves per SIMD instead of 2) -- more phases to hide the prologue / epilogue
-// of short-K tiles and each other's barriers behind -- at the price of a barrier and the loop bookkeeping every 32 MFMAs
-// instead of every 64.  Measured against the 32-k tile (same box): linears +5-8 %, Winograd convs +3-5 %, whole pass +3.5 %.
-// Same k order, so results are bit-identical.  E2V_IGEMM_K16=0 falls back to the 32-k tile (which direct convs still use).
+// The fp32 tile for taps == 1 (linears, Winograd-domain GEMMs: 95 % of the igemm time) with 16-k stages, operands by LDS-DMA.
+// A stage is 128 + BN rows of 64 bytes; `buffer_load ... lds` moves it L2 -> LDS with no register round trip (the register-staged
+// form of this tile held 32 staging registers and paid four ds_write_b128 and the selects in front of them per wave and stage), so
+// the kernel fits 128 registers and 34 KB of LDS: FOUR workgroups per CU -- more phases to hide the prologue / epilogue of short-K
+// tiles and each other's barriers behind.  One DMA instruction fills 1 KB = 16 whole rows, so rows are unpadded and the image is
+// XOR-swizzled instead: LDS position p (16 bytes) of row r holds source chunk p ^ ((r >> 2) & 3) -- the DMA lane picks its SOURCE
+// chunk, the fragment read its position, and the four 16-lane groups of a ds_read_b128 each cover all 64 banks once.
+// Ring: two buffers; stage ks+2 is issued right behind the barrier that retires stage ks and has a whole stage (32 MFMAs per
+// wave, times the resident waves) to land before the wait in front of the next barrier.  No stage past the last is issued, and
+// nothing is in flight when the ring becomes the epilogue's staging area.
+// Same k order and MFMA sequence as the 32-k tile, so results are bit-identical.  E2V_IGEMM_K16=0 falls back to the 32-k tile
+// (which direct convs still use).
 // -----------------------------------------------------------------------------------------------------
 template <int BM, int BN, int WGM, int WGN>
-__device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg, const int n0, float* smem) {
+__device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg, const int n0, float* smem_f) {
     const int z = p.batch > 1 ? rbg / p.nbm_per : 0;
     const int bm = rbg - z * p.nbm_per;
-    constexpr int BKE = 16, LD = 20;                // 16 floats + 4 pad per LDS row: conflict-free b128 reads
-    constexpr int NT = 64 * WGM * WGN;
+    constexpr int BKE = 16, ROWB = 64;              // 16 floats = 64 bytes per LDS row, unpadded
+    constexpr int NW = WGM * WGN;
     constexpr int WM = BM / WGM, WN = BN / WGN;
     constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int RPP = NT / 4;                     // rows per loader pass (4 lanes per 64-byte row piece)
-    constexpr int AR = BM / RPP;
-    constexpr int BR = (BN + RPP - 1) / RPP;        // BN = 64: one pass, upper half of the threads idle
-    float* As = smem;                               // [2][BM][LD]
-    float* Bs = smem + 2 * BM * LD;                 // [2][BN][LD]
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int A_BYTES = BM * ROWB;
+    constexpr int STAGE = (128 + 128) * ROWB;       // stage stride, sized for the wide tile
+    constexpr int APW = BM / 16 / NW, BPW = BN / 16 / NW;   // 1-KB DMA pieces (16 rows) per wave and stage
+    constexpr int PIECES = APW + BPW;
+    static_assert(APW >= 1 && BPW >= 1 && A_BYTES + BN * ROWB <= STAGE, "tile does not fit the stage");
+    char* const smem = reinterpret_cast<char*>(smem_f);
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform LDS destinations (else every DMA sits in a waterfall loop)
     const int wm = wave / WGN, wn = wave % WGN;
     const float* __restrict__ a0 = p.a0 + (size_t)z * p.sa0;
     const char* __restrict__ w = reinterpret_cast<const char*>(p.w + (size_t)z * p.sw + (size_t)n0 * p.ldw);
     float* __restrict__ out = p.out + (size_t)z * p.sout;
     const int nk = (p.c0 + BKE - 1) / BKE + (p.c1 + BKE - 1) / BKE;
-    const int q = tid & 3, r0 = tid >> 2;
-    constexpr unsigned OOB = 0x80000000u;
+    constexpr unsigned OOB = 0x80000000u;           // beyond the descriptor window: the buffer unit writes zeros
     const size_t row_base = (size_t)bm * BM;
     const float* const a0b = a0 + row_base * p.lda0;
     const float* const a1b = p.c1 > 0 ? p.a1 + row_base * p.lda1 : a0b;
@@ -547,45 +555,55 @@ __device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg
                                                  0x00020000);
     };
     const __amdgpu_buffer_rsrc_t rw = rsrc_of(w);
-    unsigned a_row[AR], b_off[BR];
+    // DMA geometry of this lane: piece q covers tile rows 16 q .. 16 q + 15, lane -> (row 16 q + (lane >> 2), LDS position lane & 3);
+    // the chunk fetched for that position is (lane & 3) ^ ((row >> 2) & 3), the same for every piece.  Rows >= M / >= N, and
+    // below the chunks past a segment's end (ragged K, the concat seam), are out-of-window offsets.
+    const int r16 = lane >> 2;
+    const int kc = (lane & 3) ^ ((lane >> 4) & 3);
+    unsigned a_voff[APW], b_off[BPW];               // the lane's fixed source offsets (A: into the current source)
+    auto set_a_voff = [&](const int lda) {
 #pragma unroll
-    for (int i = 0; i < AR; ++i) a_row[i] = (bm * BM + r0 + RPP * i < p.M) ? (unsigned)(r0 + RPP * i) : ~0u;
-#pragma unroll
-    for (int j = 0; j < BR; ++j) {
-        const int r = r0 + RPP * j;
-        b_off[j] = (r < BN && n0 + r < p.N) ? (unsigned)(r * p.ldw * 4 + q * 16) : OOB;
-    }
-    int k_src = 0, k_cb = 0, cseg = p.c0, ldb = p.lda0 * 4;
-    bool done = false;
-    f32x4 rga[2][AR], rgb[2][BR];
-    auto issue_loads = [&](f32x4 (&ra)[AR], f32x4 (&rb)[BR]) {
-        const unsigned colb = (unsigned)(k_cb + q * 4) * 4u;
-        const __amdgpu_buffer_rsrc_t rsa = rsrc_of(k_src ? a1b : a0b);
-        const bool cok = (!done) & (k_cb + q * 4 < cseg);
-#pragma unroll
-        for (int i = 0; i < AR; ++i) {
-            const unsigned rowb = __umul24(a_row[i], (unsigned)ldb) + colb;
-            ra[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsa, ((a_row[i] != ~0u) & cok) ? rowb : OOB, 0, 0));
+        for (int i = 0; i < APW; ++i) {
+            const int row = 16 * (wave * APW + i) + r16;
+            a_voff[i] = (bm * BM + row < p.M) ? (unsigned)(row * lda * 4) + kc * 16u : OOB;
         }
-        const int koffb = ((k_src ? p.c0 : 0) + k_cb) * 4;
-#pragma unroll
-        for (int j = 0; j < BR; ++j)
-            rb[j] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, cok ? b_off[j] : OOB, koffb, 0));
-        const int cb2 = k_cb + BKE;
-        const bool wrap = cb2 >= cseg;
-        k_cb = wrap ? 0 : cb2;
-        const bool more = k_src == 0 && p.c1 > 0;
-        done = done || (wrap && !more);
-        k_src = (wrap && more) ? 1 : k_src;
-        cseg = k_src ? p.c1 : p.c0;
-        ldb = (k_src ? p.lda1 : p.lda0) * 4;
     };
-    auto store_tile = [&](int buf, const f32x4 (&ra)[AR], const f32x4 (&rb)[BR]) {
+    set_a_voff(p.lda0);
 #pragma unroll
-        for (int i = 0; i < AR; ++i) *reinterpret_cast<f32x4*>(As + buf * BM * LD + (r0 + RPP * i) * LD + q * 4) = ra[i];
+    for (int j = 0; j < BPW; ++j) {
+        const int r = 16 * (wave * BPW + j) + r16;
+        b_off[j] = (n0 + r < p.N) ? (unsigned)(r * p.ldw * 4) + kc * 16u : OOB;
+    }
+    int k_src = 0, k_cb = 0, cseg = p.c0;           // the NEXT stage to issue (wave-uniform)
+    __amdgpu_buffer_rsrc_t rsa = rsrc_of(a0b);
+    typedef __attribute__((address_space(3))) void* lds_ptr;
+    auto issue = [&](const int buf) {
+        char* Ab = smem + buf * STAGE;
+        char* Bb = Ab + A_BYTES;
+        const unsigned so = (unsigned)k_cb * 4u;                                // the stage's k offset rides in soffset
+        const unsigned sob = (unsigned)((k_src ? p.c0 : 0) + k_cb) * 4u;
+        if (k_cb + BKE <= cseg) {                   // the stage lies inside the segment: no vector instruction but the loads
 #pragma unroll
-        for (int j = 0; j < BR; ++j)
-            if (r0 + RPP * j < BN) *reinterpret_cast<f32x4*>(Bs + buf * BN * LD + (r0 + RPP * j) * LD + q * 4) = rb[j];
+            for (int i = 0; i < APW; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr)(Ab + (wave * APW + i) * 1024), 16, a_voff[i], so, 0, 0);
+#pragma unroll
+            for (int j = 0; j < BPW; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(Bb + (wave * BPW + j) * 1024), 16, b_off[j], sob, 0, 0);
+        } else {
+            const bool cok = kc * 4 < cseg - k_cb;  // the lane's chunk starts inside the segment
+#pragma unroll
+            for (int i = 0; i < APW; ++i)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsa, (lds_ptr)(Ab + (wave * APW + i) * 1024), 16, cok ? a_voff[i] : OOB, so, 0, 0);
+#pragma unroll
+            for (int j = 0; j < BPW; ++j)
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr)(Bb + (wave * BPW + j) * 1024), 16, cok ? b_off[j] : OOB, sob, 0, 0);
+        }
+        k_cb += BKE;
+        if (k_cb >= cseg && k_src == 0 && p.c1 > 0) {   // the concat seam, once per tile: second source, its own row stride
+            k_src = 1; k_cb = 0; cseg = p.c1;
+            rsa = rsrc_of(a1b);
+            set_a_voff(p.lda1);
+        }
     };
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -594,19 +612,19 @@ __device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg
         for (int ni = 0; ni < TN; ++ni)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
-    issue_loads(rga[0], rgb[0]);
-    issue_loads(rga[1], rgb[1]);
-    store_tile(0, rga[0], rgb[0]);
-    __syncthreads();
-    const int frag_off = (lane & 31) * LD + (lane >> 5) * 4;
-    const float* Afr = As + wm * WM * LD + frag_off;
-    const float* Bfr = Bs + wn * WN * LD + frag_off;
+    // fragment addressing: lane -> tile row (lane & 31) of each 32-row MFMA block, k = 8 g + 4 (lane >> 5) .. + 3 = chunk 2 g + (lane >> 5)
+    // at position chunk ^ ((row >> 2) & 3); the blocks start at multiples of 32 rows, which do not enter the swizzle
+    const int fr = lane & 31;
+    const unsigned foff0 = (unsigned)((((lane >> 5) ^ (fr >> 2)) & 3) * 16);
+    const char* Afr = smem + (wm * WM + fr) * ROWB;
+    const char* Bfr = smem + A_BYTES + (wn * WN + fr) * ROWB;
     f32x4 af[2][TM], bf[2][TN];
     auto read_frags = [&](int set, int buf, int g) {
+        const unsigned fo = g ? foff0 ^ 32u : foff0;
 #pragma unroll
-        for (int mi = 0; mi < TM; ++mi) af[set][mi] = *reinterpret_cast<const f32x4*>(Afr + buf * BM * LD + mi * 32 * LD + g * 8);
+        for (int mi = 0; mi < TM; ++mi) af[set][mi] = *reinterpret_cast<const f32x4*>(Afr + buf * STAGE + mi * 32 * ROWB + fo);
 #pragma unroll
-        for (int ni = 0; ni < TN; ++ni) bf[set][ni] = *reinterpret_cast<const f32x4*>(Bfr + buf * BN * LD + ni * 32 * LD + g * 8);
+        for (int ni = 0; ni < TN; ++ni) bf[set][ni] = *reinterpret_cast<const f32x4*>(Bfr + buf * STAGE + ni * 32 * ROWB + fo);
     };
     auto mma = [&](int set) {
 #pragma unroll
@@ -617,29 +635,49 @@ __device__ __forceinline__ void igemm_tile_k16(const IgemmArgs& p, const int rbg
                 for (int ni = 0; ni < TN; ++ni)
                     acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(bf[set][ni][e], af[set][mi][e], acc[mi][ni], 0, 0, 0);
     };
+    issue(0);
+    if (nk > 1) {
+        issue(1);
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PIECES) : "memory");
+    } else {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();                   // stage 0 has landed for every wave
+    __builtin_amdgcn_sched_barrier(0);
     read_frags(0, 0, 0);
-    auto kstep = [&](auto Pc) {
+    // one k-step; P = ks & 1 is a template constant (the loop is unrolled by two), so every LDS address is static
+    auto kstep = [&](auto Pc, const int ks) {
         constexpr int P = decltype(Pc)::value;
-        issue_loads(rga[P], rgb[P]);
-        __builtin_amdgcn_sched_barrier(0);
         read_frags(1, P, 1);
         mma(0);
-        store_tile(P ^ 1, rga[P ^ 1], rgb[P ^ 1]);
-        __syncthreads();
-        read_frags(0, P ^ 1, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        mma(1);
+        __builtin_amdgcn_sched_barrier(0);          // (left alone the scheduler sinks these MFMAs below the wait and the barrier)
+        if (ks + 1 < nk) {
+            // stage ks+1 (the only one in flight) has landed, and this wave's reads of stage ks are back
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            if (ks + 2 < nk) issue(P);              // into the buffer every wave has just finished reading
+            __builtin_amdgcn_sched_barrier(0);
+            read_frags(0, P ^ 1, 0);                // first fragments of stage ks+1 ...
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        mma(1);                                     // ... land while the last k-group of stage ks is multiplied
     };
     int ks = 0;
     for (; ks + 1 < nk; ks += 2) {
-        kstep(std::integral_constant<int, 0>{});
-        kstep(std::integral_constant<int, 1>{});
+        kstep(std::integral_constant<int, 0>{}, ks);
+        kstep(std::integral_constant<int, 1>{}, ks + 1);
     }
-    if (ks < nk) kstep(std::integral_constant<int, 0>{});
-    igemm_epilogue_batched<BM, TM, TN, WM, WN>(p, acc, out, bm, n0, wm, wn, lane, smem);
+    if (ks < nk) kstep(std::integral_constant<int, 0>{}, ks);
+    // the ring becomes the epilogue's staging area: no DMA is in flight (none was issued past the last stage) and every wave's
+    // fragment reads are back
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_sched_barrier(0);
+    igemm_epilogue_batched<BM, TM, TN, WM, WN, 4>(p, acc, out, bm, n0, wm, wn, lane, smem_f);
 }
 
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void igemm_k16_kernel(const IgemmArgs p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void igemm_k16_kernel(const IgemmArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem_k16[];
     const Tile t = tile_decode(tile_sched(p), blockIdx.x & 7, blockIdx.x >> 3);
     if (!t.valid) return;
@@ -734,7 +772,7 @@ void igemm(const IgemmArgs& a_in, hipStream_t s) {
     }
     const char* cls = "igemm_f32";
     // The plan (gemm_sched.h) sizes rounds of 512 tiles (2 workgroups per CU; 256-row blocks: 256 tiles, one per CU).  The 16-k tile
-    // runs 3 per CU, but sizing its rounds at 768 measured worse (level-2 linears 129 -> 116 TFLOP/s, UNet step 272.9 -> 278.9 ms):
+    // runs 4 per CU (3 when this was measured), but sizing its rounds at 768 measured worse (level-2 linears 129 -> 116 TFLOP/s, UNet step 272.9 -> 278.9 ms):
     // the third workgroup is better spent overlapping than being planned for.
     // Launches of only a few rounds (the level-2 linears of a B = 8 pass: 1080 tiles of 128 x 128 on 768 slots = 1.4 rounds) leave the
     // chip part idle in their last round.  E2V_IGEMM_HALF_BELOW = r x 100 > 0: a launch of fewer than r rounds of full-size tiles runs
@@ -756,7 +794,7 @@ void igemm(const IgemmArgs& a_in, hipStream_t s) {
     if (a.a_bf16) { bgemm_launch(a, ntiles, s); return; }
     if (use_x3) { launch_igemm_x3(a, ntiles, s); return; }
     if (k16 && !use_bf16 && a.taps == 1 && abl == 0) {
-        constexpr size_t smem16 = (size_t)2 * (128 + 128) * 20 * sizeof(float);   // 40 KB (epilogue staging: 4 x 32 x 68 floats = 34 KB)
+        constexpr size_t smem16 = (size_t)4 * 32 * 68 * sizeof(float);   // 34 KB: the epilogue staging (the two stage buffers: 2 x 256 rows x 64 B = 32 KB)
         E2V_KATTR(&igemm_k16_kernel, smem16);
         const GemmProf pr = gemm_prof(cls, a, 4.0, 4.0, 4.0, " k16");
         ProfScope ps(pr.name.c_str(), pr.flops, pr.bytes, s);

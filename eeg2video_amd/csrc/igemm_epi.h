@@ -215,7 +215,9 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& p, f32x16 (&acc)
 // in batches of branch-free buffer loads / stores, the GEGLU gate on packed fp32 pairs.  Per element the floating-point operations
 // and their order are those of igemm_epilogue -- results are bit-identical.  (The 16-bit tiles keep the form above: with this one
 // inlined their kernels fell from three / two waves per SIMD to one.)
-template <int BM, int TM, int TN, int WM, int WN>
+// NREQ: residual requests per 32-row block -- how many rows' quads are in flight at once (2: 16 rows; 4: 8 rows, for the 128-register
+// 16-k tile).  It moves loads only: the per-element arithmetic and its order do not depend on it.
+template <int BM, int TM, int TN, int WM, int WN, int NREQ = 2>
 __device__ __forceinline__ void igemm_epilogue_batched(const IgemmArgs& p, f32x16 (&acc)[TM][TN], float* __restrict__ out, const int bm,
                                                        const int n0, const int wm, const int wn, const int lane, float* stage) {
     const int mrow = lane & 31;
@@ -313,12 +315,13 @@ __device__ __forceinline__ void igemm_epilogue_batched(const IgemmArgs& p, f32x1
         // residual, and a select per row group.  Tiny maps (TINY) load one row per row group instead, and their residual with it, NH
         // row groups at a time behind the previous stores: a code path of its own, so that the other one has no load between its
         // stores and no register of its batch is shared with it.
-        constexpr int NH = 2;                                  // row groups finished together (registers: 168 with three waves per SIMD)
+        constexpr int NH = NREQ >= 4 ? 1 : 2;                  // row groups finished together (2: 168 registers; 1 with the short requests: 128, no spill)
         auto run = [&](auto tiny_c) {
             constexpr bool TINY = decltype(tiny_c)::value;
             f32x4 res[TM][NI], tb[TM][2];
             int split[TM];                                     // rows of block mi below split[mi] belong to its first sample
-            constexpr int HB = NI / 2;                         // a request: the residual of 16 rows; with a block's first, its time-embedding rows
+            constexpr int HB = NI / NREQ > NH ? NI / NREQ : NH;   // a request: the residual of HB row groups (NREQ = 2: 16 rows); with a block's first, its time-embedding rows
+            constexpr int NR = NI / HB;                        // requests per block
             auto request = [&](const int mi, const int hh) {
                 if constexpr (TINY) return;
 #pragma unroll
@@ -352,8 +355,8 @@ __device__ __forceinline__ void igemm_epilogue_batched(const IgemmArgs& p, f32x1
                 for (int h = 0; h < NI / NH; ++h) {
                     // (requests stay where they are written, half a block ahead: left alone the scheduler issues them all up front)
                     __builtin_amdgcn_sched_barrier(0);
-                    if ((h * NH) % HB == 0) {
-                        if (h == 0) request(mi, 1);
+                    if ((h * NH) % HB == 0) {                  // one request ahead of the one this row group consumes
+                        if (h * NH / HB + 1 < NR) request(mi, h * NH / HB + 1);
                         else if (mi + 1 < TM) request(mi + 1, 0);
                     }
                     f32x4 th[NH], rh[NH];
