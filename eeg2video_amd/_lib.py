@@ -173,6 +173,9 @@ SIGNATURES = {
     "e2v_op_layernorm": (_i, [_ctx, _p, _i64, _i, _p, _p, _f, _p, _stream]),
     "e2v_op_attention": (_i, [_ctx, _p, _i, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _stream]),
     "e2v_op_temporal_attention": (_i, [_ctx, _p, _p, _i, _i, _i, _i, _i, _f, _stream]),
+    "e2v_op_vae_attention_core": (_i, [_ctx, _p, _p, _i, _i, _i, _p, _p, _stream]),
+    "e2v_op_softmax_rows": (_i, [_ctx, _p, _i, _i, _i, _p, _i, _stream]),
+    "e2v_op_transpose2d": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _i64, _i64, _i, _stream]),
     "e2v_op_causal_attention": (_i, [_ctx, _p, _i, _p, _i, _i, _i, _i, _stream]),
     "e2v_image_resize_table": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),
     "e2v_image_resize_table_filter": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int32), C.POINTER(_i)]),

@@ -1999,6 +1999,46 @@ e2v_status e2v_op_temporal_attention(e2v_ctx* c, const float* qkv, float* out, i
     });
 }
 
+// the graph's own member (Runner::vae_attention_core through e2v_ctx::vae_attention_core): conversions at the boundary happen there
+e2v_status e2v_op_vae_attention_core(e2v_ctx* c, const float* qkv, float* out, int nimg, int HW, int C, float* scores, float* probs,
+                                     e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(qkv && out && nimg > 0 && nimg <= 65535 && HW > 0 && C > 0, E2V_EINVAL, "bad VAE attention arguments");
+        E2V_REQUIRE(C % (c->bf16_compute ? 8 : 4) == 0, E2V_EINVAL, "VAE attention needs C to be a multiple of 4 (16-bit modes: 8)");
+        hipStream_t s = S(c, stream);
+        OpRecord rec;
+        c->vae_attention_core(qkv, nimg, HW, C, out, scores, probs, s);
+    });
+}
+
+e2v_status e2v_op_softmax_rows(e2v_ctx* c, float* x, int ld, int rows, int cols, void* out16, int out_mode, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(x && rows > 0 && cols > 0 && ld >= cols, E2V_EINVAL, "bad softmax arguments");
+        E2V_REQUIRE(out_mode == 0 ? out16 == nullptr : (out16 != nullptr && (out_mode == H16_BF16 || out_mode == H16_FP16)), E2V_EINVAL,
+                    "softmax: out_mode 0 takes no 16-bit copy, 1 (bf16) and 2 (fp16) need one");
+        hipStream_t s = S(c, stream);
+        OpRecord rec;
+        softmax_rows(x, ld, rows, cols, s, out16, out_mode ? out_mode : H16_BF16);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
+e2v_status e2v_op_transpose2d(e2v_ctx* c, const void* in, int ld_in, void* out, int ld_out, int rows, int cols, int batch,
+                              int64_t sb_in, int64_t sb_out, int two_byte, e2v_stream stream) {
+    if (!c) return E2V_EINVAL;
+    return guarded(c, [&] {
+        E2V_REQUIRE(in && out && rows > 0 && cols > 0 && ld_in >= cols && ld_out >= rows, E2V_EINVAL, "bad transpose arguments");
+        E2V_REQUIRE(batch > 0 && batch <= 65535 && (rows + 31) / 32 <= 65535 && (batch == 1 || (sb_in >= 0 && sb_out >= 0)), E2V_EINVAL,
+                    "transpose: 1 <= batch <= 65535, at most 65535 row tiles, batch strides not negative");
+        hipStream_t s = S(c, stream);
+        OpRecord rec;
+        transpose2d(static_cast<const float*>(in), ld_in, static_cast<float*>(out), ld_out, rows, cols, batch, sb_in, sb_out, s, two_byte ? 1 : 0);
+        E2V_HIP(hipGetLastError());
+    });
+}
+
 // fp32 in every compute mode, as e2v_text_encode runs it
 e2v_status e2v_op_causal_attention(e2v_ctx* c, const float* qkv, int ldqkv, float* out, int ldo, int B, int T, int heads, e2v_stream stream) {
     if (!c) return E2V_EINVAL;

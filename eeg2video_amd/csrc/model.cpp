@@ -1514,13 +1514,23 @@ struct Runner {
     // are fp32 in both modes; in bf16-activation mode the probabilities are rounded once, on their way into the PV product.
     Act vae_attention(const VAEAttnW& w, const Act& x, int nimg, int HW, int groups, float eps) {
         const int C = w.C;
-        E2V_REQUIRE(HW % (bf() ? 8 : 4) == 0, E2V_EINVAL, "VAE attention needs H*W to be a multiple of 4 (bf16: 8)");
         const int64_t rows = (int64_t)nimg * HW;
         Act qkv;
         {
             Act hn = gn(w.norm, x.p, C, nullptr, 0, nimg, HW, groups, eps, false);
             qkv = linear(w.qkv, hn.p, C, rows);
         }
+        Act o = vae_attention_core(qkv, nimg, HW, C);
+        return linear(w.proj, o.p, C, rows, residual(x.p, C));
+    }
+
+    // what lies between the qkv linear and the projection: softmax(q k^T C^-0.5) v per image over the fused rows qkv [nimg*HW][3C] in
+    // the activation type, which are released as soon as V is transposed.  Also e2v_op_vae_attention_core (api.cpp), which passes fp32
+    // tensors [nimg*HW][HW] to receive the scaled scores (before the softmax overwrites them) and the probabilities (16-bit modes: the
+    // 16-bit copy the PV product reads, widened); the graph passes neither.
+    Act vae_attention_core(Act& qkv, int nimg, int HW, int C, float* scores_out = nullptr, float* probs_out = nullptr) {
+        E2V_REQUIRE(HW % (bf() ? 8 : 4) == 0, E2V_EINVAL, "VAE attention needs H*W to be a multiple of 4 (bf16: 8)");
+        const int64_t rows = (int64_t)nimg * HW;
         Act sc(pool(), rows, HW);                                   // fp32 scores
         {
             IgemmArgs g;
@@ -1530,9 +1540,14 @@ struct Runner {
             if (bf()) { g.a_bf16 = h16(); g.out_f32 = 1; g.w16 = qkv.at(C); g.ldw16 = 3 * C; }
             igemm(g, s);
         }
+        if (scores_out) E2V_HIP(hipMemcpyAsync(scores_out, sc.p, sc.bytes(), hipMemcpyDeviceToDevice, s));
         Act p16;
         if (bf()) p16 = Act(pool(), rows, HW, true);
         softmax_rows(sc.p, HW, (int)rows, HW, s, bf() ? p16.p : nullptr, bf() ? h16() : H16_BF16);
+        if (probs_out) {
+            if (bf()) cvt_rows(p16.p, HW, h16(), probs_out, HW, 0, rows, HW, HW, s);      // exact
+            else E2V_HIP(hipMemcpyAsync(probs_out, sc.p, sc.bytes(), hipMemcpyDeviceToDevice, s));
+        }
         Act vt = new_act((int64_t)nimg * C, HW);
         transpose2d(qkv.at(2 * C), 3 * C, vt.p, HW, HW, C, nimg, (long long)HW * 3 * C, (long long)C * HW, s, bf() ? 1 : 0);
         qkv.reset();
@@ -1545,7 +1560,7 @@ struct Runner {
             if (bf()) { g.a_bf16 = h16(); g.w16 = vt.p; g.ldw16 = HW; }
             igemm(g, s);
         }
-        return linear(w.proj, o.p, C, rows, residual(x.p, C));
+        return o;
     }
 
     // time embedding (unet.py:324-345) of the n_t timesteps in c->d_timesteps, `rows` rows: sinusoid -> linear_1 -> SiLU -> linear_2
@@ -1827,6 +1842,24 @@ void e2v_ctx::vae_encode_frames(const float* img_cl4, int n, int H0, int W0, flo
     f32_out.out_f32 = true;                                                                            // moments: fp32
     Act m = R.linear(vae.quant, y.p, y.C, y.rows, f32_out);
     E2V_HIP(hipMemcpyAsync(moments_cl, m.p, (size_t)m.rows * m.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    E2V_HIP(hipGetLastError());
+}
+
+// e2v_op_vae_attention_core: Runner::vae_attention_core, the code the two graphs above run, on the caller's fp32 tensors.  16-bit modes:
+// qkv rounded once to the type on entry, the 16-bit result widened (exactly) on exit.
+void e2v_ctx::vae_attention_core(const float* qkv, int nimg, int HW, int C, float* out, float* scores, float* probs, hipStream_t s) {
+    Runner R{this, s, false};
+    const int64_t rows = (int64_t)nimg * HW;
+    Act in;
+    if (R.bf()) {
+        in = Act(pool, rows, 3 * C, true);
+        cvt_rows(qkv, 3 * C, 0, in.p, 3 * C, R.h16(), rows, 3 * C, 3 * C, s);
+    } else {                                     // the caller's rows as they lie (no pool: reset() leaves them alone)
+        in.p = const_cast<float*>(qkv); in.rows = rows; in.C = 3 * C;
+    }
+    Act o = R.vae_attention_core(in, nimg, HW, C, scores, probs);
+    if (R.bf()) cvt_rows(o.p, C, R.h16(), out, C, 0, rows, C, C, s);
+    else E2V_HIP(hipMemcpyAsync(out, o.p, o.bytes(), hipMemcpyDeviceToDevice, s));
     E2V_HIP(hipGetLastError());
 }
 

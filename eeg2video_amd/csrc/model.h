@@ -345,6 +345,9 @@ struct e2v_ctx {
                              int H, int W, int T, hipStream_t s, bool cfg_pair = false, const float* host_tf = nullptr);
     void vae_decode_frames(const float* z_cl, int nframes, int h, int w, float* out_cl3, hipStream_t s, bool small_family);
     void vae_encode_frames(const float* img_cl4, int n, int H, int W, float* moments_cl8, hipStream_t s);
+    // the VAE mid-block attention between its qkv linear and its projection, as both graphs above run it (e2v_op_vae_attention_core):
+    // qkv [nimg*HW][3C] fp32 -> out [nimg*HW][C]; scores / probs: fp32 [nimg*HW][HW] or null
+    void vae_attention_core(const float* qkv, int nimg, int HW, int C, float* out, float* scores, float* probs, hipStream_t s);
     // CLIPTextModel.forward(input_ids)[0]: ids [B*T] int32 on the device (range-checked by the caller), out [B*T][text_hidden] fp32
     void text_encode(const int* ids, int B, int T, float* out, hipStream_t s);
     // ViTImageProcessor + ViTForImageClassification over images img0 .. img0 + nimg - 1 of `src` ([n][F] images of H x W), walked in

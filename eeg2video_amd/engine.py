@@ -1042,6 +1042,66 @@ class Engine:
                                                        float(scale), _stream()))
         return out
 
+    def op_vae_attention_core(self, qkv, *, nimg, HW, C, out=None, scores=None, probs=None, intermediates=False):
+        """``e2v_op_vae_attention_core``: the VAE mid-block attention between its qkv linear and its projection, the graph's own code.
+        ``qkv``: contiguous ``[nimg*HW, 3C]``; returns ``[nimg*HW, C]``.  ``intermediates`` (or a ``scores=`` / ``probs=`` tensor
+        ``[nimg*HW, HW]``): returns ``(out, scores, probs)`` -- the scaled fp32 scores and the probabilities as the kernels left them."""
+        if (not isinstance(qkv, torch.Tensor) or qkv.device != self.device or qkv.dtype != torch.float32 or not qkv.is_contiguous()
+                or tuple(qkv.shape) != (nimg * HW, 3 * C)):
+            raise ValueError(f"`qkv` has to be a contiguous float32 tensor [{nimg * HW}, {3 * C}] on {self.device}")
+        out = self._op_out(out, (nimg * HW, C))
+        want = intermediates or scores is not None or probs is not None
+        if want:
+            scores, probs = self._op_out(scores, (nimg * HW, HW)), self._op_out(probs, (nimg * HW, HW))
+        self._check(self.lib.e2v_op_vae_attention_core(self.ctx, qkv.data_ptr(), out.data_ptr(), nimg, HW, C,
+                                                       scores.data_ptr() if want else None, probs.data_ptr() if want else None, _stream()))
+        return (out, scores, probs) if want else out
+
+    def _reach(self, t, name, itemsize):
+        """elements of ``itemsize`` bytes from ``t``'s first element to the end of its storage (what a strided op may address)"""
+        if not isinstance(t, torch.Tensor) or t.device != self.device or t.element_size() != itemsize:
+            raise ValueError(f"`{name}` has to be a tensor of {itemsize}-byte elements on {self.device}")
+        st = t.untyped_storage()
+        return (st.nbytes() - (t.data_ptr() - st.data_ptr())) // itemsize
+
+    def op_softmax_rows(self, x, *, out16=None):
+        """``e2v_op_softmax_rows``, IN PLACE: ``x`` a 2-D float32 view ``[rows, cols]`` with unit column stride, row stride =
+        ``.stride(0)``.  ``out16``: a bfloat16 / float16 view of the same shape and row stride that receives the rounded probabilities
+        (``x`` then keeps the exponentials, not normalised).  Returns ``x``."""
+        if x.dim() != 2 or x.dtype != torch.float32 or (x.shape[1] > 1 and x.stride(1) != 1) or x.stride(0) < x.shape[1]:
+            raise ValueError("`x` has to be a 2-D float32 view with unit column stride")
+        rows, cols = x.shape
+        ld = x.stride(0)
+        if (rows - 1) * ld + cols > self._reach(x, "x", 4):
+            raise ValueError("`x` reaches past the end of its storage")
+        mode = 0
+        if out16 is not None:
+            mode = {torch.bfloat16: 1, torch.float16: 2}.get(out16.dtype, 0)
+            if (mode == 0 or tuple(out16.shape) != (rows, cols) or out16.stride(0) != ld or (cols > 1 and out16.stride(1) != 1)
+                    or (rows - 1) * ld + cols > self._reach(out16, "out16", 2)):
+                raise ValueError("`out16` has to be a bfloat16 / float16 view of x's shape and row stride")
+        self._check(self.lib.e2v_op_softmax_rows(self.ctx, x.data_ptr(), ld, rows, cols, out16.data_ptr() if mode else None, mode, _stream()))
+        return x
+
+    def op_transpose2d(self, x, out, *, rows, cols, batch=1, ld_in=None, ld_out=None, sb_in=None, sb_out=None):
+        """``e2v_op_transpose2d``: ``out[b][c][r] = x[b][r][c]`` for ``batch`` matrices of ``rows x cols`` read from ``x``'s first element
+        on (row stride ``ld_in``, matrices ``sb_in`` elements apart) and written from ``out``'s first element on (``ld_out``, ``sb_out``).
+        ``x`` and ``out`` share an element size of 2 or 4 bytes; the payload moves as bits.  Returns ``out``."""
+        size = x.element_size()
+        if size not in (2, 4):
+            raise ValueError("the transpose moves 2- or 4-byte elements")
+        ld_in, ld_out = ld_in or cols, ld_out or rows
+        sb_in, sb_out = (rows * ld_in if sb_in is None else sb_in), (cols * ld_out if sb_out is None else sb_out)
+        if min(rows, cols, batch) < 1 or ld_in < cols or ld_out < rows or min(sb_in, sb_out) < 0:
+            raise ValueError("bad transpose sizes or strides")
+        if (batch - 1) * sb_in + (rows - 1) * ld_in + cols > self._reach(x, "x", size):
+            raise ValueError("the strides reach past the end of `x`")
+        if (batch - 1) * sb_out + (cols - 1) * ld_out + rows > self._reach(out, "out", size):
+            raise ValueError("the strides reach past the end of `out`")
+        self._check(self.lib.e2v_op_transpose2d(self.ctx, x.data_ptr(), ld_in, out.data_ptr(), ld_out, rows, cols, batch, sb_in, sb_out,
+                                                int(size == 2), _stream()))
+        return out
+
     def op_causal_attention(self, qkv, *, B, T, heads, out=None):
         """``qkv``: a 2-D view ``[B*T, 3 * heads * 64]`` (row stride = ``.stride(0)``) holding q | k | v; returns ``[B*T, heads * 64]``
         (``e2v_op_causal_attention``: query i of a prompt attends to its keys 0 .. i).  ``out``: a 2-D view with its own row stride."""

@@ -78,6 +78,27 @@ e2v_status e2v_op_attention(e2v_ctx* ctx, const float* q, int ldq, const float* 
 e2v_status e2v_op_temporal_attention(e2v_ctx* ctx, const float* qkv, float* out, int n, int F, int HW, int heads, int D,
                                      float scale, e2v_stream stream);
 
+/* AttentionBlock of the VAE mid block (diffusers 0.11.1) between its qkv linear and its projection, the code e2v_vae_decode and
+ * e2v_vae_encode run: per image, scores = q k^T * C^-0.5 (a batched GEMM whose A and W are column slices of the fused rows), a row
+ * softmax, V transposed, out = P V (a second batched GEMM).  qkv [nimg*HW][3C]: q | k | v; out [nimg*HW][C].  scores / probs: NULL, or
+ * fp32 device tensors [nimg*HW][HW] that receive the scaled scores as the first GEMM left them (fp32 in every mode) and the
+ * probabilities as the second GEMM reads them (16-bit modes: the 16-bit copy, widened exactly).  16-bit modes: qkv is rounded once to
+ * the type on entry and the 16-bit result widened exactly.  HW a multiple of 4 (16-bit modes: 8), as the graph requires, and so C. */
+e2v_status e2v_op_vae_attention_core(e2v_ctx* ctx, const float* qkv, float* out, int nimg, int HW, int C, float* scores, float* probs,
+                                     e2v_stream stream);
+
+/* The row softmax of that block on its own, in place: x [rows][ld] fp32, columns 0 .. cols - 1 of every row (ld >= cols; the columns
+ * between the rows are neither read nor written).  out_mode 0: x receives the probabilities; out16 NULL.  out_mode 1 (bf16) / 2 (fp16):
+ * out16 [rows][ld] (2-byte elements, the same row stride) receives the probabilities rounded once, and x is left holding the
+ * exponentials exp(x - max of the row), not normalised.  fp32 arithmetic in every compute mode. */
+e2v_status e2v_op_softmax_rows(e2v_ctx* ctx, float* x, int ld, int rows, int cols, void* out16, int out_mode, e2v_stream stream);
+
+/* The transpose of that block on its own: out[b][c][r] = in[b][r][c] for `batch` matrices of rows x cols, sb_in / sb_out elements
+ * apart, row strides ld_in >= cols and ld_out >= rows (all in elements).  two_byte != 0: 2-byte elements (bf16 or fp16: one kernel),
+ * else 4-byte.  The payload is moved as bits. */
+e2v_status e2v_op_transpose2d(e2v_ctx* ctx, const void* in, int ld_in, void* out, int ld_out, int rows, int cols, int batch,
+                              int64_t sb_in, int64_t sb_out, int two_byte, e2v_stream stream);
+
 /* CLIPAttention under the causal mask (transformers modeling_clip.py, as e2v_text_encode runs it): self-attention over each of B
  * prompts of T tokens, head dim 64, scale 64^-0.5, query i attends to keys 0 .. i.  qkv [B*T][ldqkv]: q | k | v, heads * 64 columns
  * each (16-byte aligned, ldqkv a multiple of 4); out [B*T][ldo], columns 0 .. heads * 64 - 1 written.  1 <= T <= 128 (E2V_ESHAPE).

@@ -654,7 +654,8 @@ def test_tiny_unet_forward_guarded(shape, tokens, mode, env, knobs):
 
 @pytest.mark.parametrize("mode", ["fp32", "bf16", "fp16"])
 def test_tiny_vae_guarded(mode):
-    """decode and encode: the batched strided GEMM, softmax_rows and transpose2d of the VAE's attention have no op entry of their own"""
+    """decode and encode, whole graphs (the batched strided GEMMs, softmax_rows and transpose2d of the VAE's attention on their own:
+    tests/test_hip_vae_attention.py)"""
     from oracle import vae_decode, vae_encode
     pp = pipes()
     who = by_engine(pp)

@@ -102,7 +102,7 @@ def test_ddim_schedule_bit_exact(tiny):
     assert np.array_equal(eng.alphas_cumprod(), tiny[0].scheduler.alphas_cumprod.numpy())      # handed over by bind()
 
 
-@pytest.mark.parametrize("n,h,w", [(2, 4, 6), (3, 6, 4)])
+@pytest.mark.parametrize("n,h,w", [(2, 4, 6), (3, 6, 4), (2, 11, 12)])      # (h w = 132: the attention of the mid block on more than one tile)
 def test_vae_decode_vs_oracle(tiny, n, h, w):
     from oracle import vae_decode
     pipe, _, vsd = tiny
